@@ -24,9 +24,14 @@ Multi-GPU: independent source vertices shard across GPUs (BASELINE.json north_st
 collective), every rank streams the same batches over its own replica of the window graph and
 solves ITS sources -> weak scaling; value = (sources summed over ranks) * c * K / max-rank time.
 
-The line also carries `parity` (checked in this very run: |r| < eps and the loop invariant for
-every source at the end of the timed region, max |p_gpu - p_cpu| against the CPU leg's batches),
-`roofline` (dominant kernel, hipEvent-bracketed launches) and `cpu_baseline`.
+A plain run sets up, warms up, times the K steps and prints the headline line. With --full the line
+also carries `parity` (checked in this very run: |r| < eps and the loop invariant for every source at
+the end of the timed region, max |p_gpu - p_cpu| against the CPU leg's batches), `roofline` (dominant
+kernel, hipEvent-bracketed launches), `cpu_baseline`, the merged-loop and at-slide passes, and (default
+workload) the configs[1] line and the configs[3] strong-scaling block.
+
+--dump-outputs DIR writes p and r of every source as the last timed step left them (a fixed, seeded
+sample of the vertices when the whole arrays would exceed 64 MB) as DIR/<name>.npy, float64.
 """
 from __future__ import annotations
 
@@ -49,6 +54,9 @@ RING = 3                # graph epochs resident in HBM on the rolling ring (the 
 BIG_WINDOW = 4_000_000  # stream edges in the window from which a few sources per GPU are solved one after the other (binned sweeps)
 CPU_SAMPLE_BATCHES = 6  # batches the live CPU leg follows when the parity comparison comes from a committed fixture (4 multi-threaded + 2 at -t 1)
 SERIES_MAX = 3          # ... up to this many sources per GPU (beyond: one source group)
+CPU_FOLLOW_BUDGET_S = 180.0  # seconds the live CPU leg may spend following every batch to the end of the timed region (beyond: a bounded sample)
+DUMP_BYTES = 64_000_000  # --dump-outputs: at most this many bytes in all
+DUMP_SEED = 20240501     # ... and the seed of the vertex sample when the whole arrays do not fit
 
 # per config: (sources per GPU, how they are picked). The 8-GPU configurations of BASELINE.json (twitter: 8 top-10 sources,
 # friendster: the 10 sources of a top1000 file) are FIXED source sets dealt round-robin over the ranks (0 = "the config's own
@@ -109,7 +117,15 @@ def parse_args():
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=INT",
                     help="engine tuning knob (hub_min_degree, big_row_edges, pull_min_frontier, chunk_iters, pull_block, sweep_bitmap, "
                          "binned=MODE[,HA_TILES,HB_TILES,TARGET_EDGES,MIN_IDS])")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: parity checks, CPU baseline, roofline profile and ceilings, merged-loop and "
+                         "at-slide passes, the configs[1] line and the configs[3] block (the --no-* options switch parts of it off)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write p and r of every source after the last timed step as DIR/<name>.npy (float64, at most 64 MB in all)")
+    a = ap.parse_args()
+    if not a.full:   # a plain run: the headline only
+        a.no_cpu_baseline = a.no_merged = a.no_extra_passes = a.no_ceilings = a.no_extra = a.no_strong_block = True
+    return a
 
 
 def main():
@@ -159,7 +175,7 @@ def main():
         # the default run also reports configs[1] (com-youtube stand-in, one top-10 source: the single-source resident
         # path) under its own key: a second, short run of this script as a child process once this one's numbers are in
         if rank == 0 and world == 1 and not a.no_cpu_baseline:
-            line["configs1_single_source"] = extra_line(["--config", "youtube", "--steps", "40", "--warmup", "5", "--no-cpu-baseline",
+            line["configs1_single_source"] = extra_line(["--config", "youtube", "--steps", "40", "--warmup", "5", "--full", "--no-cpu-baseline",
                                                          "--data-dir", a.data_dir])
         # ... and, at EVERY N, BASELINE.json configs[3] (twitter-2010 stand-in, its fixed 8 top-10 sources dealt round-robin over
         # the N ranks): the weak-scaled default workload is an uninformative N x by construction, this block is the strong-
@@ -174,7 +190,7 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0 and not parity["ok"]:
+    if rank == 0 and parity is not None and not parity["ok"]:   # (parity is checked by --full runs)
         print(f"PARITY FAILED: {parity}", file=sys.stderr, flush=True)
         sys.exit(3)
     if ranks_seen != world:
@@ -196,7 +212,7 @@ def strong_block(a, ctx):
     b.config, b.steps, b.warmup = "twitter", max(1, a.strong_steps), 1
     b.sources = b.group = b.pick = b.batch_edges = b.bin = b.directed = None
     b.no_cpu_baseline = b.no_merged = b.no_extra_passes = b.no_ceilings = True
-    b.cpu_batches, b.tune, b.prestage = None, [], False
+    b.cpu_batches, b.tune, b.prestage, b.dump_outputs = None, [], False, None
     t0 = time.perf_counter()
     # every rank must take the same decision: the slowest "can I?" wins (host memory for a 1.4 GB stream prefix + id maps per rank)
     ok_here = 1
@@ -240,6 +256,29 @@ def hbm_plan(V, W, directed, c, S, group, binned, n_resident):
     state = (416 if S > 8 else 208 if S > 4 else 104 if S > 2 else 52) * V if group else S * 44 * V
     return {"resident_epochs": n_resident, "epoch_bytes": int(epoch), "engine_bytes": int(engine), "source_state_bytes": int(state),
             "plan_bytes": int(n_resident * epoch + engine + state)}
+
+
+def dump_outputs(out_dir, solver, n_sources, V, rank, world):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- p and r of every source of this rank
+    (dppr_read / dppr_group_read) -- as DIR/p.npy and DIR/r.npy (float64, one row per source) at the vertices listed in
+    DIR/vertices.npy: all of them when that fits in DUMP_BYTES, else a fixed, seeded sample (the same for every run with the
+    same arguments). DIR/p_sum.npy and DIR/r_max_abs.npy summarise the WHOLE arrays per source. At N > 1 every rank writes
+    its own files, prefixed rank<k>_, and the ranks share the budget."""
+    row = 16 * n_sources + 8   # bytes per kept vertex: p and r of every source + its id
+    keep = (DUMP_BYTES - (1 << 20)) // (world * row)   # (1 MB for the summaries and the .npy headers)
+    ids = np.arange(V) if keep >= V else np.sort(np.random.default_rng(DUMP_SEED).choice(V, keep, replace=False))
+    P = np.empty((n_sources, len(ids)), dtype=np.float64)
+    R = np.empty((n_sources, len(ids)), dtype=np.float64)
+    p_sum = np.empty(n_sources, dtype=np.float64)
+    r_max = np.empty(n_sources, dtype=np.float64)
+    for i in range(n_sources):
+        p, r = solver.read(i)
+        P[i], R[i] = p[ids], r[ids]
+        p_sum[i], r_max[i] = np.sum(p), np.max(np.abs(r))
+    os.makedirs(out_dir, exist_ok=True)
+    pre = f"rank{rank}_" if world > 1 else ""
+    for name, arr in (("vertices", ids.astype(np.float64)), ("p", P), ("r", R), ("p_sum", p_sum), ("r_max_abs", r_max)):
+        np.save(os.path.join(out_dir, f"{pre}{name}.npy"), arr)
 
 
 def run_workload(a, ctx):
@@ -381,7 +420,7 @@ def run_workload(a, ctx):
         def follow(self, eps, timed_dist=None):
             """init solve, W warmup batches, K timed batches. Returns (init_ms, seconds of the K brackets [max over ranks when
             timed_dist is given], sum of the event times, wall seconds of the K batches incl. the untimed graph updates)."""
-            self.keep_at = n_steps
+            self.keep_at = n_steps if a.full else None   # (the window is kept for the parity check of --full runs)
             init_ms = self.solver.init_solve(eps)
             if a.prestage:
                 self.stage(n_steps + n_prof)
@@ -437,51 +476,56 @@ def run_workload(a, ctx):
     total_sources = shard.aggregate_units(S, D)
     ranks_seen, rank_dts, backend = shard.rank_census(shard.timed_region.last_local, D)
 
+    if a.dump_outputs:   # what the timed path computed in its last step, before anything else runs on the engine
+        dump_outputs(a.dump_outputs, solver, len(sources), V, rank, world)
+
     # `value` is measured under the reference's bracket (gpu/PPRGPU.cuh:138-164, gpu/StreamUpdate.cuh:7-33): CopyOutDegree and the
     # grouping of the batch's records by tail run INSIDE the timed region (the engine's default since ABI 4). What they cost, run on
     # their own (a whole-batch resident launch does both inside the launch: the figure is then what the separate kernels would cost):
-    grouping_ms = e.time_batch_grouping(epoch=n_steps, reps=5) * (1 if as_group else S)
-
-    # ---------------- parity at the end of the timed region: every source of this rank ----------------
-    w1, w2 = fw.w_keep
-    src_e, dst_e = (w1, w2) if directed else (np.concatenate([w1, w2]), np.concatenate([w2, w1]))
-    max_r, max_inv = 0.0, 0.0
-    golden = load_bench_golden(a, V, W, c, directed, sources, n_steps, e1, e2) if rank == 0 else None
-    gold_dp = gold_n = None
-    for i, s in enumerate(sources):
-        p, r = solver.read(i)
-        max_r = max(max_r, float(np.max(np.abs(r))))
-        max_inv = max(max_inv, invariant_max_err(p, r, src_e, dst_e, V, s))
+    grouping_ms = e.time_batch_grouping(epoch=n_steps, reps=5) * (1 if as_group else S) if a.full else None
+    parity = golden = None
+    p_end, p_head, p_rest = [], [], []
+    if a.full:
+        # ---------------- parity at the end of the timed region: every source of this rank ----------------
+        w1, w2 = fw.w_keep
+        src_e, dst_e = (w1, w2) if directed else (np.concatenate([w1, w2]), np.concatenate([w2, w1]))
+        max_r, max_inv = 0.0, 0.0
+        golden = load_bench_golden(a, V, W, c, directed, sources, n_steps, e1, e2) if rank == 0 else None
+        gold_dp = gold_n = None
+        for i, s in enumerate(sources):
+            p, r = solver.read(i)
+            max_r = max(max_r, float(np.max(np.abs(r))))
+            max_inv = max(max_inv, invariant_max_err(p, r, src_e, dst_e, V, s))
+            if golden:
+                d1 = float(np.max(np.abs(p[golden["sample"]] - golden["p_sample"][i])))
+                d2 = float(np.max(np.abs(p[golden["top_ids"][i]] - golden["top_p"][i])))
+                gold_dp, gold_n = max(gold_dp or 0.0, d1, d2), (gold_n or 0) + 1
+        parity = {"eps": a.eps, "max_abs_residual": max_r, "invariant_max_err": max_inv, "sources_checked": len(sources),
+                  "max_abs_dp_vs_cpu_t1": None, "tolerance": NORTH_STAR_TOL,
+                  "ok": bool(max_r < a.eps and max_inv < 1e-12)}
         if golden:
-            d1 = float(np.max(np.abs(p[golden["sample"]] - golden["p_sample"][i])))
-            d2 = float(np.max(np.abs(p[golden["top_ids"][i]] - golden["top_p"][i])))
-            gold_dp, gold_n = max(gold_dp or 0.0, d1, d2), (gold_n or 0) + 1
-    parity = {"eps": a.eps, "max_abs_residual": max_r, "invariant_max_err": max_inv, "sources_checked": len(sources),
-              "max_abs_dp_vs_cpu_t1": None, "tolerance": NORTH_STAR_TOL,
-              "ok": bool(max_r < a.eps and max_inv < 1e-12)}
-    if golden:
-        # ALL of the rank's sources against the committed -t 1 states of this very run (tests/golden/make_bench_golden.py: schedule A,
-        # every source through every batch at -t 1; stream checksum, sources, eps and batch number matched) -- VERDICT r05 item 4
-        parity.update({"sources_compared": gold_n, "max_abs_dp": gold_dp,
-                       "compared_with": f"{golden['file']}: p of all {gold_n} sources after batch {n_steps} (the end of the timed region) at "
-                                        f"{len(golden['sample'])} sampled vertices + the 1000 of largest p, CPU -t 1 (schedule A) throughout",
-                       "ok": bool(parity["ok"] and gold_dp < NORTH_STAR_TOL)})
-    p_end = [solver.read(i)[0] for i in range(min(2, len(sources)))] if want_cpu else []   # p at the END of the timed region
-    p_head = p_end if p_end else [solver.read(0)[0]]   # (what the at-slide-accounting pass must arrive at too)
-    # ... and the other sources' too, should the CPU leg turn out cheap enough to follow all of them (below)
-    p_rest = ([solver.read(i)[0] for i in range(2, len(sources))]
-              if want_cpu and not golden and len(sources) > 2 and (len(sources) - 2) * V * 8 <= (1 << 30) else [])
+            # ALL of the rank's sources against the committed -t 1 states of this very run (tests/golden/make_bench_golden.py: schedule A,
+            # every source through every batch at -t 1; stream checksum, sources, eps and batch number matched) -- VERDICT r05 item 4
+            parity.update({"sources_compared": gold_n, "max_abs_dp": gold_dp,
+                           "compared_with": f"{golden['file']}: p of all {gold_n} sources after batch {n_steps} (the end of the timed region) at "
+                                            f"{len(golden['sample'])} sampled vertices + the 1000 of largest p, CPU -t 1 (schedule A) throughout",
+                           "ok": bool(parity["ok"] and gold_dp < NORTH_STAR_TOL)})
+        p_end = [solver.read(i)[0] for i in range(min(2, len(sources)))] if want_cpu else []   # p at the END of the timed region
+        p_head = p_end if p_end else [solver.read(0)[0]]   # (what the at-slide-accounting pass must arrive at too)
+        # ... and the other sources' too, should the CPU leg turn out cheap enough to follow all of them (below)
+        p_rest = ([solver.read(i)[0] for i in range(2, len(sources))]
+                  if want_cpu and not golden and len(sources) > 2 and (len(sources) - 2) * V * 8 <= (1 << 30) else [])
 
     # ---------------- roofline of the dominant kernel ----------------
     roof = cpu = p_cpu = None
     ps = None
-    if rank == 0:
+    if rank == 0 and a.full:
         # the n_prof batches that FOLLOW the timed region on the same stream, with a hipEvent pair around every launch of the dominant kernel
         ps = solver.profile(a.eps, fw.stage, n_steps, n_prof)
     sample_hbm()
     hbm_peak = int(total_hbm - min_free[0])
     fw.close()
-    if rank == 0:
+    if rank == 0 and a.full:
         all_iters = {"launches": ps["push_launches"], "avg_launch_us": round(1e3 * ps["push_ms"] / max(ps["push_launches"], 1), 3),
                      "algorithmic_bytes_per_launch": round((72 * ps["sum_F"] + 24 * ps["sum_E"] + 4 * ps["sum_N"]) / max(ps["push_launches"], 1), 1)}
         if ps.get("sweep_launches", 0) > 0 and not ps["persist_launches"]:
@@ -509,6 +553,8 @@ def run_workload(a, ctx):
             worst = cpu.pop("max_abs_dp")
             if cpu.get("compared") is None:
                 cpu.pop("compared", None)
+            if cpu.get("bounded"):   # (a long run: the live leg could not reach the end of the timed region within its budget)
+                parity["cpu_compared_why_not"] = cpu["bounded"] + "; every source is still held to |r| < eps and the loop invariant"
             if worst is not None:
                 parity["max_abs_dp_vs_cpu_t1"] = worst
                 parity["cpu_compared"] = cpu.pop("compared")
@@ -559,7 +605,7 @@ def run_workload(a, ctx):
     # The same K steps of the same stream on an engine under dppr_set_batch_grouping(1): the records are grouped when the batch is
     # uploaded (dppr_slide), so the event-timed batch time is the at-slide accounting's. N = 1 on streams whose from-scratch solve
     # is cheap; elsewhere the figure is the subtraction (batch time - the grouping kernels on their own).
-    at_slide = {"event_ms_per_step": round(ev_ms / a.steps - grouping_ms, 4), "how": "estimated: event_ms_per_step - grouping_ms_per_step"}
+    at_slide = {"event_ms_per_step": round(ev_ms / a.steps - grouping_ms, 4), "how": "estimated: event_ms_per_step - grouping_ms_per_step"} if a.full else None
     if rank == 0 and world == 1 and stream_len < 100_000_000 and not a.no_extra_passes:
         f3 = Follower(setup=lambda en: en.set_batch_grouping(1))
         _, _, ev3, _ = f3.follow(a.eps, None)
@@ -596,7 +642,7 @@ def run_workload(a, ctx):
                                     "upload + dppr_slide, then the timed step between synchronize + host-clock brackets; value = units / the SUM of the K brackets "
                                     "(MAX over ranks), the barrier + synchronize pair around the whole run"),
                            "grouping": "in_region", "copy_out_degree": "in_region",
-                           "grouping_ms_per_step": round(grouping_ms, 4),
+                           "grouping_ms_per_step": round(grouping_ms, 4) if a.full else None,
                            "at_slide_accounting": at_slide,
                            "note": "`value` / `ms_per_step` are measured under the reference's bracket: CopyOutDegree and the grouping of the batch's "
                                    "records by tail run inside the timed region (one ranking launch up to 4 Ki records, hand-written LDS radix placement beyond; a "
@@ -617,6 +663,11 @@ def run_workload(a, ctx):
             "edges_pushed_per_step": round(stats["sum_E"] / a.steps, 1),
             "parity": parity, "roofline": roof, "cpu_baseline": cpu, "merged_loop": merged,
         }
+        if not a.full:   # a plain run carries the headline only: these blocks are measured or checked by --full runs
+            for k in ("grouping_ms_per_step", "at_slide_accounting"):
+                del line["config"]["timed_region"][k]
+            for k in ("parity", "roofline", "cpu_baseline", "merged_loop"):
+                del line[k]
         if scaling == "strong":
             # what the multi-GPU value has to be read against: ALL of the configuration's sources as one source group on ONE GPU
             # (this very script at --gpus 1; the committed line of that run is quoted when this is an N > 1 run)
@@ -931,7 +982,9 @@ def cpu_baseline(V, e1, e2, directed, W, c, sources, eps, batches, p_end, stream
     (IncExecuteImpl only, cpu/PPRCPUMTCilk.h:131-137) on the same stream. `sources` (one or two of the rank's) are
     solved from scratch and followed through `batches` batches: with OpenMP workers (in place of Cilk Plus, which this
     toolchain lacks) up to the last two, which run at -t 1. When `p_end` is given (the GPU's p of those sources at the
-    end of the timed region, `batches` = every batch up to there), the -t 1 state is compared with it."""
+    end of the timed region, `batches` = every batch up to there), the -t 1 state is compared with it -- unless following
+    every batch is projected to take longer than CPU_FOLLOW_BUDGET_S (long runs: --steps in the hundreds), in which case
+    the leg stops as a bounded sample (CPU_SAMPLE_BATCHES batches, or the ones already done, + 2 at -t 1) and compares nothing."""
     from oracle import oracle as orc
     threads = max(1, min(orc.max_threads(), os.cpu_count() or 1, 16))
     g = orc.Graph(V, e1, e2, directed, W, c)
@@ -941,7 +994,19 @@ def cpu_baseline(V, e1, e2, directed, W, c, sources, eps, batches, p_end, stream
         st.cilk_main_loop_mt(g, 0, threads)
     t_mt = t_1 = 0.0
     n_mt = n_1 = done = 0
-    for k in range(batches):
+    cut = None
+    t_follow = time.perf_counter()
+    k = -1
+    while k + 1 < batches:
+        k += 1
+        if p_end and cut is None and 0 < k < batches - 2:
+            # projected time to the end of the timed region: the multi-threaded batches at their pace so far, the last two at -t 1
+            # (about 5 x a multi-threaded one, BENCH_r06)
+            per = (time.perf_counter() - t_follow) / k
+            projected = per * (batches - 2) + 2 * 5 * per
+            if projected > CPU_FOLLOW_BUDGET_S:
+                cut = f"following all {batches} batches was projected at {projected:.0f} s (budget {CPU_FOLLOW_BUDGET_S:.0f} s)"
+                batches = max(k, min(CPU_SAMPLE_BATCHES - 2, batches - 2)) + 2
         if g.stream_updates():
             break
         g.inc_construct(1)
@@ -959,7 +1024,7 @@ def cpu_baseline(V, e1, e2, directed, W, c, sources, eps, batches, p_end, stream
             else:
                 t_mt, n_mt = t_mt + dt, n_mt + 1
     worst = None
-    if p_end and done == batches:
+    if p_end and done == batches and cut is None:
         worst = max(float(np.max(np.abs(pe - st.p))) for pe, st in zip(p_end, states))
     had_mt = n_mt > 0
     if not had_mt:
@@ -967,12 +1032,13 @@ def cpu_baseline(V, e1, e2, directed, W, c, sources, eps, batches, p_end, stream
     return {"value": round(c * n_mt / t_mt, 1) if t_mt > 0 else None, "unit": "edges/s", "cores": threads if had_mt else 1,
             "kind": "port", "ms_per_step": round(1e3 * t_mt / max(n_mt, 1), 2),
             "t1_value": round(c * n_1 / t_1, 1) if t_1 > 0 else None, "t1_ms_per_step": round(1e3 * t_1 / max(n_1, 1), 2),
-            "max_abs_dp": worst, "p_cpu": [np.array(st.p) for st in states] if done == batches else None,
+            "max_abs_dp": worst, "p_cpu": [np.array(st.p) for st in states] if done == batches and cut is None else None,
             "compared": (f"p of {len(states)} source(s) after batch {done} (the end of the timed region), CPU state reached with the "
                          f"{threads}-thread port and the last two batches at -t 1") if worst is not None else None,
             "sample": f"{len(states)} source(s) ({', '.join(str(v) for v in sources)}; value is per source and batch -- the GPU value sums all of a "
                       f"rank's sources), {done} batches of the same stream after the from-scratch solve: {n_mt} source-batches with "
-                      f"{threads} OpenMP workers, {n_1} at -t 1; oracle restatement of cpu/PPRCPUMTCilkRev, gcc -O2"}
+                      f"{threads} OpenMP workers, {n_1} at -t 1; oracle restatement of cpu/PPRCPUMTCilkRev, gcc -O2",
+            **({"bounded": f"{cut}: stopped as a sample after {done} batches, nothing compared"} if cut else {})}
 
 
 def reference_fifo_baseline(bin_path, directed, flags, source, eps, c, batches=4):

@@ -1,8 +1,10 @@
 """bench.py's pure-Python pieces on the CPU: the byte model behind `roofline.frac`, the HBM plan that decides
-whether a run is refused up front (item 1), and which sources of a rank run in series."""
+whether a run is refused up front (item 1), which sources of a rank run in series, and what --dump-outputs writes."""
 import os
 import sys
 import types
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -52,3 +54,59 @@ def test_hbm_plan_counts_what_the_engine_holds():
 
 def test_series_policy_constants():
     assert bench.SERIES_MAX == 3 and bench.BIG_WINDOW == 4_000_000 and bench.RING == 3 and bench.CPU_SAMPLE_BATCHES == 6
+
+
+class _States:
+    """p / r of n sources over V vertices, as solver.read(i) hands them out."""
+
+    def __init__(self, n, V):
+        rng = np.random.default_rng(7)
+        self.p = [rng.random(V) for _ in range(n)]
+        self.r = [rng.random(V) * 1e-10 - 5e-11 for _ in range(n)]
+
+    def read(self, i):
+        return self.p[i].copy(), self.r[i].copy()
+
+
+def test_dump_outputs_whole_arrays_when_they_fit(tmp_path):
+    s = _States(3, 1000)
+    bench.dump_outputs(str(tmp_path), s, 3, 1000, 0, 1)
+    z = {f.name[:-4]: np.load(f) for f in tmp_path.iterdir()}
+    assert set(z) == {"vertices", "p", "r", "p_sum", "r_max_abs"} and all(a.dtype == np.float64 for a in z.values())
+    assert np.array_equal(z["vertices"], np.arange(1000)) and np.array_equal(z["p"], np.stack(s.p)) and np.array_equal(z["r"], np.stack(s.r))
+    assert np.array_equal(z["p_sum"], [np.sum(p) for p in s.p]) and np.array_equal(z["r_max_abs"], [np.max(np.abs(r)) for r in s.r])
+
+
+def test_dump_outputs_fixed_sample_within_budget(tmp_path, monkeypatch):
+    monkeypatch.setattr(bench, "DUMP_BYTES", (1 << 20) + 72_000)   # room for 1 000 vertices: p and r of 4 sources + the id (72 bytes each) + 1 MB
+    s = _States(4, 5000)
+    bench.dump_outputs(str(tmp_path / "a"), s, 4, 5000, 0, 1)
+    bench.dump_outputs(str(tmp_path / "b"), s, 4, 5000, 0, 1)
+    a = {f.name[:-4]: np.load(f) for f in (tmp_path / "a").iterdir()}
+    b = {f.name[:-4]: np.load(f) for f in (tmp_path / "b").iterdir()}
+    ids = a["vertices"].astype(np.int64)
+    assert len(ids) == 1000 and np.all(np.diff(ids) > 0) and ids[-1] < 5000           # a sorted sample without repeats
+    assert all(np.array_equal(a[k], b[k]) for k in a)                                  # ... the same one every time
+    assert np.array_equal(a["p"], np.stack(s.p)[:, ids]) and np.array_equal(a["r"], np.stack(s.r)[:, ids])
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_BYTES
+    bench.dump_outputs(str(tmp_path / "c"), s, 4, 5000, 1, 2)                           # N > 1: per rank, the budget shared
+    assert len(np.load(tmp_path / "c" / "rank1_vertices.npy")) == 500
+
+
+def test_cpu_leg_beyond_its_budget_is_a_bounded_sample(tmp_path, monkeypatch):
+    """A long run (--steps in the hundreds) cannot wait for the live CPU leg to follow every batch: past CPU_FOLLOW_BUDGET_S
+    (projected) it stops as a bounded sample, compares nothing and says why; within the budget it compares at the end."""
+    from dynamicppr_amd import datagen, stream as st
+    V, e1, e2, cfg = datagen.stand_in_stream("dblp", str(tmp_path))
+    f = cfg.flags.split()
+    opt = {f[i]: f[i + 1] for i in range(0, len(f), 2)}
+    wl = st.workload_config(cfg.edges, 0.1, 0, float(opt["-r"]), int(opt["-b"]), 0, 0)
+    src = [int(s) for s in datagen.top_sources(V, e1, e2, wl.window, cfg.directed, 1)]
+    p_end = [np.zeros(V)]
+    monkeypatch.setattr(bench, "CPU_FOLLOW_BUDGET_S", 0.0)
+    cut = bench.cpu_baseline(V, e1, e2, cfg.directed, wl.window, wl.per_batch, src, 1e-9, 40, p_end, cfg.edges)
+    assert cut["max_abs_dp"] is None and cut["p_cpu"] is None and "projected" in cut["bounded"]
+    assert f"{bench.CPU_SAMPLE_BATCHES} batches of the same stream" in cut["sample"] and cut["t1_value"] > 0
+    monkeypatch.setattr(bench, "CPU_FOLLOW_BUDGET_S", 1e9)
+    full = bench.cpu_baseline(V, e1, e2, cfg.directed, wl.window, wl.per_batch, src, 1e-9, 8, p_end, cfg.edges)
+    assert "bounded" not in full and full["max_abs_dp"] > 0 and len(full["p_cpu"]) == 1

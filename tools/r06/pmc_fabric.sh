@@ -15,7 +15,7 @@ i=0
 for G in "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum" \
          "TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum TCC_HIT_sum TCC_MISS_sum" \
          "FETCH_SIZE" "WRITE_SIZE"; do
-  rocprofv3 --pmc $G --kernel-trace --output-format csv -d $OUT/raw_$i -- python3 $ROOT/bench.py --no-cpu-baseline --no-merged --no-extra "$@" > $OUT/bench_$i.log 2>&1 || true
+  rocprofv3 --pmc $G --kernel-trace --output-format csv -d $OUT/raw_$i -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-merged --no-extra "$@" > $OUT/bench_$i.log 2>&1 || true
   F=$(find $OUT/raw_$i -name "*counter_collection.csv" | head -1)
   cp "$F" $OUT/group_$i.csv
   rm -rf $OUT/raw_$i
