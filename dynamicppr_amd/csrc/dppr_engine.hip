@@ -613,9 +613,11 @@ static int slide_impl(dppr_engine *e, const int32_t *n1, const int32_t *n2, int3
     mark("hubs, CSRs, group cut + tables");
     ep.L = 0;
     ep.grouped = false;
+    ep.max_bucket = 0;
     if (e->batch_staged) {
         const int L = (int)e->st_b1.size();
         ep.L = L;
+        ep.max_bucket = largest_bucket(e->st_b1.data(), L); // (final internal ids: a renumbering at this slide has remapped them)
         if (L > 0) {
             HIP_TRY(hipMemcpyAsync(ep.b1, e->st_b1.data(), sizeof(int) * (size_t)L, hipMemcpyHostToDevice, e->bs));
             HIP_TRY(hipMemcpyAsync(ep.b2, e->st_b2.data(), sizeof(int) * (size_t)L, hipMemcpyHostToDevice, e->bs));
@@ -707,6 +709,33 @@ int dppr_time_batch_grouping(dppr_engine *e, int32_t epoch, int32_t reps, float 
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
     *out_ms = ms / (float)reps;
+    return DPPR_OK;
+}
+
+int dppr_debug_grouping(dppr_engine *e, int32_t epoch, int32_t path, uint32_t *tails_out, uint32_t *index_out, int32_t *raw_tails_out,
+                        int32_t *path_taken, int32_t *nb_out) {
+    if (!e || e->broken || path < GROUPING_AUTO || path > GROUPING_AT_SLIDE) return fail(e, DPPR_ERR_INVALID, "debug_grouping: path 0 .. 4");
+    GET_EPOCH(e, epoch);
+    const int L = ep.L;
+    GroupingPath p = (GroupingPath)path;
+    if (p == GROUPING_AUTO) p = ep.grouped ? GROUPING_AT_SLIDE : in_region_path(e, ep);
+    if (p == GROUPING_RANK && L > 65536) return fail(e, DPPR_ERR_INVALID, "debug_grouping: the rank path (quadratic) takes at most 64 Ki records");
+    if (p == GROUPING_BUCKET && L > SU_GRP_MAX_RECORDS) return fail(e, DPPR_ERR_INVALID, "debug_grouping: the bucket path takes at most SU_GRP_MAX_RECORDS records");
+    if (p == GROUPING_AT_SLIDE && !ep.grouped) return fail(e, DPPR_ERR_INVALID, "debug_grouping: the epoch was not grouped at slide");
+    if (path_taken) *path_taken = (int32_t)p;
+    if (nb_out) *nb_out = p == GROUPING_BUCKET ? grouping_buckets(L) : 0;
+    if (L <= 0) return DPPR_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    const uint32_t *tk = ep.sk, *tv = ep.sv;
+    if (p != GROUPING_AT_SLIDE) { // as dppr_time_batch_grouping: the degrees into scratch, no solver state touched
+        if (int rc = enqueue_grouping(e, ep, reinterpret_cast<int *>(e->su_term), nullptr, 0, nullptr, 0, p)) return rc;
+        tk = e->su_k[1];
+        tv = e->su_v[1];
+    }
+    if (tails_out) HIP_TRY(hipMemcpyAsync(tails_out, tk, sizeof(uint32_t) * (size_t)L, hipMemcpyDeviceToHost, e->stream));
+    if (index_out) HIP_TRY(hipMemcpyAsync(index_out, tv, sizeof(uint32_t) * (size_t)L, hipMemcpyDeviceToHost, e->stream));
+    if (raw_tails_out) HIP_TRY(hipMemcpyAsync(raw_tails_out, ep.b1, sizeof(int32_t) * (size_t)L, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
     return DPPR_OK;
 }
 

@@ -8,7 +8,7 @@
 namespace {
 
 int cut_sweep_groups(dppr_engine *e, Epoch &ep);
-struct BinBatch { // out-orientation keys (row << bits | head) of a slide's retired and inserted edges, unsorted: what the binned tables are patched with
+struct BinBatch { // in-orientation keys (dst << bits | src: k_make_keys_seg) of a slide's retired and inserted edges, unsorted: what the binned tables are patched with
     uint64_t *del = nullptr, *ins = nullptr;
     int nd = 0, ni = 0;
 };

@@ -37,7 +37,7 @@ int group_multi_capacity(dppr_engine *e, int spl) {
 }
 
 // One frontier loop of a source group. `tails`: the state was converged before the batch's stream
-// update, so only the batch tails (sorted in su_k[1]) can be legal -- no pass over all vertices.
+// update, so only the batch tails (grouped in batch_tails: each tail one run, dppr_grouping.hpp) can be legal -- no pass over all vertices.
 // The tail of a group's loop in push form (dppr_gpush.hpp). Called between two chunks of sweeps when the frontier is
 // small: g.act[0] / g.x hold the frontier the last sweep left. Returns with *converged set (the loop is over; state as
 // a finished loop leaves it) or cleared (the mode gave up -- an iteration too large for it -- and put the frontier back

@@ -516,9 +516,9 @@ int main_loop_inspect(dppr_engine *e, Slot &s, const Epoch &ep, int phase, doubl
     return run_frontier_loop(e, s, ep, phase, eps, 0, 0);
 }
 
-// Stable grouping of the epoch's batch records by tail: su_k[1] = tails ascending, su_v[1] = record indices
-// (ascending inside a tail): key extraction + the device radix sort. `zero` / `zero_ints` are cleared on the
-// way (the counters of what follows).
+// The epoch's batch records grouped by tail (dppr_grouping.hpp): batch_tails = the tails, every tail ONE run (ascending tails
+// for the at-slide, rank and radix paths; bucket by bucket for the bucket path), batch_order = the record indices, in batch
+// order inside a run.
 inline const uint32_t *batch_tails(const dppr_engine *e, const Epoch &ep) { return ep.grouped ? ep.sk : e->su_k[1]; }
 inline const uint32_t *batch_order(const dppr_engine *e, const Epoch &ep) { return ep.grouped ? ep.sv : e->su_v[1]; }
 
@@ -542,22 +542,27 @@ int epoch_group_records(dppr_engine *e, Epoch &ep) {
     return res_record_ranges(e, ep);
 }
 
+inline GroupingPath in_region_path(const dppr_engine *e, const Epoch &ep) { return grouping_path(ep.L, ep.max_bucket, e->force_radix_grouping); }
+
 // CopyOutDegree (gpu/StreamUpdate.cuh:7-17; a tail's post-batch out-degree = the length of its row in the epoch's out-CSR, written to
-// `deg`) and the stable grouping of the L records by tail into su_k[1] / su_v[1], as the timed region runs them: ranked in one launch up
-// to SU_RANK_MAX records, bucketed + ranked (three launches, dppr_update.hpp) up to SU_GRP_MAX_RECORDS, the device radix sort beyond.
-int enqueue_grouping(dppr_engine *e, const Epoch &ep, int *deg, unsigned long long *zero, int nz, int *zero_ints, int nzi) {
+// `deg`) and the stable grouping of the L records by tail into su_k[1] / su_v[1], as the timed region runs them (`path` GROUPING_AUTO:
+// in_region_path): ranked in one launch up to SU_RANK_MAX records, bucketed + ranked (three launches, dppr_update.hpp) up to
+// SU_GRP_MAX_RECORDS unless one bucket would hold more than SU_GRP_MAX_BUCKET of them, the device radix sort otherwise. A test
+// (dppr_debug_grouping) may name the path.
+int enqueue_grouping(dppr_engine *e, const Epoch &ep, int *deg, unsigned long long *zero, int nz, int *zero_ints, int nzi,
+                     GroupingPath path = GROUPING_AUTO) {
     const int L = ep.L;
-    if (L <= SU_RANK_MAX && !e->force_radix_grouping) {
+    if (path == GROUPING_AUTO) path = in_region_path(e, ep);
+    if (path == GROUPING_RANK) {
         hipLaunchKernelGGL(k_su_group_rank, dim3((L + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, e->stream, ep.b1, L, ep.out_row_ptr, e->su_k[1],
                            e->su_v[1], deg, zero, nz, zero_ints, nzi);
         HIP_TRY(hipGetLastError());
         return DPPR_OK;
     }
-    if (L <= SU_GRP_MAX_RECORDS && !e->force_radix_grouping && e->su_grp) {
+    if (path == GROUPING_BUCKET) {
         // hand-written: bucket histogram (+ CopyOutDegree + the counters), unordered scatter into the buckets, ranking inside them:
         // no library sort between the bracket's events
-        int nb = 64;
-        while (nb < SU_GRP_MAX_BUCKETS && nb * 512 < L) nb *= 2;
+        const int nb = grouping_buckets(L);
         int *hist = e->su_grp, *cursor = hist + SU_GRP_MAX_BUCKETS, *ctl = cursor + SU_GRP_MAX_BUCKETS;
         const int wgs = (L + SU_GRP_PER_WG - 1) / SU_GRP_PER_WG;
         hipLaunchKernelGGL(k_su_grp_hist, dim3(wgs), dim3(BLOCK), 0, e->stream, ep.b1, L, nb, ep.out_row_ptr, deg, hist, zero, nz, zero_ints, nzi);
@@ -567,7 +572,7 @@ int enqueue_grouping(dppr_engine *e, const Epoch &ep, int *deg, unsigned long lo
         HIP_TRY(hipGetLastError());
         return DPPR_OK;
     }
-    // (batches beyond 4 Mi records, or DPPR_GROUPING_RADIX=1: the device radix sort of rounds 1-5)
+    // (batches beyond 4 Mi records or with a bucket above SU_GRP_MAX_BUCKET, or DPPR_GROUPING_RADIX=1: the device radix sort of rounds 1-5)
     hipLaunchKernelGGL(k_copy_out_degree, dim3(grid_for(L)), dim3(BLOCK), 0, e->stream, ep.b1, L, ep.out_row_ptr, deg);
     hipLaunchKernelGGL(k_su_keys, dim3(grid_for(L)), dim3(BLOCK), 0, e->stream, ep.b1, L, e->su_k[0], e->su_v[0], zero, nz, zero_ints, nzi);
     size_t tmp = e->su_tmp_bytes;

@@ -31,6 +31,7 @@ struct Epoch {
     uint8_t *ins = nullptr;
     int L = 0;
     uint32_t *sk = nullptr, *sv = nullptr; // the batch's records grouped by tail at slide time: tails ascending, record indices (stable)
+    int max_bucket = 0; // records in the fullest bucket of the bucket path (largest_bucket, dppr_grouping.hpp), counted at upload
     bool grouped = false;
     int id = -1; // global epoch number stored in this ring entry
     // sweep groups: tiles [grp_tile[g], grp_tile[g+1]) per workgroup, about equal edges each

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "dppr_common.hpp"
+#include "dppr_grouping.hpp"
 
 namespace dppr {
 
@@ -12,8 +13,8 @@ namespace dppr {
 // The reference serialises records that share a tail u with a per-vertex spin
 // lock taken inside a WarpAny loop; under wave64 lock-step that is a deadlock
 // hazard and its application order is arbitrary. Here the records are stably
-// grouped by tail (radix sort of (u, index)), and one lane applies each group in
-// batch-index order -- exactly the order cpu/PPRCPUMTCilkRev.h:108-124 applies them
+// grouped by tail (dppr_grouping.hpp: equal tails contiguous, batch order inside a
+// tail), and one lane applies each group in batch-index order -- exactly the order cpu/PPRCPUMTCilkRev.h:108-124 applies them
 // at -t 1, so the updated residuals are bit-identical to that CPU path. Records of
 // different tails are independent (only r[u] and predeg[u] are written; p is
 // read-only during the update).
@@ -58,7 +59,7 @@ __global__ __launch_bounds__(BLOCK) void k_su_keys(const int *__restrict__ e1, i
 // 400 us for 12 K records.) The same launch does CopyOutDegree
 // (gpu/StreamUpdate.cuh:7-17) -- the post-batch out-degree of a tail is the length of its row in the epoch's out-CSR, built
 // from the post-batch window -- and clears the loop's counters.
-constexpr int SU_RANK_MAX = 4096;
+// (SU_RANK_MAX: dppr_grouping.hpp)
 constexpr int SU_RANK_TILE = 2048;
 __global__ __launch_bounds__(BLOCK) void k_su_group_rank(const int *__restrict__ e1, int L, const int *__restrict__ out_row_ptr,
                                                         uint32_t *__restrict__ skeys, uint32_t *__restrict__ svals,
@@ -112,12 +113,13 @@ __global__ __launch_bounds__(BLOCK) void k_su_group_rank(const int *__restrict__
 //                      with one atomic each and writes (tail, index) pairs into the buckets -- in NO particular order inside one;
 //   k_su_grp_rank    : one workgroup per 256 records of a bucket: record i goes to  bucket start + #{j in the bucket :
 //                      (tail_j, j) < (tail_i, i)} -- k_su_group_rank's rule inside a bucket, the pairs passing through LDS in tiles.
-// The result is a stable GROUPING by tail: every tail's records side by side in batch order, tails ascending inside a bucket (that is all
-// IncrementalBatchUpdate and the seeding need: leaders are found by comparing neighbours). The LOW bits pick the bucket on purpose: ids are
+// The result is a stable GROUPING by tail, not a sort: every tail's records side by side in batch order, buckets in order, tails ascending
+// only INSIDE a bucket (that is all IncrementalBatchUpdate and the seeding need: leaders are found by comparing neighbours). The LOW bits pick the bucket on purpose: ids are
 // numbered by falling in-degree (dppr_idspace.hpp), and the id range of the first high-bit bucket owned a third of a twitter-size batch's
-// records -- 39 ms of ranking. Work per thread of the last launch = the size of its bucket (a few hundred records; a hub tail's thousands
-// at most; a batch whose records all share ONE tail degenerates to L comparisons per thread -- bounded, never seen).
-constexpr int SU_GRP_MAX_BUCKETS = 4096, SU_GRP_PER_WG = 2048, SU_GRP_TILE = 2048, SU_GRP_MAX_RECORDS = 1 << 22;
+// records -- 39 ms of ranking. Work per thread of the last launch = the size of its bucket: a few hundred records, a hub tail's thousands,
+// at most SU_GRP_MAX_BUCKET (dppr_grouping.hpp). Low bits cannot split ONE hot tail, so a batch whose fullest bucket holds more records
+// than that (counted on the host when the batch is uploaded, Epoch::max_bucket) is grouped by the device radix sort instead.
+constexpr int SU_GRP_PER_WG = 2048, SU_GRP_TILE = 2048; // (SU_GRP_MAX_BUCKETS, SU_GRP_MAX_RECORDS, SU_GRP_MAX_BUCKET: dppr_grouping.hpp)
 __global__ __launch_bounds__(BLOCK) void k_su_grp_hist(const int *__restrict__ e1, int L, int nb, const int *__restrict__ out_row_ptr,
                                                       int *__restrict__ deg_after, int *__restrict__ hist, unsigned long long *__restrict__ zero, int nz,
                                                       int *__restrict__ zero_ints, int nzi) {
@@ -294,7 +296,7 @@ __global__ __launch_bounds__(BLOCK) void k_su_apply(const uint32_t *__restrict__
             u = (int)skeys[j];
             const bool leader = (j == 0) || ((int)skeys[j - 1] != u);
             if (leader) {
-                int lo = j, hi = L; // end of the group: first record behind j whose tail is not u (the keys are sorted)
+                int lo = j, hi = L; // end of the group: first record behind j whose tail is not u (u appears in ONE run, so "== u" is monotone on [j, L))
                 while (hi - lo > 1) {
                     const int mid = lo + ((hi - lo) >> 1);
                     if ((int)skeys[mid] == u) lo = mid; else hi = mid;

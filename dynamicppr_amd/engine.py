@@ -60,6 +60,7 @@ EXPORTS = [
     "dppr_set_renumbering", "dppr_id_space", "dppr_set_group_push", "dppr_set_binned_sweep", "dppr_device_count", "dppr_set_phase_merge", "dppr_init_solve_at", "dppr_group_init_solve_at", "dppr_set_variant", "dppr_set_batch_grouping",
     "dppr_time_batch_grouping", "dppr_debug_dump", "dppr_hint_next_batch",
     "dppr_bench_line_fills", "dppr_bench_stream_copy", "dppr_build_id", "dppr_heartbeat", "dppr_slide_concurrent", "dppr_renumbering_due", "dppr_debug_bin_tables",
+    "dppr_debug_grouping",
 ]
 
 
@@ -139,6 +140,8 @@ def lib():
     L.dppr_renumbering_due.argtypes = [vp]
     u16p = C.POINTER(C.c_uint16)
     L.dppr_debug_bin_tables.argtypes = [vp, C.c_int32, ip, ip, ip, ip, ip, ip, ip, u16p, ip, ip, u16p, ip, i64p, i64p]
+    u32p = C.POINTER(C.c_uint32)
+    L.dppr_debug_grouping.argtypes = [vp, C.c_int32, C.c_int32, u32p, u32p, ip, ip, ip]
     L.dppr_heartbeat.restype = C.c_ulonglong
     for name in EXPORTS:
         if name not in ("dppr_strerror", "dppr_last_error", "dppr_destroy", "dppr_build_id", "dppr_heartbeat"):
@@ -167,6 +170,7 @@ class Engine:
                  persistent=None, persist_timeout_us=None, sweep_bitmap=None, binned=None, merge_phases=None, variant=None, group_at_slide=None, resident_slots=None, resident_update=None):
         self._L = lib()
         self._h = C.c_void_p()
+        self._batch_len, self._staged_len = {0: 0}, 0
         self.V, self.W, self.directed, self.c = int(V), int(W), int(directed), int(max_batch)
         rc = self._L.dppr_create(C.byref(self._h), int(device), self.V, self.W, self.directed, self.c, int(n_epochs))
         if rc:
@@ -272,12 +276,15 @@ class Engine:
         a, pa = _i32(e1)
         b, pb = _i32(e2)
         self._ck(self._L.dppr_load_window(self._h, pa, pb, len(a)), "load_window")
+        self._batch_len = {0: 0}   # epoch -> records of its batch (debug_grouping sizes its arrays with it)
+        self._staged_len = 0
 
     def set_batch(self, b1, b2, ins):
         a, pa = _i32(b1)
         b, pb = _i32(b2)
         i = np.ascontiguousarray(ins, dtype=np.uint8)
         self._ck(self._L.dppr_set_batch(self._h, pa, pb, i.ctypes.data_as(C.POINTER(C.c_uint8)), len(a)), "set_batch")
+        self._staged_len = len(a)
 
     def hint_next_batch(self, b1, b2, n1, n2):
         """Lookahead (dppr_hint_next_batch): the id lookups of the next set_batch(b1, b2, ..) / slide(n1, n2) run on helper
@@ -299,6 +306,8 @@ class Engine:
         ep = C.c_int32(-1)
         fn = self._L.dppr_slide_concurrent if concurrent else self._L.dppr_slide
         self._ck(fn(self._h, pa, pb, len(a), C.byref(ep)), "slide")
+        self._batch_len[ep.value] = self._staged_len
+        self._staged_len = 0
         return ep.value
 
     def add_source(self, s):
@@ -441,6 +450,20 @@ class Engine:
         ms = C.c_float(0)
         self._ck(self._L.dppr_time_batch_grouping(self._h, int(epoch), int(reps), C.byref(ms)), "time_batch_grouping")
         return ms.value
+
+    def debug_grouping(self, epoch=-1, path=0):
+        """Test hook (dppr_debug_grouping): the grouping of the epoch's records by tail on `path` (0: what the timed region runs,
+        1: rank, 2: bucket, 3: radix, 4: grouped at slide). Returns (tails, index, raw_tails, path_taken, nb): the grouped tails and
+        record indices (uint32), the epoch's tails in batch order (int32, internal ids), the path that ran, and the buckets of path 2."""
+        L = self._batch_len.get(max(self._batch_len) if epoch < 0 else int(epoch), 0)   # (an epoch that is not resident: refused below)
+        cap = max(4 * self.c, 1)   # (room for the longest batch there can be, whatever L is)
+        tails, index = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+        raw = np.zeros(cap, np.int32)
+        taken, nb = C.c_int32(0), C.c_int32(0)
+        u32p = C.POINTER(C.c_uint32)
+        self._ck(self._L.dppr_debug_grouping(self._h, int(epoch), int(path), tails.ctypes.data_as(u32p), index.ctypes.data_as(u32p),
+                                             raw.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(taken), C.byref(nb)), "debug_grouping")
+        return tails[:L].copy(), index[:L].copy(), raw[:L].copy(), taken.value, nb.value
 
     def debug_dump(self):
         """Post-mortem text of the engine (dppr_debug_dump): callable from another thread than the one stuck in a call."""

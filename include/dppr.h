@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define DPPR_ABI_VERSION 5
+#define DPPR_ABI_VERSION 6
 
 typedef struct dppr_engine dppr_engine; /* opaque */
 
@@ -88,9 +88,12 @@ int dppr_device_count(void);
 /* IncrementalBatchUpdate replays a batch's records tail by tail, each tail's records in batch order (lock-free; the
  * reference serialises them with a spin lock per tail, gpu/StreamUpdate.cuh:50-72), after CopyOutDegree (gpu/StreamUpdate.cuh:7-17).
  * at_slide = 0 (DEFAULT since ABI 4): both run inside dppr_update / dppr_group_update / dppr_incremental_batch_update -- the
- * reference's bracket (gpu/PPRGPU.cuh:138-164 times all of IncrementalBatchUpdate). Up to 4 Ki records (SU_RANK_MAX) the grouping is one
- * ranking launch (k_su_group_rank), beyond that a stable LDS radix placement on the tail id; a whole-batch resident launch takes the records raw and
- * groups them itself (dppr_resident.hpp). at_slide = 1 (rounds 3-4): the grouping and the degree gather, functions of the batch
+ * reference's bracket (gpu/PPRGPU.cuh:138-164 times all of IncrementalBatchUpdate). The grouping's contract: equal tails are
+ * contiguous and keep batch order; the order of the tails depends on the path. Up to 4 Ki records (SU_RANK_MAX) it is one ranking
+ * launch (k_su_group_rank; tails ascending); up to 4 Mi records (SU_GRP_MAX_RECORDS) records go into buckets by the low bits of the
+ * tail and are ranked inside them (tails ascending only inside a bucket), unless one bucket would hold more than 16 Ki records
+ * (SU_GRP_MAX_BUCKET: a hot tail); those batches and longer ones go through the device radix sort (tails ascending). A whole-batch
+ * resident launch takes the records raw and groups them itself (dppr_resident.hpp). at_slide = 1 (rounds 3-4): the grouping and the degree gather, functions of the batch
  * alone, are done when the batch is uploaded (dppr_slide; for epochs that already exist: on entry to the next call, BEFORE its
  * event bracket opens) and the timed region holds only the replay. Same results bit for bit. */
 int dppr_set_batch_grouping(dppr_engine *e, int at_slide);
@@ -392,10 +395,17 @@ int dppr_hint_next_batch(dppr_engine *e, const int32_t *b1, const int32_t *b2, i
 
 /* What dppr_set_batch_grouping(at_slide = 1) and the batch upload move out of the reference's timed region
  * (gpu/PPRGPU.cuh:138-164 times CopyOutDegree + the whole IncrementalBatchUpdate): the post-batch out-degree gather and the
- * grouping of epoch `epoch`'s L records by tail (device radix sort), run `reps` times on the engine's stream between two
+ * grouping of epoch `epoch`'s L records by tail (on the path the timed region takes), run `reps` times on the engine's stream between two
  * events; *out_ms = milliseconds per repetition. bench.py adds it to the measured batch time and reports both accountings
  * (config.timed_region). Touches scratch only. */
 int dppr_time_batch_grouping(dppr_engine *e, int32_t epoch, int32_t reps, float *out_ms);
+/* Test hook (ABI 6): the grouping of epoch `epoch`'s L records by tail, read back. path 0 = what the timed region would use for
+ * this epoch (4 when it was grouped at slide; DPPR_GROUPING_RADIX counts), 1 = rank (L <= 64 Ki), 2 = bucket (L <= 4 Mi),
+ * 3 = radix, 4 = the arrays grouped at slide (error when the epoch was not). Paths 0-3 run as dppr_time_batch_grouping does
+ * (degrees into scratch; no solver state changes). tails_out / index_out: the L grouped (tail, record index) pairs (internal ids);
+ * raw_tails_out: the epoch's L tails in batch order; *path_taken: 1-4; *nb_out: the buckets of path 2, else 0. Any pointer may be NULL. */
+int dppr_debug_grouping(dppr_engine *e, int32_t epoch, int32_t path, uint32_t *tails_out, uint32_t *index_out, int32_t *raw_tails_out,
+                        int32_t *path_taken, int32_t *nb_out);
 
 /* Diagnostics for a call that does not come back (one unexplained 300-second guard in 13 suite runs). Writes a
  * text report into buf (at most cap bytes, NUL-terminated; returns the length written): last error, epoch / id-space

@@ -25,14 +25,15 @@ def test_header_declares_expected_surface():
         assert must in syms
 
 
-def test_library_builds_and_exports_every_declared_symbol():
+def test_library_builds_and_exports_every_declared_symbol_abi6():
     path = eng.build()
     assert os.path.exists(path)
     lib = ctypes.CDLL(path)
     for name in declared_symbols():
         assert hasattr(lib, name), f"{name} declared in include/dppr.h but not exported"
     assert sorted(eng.EXPORTS) == declared_symbols()
-    assert lib.dppr_abi_version() == 5   # 5: binned tables as runs + tiles (dppr_debug_bin_tables), map lock for reads beside a concurrent slide (round 6)
+    assert lib.dppr_abi_version() == 6   # 6: dppr_debug_grouping (the grouping of a batch by tail, read back per path)
+    assert "dppr_debug_grouping" in declared_symbols()
     # the library knows which sources it was built from, and says the same as the tree (profiles are stamped with it)
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))

@@ -197,6 +197,56 @@ def test_incremental_batch_update_large_batches(shape, grouping, monkeypatch):
     assert np.array_equal(r, sc.s.r)
 
 
+def _boundary_batch_update(L, V, hub_frac, at_slide, want_path):
+    """One directed batch of exactly L records (c = ceil(L / 2) stream edges retired and inserted; an odd L drops the last insert
+    record on both sides), from a random state written to the engine and the oracle alike: r after IncrementalBatchUpdate must equal
+    the oracle's stream_update bit for bit. No environment switch: the grouping path is the one the batch selects by itself, read
+    back first (dppr_debug_grouping) -- which must leave the batch's residuals untouched."""
+    c = (L + 1) // 2
+    W = c
+    rng = np.random.default_rng(L + int(hub_frac * 100))
+    n = W + c
+    e1 = rng.integers(0, V, n)
+    if hub_frac:
+        e1 = np.where(rng.random(n) < hub_frac, 5, e1)
+    e1 = e1.astype(np.int32)
+    e2 = rng.integers(0, V, n).astype(np.int32)
+    e2 = np.where(e2 == e1, (e2 + 1) % V, e2).astype(np.int32)
+    sc = Scenario(V, e1, e2, 1, W, c, 5, 1e-9, group_at_slide=at_slide)
+    p = rng.random(V) * 1e-3
+    r = rng.normal(0.0, 1e-6, V)
+    sc.e.write(sc.slot, p, r)
+    sc.s.p[:] = p
+    sc.s.r[:] = r
+    assert not sc.g.stream_updates()
+    sc.g.inc_construct(1)
+    b1, b2, ins = sc.g.batch()
+    assert len(b1) >= L
+    sc.g._g.contents.blen = L                      # (the oracle replays its first L records; the window is the full slide's)
+    sc.e.set_batch(b1[:L], b2[:L], ins[:L])
+    sc.e.slide(*sc.g.new_stream())
+    assert sc.e.debug_grouping(path=0)[3] == want_path
+    sc.s.copy_revert_out_degree(sc.g)
+    sc.s.stream_update(sc.g)
+    sc.e.incremental_batch_update(sc.slot)
+    _, r = sc.e.read(sc.slot)
+    assert np.array_equal(r, sc.s.r)
+    sc.e.close()
+
+
+@pytest.mark.parametrize("L,path", [(4096, 1), (4097, 2), ((1 << 22) + 1, 3)], ids=["4096-rank", "4097-bucket", "4Mi+1-radix"])
+def test_incremental_batch_update_at_grouping_boundaries(L, path):
+    """The last length of the ranking launch, the first of the bucket path, and the first the radix sort takes by length alone."""
+    _boundary_batch_update(L, 1 << 20 if L > 4097 else 4096, 0.0, 0, path)
+
+
+@pytest.mark.parametrize("at_slide", [0, 1])
+def test_incremental_batch_update_one_tail_million_records(at_slide):
+    """1 Mi records, 90 % of them on one tail: grouped by the radix sort (the fullest bucket is far above SU_GRP_MAX_BUCKET), or at
+    slide; k_su_apply walks a ~940 000-record group with the whole wave."""
+    _boundary_batch_update(1 << 20, 1 << 16, 0.9, at_slide, 4 if at_slide else 3)
+
+
 @pytest.mark.parametrize("tuning", TUNINGS, ids=TUNING_IDS)
 @pytest.mark.parametrize("directed", [1, 0])
 def test_sync_schedule_frontier_sets_bit_exact(directed, tuning):

@@ -68,3 +68,14 @@ def test_sweep_group_cuts(tmp_path, seed):
                            "-Werror", "-o", exe, os.path.join(ROOT, "tests", "native", "cut_test.cpp")])
     r = subprocess.run([exe, str(seed), "3000"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
     assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-2000:]
+
+
+@pytest.mark.parametrize("seed", [1, 2])
+def test_grouping_path_selection(tmp_path, seed):
+    """dppr_grouping.hpp: the bucket count of the bucket path steps at its lengths, the fullest bucket counted at upload equals a
+    plain count (skewed and uniform tails), and a batch whose fullest bucket is above SU_GRP_MAX_BUCKET goes to the radix sort."""
+    exe = str(tmp_path / "grouping_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall",
+                           "-Werror", "-o", exe, os.path.join(ROOT, "tests", "native", "grouping_test.cpp")])
+    r = subprocess.run([exe, str(seed), "60"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-2000:]
