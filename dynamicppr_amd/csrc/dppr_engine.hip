@@ -36,6 +36,7 @@
 #include "dppr_gpush.hpp"
 #include "dppr_binned.hpp"
 #include "dppr_calib.hpp"
+#include "dppr_topk.hpp"
 
 using namespace dppr;
 
@@ -43,6 +44,7 @@ using namespace dppr;
 #include "dppr_host_graph.hpp"
 #include "dppr_host_loop.hpp"
 #include "dppr_host_group.hpp"
+#include "dppr_host_query.hpp"
 
 
 extern "C" {
@@ -223,6 +225,9 @@ void dppr_destroy(dppr_engine *e) {
     (void)hipFree(e->bar);
     (void)hipFree(e->res_arena);
     (void)hipFree(e->hub_slot_of); (void)hipFree(e->hub_hist); (void)hipFree(e->d_ext2int); (void)hipFree(e->d_xfer);
+    (void)hipFree(e->d_int2ext); (void)hipFree(e->tk_ws); (void)hipFree(e->tk_out_key); (void)hipFree(e->tk_out_row);
+    (void)hipFree(e->tk_cand); (void)hipFree(e->tk_res); (void)hipFree(e->ra_buf);
+    if (e->tk_pin) (void)hipHostFree(e->tk_pin);
     (void)hipFree(e->mv_idx); (void)hipFree(e->mv_tmp);
     (void)hipFree(e->keys_a); (void)hipFree(e->keys_b); (void)hipFree(e->sort_tmp);
     (void)hipFree(e->in_sorted); (void)hipFree(e->out_sorted); (void)hipFree(e->delpos);
@@ -1363,6 +1368,52 @@ int dppr_group_read(dppr_engine *e, int32_t group, int32_t index, double *p, dou
         HIP_TRY(hipStreamSynchronize(e->stream));
     }
     return DPPR_OK;
+}
+
+// ---- queries of a state (dppr_topk.hpp, dppr_host_query.hpp) -----------------------------------------------------------
+// Arguments are checked before any device work and before anything is written.
+static bool topk_args_ok(int32_t k, double min_p, const void *ids, const void *p, const void *cnt) {
+    return k >= 1 && k <= DPPR_TOPK_MAX && min_p >= 0.0 && ids && p && cnt; // (min_p >= 0 is false for NaN)
+}
+static bool read_at_args_ok(const dppr_engine *e, const int32_t *ids, int32_t m) {
+    if (m < 0 || (m > 0 && !ids)) return false;
+    for (int32_t i = 0; i < m; ++i)
+        if (ids[i] < 0 || ids[i] >= e->V) return false;
+    return true;
+}
+
+int dppr_topk(dppr_engine *e, int32_t slot, int32_t k, double min_p, int32_t *out_ids, double *out_p, double *out_r,
+              int32_t *out_count) {
+    GET_SLOT(e, slot);
+    if (!topk_args_ok(k, min_p, out_ids, out_p, out_count))
+        return fail(e, DPPR_ERR_INVALID, "topk: k in [1, DPPR_TOPK_MAX], min_p >= 0, non-null ids / p / count");
+    std::lock_guard<std::mutex> map_lk(e->map_mu); // (as dppr_read: one state of the id space for the whole query)
+    return run_topk(e, s.p, s.r, 1, 1, k, min_p, out_ids, out_p, out_r, out_count);
+}
+
+int dppr_group_topk(dppr_engine *e, int32_t group, int32_t k, double min_p, int32_t *out_ids, double *out_p, double *out_r,
+                    int32_t *out_counts) {
+    GET_GROUP(e, group);
+    if (!topk_args_ok(k, min_p, out_ids, out_p, out_counts))
+        return fail(e, DPPR_ERR_INVALID, "group_topk: k in [1, DPPR_TOPK_MAX], min_p >= 0, non-null ids / p / counts");
+    std::lock_guard<std::mutex> map_lk(e->map_mu);
+    return run_topk(e, g.p, g.r, g.gw, g.n, k, min_p, out_ids, out_p, out_r, out_counts);
+}
+
+int dppr_read_at(dppr_engine *e, int32_t slot, const int32_t *ids, int32_t m, double *out_p, double *out_r) {
+    GET_SLOT(e, slot);
+    if (!read_at_args_ok(e, ids, m)) return fail(e, DPPR_ERR_INVALID, "read_at: ids in [0, V)");
+    if (m == 0 || (!out_p && !out_r)) return DPPR_OK;
+    std::lock_guard<std::mutex> map_lk(e->map_mu);
+    return run_read_at(e, s.p, s.r, 1, 1, ids, m, out_p, out_r);
+}
+
+int dppr_group_read_at(dppr_engine *e, int32_t group, const int32_t *ids, int32_t m, double *out_p, double *out_r) {
+    GET_GROUP(e, group);
+    if (!read_at_args_ok(e, ids, m)) return fail(e, DPPR_ERR_INVALID, "group_read_at: ids in [0, V)");
+    if (m == 0 || (!out_p && !out_r)) return DPPR_OK;
+    std::lock_guard<std::mutex> map_lk(e->map_mu);
+    return run_read_at(e, g.p, g.r, g.gw, g.n, ids, m, out_p, out_r);
 }
 
 int dppr_group_reset_stats(dppr_engine *e, int32_t group) {

@@ -1,0 +1,133 @@
+// dppr_host_query.hpp -- host side of the state queries (dppr_topk / dppr_group_topk / dppr_read_at / dppr_group_read_at):
+// workspace, the device copy of int2ext and the launch sequence of dppr_topk.hpp. Called with map_mu held, on the solver
+// stream; nothing here is reached from the update path.
+#pragma once
+
+namespace {
+
+constexpr size_t TK_RES_IDS = 64; // byte offset of the ids in a result block (the 16 counts come first)
+
+size_t tk_res_bytes(int n, int k, bool with_r) {
+    const size_t nk = (size_t)n * (size_t)k;
+    return TK_RES_IDS + ((sizeof(int) * nk + 7) & ~(size_t)7) + sizeof(double) * nk * (with_r ? 2 : 1);
+}
+
+// int2ext on the device, for the tie order (ids are compared in external numbering). Only the occupied zones are copied.
+int sync_int2ext(dppr_engine *e) {
+    const unsigned gen = e->map_gen.load(std::memory_order_acquire);
+    if (e->d_int2ext && gen == e->i2e_gen_on_device) return DPPR_OK;
+    if (!e->d_int2ext) HIP_TRY(hipMalloc((void **)&e->d_int2ext, sizeof(int) * (size_t)e->V));
+    if (e->n_int > 0)
+        HIP_TRY(hipMemcpyAsync(e->d_int2ext, e->int2ext.data(), sizeof(int) * (size_t)e->n_int, hipMemcpyHostToDevice, e->stream));
+    if (e->n_parked > 0) {
+        const size_t lo = (size_t)(e->V - e->n_parked);
+        HIP_TRY(hipMemcpyAsync(e->d_int2ext + lo, e->int2ext.data() + lo, sizeof(int) * (size_t)e->n_parked, hipMemcpyHostToDevice,
+                               e->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream)); // (the host map may change once map_mu is released)
+    e->i2e_gen_on_device = gen;
+    return DPPR_OK;
+}
+
+int topk_workspace(dppr_engine *e, int n, size_t rows) {
+    if (!e->tk_ws) {
+        HIP_TRY(hipMalloc((void **)&e->tk_ws, sizeof(unsigned) * GS_MAX * (TK_BINS1 + TK_BINS2) + sizeof(TkLane) * GS_MAX));
+        HIP_TRY(hipMalloc((void **)&e->tk_out_key, sizeof(unsigned long long) * GS_MAX * DPPR_TOPK_MAX));
+        HIP_TRY(hipMalloc((void **)&e->tk_out_row, sizeof(int) * GS_MAX * DPPR_TOPK_MAX));
+        HIP_TRY(hipMalloc((void **)&e->tk_res, tk_res_bytes(GS_MAX, DPPR_TOPK_MAX, true)));
+        HIP_TRY(hipHostMalloc((void **)&e->tk_pin, tk_res_bytes(GS_MAX, DPPR_TOPK_MAX, true)));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_tk_hist1), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)(sizeof(unsigned) * GS_MAX * TK_BINS1)));
+    }
+    // a candidate list can hold every occupied row of its lane (the boundary bin of a state whose values crowd one exponent)
+    const size_t need = (size_t)n * std::max<size_t>(rows, 1);
+    if (need > e->tk_cand_cap) {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        (void)hipFree(e->tk_cand);
+        e->tk_cand = nullptr;
+        e->tk_cand_cap = 0;
+        const size_t cap = std::min<size_t>((size_t)GS_MAX * (size_t)e->V, need + need / 4);
+        HIP_TRY(hipMalloc((void **)&e->tk_cand, sizeof(int) * cap));
+        e->tk_cand_cap = cap;
+    }
+    return DPPR_OK;
+}
+
+// Top k of every lane of a state (p / r rows gw doubles wide, n lanes). Results are lane-major: [n][k].
+int run_topk(dppr_engine *e, const double *p, const double *r, int gw, int n, int k, double min_p, int32_t *out_ids,
+             double *out_p, double *out_r, int32_t *out_counts) {
+    HIP_TRY(hipSetDevice(e->device));
+    TkState st;
+    st.p = p;
+    st.r = r;
+    st.gw = gw;
+    st.n = n;
+    st.n_int = e->n_int;
+    st.lo_parked = e->V - e->n_parked;
+    st.rows = e->n_int + e->n_parked;
+    int rc = sync_int2ext(e);
+    if (rc) return rc;
+    rc = topk_workspace(e, n, (size_t)st.rows);
+    if (rc) return rc;
+    unsigned *hist1 = reinterpret_cast<unsigned *>(e->tk_ws), *hist2 = hist1 + GS_MAX * TK_BINS1;
+    TkLane *ctl = reinterpret_cast<TkLane *>(hist2 + GS_MAX * TK_BINS2);
+    const int cand_cap = (int)std::max<size_t>(st.rows, 1);
+    HIP_TRY(hipMemsetAsync(e->tk_ws, 0, sizeof(unsigned) * GS_MAX * (TK_BINS1 + TK_BINS2) + sizeof(TkLane) * GS_MAX, e->stream));
+    const int n_chunks = std::max((st.rows + TK_ROWS - 1) / TK_ROWS, 1);
+    const int grid1 = std::min(n_chunks, 512); // (<= 2 workgroups of 1024 threads per CU)
+    hipLaunchKernelGGL(k_tk_hist1, dim3(grid1), dim3(TK_BLOCK), sizeof(unsigned) * n * TK_BINS1, e->stream, st, min_p, hist1);
+    hipLaunchKernelGGL(k_tk_select1, dim3(n), dim3(256), 0, e->stream, hist1, k, ctl);
+    hipLaunchKernelGGL(k_tk_compact, dim3(grid1), dim3(TK_BLOCK), 0, e->stream, st, min_p, ctl, k, e->tk_out_key, e->tk_out_row,
+                       e->tk_cand, cand_cap);
+    const int grid2 = std::min(std::max(st.rows / 4096, 1), 64);
+    for (int round = 0; round < TK_ROUNDS; ++round) {
+        const int s = TK_SHIFT1 - TK_DIGIT * (round + 1);
+        hipLaunchKernelGGL(k_tk_hist2, dim3(grid2, n), dim3(256), 0, e->stream, st, e->d_int2ext, ctl, e->tk_cand, cand_cap, s, hist2);
+        hipLaunchKernelGGL(k_tk_select2, dim3(n), dim3(256), 0, e->stream, hist2, s, ctl);
+    }
+    hipLaunchKernelGGL(k_tk_take, dim3(grid2, n), dim3(256), 0, e->stream, st, e->d_int2ext, ctl, e->tk_cand, cand_cap, k,
+                       e->tk_out_key, e->tk_out_row);
+    const size_t nk = (size_t)n * (size_t)k;
+    int *res_cnt = reinterpret_cast<int *>(e->tk_res), *res_id = reinterpret_cast<int *>(e->tk_res + TK_RES_IDS);
+    const size_t off_p = TK_RES_IDS + ((sizeof(int) * nk + 7) & ~(size_t)7), off_r = off_p + sizeof(double) * nk;
+    double *res_p = reinterpret_cast<double *>(e->tk_res + off_p), *res_r = reinterpret_cast<double *>(e->tk_res + off_r);
+    hipLaunchKernelGGL(k_tk_rank, dim3((k + 255) / 256, n), dim3(256), 0, e->stream, st, e->d_int2ext, ctl, k, e->tk_out_key,
+                       e->tk_out_row, res_cnt, res_id, res_p, res_r);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(e->tk_pin, e->tk_res, tk_res_bytes(n, k, out_r != nullptr), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    memcpy(out_counts, e->tk_pin, sizeof(int) * (size_t)n);
+    memcpy(out_ids, e->tk_pin + TK_RES_IDS, sizeof(int) * nk);
+    memcpy(out_p, e->tk_pin + off_p, sizeof(double) * nk);
+    if (out_r) memcpy(out_r, e->tk_pin + off_r, sizeof(double) * nk);
+    return DPPR_OK;
+}
+
+// p / r at m external ids (validated by the caller), [m][n]
+int run_read_at(dppr_engine *e, const double *p, const double *r, int gw, int n, const int32_t *ids, int m, double *out_p,
+                double *out_r) {
+    HIP_TRY(hipSetDevice(e->device));
+    int rc = sync_map(e);
+    if (rc) return rc;
+    const size_t mn = (size_t)m * (size_t)n;
+    const size_t ids_bytes = (sizeof(int) * (size_t)m + 7) & ~(size_t)7, need = ids_bytes + 2 * sizeof(double) * mn;
+    if (need > e->ra_cap) {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        (void)hipFree(e->ra_buf);
+        e->ra_buf = nullptr;
+        e->ra_cap = 0;
+        HIP_TRY(hipMalloc((void **)&e->ra_buf, need));
+        e->ra_cap = need;
+    }
+    double *d_p = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(e->ra_buf) + ids_bytes), *d_r = d_p + mn;
+    HIP_TRY(hipMemcpyAsync(e->ra_buf, ids, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(k_read_at, dim3(grid_for((int64_t)mn)), dim3(BLOCK), 0, e->stream, p, r, gw, n, e->d_ext2int, e->ra_buf, m,
+                       d_p, d_r);
+    HIP_TRY(hipGetLastError());
+    if (out_p) HIP_TRY(hipMemcpyAsync(out_p, d_p, sizeof(double) * mn, hipMemcpyDeviceToHost, e->stream));
+    if (out_r) HIP_TRY(hipMemcpyAsync(out_r, d_r, sizeof(double) * mn, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return DPPR_OK;
+}
+
+} // namespace

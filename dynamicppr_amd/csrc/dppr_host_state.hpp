@@ -307,6 +307,17 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     size_t mv_tmp_cap = 0;
     int *d_ext2int = nullptr;  // device copy of ext2int, refreshed on demand
     double *d_xfer = nullptr;  // V doubles: staging of p / r in external order
+    // queries of a state (dppr_topk.hpp), all allocated on the first query
+    int *d_int2ext = nullptr;          // device copy of int2ext (live and parked zones), refreshed by the queries only
+    unsigned i2e_gen_on_device = 0;    // IdSpace::map_gen that copy was taken at
+    unsigned char *tk_ws = nullptr;    // pass-1 and refinement histograms, per-lane control words (zeroed per query)
+    unsigned long long *tk_out_key = nullptr; // [16][DPPR_TOPK_MAX] result lists before ordering
+    int *tk_out_row = nullptr;
+    int *tk_cand = nullptr;            // candidate lists: [n][cap] internal rows
+    size_t tk_cand_cap = 0;            // ints allocated
+    unsigned char *tk_res = nullptr, *tk_pin = nullptr; // ordered results (device / pinned host): counts, ids, p, r
+    int *ra_buf = nullptr;             // point reads: ids, then p and r outputs
+    size_t ra_cap = 0;                 // bytes allocated
     std::vector<int32_t> h_tmp1, h_tmp2;
     std::vector<int32_t> h_tiles; // host copy of the tile edge prefix / group table
     int max_iters = 1 << 20;

@@ -60,7 +60,7 @@ EXPORTS = [
     "dppr_set_renumbering", "dppr_id_space", "dppr_set_group_push", "dppr_set_binned_sweep", "dppr_device_count", "dppr_set_phase_merge", "dppr_init_solve_at", "dppr_group_init_solve_at", "dppr_set_variant", "dppr_set_batch_grouping",
     "dppr_time_batch_grouping", "dppr_debug_dump", "dppr_hint_next_batch",
     "dppr_bench_line_fills", "dppr_bench_stream_copy", "dppr_build_id", "dppr_heartbeat", "dppr_slide_concurrent", "dppr_renumbering_due", "dppr_debug_bin_tables",
-    "dppr_debug_grouping",
+    "dppr_debug_grouping", "dppr_topk", "dppr_group_topk", "dppr_read_at", "dppr_group_read_at",
 ]
 
 
@@ -143,6 +143,10 @@ def lib():
     u32p = C.POINTER(C.c_uint32)
     L.dppr_debug_grouping.argtypes = [vp, C.c_int32, C.c_int32, u32p, u32p, ip, ip, ip]
     L.dppr_heartbeat.restype = C.c_ulonglong
+    L.dppr_topk.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, ip, dp, dp, ip]
+    L.dppr_group_topk.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, ip, dp, dp, ip]
+    L.dppr_read_at.argtypes = [vp, C.c_int32, ip, C.c_int32, dp, dp]
+    L.dppr_group_read_at.argtypes = [vp, C.c_int32, ip, C.c_int32, dp, dp]
     for name in EXPORTS:
         if name not in ("dppr_strerror", "dppr_last_error", "dppr_destroy", "dppr_build_id", "dppr_heartbeat"):
             getattr(L, name).restype = C.c_int
@@ -171,6 +175,7 @@ class Engine:
         self._L = lib()
         self._h = C.c_void_p()
         self._batch_len, self._staged_len = {0: 0}, 0
+        self._group_n = {}  # group -> number of sources
         self.V, self.W, self.directed, self.c = int(V), int(W), int(directed), int(max_batch)
         rc = self._L.dppr_create(C.byref(self._h), int(device), self.V, self.W, self.directed, self.c, int(n_epochs))
         if rc:
@@ -404,6 +409,7 @@ class Engine:
         a, pa = _i32(sources)
         gid = C.c_int32(-1)
         self._ck(self._L.dppr_add_source_group(self._h, pa, len(a), C.byref(gid)), "add_source_group")
+        self._group_n[gid.value] = len(a)
         return gid.value
 
     def group_init_solve(self, group, eps, epoch=-1):
@@ -422,6 +428,48 @@ class Engine:
         dp = C.POINTER(C.c_double)
         self._ck(self._L.dppr_group_read(self._h, group, int(index), p.ctypes.data_as(dp), r.ctypes.data_as(dp)),
                  "group_read")
+        return p, r
+
+    # ---- queries of a state (top-k and point reads on the device) ----
+    def topk(self, slot, k, min_p=0.0):
+        """The k vertices of largest p with p > min_p, by p descending then id ascending: (ids, p, r), trimmed to the count."""
+        ids, p, r, cnt = self._topk(self._L.dppr_topk, slot, 1, k, min_p, "topk")
+        return ids[0, :cnt[0]].copy(), p[0, :cnt[0]].copy(), r[0, :cnt[0]].copy()
+
+    def group_topk(self, group, k, min_p=0.0):
+        """topk for every source of a group at once: a list of (ids, p, r), one per source in group order."""
+        ids, p, r, cnt = self._topk(self._L.dppr_group_topk, group, self._group_n.get(group, 1), k, min_p, "group_topk")
+        return [(ids[i, :c].copy(), p[i, :c].copy(), r[i, :c].copy()) for i, c in enumerate(cnt)]
+
+    def _topk(self, fn, which, n, k, min_p, what):
+        kk = max(int(k), 1)
+        ids = np.empty((n, kk), dtype=np.int32)
+        p = np.empty((n, kk), dtype=np.float64)
+        r = np.empty((n, kk), dtype=np.float64)
+        cnt = np.empty(n, dtype=np.int32)
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        self._ck(fn(self._h, int(which), int(k), float(min_p), ids.ctypes.data_as(ip), p.ctypes.data_as(dp),
+                    r.ctypes.data_as(dp), cnt.ctypes.data_as(ip)), what)
+        return ids, p, r, cnt
+
+    def read_at(self, slot, ids):
+        """p and r at the given external ids (0.0 where a vertex has no id): two arrays of len(ids)."""
+        a, pa = _i32(ids)
+        p = np.empty(len(a), dtype=np.float64)
+        r = np.empty(len(a), dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        self._ck(self._L.dppr_read_at(self._h, int(slot), pa, len(a), p.ctypes.data_as(dp), r.ctypes.data_as(dp)), "read_at")
+        return p, r
+
+    def group_read_at(self, group, ids):
+        """p and r of every source of a group at the given ids: two [len(ids)][n] arrays (vertex-major, as the state)."""
+        a, pa = _i32(ids)
+        n = self._group_n.get(group, 1)
+        p = np.empty((len(a), n), dtype=np.float64)
+        r = np.empty((len(a), n), dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        self._ck(self._L.dppr_group_read_at(self._h, int(group), pa, len(a), p.ctypes.data_as(dp), r.ctypes.data_as(dp)),
+                 "group_read_at")
         return p, r
 
     def group_stats(self, group):

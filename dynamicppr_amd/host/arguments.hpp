@@ -9,6 +9,7 @@
 #include <iostream>
 #include <string>
 
+#include "../../include/dppr.h" // (DPPR_TOPK_MAX)
 #include "meta.hpp"
 
 namespace args_detail {
@@ -57,6 +58,8 @@ inline void PrintUsage() {
               << "-g: number of GPUs (sources are dealt round-robin)\n"
               << "--sources <file>: one source vertex id per line (overrides -s)\n"
               << "--dump <path>: write pagerank/residual of every source after the last batch\n"
+              << "--topk <K>: after the last batch print the K vertices of largest pagerank of every source (1 <= K <= 8192),\n"
+              << "            one line each, in source order: topk <source> <rank from 1> <vertex> <pagerank>\n"
               << "--validate: residual bound + power-iteration check after every solve\n"
               << "--split: drive each batch through IncrementalBatchUpdate/ExecuteMainLoop(0)/(1)\n"
               << "--sync: synchronous (deterministic) push schedule\n"
@@ -95,6 +98,7 @@ inline void ArgumentsChecker() {
         ok = false;
     }
     if (gVariant < 0 || gVariant >= kVariantTypeSize) ok = false;
+    if (gTopK < 0 || gTopK > DPPR_TOPK_MAX) ok = false;
     if (!ok) {
         std::cout << "invalid arguments" << std::endl;
         PrintUsage();
@@ -121,6 +125,7 @@ inline void ArgumentsParser(int argc, char **argv) {
     gNumGpus = as_int(argc, argv, "-g", 1);
     if (const char *f = find(argc, argv, "--sources")) gSourcesFile = f;
     if (const char *f = find(argc, argv, "--dump")) gDumpPath = f;
+    gTopK = as_int(argc, argv, "--topk", 0);
     gValidate = has(argc, argv, "--validate");
     gSplitInterface = has(argc, argv, "--split");
     gSchedule = has(argc, argv, "--sync") ? 1 : 0;

@@ -39,6 +39,7 @@ inline ValueType gTolerance = 1e-9;
 inline int gNumGpus = 1;              // -g : devices; sources are dealt round-robin over them
 inline std::string gSourcesFile;      // --sources : file with one source vertex id per line
 inline std::string gDumpPath;         // --dump : write p/r of every source after the last batch
+inline int gTopK = 0;                 // --topk K : print the K vertices of largest p of every source after the last batch (0: off)
 inline bool gValidate = false;        // --validate : the reference's -DVALIDATE checks at run time
 inline bool gShareDevice = false;     // --share-device (or DPPR_DEVICE_ALIAS=1): the -g N device threads share the devices that exist (d % count)
 inline bool gPushOnly = false;        // --push-only : no pull sweeps (the ablation of the -o variants times their push mechanisms)

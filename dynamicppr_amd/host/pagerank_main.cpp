@@ -4,6 +4,7 @@
 // (one host thread and one full window-graph replica per device, no collective).
 #include <atomic>
 #include <chrono>
+#include <cstdio>
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
@@ -129,6 +130,19 @@ int main(int argc, char *argv[]) {
         std::cout << "aggregate_ppr_time_slowest_gpu " << slowest << std::endl;
         std::cout << "aggregate_ppr_throughput " << edges / slowest * 1000.0 << std::endl;
         std::cout << "wall_ms " << wall_ms << std::endl;
+    }
+    if (gTopK > 0) { // (not a line of the reference) source j lives on device j % ngpu, as that device's source j / ngpu
+        std::vector<std::vector<std::vector<PPRGPU::TopEntry>>> top((size_t)ngpu);
+        for (int d = 0; d < ngpu; ++d) top[(size_t)d] = drivers[(size_t)d]->TopK(gTopK);
+        char line[160];
+        for (size_t j = 0; j < sources.size(); ++j) {
+            const auto &list = top[j % (size_t)ngpu][j / (size_t)ngpu];
+            for (size_t t = 0; t < list.size(); ++t) {
+                std::snprintf(line, sizeof(line), "topk %d %zu %d %.17g", (int)sources[j], t + 1, (int)list[t].vertex, list[t].p);
+                std::cout << line << "\n";
+            }
+        }
+        std::cout << std::flush;
     }
     if (!gDumpPath.empty())
         for (int d = 0; d < ngpu; ++d) drivers[(size_t)d]->Dump(gDumpPath + (ngpu > 1 ? "." + std::to_string(d) : ""));

@@ -423,6 +423,32 @@ public:
         std::fclose(f);
     }
 
+    // --topk: the k vertices of largest p of every source of this device, in this device's source order, through the device-side
+    // selection (dppr_topk / dppr_group_topk: one call per slot or per group of up to 16)
+    struct TopEntry {
+        int32_t vertex;
+        double p;
+    };
+    std::vector<std::vector<TopEntry>> TopK(int k) {
+        const size_t n_src = source_vertex_ids.size();
+        std::vector<std::vector<TopEntry>> out(n_src);
+        std::vector<int32_t> ids, cnt;
+        std::vector<double> p;
+        for (size_t first = 0; first < n_src; first += use_groups ? kGroupMax : 1) {
+            const size_t n = use_groups ? std::min(kGroupMax, n_src - first) : 1;
+            ids.assign(n * (size_t)k, -1);
+            p.assign(n * (size_t)k, 0.0);
+            cnt.assign(n, 0);
+            if (use_groups)
+                DPPR_CHECK(engine, dppr_group_topk(engine, groups[first / kGroupMax], k, 0.0, ids.data(), p.data(), nullptr, cnt.data()));
+            else
+                DPPR_CHECK(engine, dppr_topk(engine, slots[first], k, 0.0, ids.data(), p.data(), nullptr, cnt.data()));
+            for (size_t j = 0; j < n; ++j)
+                for (int32_t t = 0; t < cnt[j]; ++t) out[first + j].push_back({ids[j * (size_t)k + t], p[j * (size_t)k + t]});
+        }
+        return out;
+    }
+
     double TotalPprTime() const {
         double t = 0;
         for (float x : ppr_time) t += x;

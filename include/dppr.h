@@ -321,6 +321,40 @@ int dppr_group_update(dppr_engine *e, int32_t group, int32_t epoch, double eps, 
 int dppr_group_read(dppr_engine *e, int32_t group, int32_t index, double *p, double *r);
 int dppr_group_stats(dppr_engine *e, int32_t group, dppr_stats_t *out); /* summed over the sources */
 int dppr_group_reset_stats(dppr_engine *e, int32_t group);
+
+/* ---- queries of a state: top-k and point reads (added in ABI 6, backward compatible) ----
+ * The answer a dense dppr_read / dppr_group_read would give, without moving V doubles per source to the
+ * host: a radix select runs on the device over the rows that hold a vertex (the live and the parked
+ * zone), two streaming passes over p for all sources of a group at once (dppr_topk.hpp), and one copy of
+ * the n x k results comes back.
+ *
+ * dppr_topk / dppr_group_topk: for each source the qualifying vertices are the external ids v with
+ * p[v] > min_p, p being exactly what dppr_read / dppr_group_read returns. They are ordered by p
+ * descending, then external id ascending, and the first min(k, #qualifying) are returned with their
+ * count: ids, the stored p (bit for bit, not recomputed) and, if out_r is not NULL, r at those vertices.
+ * Entries of a row past its count hold id -1 and 0.0. Group outputs are source-major: [n][k], counts [n].
+ * Since min_p >= 0, a vertex without an internal id (p exactly 0.0) never qualifies, nor a negative p,
+ * -0.0 or NaN.
+ *
+ * dppr_read_at / dppr_group_read_at: p and r at m caller-given external ids (0.0 for a vertex without an
+ * id), as a dense read would return them. Group outputs are vertex-major, [m][n] like the state; either
+ * output may be NULL.
+ *
+ * Rejected with DPPR_ERR_INVALID before any device work, nothing written: k outside [1, DPPR_TOPK_MAX],
+ * min_p negative or NaN, a bad slot / group, a NULL out_ids, out_p or count pointer, an id outside
+ * [0, V) (read_at). All four hold the id-map lock as dppr_read does (safe beside dppr_slide_concurrent),
+ * run on the solver stream, work on any state (converged or not, or set by dppr_write) and are never
+ * part of the update path. */
+#define DPPR_TOPK_MAX 8192
+int dppr_topk(dppr_engine *e, int32_t slot, int32_t k, double min_p,
+              int32_t *out_ids, double *out_p, double *out_r /* may be NULL */, int32_t *out_count);
+int dppr_group_topk(dppr_engine *e, int32_t group, int32_t k, double min_p,
+                    int32_t *out_ids /* [n][k] */, double *out_p /* [n][k] */, double *out_r /* [n][k] or NULL */,
+                    int32_t *out_counts /* [n] */);
+int dppr_read_at(dppr_engine *e, int32_t slot, const int32_t *ids, int32_t m, double *out_p, double *out_r);
+int dppr_group_read_at(dppr_engine *e, int32_t group, const int32_t *ids, int32_t m,
+                       double *out_p /* [m][n] */, double *out_r /* [m][n] */); /* either output may be NULL */
+
 /* Windows whose sweep groups are all resident at once run a frontier loop of a source group as
  * multi-sweep launches (grid barrier between sweeps, row tables kept in LDS; dppr_multi.hpp). on by
  * default; 0 = one launch per sweep everywhere. The roll-call / time-out rules are those of
