@@ -30,6 +30,7 @@
 
 #include "../../include/dppr.h"
 #include "dppr_cut.hpp"
+#include "dppr_devbuf.hpp"
 #include "dppr_idspace.hpp"
 #include "dppr_kernels.hpp"
 #include "dppr_multi.hpp"
@@ -83,7 +84,7 @@ int dppr_create(dppr_engine **out, int device, int32_t V, int32_t W, int directe
     };
 #define HIP_TRY_C(call)                                                                 \
     do {                                                                                \
-        hipError_t _e = (call);                                                         \
+        const hipError_t _e = static_cast<hipError_t>(call);                            \
         if (_e != hipSuccess) {                                                         \
             fprintf(stderr, "dppr_create: %s at line %d\n", hipGetErrorString(_e), __LINE__); \
             return bail(_e == hipErrorOutOfMemory ? DPPR_ERR_NOMEM : DPPR_ERR_HIP);     \
@@ -133,63 +134,63 @@ int dppr_create(dppr_engine **out, int device, int32_t V, int32_t W, int directe
     HIP_TRY_C(hipEventCreate(&e->ev0));
     HIP_TRY_C(hipEventCreate(&e->ev1));
     for (auto &ev : e->evpool) HIP_TRY_C(hipEventCreate(&ev));
-    HIP_TRY_C(hipHostMalloc((void **)&e->dump_pin, dppr_engine::DUMP_PIN_BYTES, hipHostMallocDefault));
-    HIP_TRY_C(hipHostMalloc((void **)&e->pinned, sizeof(int) * ((GMULTI_MAX + 2) * GS_MAX + 3 * GS_MAX + MAX_CHUNK * GS_MAX + 16), hipHostMallocDefault));
+    HIP_TRY_C(e->dump_pin.alloc(dppr_engine::DUMP_PIN_BYTES));
+    HIP_TRY_C(e->pinned.alloc((GMULTI_MAX + 2) * GS_MAX + 3 * GS_MAX + MAX_CHUNK * GS_MAX + 16));
     const size_t Wn = (size_t)std::max(W, 1), Edn = (size_t)std::max(e->Ed, 1), Ln = (size_t)std::max(4 * c, 1);
-    HIP_TRY_C(hipMalloc((void **)&e->w1, sizeof(int) * Wn));
-    HIP_TRY_C(hipMalloc((void **)&e->w2, sizeof(int) * Wn));
-    HIP_TRY_C(hipMalloc((void **)&e->outdeg, sizeof(int) * (size_t)V));
+    HIP_TRY_C(e->w1.alloc(Wn));
+    HIP_TRY_C(e->w2.alloc(Wn));
+    HIP_TRY_C(e->outdeg.alloc((size_t)V));
     // every memset / copy of the engine goes on ITS stream: the stream is non-blocking, so work on
     // the null stream (plain hipMemset / hipMemcpy) is not ordered with it
     HIP_TRY_C(hipMemsetAsync(e->outdeg, 0, sizeof(int) * (size_t)V, e->stream));
-    HIP_TRY_C(hipMalloc((void **)&e->hub_slot_of, sizeof(int) * (size_t)V));
-    HIP_TRY_C(hipMalloc((void **)&e->d_ext2int, sizeof(int) * (size_t)V));
-    HIP_TRY_C(hipMalloc((void **)&e->d_xfer, sizeof(double) * (size_t)V));
+    HIP_TRY_C(e->hub_slot_of.alloc((size_t)V));
+    HIP_TRY_C(e->d_ext2int.alloc((size_t)V));
+    HIP_TRY_C(e->d_xfer.alloc((size_t)V));
     e->init_ids(V);
-    HIP_TRY_C(hipMalloc((void **)&e->hub_hist, sizeof(int) * 64));
-    HIP_TRY_C(hipMalloc((void **)&e->bar, sizeof(GridBar)));
-    HIP_TRY_C(hipMalloc((void **)&e->keys_a, sizeof(uint64_t) * Edn));
-    HIP_TRY_C(hipMalloc((void **)&e->keys_b, sizeof(uint64_t) * Edn));
-    HIP_TRY_C(hipMalloc((void **)&e->in_sorted, sizeof(uint64_t) * Edn));
-    if (e->directed) HIP_TRY_C(hipMalloc((void **)&e->out_sorted, sizeof(uint64_t) * Edn));
-    HIP_TRY_C(hipMalloc((void **)&e->delpos, sizeof(int) * ((size_t)2 * (size_t)std::max(c, 1) + 16)));
+    HIP_TRY_C(e->hub_hist.alloc(64));
+    HIP_TRY_C(e->bar.alloc(1));
+    HIP_TRY_C(e->keys_a.alloc(Edn));
+    HIP_TRY_C(e->keys_b.alloc(Edn));
+    HIP_TRY_C(e->in_sorted.alloc(Edn));
+    if (e->directed) HIP_TRY_C(e->out_sorted.alloc(Edn));
+    HIP_TRY_C(e->delpos.alloc((size_t)2 * (size_t)std::max(c, 1) + 16));
     {
         const size_t bn = (size_t)std::max(2 * c, 1);
         for (int k = 0; k < 4; ++k) {
-            HIP_TRY_C(hipMalloc((void **)&e->bk[k], sizeof(uint64_t) * bn));
-            HIP_TRY_C(hipMalloc((void **)&e->bks[k], sizeof(uint64_t) * bn));
+            HIP_TRY_C(e->bk[k].alloc(bn));
+            HIP_TRY_C(e->bks[k].alloc(bn));
         }
     }
-    HIP_TRY_C(rocprim::radix_sort_keys(nullptr, e->sort_tmp_bytes, e->keys_a, e->keys_b, Edn, 0u,
+    HIP_TRY_C(rocprim::radix_sort_keys(nullptr, e->sort_tmp_bytes, e->keys_a.get(), e->keys_b.get(), Edn, 0u,
                                        (unsigned)(2 * e->bits), e->stream));
-    HIP_TRY_C(hipMalloc(&e->sort_tmp, std::max<size_t>(e->sort_tmp_bytes, 16)));
+    HIP_TRY_C(e->sort_tmp.alloc(std::max<size_t>(e->sort_tmp_bytes, 16)));
     for (int k = 0; k < 2; ++k) {
-        HIP_TRY_C(hipMalloc((void **)&e->su_k[k], sizeof(uint32_t) * Ln));
-        HIP_TRY_C(hipMalloc((void **)&e->su_v[k], sizeof(uint32_t) * Ln));
+        HIP_TRY_C(e->su_k[k].alloc(Ln));
+        HIP_TRY_C(e->su_v[k].alloc(Ln));
     }
-    HIP_TRY_C(hipMalloc((void **)&e->su_grp, sizeof(int) * (4 * SU_GRP_MAX_BUCKETS + 8)));
+    HIP_TRY_C(e->su_grp.alloc(4 * SU_GRP_MAX_BUCKETS + 8));
     HIP_TRY_C(hipMemsetAsync(e->su_grp, 0, sizeof(int) * (4 * SU_GRP_MAX_BUCKETS + 8), e->stream)); // (the ranking launch leaves histogram and cursors cleared for the next batch)
-    HIP_TRY_C(hipMalloc((void **)&e->su_term, sizeof(double) * Ln * GS_MAX)); // one term array per source lane of a group
-    HIP_TRY_C(hipMalloc((void **)&e->su_ins, Ln));
-    HIP_TRY_C(rocprim::radix_sort_pairs(nullptr, e->su_tmp_bytes, e->su_k[0], e->su_k[1], e->su_v[0], e->su_v[1], Ln,
+    HIP_TRY_C(e->su_term.alloc(Ln * GS_MAX)); // one term array per source lane of a group
+    HIP_TRY_C(e->su_ins.alloc(Ln));
+    HIP_TRY_C(rocprim::radix_sort_pairs(nullptr, e->su_tmp_bytes, e->su_k[0].get(), e->su_k[1].get(), e->su_v[0].get(), e->su_v[1].get(), Ln,
                                         0u, (unsigned)e->bits, e->stream));
-    HIP_TRY_C(hipMalloc(&e->su_tmp, std::max<size_t>(e->su_tmp_bytes, 16)));
+    HIP_TRY_C(e->su_tmp.alloc(std::max<size_t>(e->su_tmp_bytes, 16)));
     e->epochs.resize((size_t)n_epochs);
     for (auto &ep : e->epochs) {
-        HIP_TRY_C(hipMalloc((void **)&ep.row_ptr, sizeof(int) * ((size_t)V + 1)));
-        HIP_TRY_C(hipMalloc((void **)&ep.adj, sizeof(Adj) * Edn));
-        HIP_TRY_C(hipMalloc((void **)&ep.out_row_ptr, sizeof(int) * ((size_t)V + 1)));
-        HIP_TRY_C(hipMalloc((void **)&ep.out_col, sizeof(int) * Edn));
-        HIP_TRY_C(hipMalloc((void **)&ep.b1, sizeof(int) * Ln));
-        HIP_TRY_C(hipMalloc((void **)&ep.b2, sizeof(int) * Ln));
-        HIP_TRY_C(hipMalloc((void **)&ep.deg_after, sizeof(int) * Ln));
-        HIP_TRY_C(hipMalloc((void **)&ep.ins, Ln));
-        HIP_TRY_C(hipMalloc((void **)&ep.sk, sizeof(uint32_t) * Ln));
-        HIP_TRY_C(hipMalloc((void **)&ep.sv, sizeof(uint32_t) * Ln));
-        HIP_TRY_C(hipMalloc((void **)&ep.grp_tile, sizeof(int) * ((size_t)V / WAVE + 3)));
-        HIP_TRY_C(hipMalloc((void **)&ep.ggrp_tile, sizeof(int) * ((size_t)V / WAVE + 3)));
-        HIP_TRY_C(hipMalloc((void **)&ep.hub_v, sizeof(int) * HUB_CAP));
-        HIP_TRY_C(hipMalloc((void **)&ep.hub_degp1, sizeof(int) * HUB_CAP));
+        HIP_TRY_C(ep.row_ptr.alloc((size_t)V + 1));
+        HIP_TRY_C(ep.adj.alloc(Edn));
+        HIP_TRY_C(ep.out_row_ptr.alloc((size_t)V + 1));
+        HIP_TRY_C(ep.out_col.alloc(Edn));
+        HIP_TRY_C(ep.b1.alloc(Ln));
+        HIP_TRY_C(ep.b2.alloc(Ln));
+        HIP_TRY_C(ep.deg_after.alloc(Ln));
+        HIP_TRY_C(ep.ins.alloc(Ln));
+        HIP_TRY_C(ep.sk.alloc(Ln));
+        HIP_TRY_C(ep.sv.alloc(Ln));
+        HIP_TRY_C(ep.grp_tile.alloc((size_t)V / WAVE + 3));
+        HIP_TRY_C(ep.ggrp_tile.alloc((size_t)V / WAVE + 3));
+        HIP_TRY_C(ep.hub_v.alloc(HUB_CAP));
+        HIP_TRY_C(ep.hub_degp1.alloc(HUB_CAP));
     }
     HIP_TRY_C(hipStreamSynchronize(e->stream)); // (the builder's stream is another one: nothing of this set-up may still be in flight)
 #undef HIP_TRY_C
@@ -203,39 +204,6 @@ void dppr_destroy(dppr_engine *e) {
     (void)hipSetDevice(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     if (e->bs) (void)hipStreamSynchronize(e->bs);
-    for (auto &s : e->slots) {
-        (void)hipFree(s.p); (void)hipFree(s.r); (void)hipFree(s.x); (void)hipFree(s.x2);
-        (void)hipFree(s.ft[0]); (void)hipFree(s.ft[1]); (void)hipFree(s.neg); (void)hipFree(s.status); (void)hipFree(s.act[0]); (void)hipFree(s.act[1]);
-        (void)hipFree(s.cnt); (void)hipFree(s.dstats); (void)hipFree(s.big);
-    }
-    for (auto &g : e->groups) {
-        (void)hipFree(g.p); (void)hipFree(g.r); (void)hipFree(g.x); (void)hipFree(g.x2);
-        (void)hipFree(g.act[0]); (void)hipFree(g.act[1]);
-        (void)hipFree(g.cnt); (void)hipFree(g.mlog); (void)hipFree(g.dstats); (void)hipFree(g.gq);
-    }
-    for (auto &ep : e->epochs) {
-        (void)hipFree(ep.row_ptr); (void)hipFree(ep.adj); (void)hipFree(ep.out_row_ptr); (void)hipFree(ep.out_col); (void)hipFree(ep.b1); (void)hipFree(ep.b2);
-        (void)hipFree(ep.deg_after); (void)hipFree(ep.ins); (void)hipFree(ep.sk); (void)hipFree(ep.sv); (void)hipFree(ep.hub_v); (void)hipFree(ep.hub_degp1); (void)hipFree(ep.grp_tile); (void)hipFree(ep.ggrp_tile); (void)hipFree(ep.gtab);
-        (void)hipFree(ep.acut); (void)hipFree(ep.chunks); (void)hipFree(ep.hl); (void)hipFree(ep.dl); (void)hipFree(ep.vb); (void)hipFree(ep.tb); (void)hipFree(ep.tdelta);
-        (void)hipFree(ep.res_pk); (void)hipFree(ep.su_rng);
-    }
-    (void)hipFree(e->bin_vblk_a); (void)hipFree(e->bin_small); (void)hipFree(e->bin_scan); (void)hipFree(e->bin_vals); (void)hipFree(e->bin_tmp);
-    (void)hipFree(e->bin_wb); (void)hipFree(e->bin_wa); (void)hipFree(e->bin_first);
-    (void)hipFree(e->w1); (void)hipFree(e->w2); (void)hipFree(e->outdeg);
-    (void)hipFree(e->bar);
-    (void)hipFree(e->res_arena);
-    (void)hipFree(e->hub_slot_of); (void)hipFree(e->hub_hist); (void)hipFree(e->d_ext2int); (void)hipFree(e->d_xfer);
-    (void)hipFree(e->d_int2ext); (void)hipFree(e->tk_ws); (void)hipFree(e->tk_out_key); (void)hipFree(e->tk_out_row);
-    (void)hipFree(e->tk_cand); (void)hipFree(e->tk_res); (void)hipFree(e->ra_buf);
-    if (e->tk_pin) (void)hipHostFree(e->tk_pin);
-    (void)hipFree(e->mv_idx); (void)hipFree(e->mv_tmp);
-    (void)hipFree(e->keys_a); (void)hipFree(e->keys_b); (void)hipFree(e->sort_tmp);
-    (void)hipFree(e->in_sorted); (void)hipFree(e->out_sorted); (void)hipFree(e->delpos);
-    for (int k = 0; k < 4; ++k) { (void)hipFree(e->bk[k]); (void)hipFree(e->bks[k]); }
-    for (int k = 0; k < 2; ++k) { (void)hipFree(e->su_k[k]); (void)hipFree(e->su_v[k]); }
-    (void)hipFree(e->su_term); (void)hipFree(e->su_ins); (void)hipFree(e->su_tmp); (void)hipFree(e->su_grp);
-    if (e->pinned) (void)hipHostFree(e->pinned);
-    if (e->dump_pin) (void)hipHostFree(e->dump_pin);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
     for (auto &ev : e->evpool)
@@ -243,7 +211,7 @@ void dppr_destroy(dppr_engine *e) {
     if (e->stream) (void)hipStreamDestroy(e->stream);
     if (e->bs) (void)hipStreamDestroy(e->bs);
     dppr::g_live_engines.fetch_sub(1, std::memory_order_relaxed);
-    delete e;
+    delete e; // every buffer goes with its owner (dppr_devbuf.hpp), after both streams have drained
 }
 
 int dppr_set_schedule(dppr_engine *e, int schedule) {
@@ -654,26 +622,26 @@ int dppr_add_source(dppr_engine *e, int32_t source, int32_t *out_slot) {
     source = s.source;
     if (int rc = flush_moves(e)) return rc;
     const size_t V = (size_t)e->V;
-    HIP_TRY(hipMalloc((void **)&s.p, sizeof(double) * V));
-    HIP_TRY(hipMalloc((void **)&s.r, sizeof(double) * V));
-    HIP_TRY(hipMalloc((void **)&s.x, sizeof(double) * V));
-    HIP_TRY(hipMalloc((void **)&s.x2, sizeof(double) * V));
+    HIP_TRY(s.p.alloc(V));
+    HIP_TRY(s.r.alloc(V));
+    HIP_TRY(s.x.alloc(V));
+    HIP_TRY(s.x2.alloc(V));
     HIP_TRY(hipMemsetAsync(s.x, 0, sizeof(double) * V, e->stream));
     HIP_TRY(hipMemsetAsync(s.x2, 0, sizeof(double) * V, e->stream));
     s.act_bytes = (V / 32 + 64) * sizeof(uint32_t);
-    HIP_TRY(hipMalloc((void **)&s.act[0], s.act_bytes));
-    HIP_TRY(hipMalloc((void **)&s.act[1], s.act_bytes));
+    HIP_TRY(s.act[0].alloc(s.act_bytes / sizeof(uint32_t)));
+    HIP_TRY(s.act[1].alloc(s.act_bytes / sizeof(uint32_t)));
     HIP_TRY(hipMemsetAsync(s.act[0], 0, s.act_bytes, e->stream));
     HIP_TRY(hipMemsetAsync(s.act[1], 0, s.act_bytes, e->stream));
-    HIP_TRY(hipMalloc((void **)&s.ft[0], sizeof(int) * V));
-    HIP_TRY(hipMalloc((void **)&s.ft[1], sizeof(int) * V));
-    HIP_TRY(hipMalloc((void **)&s.neg, sizeof(int) * (size_t)std::max(4 * e->c, 1)));
-    HIP_TRY(hipMalloc((void **)&s.cnt, sizeof(int) * (CNT_HDR + 2 * MAX_CHUNK)));
+    HIP_TRY(s.ft[0].alloc(V));
+    HIP_TRY(s.ft[1].alloc(V));
+    HIP_TRY(s.neg.alloc((size_t)std::max(4 * e->c, 1)));
+    HIP_TRY(s.cnt.alloc(CNT_HDR + 2 * MAX_CHUNK));
     s.log = s.cnt + CNT_HDR; // the per-chunk log sits right behind the counters: one read-back fetches both
     // a row is deferred only if it has >= big_row edges, so at most Ed / big_row of them exist
     // (pieces of <= 1024 edges of rows of >= big_row edges: a row of d edges has ceil(d / 1024) <= d / min(big_row, 512) of them)
-    HIP_TRY(hipMalloc((void **)&s.big, sizeof(BigItem) * ((size_t)e->Ed / (size_t)std::min(std::max(e->big_row, 1), 512) + 64)));
-    HIP_TRY(hipMalloc((void **)&s.dstats, 2 * sizeof(IterStats)));
+    HIP_TRY(s.big.alloc((size_t)e->Ed / (size_t)std::min(std::max(e->big_row, 1), 512) + 64));
+    HIP_TRY(s.dstats.alloc(2));
     HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(int) * (CNT_HDR + 2 * MAX_CHUNK), e->stream));
     HIP_TRY(hipMemsetAsync(s.dstats, 0, 2 * sizeof(IterStats), e->stream));
     hipLaunchKernelGGL(k_init, dim3(grid_for(e->V)), dim3(BLOCK), 0, e->stream, s.p, s.r, e->V, source);
@@ -705,7 +673,7 @@ int dppr_time_batch_grouping(dppr_engine *e, int32_t epoch, int32_t reps, float 
     const int L = ep.L;
     if (L <= 0) return DPPR_OK;
     HIP_TRY(hipEventRecord(e->ev0, e->stream));
-    int *deg_scratch = reinterpret_cast<int *>(e->su_term);
+    int *deg_scratch = reinterpret_cast<int *>(e->su_term.get());
     for (int k = 0; k < reps; ++k) // what group_records_by_tail enqueues inside the timed region, the degrees into scratch
         if (int rc = enqueue_grouping(e, ep, deg_scratch, nullptr, 0, nullptr, 0)) return rc;
     HIP_TRY(hipGetLastError());
@@ -733,7 +701,7 @@ int dppr_debug_grouping(dppr_engine *e, int32_t epoch, int32_t path, uint32_t *t
     HIP_TRY(hipSetDevice(e->device));
     const uint32_t *tk = ep.sk, *tv = ep.sv;
     if (p != GROUPING_AT_SLIDE) { // as dppr_time_batch_grouping: the degrees into scratch, no solver state touched
-        if (int rc = enqueue_grouping(e, ep, reinterpret_cast<int *>(e->su_term), nullptr, 0, nullptr, 0, p)) return rc;
+        if (int rc = enqueue_grouping(e, ep, reinterpret_cast<int *>(e->su_term.get()), nullptr, 0, nullptr, 0, p)) return rc;
         tk = e->su_k[1];
         tv = e->su_v[1];
     }
@@ -922,7 +890,7 @@ int dppr_update(dppr_engine *e, int32_t slot, int32_t epoch, double eps, float *
     bool inline_su = ahead && e->res_update && ((ep.su_inline && ep.grouped) || raw_ok);
     if (inline_su) {
         hipLaunchKernelGGL(k_su_keys, dim3(1), dim3(BLOCK), 0, e->stream, ep.b1, 0, e->su_k[0], e->su_v[0],
-                           reinterpret_cast<unsigned long long *>(e->bar), (int)(sizeof(GridBar) / sizeof(unsigned long long)), s.cnt, 5);
+                           reinterpret_cast<unsigned long long *>(e->bar.get()), (int)(sizeof(GridBar) / sizeof(unsigned long long)), s.cnt, 5);
         HIP_TRY(hipGetLastError());
     } else {
         rc = stream_update(e, s, ep, eps, seeded, ahead);
@@ -1172,7 +1140,7 @@ int dppr_read_graph(dppr_engine *e, int32_t epoch, int32_t *row_ptr, int32_t *co
     std::vector<int> irow((size_t)e->V + 1), icol((size_t)std::max(ep.Ed, 1)), ideg((size_t)e->V);
     HIP_TRY(hipMemcpyAsync(irow.data(), ep.row_ptr, sizeof(int) * ((size_t)e->V + 1), hipMemcpyDeviceToHost, e->stream));
     if (ep.Ed > 0) {
-        int *tmp = reinterpret_cast<int *>(e->keys_a); // scratch
+        int *tmp = reinterpret_cast<int *>(e->keys_a.get()); // scratch
         hipLaunchKernelGGL(k_split_adj, dim3(grid_for(ep.Ed)), dim3(BLOCK), 0, e->stream, ep.adj, ep.Ed, tmp);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(icol.data(), tmp, sizeof(int) * (size_t)ep.Ed, hipMemcpyDeviceToHost, e->stream));
@@ -1234,51 +1202,35 @@ int dppr_add_source_group(dppr_engine *e, const int32_t *sources, int32_t n, int
     g.spl = row_spl(g.gw);
     for (int s = 0; s < GS_MAX; ++s) g.src.s[s] = -1;
     for (int s = 0; s < n; ++s) g.src_ext[s] = sources[s];
-    const size_t V = (size_t)e->V, row = sizeof(double) * (size_t)g.gw;
+    const size_t V = (size_t)e->V;
     g.act_bytes = (V / 32 + 1024 / 32 + 4) * sizeof(uint32_t);
-    auto release = [&]() { // (an allocation failed: nothing of this group stays behind)
-        (void)hipFree(g.p); (void)hipFree(g.r); (void)hipFree(g.x); (void)hipFree(g.x2); (void)hipFree(g.act[0]); (void)hipFree(g.act[1]);
-        (void)hipFree(g.cnt); (void)hipFree(g.mlog); (void)hipFree(g.dstats); (void)hipFree(g.gq);
-    };
-#define GRP_TRY(call)                                                                                   \
-    do {                                                                                                \
-        hipError_t _e = (call);                                                                         \
-        if (_e != hipSuccess) {                                                                         \
-            release();                                                                                  \
-            e->err = std::string("add_source_group: ") + hipGetErrorString(_e);                         \
-            return _e == hipErrorOutOfMemory ? DPPR_ERR_NOMEM : DPPR_ERR_HIP;                           \
-        }                                                                                               \
-    } while (0)
-    GRP_TRY(hipMalloc((void **)&g.p, row * V));
-    GRP_TRY(hipMalloc((void **)&g.r, row * V));
-    const size_t xrow = sizeof(double) * (size_t)x_stride(g.gw); // snapshot rows never straddle a 128-byte line (dppr_multi.hpp)
-    GRP_TRY(hipMalloc((void **)&g.x, xrow * V));
-    GRP_TRY(hipMalloc((void **)&g.x2, xrow * V));
-    GRP_TRY(hipMalloc((void **)&g.act[0], g.act_bytes));
-    GRP_TRY(hipMalloc((void **)&g.act[1], g.act_bytes));
-    GRP_TRY(hipMalloc((void **)&g.cnt, sizeof(int) * (5 * GS_MAX + MAX_CHUNK * GS_MAX))); // rows 3, 4: scratch of multi-sweep launches
-    GRP_TRY(hipMalloc((void **)&g.mlog, sizeof(int) * (size_t)(GMULTI_MAX + 2) * GS_MAX));
-    GRP_TRY(hipMalloc((void **)&g.dstats, 2 * sizeof(IterStats)));
-    GRP_TRY(hipMalloc((void **)&g.gq, sizeof(int) * 3 * GQ_PAD));
-    GRP_TRY(hipMemsetAsync(g.gq, 0, sizeof(int) * 3 * GQ_PAD, e->stream));
-    GRP_TRY(hipMemsetAsync(g.act[0], 0, g.act_bytes, e->stream));
-    GRP_TRY(hipMemsetAsync(g.act[1], 0, g.act_bytes, e->stream));
-    GRP_TRY(hipMemsetAsync(g.cnt, 0, sizeof(int) * (5 * GS_MAX + MAX_CHUNK * GS_MAX), e->stream));
-    GRP_TRY(hipMemsetAsync(g.dstats, 0, 2 * sizeof(IterStats), e->stream));
+    const size_t xw = (size_t)x_stride(g.gw); // snapshot rows never straddle a 128-byte line (dppr_multi.hpp)
+    // (an allocation that fails: `g` goes out of scope and nothing of this group stays behind)
+    HIP_TRY_MSG("add_source_group: ", g.p.alloc((size_t)g.gw * V));
+    HIP_TRY_MSG("add_source_group: ", g.r.alloc((size_t)g.gw * V));
+    HIP_TRY_MSG("add_source_group: ", g.x.alloc(xw * V));
+    HIP_TRY_MSG("add_source_group: ", g.x2.alloc(xw * V));
+    HIP_TRY_MSG("add_source_group: ", g.act[0].alloc(g.act_bytes / sizeof(uint32_t)));
+    HIP_TRY_MSG("add_source_group: ", g.act[1].alloc(g.act_bytes / sizeof(uint32_t)));
+    HIP_TRY_MSG("add_source_group: ", g.cnt.alloc(5 * GS_MAX + MAX_CHUNK * GS_MAX)); // rows 3, 4: scratch of multi-sweep launches
+    HIP_TRY_MSG("add_source_group: ", g.mlog.alloc((size_t)(GMULTI_MAX + 2) * GS_MAX));
+    HIP_TRY_MSG("add_source_group: ", g.dstats.alloc(2));
+    HIP_TRY_MSG("add_source_group: ", g.gq.alloc(3 * GQ_PAD));
+    HIP_TRY_MSG("add_source_group: ", hipMemsetAsync(g.gq, 0, sizeof(int) * 3 * GQ_PAD, e->stream));
+    HIP_TRY_MSG("add_source_group: ", hipMemsetAsync(g.act[0], 0, g.act_bytes, e->stream));
+    HIP_TRY_MSG("add_source_group: ", hipMemsetAsync(g.act[1], 0, g.act_bytes, e->stream));
+    HIP_TRY_MSG("add_source_group: ", hipMemsetAsync(g.cnt, 0, sizeof(int) * (5 * GS_MAX + MAX_CHUNK * GS_MAX), e->stream));
+    HIP_TRY_MSG("add_source_group: ", hipMemsetAsync(g.dstats, 0, 2 * sizeof(IterStats), e->stream));
     // the memory is there: now the ids (a source outside the window receives one; a parked one is revived)
     for (int s = 0; s < n; ++s) (void)to_int(e, sources[s]);
     for (int s = 0; s < n; ++s) g.src.s[s] = e->ext2int[(size_t)sources[s]]; // (after ALL revivals: one may move another)
-    if (int rc = flush_moves(e)) {
-        release();
-        return rc;
-    }
+    if (int rc = flush_moves(e)) return rc;
     hipLaunchKernelGGL(k_ginit, dim3(grid_for((int64_t)e->V * g.gw)), dim3(BLOCK), 0, e->stream, g.p, g.r, e->V, g.gw, g.src);
-    GRP_TRY(hipGetLastError());
-    GRP_TRY(hipStreamSynchronize(e->stream));
-#undef GRP_TRY
-    e->groups.push_back(g);
-    e->any_groups = true; // (recut_stale_groups below adds the second group table to resident epochs)
+    HIP_TRY_MSG("add_source_group: ", hipGetLastError());
+    HIP_TRY_MSG("add_source_group: ", hipStreamSynchronize(e->stream));
     if (g.spl == 2) e->wide_groups = true;
+    e->groups.push_back(std::move(g));
+    e->any_groups = true; // (recut_stale_groups below adds the second group table to resident epochs)
     if (int rc = recut_stale_groups(e)) return rc;
     if (out_group) *out_group = (int)e->groups.size() - 1;
     return DPPR_OK;
@@ -1463,10 +1415,10 @@ int dppr_bench_atomics(int device, int64_t table_elems, int64_t n, int scope, in
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return DPPR_ERR_NO_DEVICE;
     if (hipSetDevice(device) != hipSuccess) return DPPR_ERR_HIP;
-    double *table = nullptr, *sink = nullptr;
+    DevBuf<double> table, sink;
     hipEvent_t a, b;
-    if (hipMalloc((void **)&table, sizeof(double) * (size_t)table_elems) != hipSuccess) return DPPR_ERR_NOMEM;
-    (void)hipMalloc((void **)&sink, sizeof(double));
+    if (table.alloc((size_t)table_elems) != 0) return DPPR_ERR_NOMEM;
+    (void)sink.alloc(1);
     (void)hipMemset(table, 0, sizeof(double) * (size_t)table_elems);
     (void)hipEventCreate(&a);
     (void)hipEventCreate(&b);
@@ -1493,8 +1445,6 @@ int dppr_bench_atomics(int device, int64_t table_elems, int64_t n, int scope, in
     *out_ms = ms / reps;
     (void)hipEventDestroy(a);
     (void)hipEventDestroy(b);
-    (void)hipFree(table);
-    (void)hipFree(sink);
     return err == hipSuccess ? DPPR_OK : DPPR_ERR_HIP;
 }
 
@@ -1503,10 +1453,10 @@ int dppr_bench_line_fills(int device, int64_t table_bytes, int64_t lines, int re
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return DPPR_ERR_NO_DEVICE;
     if (hipSetDevice(device) != hipSuccess) return DPPR_ERR_HIP;
-    double2 *table = nullptr;
-    double *sink = nullptr;
-    if (hipMalloc((void **)&table, (size_t)table_bytes) != hipSuccess) return DPPR_ERR_NOMEM;
-    (void)hipMalloc((void **)&sink, sizeof(double));
+    DevBuf<double2> table;
+    DevBuf<double> sink;
+    if (table.alloc((size_t)table_bytes / sizeof(double2)) != 0) return DPPR_ERR_NOMEM; // (a power of two >= 128)
+    (void)sink.alloc(1);
     (void)hipMemset(table, 0, (size_t)table_bytes);
     hipEvent_t a, b;
     (void)hipEventCreate(&a);
@@ -1527,8 +1477,6 @@ int dppr_bench_line_fills(int device, int64_t table_bytes, int64_t lines, int re
     *out_ms = ms / reps * (float)((double)lines / ((double)grid * 128.0 * per));
     (void)hipEventDestroy(a);
     (void)hipEventDestroy(b);
-    (void)hipFree(table);
-    (void)hipFree(sink);
     return err == hipSuccess ? DPPR_OK : DPPR_ERR_HIP;
 }
 
@@ -1537,18 +1485,15 @@ int dppr_bench_stream_copy(int device, int64_t bytes, int reps, float *out_ms) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return DPPR_ERR_NO_DEVICE;
     if (hipSetDevice(device) != hipSuccess) return DPPR_ERR_HIP;
-    double2 *src = nullptr, *dst = nullptr;
-    if (hipMalloc((void **)&src, (size_t)bytes) != hipSuccess) return DPPR_ERR_NOMEM;
-    if (hipMalloc((void **)&dst, (size_t)bytes) != hipSuccess) {
-        (void)hipFree(src);
-        return DPPR_ERR_NOMEM;
-    }
+    DevBuf<unsigned char> src, dst; // (`bytes` need not be a multiple of 16: the kernel copies bytes / 16 double2s)
+    if (src.alloc((size_t)bytes) != 0 || dst.alloc((size_t)bytes) != 0) return DPPR_ERR_NOMEM;
     (void)hipMemset(src, 0, (size_t)bytes);
     (void)hipMemset(dst, 0, (size_t)bytes);
     hipEvent_t a, b;
     (void)hipEventCreate(&a);
     (void)hipEventCreate(&b);
-    auto launch = [&]() { hipLaunchKernelGGL(k_bench_copy, dim3(4096), dim3(1024), 0, 0, src, dst, bytes / 16); };
+    auto launch = [&]() { hipLaunchKernelGGL(k_bench_copy, dim3(4096), dim3(1024), 0, 0, reinterpret_cast<const double2 *>(src.get()),
+                                            reinterpret_cast<double2 *>(dst.get()), bytes / 16); };
     launch();
     (void)hipEventRecord(a, 0);
     for (int i = 0; i < reps; ++i) launch();
@@ -1559,8 +1504,6 @@ int dppr_bench_stream_copy(int device, int64_t bytes, int reps, float *out_ms) {
     *out_ms = ms / reps;
     (void)hipEventDestroy(a);
     (void)hipEventDestroy(b);
-    (void)hipFree(src);
-    (void)hipFree(dst);
     return err == hipSuccess ? DPPR_OK : DPPR_ERR_HIP;
 }
 
@@ -1586,6 +1529,12 @@ int dppr_debug_bin_tables(dppr_engine *e, int32_t epoch, int32_t *n_a, int32_t *
     if (tb) HIP_TRY(hipMemcpy(tb, ep.tb, sizeof(int) * (n_rb + 1), hipMemcpyDeviceToHost));
     if (dl) HIP_TRY(hipMemcpy(dl, ep.dl, sizeof(uint16_t) * (size_t)ep.Ed, hipMemcpyDeviceToHost));
     if (vb) HIP_TRY(hipMemcpy(vb, ep.vb, sizeof(int) * (n_blk + 1), hipMemcpyDeviceToHost));
+    return DPPR_OK;
+}
+
+int dppr_debug_live_bytes(int64_t *device_bytes, int64_t *pinned_bytes) {
+    if (device_bytes) *device_bytes = dppr::g_device_bytes.load(std::memory_order_relaxed);
+    if (pinned_bytes) *pinned_bytes = dppr::g_pinned_bytes.load(std::memory_order_relaxed);
     return DPPR_OK;
 }
 

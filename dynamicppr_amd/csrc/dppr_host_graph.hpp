@@ -47,22 +47,14 @@ int flush_moves(dppr_engine *e) {
     const int n = (int)e->mv_src.size(), nz = (int)e->mv_zero.size();
     if (e->slots.empty() && e->groups.empty()) return DPPR_OK;
     const size_t need_idx = (size_t)2 * n + nz + 1;
-    if (need_idx > e->mv_idx_cap) {
+    if (e->mv_idx.capacity() < need_idx) {
         HIP_TRY(hipStreamSynchronize(e->bs));
-        (void)hipFree(e->mv_idx);
-        e->mv_idx = nullptr;
-        e->mv_idx_cap = 0;
-        HIP_TRY(hipMalloc((void **)&e->mv_idx, sizeof(int) * (need_idx * 2 + 1024)));
-        e->mv_idx_cap = need_idx * 2 + 1024;
+        HIP_TRY(e->mv_idx.regrow(need_idx * 2 + 1024));
     }
     const size_t need_tmp = (size_t)std::max(n, 1) * GS_MAX;
-    if (need_tmp > e->mv_tmp_cap) {
+    if (e->mv_tmp.capacity() < need_tmp) {
         HIP_TRY(hipStreamSynchronize(e->bs));
-        (void)hipFree(e->mv_tmp);
-        e->mv_tmp = nullptr;
-        e->mv_tmp_cap = 0;
-        HIP_TRY(hipMalloc((void **)&e->mv_tmp, sizeof(double) * (need_tmp * 2 + 4096)));
-        e->mv_tmp_cap = need_tmp * 2 + 4096;
+        HIP_TRY(e->mv_tmp.regrow(need_tmp * 2 + 4096));
     }
     int *d_src = e->mv_idx, *d_dst = e->mv_idx + n, *d_zero = e->mv_idx + 2 * n;
     if (n > 0) {
@@ -125,65 +117,49 @@ int device_numbering_order(dppr_engine *e, const std::vector<uint8_t> &live, int
     order.clear();
     if (n_live <= 0) return DPPR_OK;
     const size_t n = (size_t)n_old;
-    uint8_t *d_live = nullptr;
-    int *d_i2e = nullptr, *d_vals = nullptr, *d_vals2 = nullptr, *d_deg2 = nullptr;
-    uint64_t *d_keys = nullptr, *d_keys2 = nullptr;
-    void *d_tmp = nullptr;
-    auto cleanup = [&]() {
-        (void)hipFree(d_live); (void)hipFree(d_i2e); (void)hipFree(d_vals); (void)hipFree(d_vals2); (void)hipFree(d_deg2);
-        (void)hipFree(d_keys); (void)hipFree(d_keys2); (void)hipFree(d_tmp);
-    };
-#define NO_TRY(call)                                                          \
-    do {                                                                      \
-        hipError_t _e = (call);                                               \
-        if (_e != hipSuccess) {                                               \
-            cleanup();                                                        \
-            e->err = std::string("renumbering order: ") + hipGetErrorString(_e); \
-            return _e == hipErrorOutOfMemory ? DPPR_ERR_NOMEM : DPPR_ERR_HIP; \
-        }                                                                     \
-    } while (0)
-    NO_TRY(hipMalloc((void **)&d_live, n));
-    NO_TRY(hipMalloc((void **)&d_i2e, sizeof(int) * n));
-    NO_TRY(hipMalloc((void **)&d_vals, sizeof(int) * n));
-    NO_TRY(hipMalloc((void **)&d_vals2, sizeof(int) * n));
-    NO_TRY(hipMalloc((void **)&d_keys, sizeof(uint64_t) * n));
-    NO_TRY(hipMalloc((void **)&d_keys2, sizeof(uint64_t) * n));
-    NO_TRY(hipMemcpyAsync(d_live, live.data(), n, hipMemcpyHostToDevice, e->bs));
-    NO_TRY(hipMemcpyAsync(d_i2e, e->int2ext.data(), sizeof(int) * n, hipMemcpyHostToDevice, e->bs));
+    DevBuf<uint8_t> d_live;
+    DevBuf<int> d_i2e, d_vals, d_vals2, d_deg2;
+    DevBuf<uint64_t> d_keys, d_keys2;
+    DevBuf<unsigned char> d_tmp;
+    HIP_TRY_MSG("renumbering order: ", d_live.alloc(n));
+    HIP_TRY_MSG("renumbering order: ", d_i2e.alloc(n));
+    HIP_TRY_MSG("renumbering order: ", d_vals.alloc(n));
+    HIP_TRY_MSG("renumbering order: ", d_vals2.alloc(n));
+    HIP_TRY_MSG("renumbering order: ", d_keys.alloc(n));
+    HIP_TRY_MSG("renumbering order: ", d_keys2.alloc(n));
+    HIP_TRY_MSG("renumbering order: ", hipMemcpyAsync(d_live, live.data(), n, hipMemcpyHostToDevice, e->bs));
+    HIP_TRY_MSG("renumbering order: ", hipMemcpyAsync(d_i2e, e->int2ext.data(), sizeof(int) * n, hipMemcpyHostToDevice, e->bs));
     HotThresholds ht{};
     int *d_deg = e->hub_slot_of; // (scratch of the CSR build, V ints)
     if ((size_t)n_live > HOT_WINDOW_MIN) {
-        NO_TRY(hipMalloc((void **)&d_deg2, sizeof(int) * n));
-        NO_TRY(hipMemsetAsync(d_deg, 0, sizeof(int) * n, e->bs));
+        HIP_TRY_MSG("renumbering order: ", d_deg2.alloc(n));
+        HIP_TRY_MSG("renumbering order: ", hipMemsetAsync(d_deg, 0, sizeof(int) * n, e->bs));
         hipLaunchKernelGGL(k_in_degree, dim3(grid_for(e->W)), dim3(BLOCK), 0, e->bs, e->w1, e->w2, e->W, e->directed, d_deg);
         hipLaunchKernelGGL(k_live_degree, dim3(grid_for(n_old)), dim3(BLOCK), 0, e->bs, d_live, d_deg, n_old, d_vals);
         size_t tb = 0;
-        NO_TRY(rocprim::radix_sort_keys_desc(nullptr, tb, d_vals, d_deg2, n, 0u, 32u, e->bs));
-        NO_TRY(hipMalloc(&d_tmp, tb));
-        NO_TRY(rocprim::radix_sort_keys_desc(d_tmp, tb, d_vals, d_deg2, n, 0u, 32u, e->bs));
+        HIP_TRY_MSG("renumbering order: ", rocprim::radix_sort_keys_desc(nullptr, tb, d_vals.get(), d_deg2.get(), n, 0u, 32u, e->bs));
+        HIP_TRY_MSG("renumbering order: ", d_tmp.alloc(tb));
+        HIP_TRY_MSG("renumbering order: ", rocprim::radix_sort_keys_desc(d_tmp.get(), tb, d_vals.get(), d_deg2.get(), n, 0u, 32u, e->bs));
         // in-degree of rank k among the live vertices (the non-live ones sorted last as -1)
         for (size_t k = HOT_SET; k >= (e->hot_blocks ? HOT_MIN : HOT_SET); k >>= 1) {
             if (k >= (size_t)n_live) continue;
-            NO_TRY(hipMemcpyAsync(&ht.thr[ht.n], d_deg2 + k, sizeof(int), hipMemcpyDeviceToHost, e->bs));
+            HIP_TRY_MSG("renumbering order: ", hipMemcpyAsync(&ht.thr[ht.n], d_deg2 + k, sizeof(int), hipMemcpyDeviceToHost, e->bs));
             ht.n++;
         }
-        NO_TRY(hipStreamSynchronize(e->bs));
-        (void)hipFree(d_tmp);
-        d_tmp = nullptr;
+        HIP_TRY_MSG("renumbering order: ", hipStreamSynchronize(e->bs));
+        d_tmp.reset(); // (early: the second sort's scratch is not held on top of it)
     }
     hipLaunchKernelGGL(k_number_keys, dim3(grid_for(n_old)), dim3(BLOCK), 0, e->bs, d_live, d_i2e, d_deg, ht, n_old, d_keys, d_vals);
     {
         size_t tb = 0;
-        NO_TRY(rocprim::radix_sort_pairs(nullptr, tb, d_keys, d_keys2, d_vals, d_vals2, n, 0u, 64u, e->bs));
-        NO_TRY(hipMalloc(&d_tmp, tb));
-        NO_TRY(rocprim::radix_sort_pairs(d_tmp, tb, d_keys, d_keys2, d_vals, d_vals2, n, 0u, 64u, e->bs));
+        HIP_TRY_MSG("renumbering order: ", rocprim::radix_sort_pairs(nullptr, tb, d_keys.get(), d_keys2.get(), d_vals.get(), d_vals2.get(), n, 0u, 64u, e->bs));
+        HIP_TRY_MSG("renumbering order: ", d_tmp.alloc(tb));
+        HIP_TRY_MSG("renumbering order: ", rocprim::radix_sort_pairs(d_tmp.get(), tb, d_keys.get(), d_keys2.get(), d_vals.get(), d_vals2.get(), n, 0u, 64u, e->bs));
     }
     order.resize((size_t)n_live);
-    NO_TRY(hipMemcpyAsync(order.data(), d_vals2, sizeof(int) * (size_t)n_live, hipMemcpyDeviceToHost, e->bs));
-    NO_TRY(hipStreamSynchronize(e->bs));
-    NO_TRY(hipGetLastError());
-#undef NO_TRY
-    cleanup();
+    HIP_TRY_MSG("renumbering order: ", hipMemcpyAsync(order.data(), d_vals2, sizeof(int) * (size_t)n_live, hipMemcpyDeviceToHost, e->bs));
+    HIP_TRY_MSG("renumbering order: ", hipStreamSynchronize(e->bs));
+    HIP_TRY_MSG("renumbering order: ", hipGetLastError());
     return DPPR_OK;
 }
 
@@ -215,14 +191,14 @@ int compact_ids(dppr_engine *e, bool *did) {
         t_mark = now;
     };
     // which ids have an edge in the window
-    uint8_t *d_live = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_live, (size_t)std::max(n_old, 1)));
+    DevBuf<uint8_t> d_live;
+    HIP_TRY(d_live.alloc((size_t)std::max(n_old, 1)));
     HIP_TRY(hipMemsetAsync(d_live, 0, (size_t)std::max(n_old, 1), e->bs));
     hipLaunchKernelGGL(k_mark_live, dim3(grid_for(e->W)), dim3(BLOCK), 0, e->bs, e->w1, e->w2, e->W, d_live);
     std::vector<uint8_t> live((size_t)std::max(n_old, 1));
     hipError_t herr = hipMemcpyAsync(live.data(), d_live, (size_t)n_old, hipMemcpyDeviceToHost, e->bs);
     if (herr == hipSuccess) herr = hipStreamSynchronize(e->bs);
-    (void)hipFree(d_live);
+    d_live.reset();
     HIP_TRY(herr);
     if (e->batch_staged) { // the staged records are in internal ids already: their vertices stay where they are
         for (int v : e->st_b1) live[(size_t)v] = 1;
@@ -246,25 +222,18 @@ int compact_ids(dppr_engine *e, bool *did) {
     // same work). The order is computed on the device (hash + in-degree blocks as keys, one radix sort).
     // Renumbering is an optimisation: whatever can fail for lack of memory is obtained BEFORE anything is changed, and
     // then the slide simply goes on in the old numbering (and looks again after some more growth).
-    int *d_perm = nullptr;
-    double *tmp = nullptr;
+    DevBuf<int> d_perm;
+    DevBuf<double> tmp;
     int maxw = 1;
     for (const auto &g : e->groups) maxw = std::max(maxw, g.gw);
-    auto cleanup = [&]() {
-        (void)hipFree(d_perm);
-        (void)hipFree(tmp);
-    };
-    if (hipMalloc((void **)&d_perm, sizeof(int) * (size_t)V) != hipSuccess ||
-        hipMalloc((void **)&tmp, sizeof(double) * (size_t)V * (size_t)maxw) != hipSuccess) {
+    if (d_perm.alloc((size_t)V) != 0 || tmp.alloc((size_t)V * (size_t)maxw) != 0) {
         (void)hipGetLastError();
-        cleanup();
         e->renumber_next = renumber_threshold(n_old, 12);
         return DPPR_OK;
     }
     mark("scratch allocation");
     std::vector<int32_t> perm, order;
     if (int rc = device_numbering_order(e, live, n_old, n_live, order)) {
-        cleanup();
         if (rc != DPPR_ERR_NOMEM) return rc;
         e->renumber_next = renumber_threshold(n_old, 12);
         return DPPR_OK;
@@ -276,9 +245,8 @@ int compact_ids(dppr_engine *e, bool *did) {
     // part new -- the engine refuses all further work (`broken`).
 #define RN_TRY(call)                                                     \
     do {                                                                 \
-        hipError_t _e = (call);                                          \
+        const hipError_t _e = (call);                                    \
         if (_e != hipSuccess) {                                          \
-            cleanup();                                                   \
             e->broken = true;                                            \
             for (auto &ep : e->epochs) ep.id = -1;                       \
             e->err = std::string("renumbering failed half way (") + hipGetErrorString(_e) + "): the engine is unusable, destroy it"; \
@@ -289,12 +257,12 @@ int compact_ids(dppr_engine *e, bool *did) {
     hipLaunchKernelGGL(k_remap_ids, dim3(grid_for(e->W)), dim3(BLOCK), 0, e->bs, e->w1, e->W, d_perm);
     hipLaunchKernelGGL(k_remap_ids, dim3(grid_for(e->W)), dim3(BLOCK), 0, e->bs, e->w2, e->W, d_perm);
     { // out-degrees (ints) through the row scratch
-        int *itmp = reinterpret_cast<int *>(tmp);
+        int *itmp = reinterpret_cast<int *>(tmp.get());
         RN_TRY(hipMemsetAsync(itmp, 0, sizeof(int) * (size_t)V, e->bs));
         hipLaunchKernelGGL(k_permute_rows<int>, dim3(grid_for(V)), dim3(BLOCK), 0, e->bs, itmp, e->outdeg, d_perm, V, 1);
         RN_TRY(hipMemcpyAsync(e->outdeg, itmp, sizeof(int) * (size_t)V, hipMemcpyDeviceToDevice, e->bs));
     }
-    auto permute = [&](double *&a, int w) -> hipError_t { // a's rows in the new order; the old array becomes the scratch
+    auto permute = [&](double *a, int w) -> hipError_t { // a's rows in the new order, through the scratch
         hipError_t r = hipMemsetAsync(tmp, 0, sizeof(double) * (size_t)V * (size_t)w, e->bs);
         if (r != hipSuccess) return r;
         hipLaunchKernelGGL(k_permute_rows<double>, dim3(grid_for((int64_t)V * w)), dim3(BLOCK), 0, e->bs, tmp, a, d_perm, V, w);
@@ -326,7 +294,8 @@ int compact_ids(dppr_engine *e, bool *did) {
     RN_TRY(hipStreamSynchronize(e->bs));
 #undef RN_TRY
     mark("ring, degrees, state rows");
-    cleanup();
+    d_perm.reset();
+    tmp.reset();
     mark("scratch release");
     if (e->batch_staged) {
         for (auto &v : e->st_b1) v = perm[(size_t)v];
@@ -360,20 +329,20 @@ int sort_window_full(dppr_engine *e) {
                        e->keys_a);
     HIP_TRY(hipGetLastError());
     size_t tmp = e->sort_tmp_bytes;
-    HIP_TRY(rocprim::radix_sort_keys(e->sort_tmp, tmp, e->keys_a, e->in_sorted, (size_t)Ed, 0u, (unsigned)(2 * e->bits),
+    HIP_TRY(rocprim::radix_sort_keys(e->sort_tmp.get(), tmp, e->keys_a.get(), e->in_sorted.get(), (size_t)Ed, 0u, (unsigned)(2 * e->bits),
                                      e->bs));
     if (e->directed) { // undirected: the out-orientation is the same multiset, out_sorted aliases in_sorted
         hipLaunchKernelGGL(k_make_out_keys, dim3(grid_for(W)), dim3(BLOCK), 0, e->bs, e->w1, e->w2, W, e->directed,
                            e->bits, e->keys_a);
         tmp = e->sort_tmp_bytes;
-        HIP_TRY(rocprim::radix_sort_keys(e->sort_tmp, tmp, e->keys_a, e->out_sorted, (size_t)Ed, 0u,
+        HIP_TRY(rocprim::radix_sort_keys(e->sort_tmp.get(), tmp, e->keys_a.get(), e->out_sorted.get(), (size_t)Ed, 0u,
                                          (unsigned)(2 * e->bits), e->bs));
     }
     return DPPR_OK;
 }
 
 // One orientation of the incremental update: sorted' = (sorted minus deleted instances) merged with inserted.
-int merge_batch_keys(dppr_engine *e, uint64_t *&sorted, uint64_t *del_unsorted, uint64_t *del_sorted, int nd,
+int merge_batch_keys(dppr_engine *e, DevBuf<uint64_t> &sorted, uint64_t *del_unsorted, uint64_t *del_sorted, int nd,
                      uint64_t *ins_unsorted, uint64_t *ins_sorted, int ni, unsigned key_bits = 0, int miss_word = MERGE_MISS_WORD) {
     const int Ed = e->Ed;
     if (key_bits == 0) key_bits = (unsigned)(2 * e->bits); // (the CSR keys; the binned tables' words say how many bits they use)
@@ -429,7 +398,7 @@ int cut_sweep_groups(dppr_engine *e, Epoch &ep) {
     const int max_tiles = sweep_block(e) / WAVE;
     e->h_tiles.resize((size_t)n_tiles + 2);
     if (n_tiles > 0) {
-        int *scratch = reinterpret_cast<int *>(e->keys_a); // Ed * 8 bytes >= (n_tiles + 1) * 4 unless the graph is tiny
+        int *scratch = reinterpret_cast<int *>(e->keys_a.get()); // Ed * 8 bytes >= (n_tiles + 1) * 4 unless the graph is tiny
         const bool fits = (size_t)e->Ed * sizeof(uint64_t) >= ((size_t)n_tiles + 1) * sizeof(int);
         if (!fits) scratch = e->hub_slot_of;               // V ints: always large enough
         hipLaunchKernelGGL(k_tile_prefix, dim3(grid_for(n_tiles + 1)), dim3(BLOCK), 0, e->bs, ep.out_row_ptr, NV,
@@ -463,13 +432,9 @@ int cut_sweep_groups(dppr_engine *e, Epoch &ep) {
         long long largest = 0;
         for (size_t g = 0; g + 1 < cut.size(); ++g) largest = std::max<long long>(largest, (long long)prefix[cut[g + 1]] - prefix[cut[g]]);
         if (largest <= RES_SORT_MAX) {
-            if ((size_t)ep.Ed > ep.res_pk_cap) {
+            if (ep.res_pk.capacity() < (size_t)ep.Ed) {
                 HIP_TRY(hipStreamSynchronize(e->bs));
-                (void)hipFree(ep.res_pk);
-                ep.res_pk = nullptr;
-                ep.res_pk_cap = 0;
-                HIP_TRY(hipMalloc((void **)&ep.res_pk, sizeof(uint32_t) * ((size_t)ep.Ed + (size_t)ep.Ed / 8 + 1024)));
-                ep.res_pk_cap = (size_t)ep.Ed + (size_t)ep.Ed / 8 + 1024;
+                HIP_TRY(ep.res_pk.regrow((size_t)ep.Ed + (size_t)ep.Ed / 8 + 1024));
             }
             hipLaunchKernelGGL(k_res_slots, dim3(ep.n_groups), dim3(1024), 0, e->bs, NV, ep.grp_tile, ep.out_row_ptr, ep.out_col, ep.res_pk);
             HIP_TRY(hipGetLastError());
@@ -491,13 +456,9 @@ int cut_sweep_groups(dppr_engine *e, Epoch &ep) {
         // the groups' row tables, once per epoch (every sweep of every source group of this epoch loads them)
         const int nvx = gmax * WAVE;
         const size_t need = (size_t)ep.n_ggroups * (size_t)GT_STRIDE(nvx);
-        if (need > ep.gtab_cap) {
+        if (ep.gtab.capacity() < need) {
             HIP_TRY(hipStreamSynchronize(e->bs));
-            (void)hipFree(ep.gtab);
-            ep.gtab = nullptr;
-            ep.gtab_cap = 0;
-            HIP_TRY(hipMalloc((void **)&ep.gtab, sizeof(int) * (need + need / 8 + 1024)));
-            ep.gtab_cap = need + need / 8 + 1024;
+            HIP_TRY(ep.gtab.regrow(need + need / 8 + 1024));
         }
         if (ep.n_ggroups <= 0) {
             // (no vertex has an id yet: nothing to sweep)
@@ -531,14 +492,11 @@ static_assert(BIN_RL + BIN_HL + 32 <= 64, "table words: two block numbers of <= 
 
 // An allocation of the (optional) binned-sweep tables that fails is not an error of the call that wanted them: the
 // partial allocations are released, the sticky HIP error is cleared and the epoch sweeps with k_pull_iter.
-static bool bin_alloc(void **p, size_t bytes) {
-    if (*p) return true;
-    if (getenv("DPPR_TEST_BIN_OOM")) { // (test hook: these allocations fail as if the device were out of memory)
-        *p = nullptr;
-        return false;
-    }
-    if (hipMalloc(p, bytes) == hipSuccess) return true;
-    *p = nullptr;
+template <class T>
+static bool bin_alloc(DevBuf<T> &b, size_t count) {
+    if (b) return true;
+    if (getenv("DPPR_TEST_BIN_OOM")) return false; // (test hook: these allocations fail as if the device were out of memory)
+    if (b.alloc(count) == 0) return true;
     (void)hipGetLastError();
     return false;
 }
@@ -551,28 +509,23 @@ int bin_prepare(dppr_engine *e, bool *have) { // engine-level scratch, once (ide
     }
     const size_t Edn = (size_t)std::max(e->Ed, 1);
     bool ok = true;
-    ok = ok && bin_alloc((void **)&e->bin_vblk_a, sizeof(int) * (size_t)e->V);
-    ok = ok && bin_alloc((void **)&e->bin_small, sizeof(int) * BIN_SMALL_INTS);
-    ok = ok && bin_alloc((void **)&e->bin_scan, sizeof(unsigned long long) * ((size_t)4 * (Edn / WAVE + 3)));
-    ok = ok && bin_alloc((void **)&e->bin_vals, sizeof(double) * (Edn + 64));
-    ok = ok && bin_alloc((void **)&e->bin_wb, sizeof(uint64_t) * Edn) && bin_alloc((void **)&e->bin_wa, sizeof(uint64_t) * Edn); // (rotate with keys_a / keys_b: same size)
+    ok = ok && bin_alloc(e->bin_vblk_a, (size_t)e->V);
+    ok = ok && bin_alloc(e->bin_small, BIN_SMALL_INTS);
+    ok = ok && bin_alloc(e->bin_scan, (size_t)4 * (Edn / WAVE + 3));
+    ok = ok && bin_alloc(e->bin_vals, Edn + 64);
+    ok = ok && bin_alloc(e->bin_wb, Edn) && bin_alloc(e->bin_wa, Edn); // (rotate with keys_a / keys_b: same size)
     if (ok && !e->bin_tmp) {
-        HIP_TRY(rocprim::radix_sort_keys(nullptr, e->bin_tmp_bytes, e->keys_a, e->keys_b, Edn, 0u, 64u, e->bs));
+        HIP_TRY(rocprim::radix_sort_keys(nullptr, e->bin_tmp_bytes, e->keys_a.get(), e->keys_b.get(), Edn, 0u, 64u, e->bs));
         size_t scan_bytes = 0, scan_bytes32 = 0; // (the scans of the tables' tail share the scratch: sized for whichever needs most)
         HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr, 0ull, Edn / WAVE + 3,
                                         rocprim::plus<unsigned long long>(), e->bs));
         HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes32, (int *)nullptr, (int *)nullptr, 0, Edn / WAVE + 3, rocprim::plus<int>(), e->bs));
         e->bin_tmp_bytes = std::max(e->bin_tmp_bytes, std::max(scan_bytes, scan_bytes32));
-        ok = bin_alloc(&e->bin_tmp, std::max<size_t>(e->bin_tmp_bytes, 16));
+        ok = bin_alloc(e->bin_tmp, std::max<size_t>(e->bin_tmp_bytes, 16));
     }
     if (!ok) { // out of memory: nothing half-built stays behind, the sweeps of this engine gather (k_pull_iter)
-        (void)hipFree(e->bin_vblk_a); (void)hipFree(e->bin_small); (void)hipFree(e->bin_vals); (void)hipFree(e->bin_tmp);
-        (void)hipFree(e->bin_wb); (void)hipFree(e->bin_wa); (void)hipFree(e->bin_scan);
-        e->bin_vblk_a = e->bin_small = nullptr;
-        e->bin_scan = nullptr;
-        e->bin_vals = nullptr;
-        e->bin_tmp = nullptr;
-        e->bin_wb = e->bin_wa = nullptr;
+        e->bin_vblk_a.reset(); e->bin_small.reset(); e->bin_vals.reset(); e->bin_tmp.reset();
+        e->bin_wb.reset(); e->bin_wa.reset(); e->bin_scan.reset();
         return DPPR_OK;
     }
     // (the attribute belongs to the kernel, not to this engine: the largest shapes dppr_set_binned_sweep admits, so that engines
@@ -647,12 +600,9 @@ int build_bins(dppr_engine *e, Epoch &ep, const BinBatch *batch) {
     const int n_blk = (Ed + WAVE - 1) / WAVE; // aligned blocks of 64 words: the per-block tables have n_blk + 1 entries
     if (!ep.hl || !ep.dl || !ep.vb || !ep.tb) { // all four or none (a partial set from a failed attempt is released first)
         const size_t Edn = (size_t)Ed, nb1 = (size_t)n_blk + 2;
-        const bool ok = bin_alloc((void **)&ep.hl, sizeof(uint16_t) * (Edn + WAVE)) && bin_alloc((void **)&ep.dl, sizeof(uint16_t) * (Edn + WAVE)) &&
-                        bin_alloc((void **)&ep.vb, sizeof(int) * nb1) && bin_alloc((void **)&ep.tb, sizeof(int) * nb1);
+        const bool ok = bin_alloc(ep.hl, Edn + WAVE) && bin_alloc(ep.dl, Edn + WAVE) && bin_alloc(ep.vb, nb1) && bin_alloc(ep.tb, nb1);
         if (!ok) {
-            (void)hipFree(ep.hl); (void)hipFree(ep.dl); (void)hipFree(ep.vb); (void)hipFree(ep.tb);
-            ep.hl = ep.dl = nullptr;
-            ep.vb = ep.tb = nullptr;
+            ep.hl.reset(); ep.dl.reset(); ep.vb.reset(); ep.tb.reset();
             e->bin_words_valid = false;
             return DPPR_OK; // (bin_valid stays false: this epoch's sweeps gather)
         }
@@ -671,7 +621,7 @@ int build_bins(dppr_engine *e, Epoch &ep, const BinBatch *batch) {
         bin_extend_cut(e->bin_cut_a, cap_a, NV);
         bin_extend_cut(e->bin_cut_b, cap_b, NV);
         if ((int)e->bin_cut_a.size() - 1 > (1 << e->bin_abits) || (int)e->bin_cut_b.size() - 1 > (1 << e->bin_bbits) ||
-            (size_t)(e->bin_cut_a.size() - 1) * (size_t)(e->bin_cut_b.size() - 1) > e->bin_first_cap)
+            (size_t)(e->bin_cut_a.size() - 1) * (size_t)(e->bin_cut_b.size() - 1) > e->bin_first.capacity())
             patch = keep_cuts = false; // the block numbers outgrew their fields / the tile table: cut afresh
     }
     if (!keep_cuts) {
@@ -693,27 +643,19 @@ int build_bins(dppr_engine *e, Epoch &ep, const BinBatch *batch) {
     if (abits + bbits > 32 || ep.n_a + 2 > BIN_MAX_BLOCKS || ep.n_b + 2 > BIN_MAX_BLOCKS) return DPPR_OK; // (a window of that many blocks: the sweep stays k_pull_iter)
     if (!keep_cuts) { // the tile table (run index of every block pair's first run, B-major), with the fields' headroom
         const size_t need = ((size_t)ep.n_a + ep.n_a / 8 + 16) * ((size_t)ep.n_b + ep.n_b / 8 + 16);
-        if (need > e->bin_first_cap) {
+        if (e->bin_first.capacity() < need) {
             HIP_TRY(hipStreamSynchronize(e->bs));
-            (void)hipFree(e->bin_first);
-            e->bin_first = nullptr;
-            e->bin_first_cap = 0;
-            if (hipMalloc((void **)&e->bin_first, sizeof(int) * need) != hipSuccess) {
+            if (e->bin_first.regrow(need) != 0) {
                 (void)hipGetLastError();
                 return DPPR_OK; // (no tables: this epoch's sweeps gather)
             }
-            e->bin_first_cap = need;
         }
     }
     // per epoch: acut | arun | bcut (block tables), then the chunk table
     const size_t tab_ints = (size_t)2 * (ep.n_a + 1) + (ep.n_b + 1);
-    if (tab_ints > ep.bin_tab_cap) {
+    if (ep.acut.capacity() < tab_ints) {
         HIP_TRY(hipStreamSynchronize(e->bs));
-        (void)hipFree(ep.acut);
-        ep.acut = nullptr;
-        ep.bin_tab_cap = 0;
-        HIP_TRY(hipMalloc((void **)&ep.acut, sizeof(int) * (tab_ints + tab_ints / 4 + 1024)));
-        ep.bin_tab_cap = tab_ints + tab_ints / 4 + 1024;
+        HIP_TRY(ep.acut.regrow(tab_ints + tab_ints / 4 + 1024));
     }
     int *d_arun = ep.acut + (ep.n_a + 1);
     ep.bcut = d_arun + (ep.n_a + 1);
@@ -757,12 +699,12 @@ int build_bins(dppr_engine *e, Epoch &ep, const BinBatch *batch) {
             hipLaunchKernelGGL(k_bin_group, dim3(ep.n_a), dim3(BIN_CS_NT), sizeof(int) * (size_t)n_pad, e->bs, e->keys_b, d_astart, ep.acut, ep.n_b,
                                n_pad, bbits, e->bin_wa);
         } else {
-            HIP_TRY(rocprim::radix_sort_keys(e->bin_tmp, tmp, e->keys_b, e->bin_wa, (size_t)Ed, (unsigned)BIN_LO, word_bits, e->bs));
+            HIP_TRY(rocprim::radix_sort_keys(e->bin_tmp.get(), tmp, e->keys_b.get(), e->bin_wa.get(), (size_t)Ed, (unsigned)BIN_LO, word_bits, e->bs));
         }
         hipLaunchKernelGGL(k_bin_swap_blocks, dim3(grid_for(Ed)), dim3(BLOCK), 0, e->bs, e->bin_wa, Ed, bbits, abits, e->keys_b);
         HIP_TRY(hipGetLastError());
         tmp = e->bin_tmp_bytes;        // B-major: the A-major sequence, stable by B-block (the top field of the B-major form)
-        HIP_TRY(rocprim::radix_sort_keys(e->bin_tmp, tmp, e->keys_b, e->bin_wb, (size_t)Ed, (unsigned)(BIN_LO + abits), word_bits, e->bs));
+        HIP_TRY(rocprim::radix_sort_keys(e->bin_tmp.get(), tmp, e->keys_b.get(), e->bin_wb.get(), (size_t)Ed, (unsigned)(BIN_LO + abits), word_bits, e->bs));
         e->bin_miss_host = 0;
     }
     // ---- the tail both ways (dppr_binned.hpp): runs and tiles counted per aligned block of 64 words, scanned, then the tables
@@ -789,16 +731,11 @@ int build_bins(dppr_engine *e, Epoch &ep, const BinBatch *batch) {
     const int R = (int)(totals[0] >> 32), T = (int)(totals[0] & 0xffffffffull);
     if (R != (int)(totals[1] >> 32) || T != (int)(totals[1] & 0xffffffffull) || R <= 0 || T <= 0)
         return fail(e, DPPR_ERR_HIP, "binned tables: the two orders of the window's edges disagree about their runs / tiles");
-    if ((size_t)T + WAVE > ep.tdelta_cap) {
-        (void)hipFree(ep.tdelta);
-        ep.tdelta = nullptr;
-        ep.tdelta_cap = 0;
-        const size_t want = (size_t)T + (size_t)T / 4 + 1024;
-        if (hipMalloc((void **)&ep.tdelta, sizeof(int) * want) != hipSuccess) {
+    if (ep.tdelta.capacity() < (size_t)T + WAVE) {
+        if (ep.tdelta.regrow((size_t)T + (size_t)T / 4 + 1024) != 0) {
             (void)hipGetLastError();
             return DPPR_OK; // (this epoch's sweeps gather; the words were not kept either: the next slide sorts)
         }
-        ep.tdelta_cap = want;
     }
     ep.n_runs = R;
     ep.n_tiles = T;
@@ -838,13 +775,7 @@ int build_bins(dppr_engine *e, Epoch &ep, const BinBatch *batch) {
         }
     }
     ep.n_chunks = (int)chunks.size();
-    if (chunks.size() > ep.chunk_cap) {
-        (void)hipFree(ep.chunks);
-        ep.chunks = nullptr;
-        ep.chunk_cap = 0;
-        HIP_TRY(hipMalloc((void **)&ep.chunks, sizeof(BinChunk) * (chunks.size() + chunks.size() / 4 + 256)));
-        ep.chunk_cap = chunks.size() + chunks.size() / 4 + 256;
-    }
+    if (ep.chunks.capacity() < chunks.size()) HIP_TRY(ep.chunks.regrow(chunks.size() + chunks.size() / 4 + 256));
     if (!chunks.empty()) HIP_TRY(hipMemcpy(ep.chunks, chunks.data(), sizeof(BinChunk) * chunks.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipStreamSynchronize(e->bs));
     ep.bin_n_int = NV;
@@ -901,13 +832,9 @@ int res_record_ranges(dppr_engine *e, Epoch &ep) {
     const int pb = sweep_block(e);
     if (!e->res_update || !ep.grouped || ep.L <= 0 || ep.L >= SU_SPLIT_MIN || ep.n_groups <= 0 || ep.n_groups > persist_capacity(e)) return DPPR_OK;
     const size_t need = (size_t)ep.n_groups + 3;
-    if (need > ep.su_rng_cap) {
+    if (ep.su_rng.capacity() < need) {
         HIP_TRY(hipStreamSynchronize(e->bs));
-        (void)hipFree(ep.su_rng);
-        ep.su_rng = nullptr;
-        ep.su_rng_cap = 0;
-        HIP_TRY(hipMalloc((void **)&ep.su_rng, sizeof(int) * (need + 1024)));
-        ep.su_rng_cap = need + 1024;
+        HIP_TRY(ep.su_rng.regrow(need + 1024));
     }
     int *stat = ep.su_rng + ep.n_groups + 1;
     HIP_TRY(hipMemsetAsync(stat, 0, sizeof(int) * 2, e->bs));
@@ -929,13 +856,10 @@ bool resident_arena(dppr_engine *e, const Epoch &ep) {
     const long long stride = ((long long)ep.grp_n_int + 1023) / 1024 * 1024;
     if (stride <= e->res_arena_stride) return true;
     if (hipStreamSynchronize(e->stream) != hipSuccess) return false;
-    (void)hipFree(e->res_arena);
-    e->res_arena = nullptr;
     e->res_arena_stride = 0;
     const long long want = std::min<long long>(((long long)e->V + 1023) / 1024 * 1024, stride + stride / 4);
-    if (hipMalloc((void **)&e->res_arena, sizeof(double) * (size_t)want * RES_VECTORS) != hipSuccess) {
+    if (e->res_arena.regrow((size_t)want * RES_VECTORS) != 0) {
         (void)hipGetLastError();
-        e->res_arena = nullptr;
         return false;
     }
     e->res_arena_stride = want;

@@ -51,17 +51,13 @@ int group_push_tail(dppr_engine *e, Group &g, const Epoch &ep, int phase, double
     *converged = false;
     const int GWM = GS_MAX;
     const int cap = std::max(1024, std::min(e->gpush_list_cap, e->V));
-    if (g.plist_cap != cap) {
+    if (g.plist[0].capacity() != (size_t)cap || !g.pctl) { // (pctl comes last: a set that failed half way is made again)
         HIP_TRY(loop_wait(e));
-        (void)hipFree(g.plist[0]); (void)hipFree(g.plist[1]); (void)hipFree(g.ppre); (void)hipFree(g.pctl);
-        g.plist[0] = g.plist[1] = g.ppre = nullptr;
-        g.pctl = nullptr;
-        g.plist_cap = 0;
-        HIP_TRY(hipMalloc((void **)&g.plist[0], sizeof(int) * (size_t)cap));
-        HIP_TRY(hipMalloc((void **)&g.plist[1], sizeof(int) * (size_t)cap));
-        HIP_TRY(hipMalloc((void **)&g.ppre, sizeof(int) * ((size_t)cap + 1)));
-        HIP_TRY(hipMalloc((void **)&g.pctl, sizeof(GPushCtl)));
-        g.plist_cap = cap;
+        g.plist[0].reset(); g.plist[1].reset(); g.ppre.reset(); g.pctl.reset();
+        HIP_TRY(g.plist[0].alloc((size_t)cap));
+        HIP_TRY(g.plist[1].alloc((size_t)cap));
+        HIP_TRY(g.ppre.alloc((size_t)cap + 1));
+        HIP_TRY(g.pctl.alloc(1));
     }
     static thread_local GPushCtl h;
     // no host round trip on the way in: a list that does not fit (overflow) moves nothing and makes the first scan call

@@ -57,7 +57,7 @@ int run_frontier_loop(dppr_engine *e, Slot &s, const Epoch &ep, int phase, doubl
     // overflow. One entry per vertex and launch keeps it bounded.
     const bool use_status = e->status_dedup || phase == PHASE_BOTH;
     if (use_status && !s.status) { // (first use: -1 everywhere = "never queued")
-        HIP_TRY(hipMalloc((void **)&s.status, sizeof(int) * (size_t)e->V));
+        HIP_TRY(s.status.alloc((size_t)e->V));
         HIP_TRY(hipMemsetAsync(s.status, 0xff, sizeof(int) * (size_t)e->V, e->stream));
     }
     bool extracted = false;         // ... and that snapshot zeroed the residuals it took (InspectExtra): the push needs no repair
@@ -537,7 +537,7 @@ int epoch_group_records(dppr_engine *e, Epoch &ep) {
     hipLaunchKernelGGL(k_su_keys, dim3(grid_for(ep.L)), dim3(BLOCK), 0, e->bs, ep.b1, ep.L, e->su_k[0], e->su_v[0],
                        (unsigned long long *)nullptr, 0, (int *)nullptr, 0);
     size_t tmp = e->su_tmp_bytes;
-    HIP_TRY(rocprim::radix_sort_pairs(e->su_tmp, tmp, e->su_k[0], ep.sk, e->su_v[0], ep.sv, (size_t)ep.L, 0u, (unsigned)e->bits, e->bs));
+    HIP_TRY(rocprim::radix_sort_pairs(e->su_tmp.get(), tmp, e->su_k[0].get(), ep.sk.get(), e->su_v[0].get(), ep.sv.get(), (size_t)ep.L, 0u, (unsigned)e->bits, e->bs));
     ep.grouped = true;
     return res_record_ranges(e, ep);
 }
@@ -576,7 +576,7 @@ int enqueue_grouping(dppr_engine *e, const Epoch &ep, int *deg, unsigned long lo
     hipLaunchKernelGGL(k_copy_out_degree, dim3(grid_for(L)), dim3(BLOCK), 0, e->stream, ep.b1, L, ep.out_row_ptr, deg);
     hipLaunchKernelGGL(k_su_keys, dim3(grid_for(L)), dim3(BLOCK), 0, e->stream, ep.b1, L, e->su_k[0], e->su_v[0], zero, nz, zero_ints, nzi);
     size_t tmp = e->su_tmp_bytes;
-    HIP_TRY(rocprim::radix_sort_pairs(e->su_tmp, tmp, e->su_k[0], e->su_k[1], e->su_v[0], e->su_v[1], (size_t)L, 0u, (unsigned)e->bits, e->stream));
+    HIP_TRY(rocprim::radix_sort_pairs(e->su_tmp.get(), tmp, e->su_k[0].get(), e->su_k[1].get(), e->su_v[0].get(), e->su_v[1].get(), (size_t)L, 0u, (unsigned)e->bits, e->stream));
     return DPPR_OK;
 }
 
@@ -606,7 +606,7 @@ int stream_update(dppr_engine *e, Slot &s, const Epoch &ep, double eps, bool see
         return DPPR_OK;
     }
     // (the batch's first kernel also clears cnt[0..4] and, for a resident launch enqueued ahead, its GridBar)
-    int rc = group_records_by_tail(e, ep, zero_bars ? reinterpret_cast<unsigned long long *>(e->bar) : nullptr,
+    int rc = group_records_by_tail(e, ep, zero_bars ? reinterpret_cast<unsigned long long *>(e->bar.get()) : nullptr,
                                    zero_bars ? (int)(sizeof(GridBar) / sizeof(unsigned long long)) : 0, s.cnt, 5);
     if (rc) return rc;
     // without seeding the lists go to scratch space (cnt[4] / neg) and are ignored

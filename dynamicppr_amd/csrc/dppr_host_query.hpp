@@ -16,7 +16,7 @@ size_t tk_res_bytes(int n, int k, bool with_r) {
 int sync_int2ext(dppr_engine *e) {
     const unsigned gen = e->map_gen.load(std::memory_order_acquire);
     if (e->d_int2ext && gen == e->i2e_gen_on_device) return DPPR_OK;
-    if (!e->d_int2ext) HIP_TRY(hipMalloc((void **)&e->d_int2ext, sizeof(int) * (size_t)e->V));
+    if (!e->d_int2ext) HIP_TRY(e->d_int2ext.alloc((size_t)e->V));
     if (e->n_int > 0)
         HIP_TRY(hipMemcpyAsync(e->d_int2ext, e->int2ext.data(), sizeof(int) * (size_t)e->n_int, hipMemcpyHostToDevice, e->stream));
     if (e->n_parked > 0) {
@@ -30,25 +30,20 @@ int sync_int2ext(dppr_engine *e) {
 }
 
 int topk_workspace(dppr_engine *e, int n, size_t rows) {
-    if (!e->tk_ws) {
-        HIP_TRY(hipMalloc((void **)&e->tk_ws, sizeof(unsigned) * GS_MAX * (TK_BINS1 + TK_BINS2) + sizeof(TkLane) * GS_MAX));
-        HIP_TRY(hipMalloc((void **)&e->tk_out_key, sizeof(unsigned long long) * GS_MAX * DPPR_TOPK_MAX));
-        HIP_TRY(hipMalloc((void **)&e->tk_out_row, sizeof(int) * GS_MAX * DPPR_TOPK_MAX));
-        HIP_TRY(hipMalloc((void **)&e->tk_res, tk_res_bytes(GS_MAX, DPPR_TOPK_MAX, true)));
-        HIP_TRY(hipHostMalloc((void **)&e->tk_pin, tk_res_bytes(GS_MAX, DPPR_TOPK_MAX, true)));
+    if (!e->tk_pin) { // (the last of the set: one that failed half way is made again)
+        HIP_TRY(e->tk_ws.regrow(sizeof(unsigned) * GS_MAX * (TK_BINS1 + TK_BINS2) + sizeof(TkLane) * GS_MAX));
+        HIP_TRY(e->tk_out_key.regrow((size_t)GS_MAX * DPPR_TOPK_MAX));
+        HIP_TRY(e->tk_out_row.regrow((size_t)GS_MAX * DPPR_TOPK_MAX));
+        HIP_TRY(e->tk_res.regrow(tk_res_bytes(GS_MAX, DPPR_TOPK_MAX, true)));
+        HIP_TRY(e->tk_pin.regrow(tk_res_bytes(GS_MAX, DPPR_TOPK_MAX, true)));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_tk_hist1), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)(sizeof(unsigned) * GS_MAX * TK_BINS1)));
     }
     // a candidate list can hold every occupied row of its lane (the boundary bin of a state whose values crowd one exponent)
     const size_t need = (size_t)n * std::max<size_t>(rows, 1);
-    if (need > e->tk_cand_cap) {
+    if (e->tk_cand.capacity() < need) {
         HIP_TRY(hipStreamSynchronize(e->stream));
-        (void)hipFree(e->tk_cand);
-        e->tk_cand = nullptr;
-        e->tk_cand_cap = 0;
-        const size_t cap = std::min<size_t>((size_t)GS_MAX * (size_t)e->V, need + need / 4);
-        HIP_TRY(hipMalloc((void **)&e->tk_cand, sizeof(int) * cap));
-        e->tk_cand_cap = cap;
+        HIP_TRY(e->tk_cand.regrow(std::min<size_t>((size_t)GS_MAX * (size_t)e->V, need + need / 4)));
     }
     return DPPR_OK;
 }
@@ -69,7 +64,7 @@ int run_topk(dppr_engine *e, const double *p, const double *r, int gw, int n, in
     if (rc) return rc;
     rc = topk_workspace(e, n, (size_t)st.rows);
     if (rc) return rc;
-    unsigned *hist1 = reinterpret_cast<unsigned *>(e->tk_ws), *hist2 = hist1 + GS_MAX * TK_BINS1;
+    unsigned *hist1 = reinterpret_cast<unsigned *>(e->tk_ws.get()), *hist2 = hist1 + GS_MAX * TK_BINS1;
     TkLane *ctl = reinterpret_cast<TkLane *>(hist2 + GS_MAX * TK_BINS2);
     const int cand_cap = (int)std::max<size_t>(st.rows, 1);
     HIP_TRY(hipMemsetAsync(e->tk_ws, 0, sizeof(unsigned) * GS_MAX * (TK_BINS1 + TK_BINS2) + sizeof(TkLane) * GS_MAX, e->stream));
@@ -88,7 +83,7 @@ int run_topk(dppr_engine *e, const double *p, const double *r, int gw, int n, in
     hipLaunchKernelGGL(k_tk_take, dim3(grid2, n), dim3(256), 0, e->stream, st, e->d_int2ext, ctl, e->tk_cand, cand_cap, k,
                        e->tk_out_key, e->tk_out_row);
     const size_t nk = (size_t)n * (size_t)k;
-    int *res_cnt = reinterpret_cast<int *>(e->tk_res), *res_id = reinterpret_cast<int *>(e->tk_res + TK_RES_IDS);
+    int *res_cnt = reinterpret_cast<int *>(e->tk_res.get()), *res_id = reinterpret_cast<int *>(e->tk_res.get() + TK_RES_IDS);
     const size_t off_p = TK_RES_IDS + ((sizeof(int) * nk + 7) & ~(size_t)7), off_r = off_p + sizeof(double) * nk;
     double *res_p = reinterpret_cast<double *>(e->tk_res + off_p), *res_r = reinterpret_cast<double *>(e->tk_res + off_r);
     hipLaunchKernelGGL(k_tk_rank, dim3((k + 255) / 256, n), dim3(256), 0, e->stream, st, e->d_int2ext, ctl, k, e->tk_out_key,
@@ -111,17 +106,14 @@ int run_read_at(dppr_engine *e, const double *p, const double *r, int gw, int n,
     if (rc) return rc;
     const size_t mn = (size_t)m * (size_t)n;
     const size_t ids_bytes = (sizeof(int) * (size_t)m + 7) & ~(size_t)7, need = ids_bytes + 2 * sizeof(double) * mn;
-    if (need > e->ra_cap) {
+    if (e->ra_buf.capacity() < need) {
         HIP_TRY(hipStreamSynchronize(e->stream));
-        (void)hipFree(e->ra_buf);
-        e->ra_buf = nullptr;
-        e->ra_cap = 0;
-        HIP_TRY(hipMalloc((void **)&e->ra_buf, need));
-        e->ra_cap = need;
+        HIP_TRY(e->ra_buf.regrow(need));
     }
-    double *d_p = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(e->ra_buf) + ids_bytes), *d_r = d_p + mn;
-    HIP_TRY(hipMemcpyAsync(e->ra_buf, ids, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, e->stream));
-    hipLaunchKernelGGL(k_read_at, dim3(grid_for((int64_t)mn)), dim3(BLOCK), 0, e->stream, p, r, gw, n, e->d_ext2int, e->ra_buf, m,
+    int *d_ids = reinterpret_cast<int *>(e->ra_buf.get());
+    double *d_p = reinterpret_cast<double *>(e->ra_buf + ids_bytes), *d_r = d_p + mn;
+    HIP_TRY(hipMemcpyAsync(d_ids, ids, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(k_read_at, dim3(grid_for((int64_t)mn)), dim3(BLOCK), 0, e->stream, p, r, gw, n, e->d_ext2int, d_ids, m,
                        d_p, d_r);
     HIP_TRY(hipGetLastError());
     if (out_p) HIP_TRY(hipMemcpyAsync(out_p, d_p, sizeof(double) * mn, hipMemcpyDeviceToHost, e->stream));

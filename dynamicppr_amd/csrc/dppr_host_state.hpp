@@ -2,6 +2,9 @@
 // gpu/GPUEdgeBatch.cuh and the members of gpu/SlidingGraphBuilder.cuh) -- the resident graph epochs, the per-source slots and source
 // groups, the two HIP streams (solver / builder) and their scratch -- plus the small helpers every other part uses (error
 // reporting, the bounded stream wait, the id lookahead of dppr_hint_next_batch).
+// Every device or pinned-host allocation is a DevBuf / PinBuf (dppr_devbuf.hpp) that is a member of its owner -- Epoch, Slot, Group,
+// dppr_engine -- or a local of the function that needs it: memory goes when its owner goes, dppr_destroy lists nothing, and a call
+// that fails half way leaves nothing behind. The HIP runtime's allocation calls appear in the two policies below and nowhere else.
 // Included by dppr_engine.hip only, after the kernel headers (one translation unit: the kernels are templates).
 #pragma once
 
@@ -18,74 +21,102 @@ static constexpr int SU_SPLIT_MIN = 1 << 16;  // batch records from which Increm
 static constexpr int MERGE_MISS_WORD = 44; // word of hub_hist (64 ints) that counts the retired keys a slide's merge did not find
 static constexpr int RESIDENT_MARGIN = 8; // sweeps a resident launch is given beyond what the last batch needed
 
+namespace dppr {
+
+// bytes this PROCESS holds through the two policies (dppr_debug_live_bytes: a leak check that ignores the device's other tenants)
+inline std::atomic<long long> g_device_bytes{0}, g_pinned_bytes{0};
+
+struct DeviceAlloc {
+    static int alloc(void **p, size_t bytes) {
+        const hipError_t rc = hipMalloc(p, bytes);
+        if (rc == hipSuccess) g_device_bytes.fetch_add((long long)bytes, std::memory_order_relaxed);
+        return (int)rc;
+    }
+    static int free(void *p, size_t bytes) {
+        g_device_bytes.fetch_sub((long long)bytes, std::memory_order_relaxed);
+        return (int)hipFree(p);
+    }
+};
+
+struct PinnedAlloc {
+    static int alloc(void **p, size_t bytes) {
+        const hipError_t rc = hipHostMalloc(p, bytes, hipHostMallocDefault);
+        if (rc == hipSuccess) g_pinned_bytes.fetch_add((long long)bytes, std::memory_order_relaxed);
+        return (int)rc;
+    }
+    static int free(void *p, size_t bytes) {
+        g_pinned_bytes.fetch_sub((long long)bytes, std::memory_order_relaxed);
+        return (int)hipHostFree(p);
+    }
+};
+
+template <class T> using DevBuf = Buf<T, DeviceAlloc>;
+template <class T> using PinBuf = Buf<T, PinnedAlloc>;
+
+} // namespace dppr
+
 namespace {
 
 struct Epoch {
-    int *row_ptr = nullptr; // V+1   in-CSR (push)
-    Adj *adj = nullptr;     // Ed
-    int *out_row_ptr = nullptr; // V+1  out-CSR (pull)
-    int *out_col = nullptr;     // Ed
+    DevBuf<int> row_ptr; // V+1   in-CSR (push)
+    DevBuf<Adj> adj;     // Ed
+    DevBuf<int> out_row_ptr; // V+1  out-CSR (pull)
+    DevBuf<int> out_col;     // Ed
     int Ed = 0;
     // batch that produced this epoch (empty for epoch 0)
-    int *b1 = nullptr, *b2 = nullptr, *deg_after = nullptr; // 4c each
-    uint8_t *ins = nullptr;
+    DevBuf<int> b1, b2, deg_after; // 4c each
+    DevBuf<uint8_t> ins;
     int L = 0;
-    uint32_t *sk = nullptr, *sv = nullptr; // the batch's records grouped by tail at slide time: tails ascending, record indices (stable)
+    DevBuf<uint32_t> sk, sv; // the batch's records grouped by tail at slide time: tails ascending, record indices (stable)
     int max_bucket = 0; // records in the fullest bucket of the bucket path (largest_bucket, dppr_grouping.hpp), counted at upload
     bool grouped = false;
     int id = -1; // global epoch number stored in this ring entry
     // sweep groups: tiles [grp_tile[g], grp_tile[g+1]) per workgroup, about equal edges each
-    int *grp_tile = nullptr; // V/64 + 2
+    DevBuf<int> grp_tile; // V/64 + 2
     int n_groups = 0;
     int grp_n_int = 0;       // internal ids covered by the table
     // the same for the source-group sweeps (k_gsweep), cut once a source group exists: many small groups --
     // two workgroups per CU and an even spread matter there, a bound on the group count does not; at
     // most 512 vertices each when a 16-wide source group exists
-    int *ggrp_tile = nullptr;
+    DevBuf<int> ggrp_tile;
     int n_ggroups = 0;
     int ggrp_max_tiles = 0;
-    int *gtab = nullptr;     // row tables of those groups (k_gtables): GT_STRIDE(512 | 1024) ints per group
-    size_t gtab_cap = 0;     // ints allocated
+    DevBuf<int> gtab;     // row tables of those groups (k_gtables): GT_STRIDE(512 | 1024) ints per group
     // hub directory of this epoch (vertices whose pushes are aggregated in LDS)
-    int *hub_v = nullptr, *hub_degp1 = nullptr;
+    DevBuf<int> hub_v, hub_degp1;
     int n_hubs = 0;
     // binned sweep (dppr_binned.hpp): block cuts (first tile of every A- / B-block), per edge the head index inside
     // its A-block + B-major position (A-major order) and the row index inside its B-block (B-major order)
-    int *acut = nullptr, *bcut = nullptr; // first vertex of every A- / B-block (one allocation; bcut points into it)
-    size_t bin_tab_cap = 0;
+    DevBuf<int> acut; int *bcut = nullptr; // first vertex of every A- / B-block (one allocation; bcut points into it)
     int n_a = 0, n_b = 0;
-    BinChunk *chunks = nullptr;           // work items of k_bin_scatter
-    size_t chunk_cap = 0;
+    DevBuf<BinChunk> chunks;           // work items of k_bin_scatter
     int n_chunks = 0;
-    uint16_t *hl = nullptr, *dl = nullptr; // hl: per RUN (A-major), head index + first-of-tile bit; dl: per edge (B-major), row index + first-of-run bit
-    int *vb = nullptr, *tb = nullptr;      // per aligned block of 64 edges: run that holds its first edge; per 64 runs: tile that holds the first run
-    int *tdelta = nullptr;                 // per tile (A-major order): B-major run index - A-major run index of its runs
-    size_t tdelta_cap = 0;
+    DevBuf<uint16_t> hl, dl; // hl: per RUN (A-major), head index + first-of-tile bit; dl: per edge (B-major), row index + first-of-run bit
+    DevBuf<int> vb, tb;      // per aligned block of 64 edges: run that holds its first edge; per 64 runs: tile that holds the first run
+    DevBuf<int> tdelta;                 // per tile (A-major order): B-major run index - A-major run index of its runs
     int n_runs = 0, n_tiles = 0;
     bool bin_valid = false;
     int bin_n_int = 0; // internal ids the tables cover (<= grp_n_int: later ids have no edge in this epoch)
     // slot table of the resident sweep (dppr_resident.hpp: k_res_slots), rebuilt with every group cut
-    uint32_t *res_pk = nullptr; // Ed entries, group by group, sorted by gather position
-    size_t res_pk_cap = 0;
+    DevBuf<uint32_t> res_pk; // Ed entries, group by group, sorted by gather position
     bool res_valid = false;
     // the batch's records (sk / sv) cut into the sweep groups' ranges, for IncrementalBatchUpdate inside a resident launch
-    int *su_rng = nullptr;      // n_groups + 1 first-record indices, then two result words of k_res_rec_ranges
-    size_t su_rng_cap = 0;
+    DevBuf<int> su_rng;      // n_groups + 1 first-record indices, then two result words of k_res_rec_ranges
     bool su_inline = false;     // every group's range fits the launch's workgroup and no tail lies beyond the groups
 };
 
 struct Slot {
     int source = 0;     // internal id
     int source_ext = 0; // id the caller gave
-    double *p = nullptr, *r = nullptr;
-    double *x = nullptr, *x2 = nullptr; // dense per-iteration push amounts (x) and pull output (x2)
-    uint32_t *act[2] = {nullptr, nullptr}; // activity bitmaps of x / x2 for sweeps on windows that cannot run resident
+    DevBuf<double> p, r;
+    DevBuf<double> x, x2; // dense per-iteration push amounts (x) and pull output (x2)
+    DevBuf<uint32_t> act[2]; // activity bitmaps of x / x2 for sweeps on windows that cannot run resident
     size_t act_bytes = 0;
-    int *ft[2] = {nullptr, nullptr};
-    int *neg = nullptr;     // phase-1 candidates
-    int *status = nullptr;  // status-array duplicate filter (variants EAGER / VANILLA): launch number that queued the vertex last; allocated on first use
-    int *cnt = nullptr;     // [0..2] rotating frontier counters, [3] neg candidates, [4] scratch, [5..6] big-row counters
-    BigItem *big = nullptr; // deferred big rows of the current iteration
+    DevBuf<int> ft[2];
+    DevBuf<int> neg;     // phase-1 candidates
+    DevBuf<int> status;  // status-array duplicate filter (variants EAGER / VANILLA): launch number that queued the vertex last; allocated on first use
+    DevBuf<int> cnt;     // [0..2] rotating frontier counters, [3] neg candidates, [4] scratch, [5..6] big-row counters
+    DevBuf<BigItem> big; // deferred big rows of the current iteration
     int *log = nullptr;     // per-chunk log: frontier size seen by each enqueued iteration
     long long iter_seq = 0; // running iteration number (selects the big-row counter)
     double sweep_us = 0;       // binned windows: running mean of a sweep's time (the push / sweep decision)
@@ -94,7 +125,7 @@ struct Slot {
     int iter_hist[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}; // ... and the last four
     bool start_dense[2] = {false, false}; // the last loop of each phase began with a frontier worth a sweep
     int last_F0[2] = {0, 0};   // ... and its size
-    IterStats *dstats = nullptr; // two blocks: [0] push iterations (and resident launches), [1] dense sweeps -- the roofline of the sweep kernel counts its own edges
+    DevBuf<IterStats> dstats; // two blocks: [0] push iterations (and resident launches), [1] dense sweeps -- the roofline of the sweep kernel counts its own edges
     bool converged = false; // |r| <= eps everywhere (state after a completed solve)
     double conv_eps = 0.0;
     double park_eps = 0.0;  // parked rows satisfy |r| <= park_eps (0: they are exactly zero)
@@ -115,23 +146,22 @@ struct Group {
     int gw = OCT;              // doubles per vertex = row_width(n): 2, 4, .. 16 (dppr_multi.hpp)
     int src_ext[GS_MAX] = {0}; // ids the caller gave
     SrcN src{};                // internal ids, -1 = unused lane
-    double *p = nullptr, *r = nullptr, *x = nullptr, *x2 = nullptr; // [V][gw]
-    uint32_t *act[2] = {nullptr, nullptr}; // activity bitmaps that go with x / x2
+    DevBuf<double> p, r, x, x2; // [V][gw]
+    DevBuf<uint32_t> act[2]; // activity bitmaps that go with x / x2
     size_t act_bytes = 0;
-    int *cnt = nullptr;        // [3][GS_MAX] rotating frontier sizes, then the per-chunk log [MAX][GS_MAX]
-    int *gq = nullptr;         // one-sweep launches: three rotating group counters (a launch takes tickets from one and zeroes the next), GQ_PAD ints apart
+    DevBuf<int> cnt;        // [3][GS_MAX] rotating frontier sizes, then the per-chunk log [MAX][GS_MAX]
+    DevBuf<int> gq;         // one-sweep launches: three rotating group counters (a launch takes tickets from one and zeroes the next), GQ_PAD ints apart
     unsigned gq_seq = 0;       // one-sweep launches enqueued so far
-    int *mlog = nullptr;       // multi-sweep launches: [GS_MAX] status word + padding, then one row of frontier sizes per sweep
-    IterStats *dstats = nullptr; // two blocks: [0] push iterations (and resident launches), [1] dense sweeps -- the roofline of the sweep kernel counts its own edges
+    DevBuf<int> mlog;       // multi-sweep launches: [GS_MAX] status word + padding, then one row of frontier sizes per sweep
+    DevBuf<IterStats> dstats; // two blocks: [0] push iterations (and resident launches), [1] dense sweeps -- the roofline of the sweep kernel counts its own edges
     dppr_stats_t st{};
     int iter_hint[2] = {0, 0};
     int iter_hist[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}; // sweeps the last four loops of each phase took
     int dense_hist[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}; // ... before the frontier was small enough for the push form
     // the tail of a loop as pushes (dppr_gpush.hpp): vertex lists, scan, control block; allocated on first use
-    int *plist[2] = {nullptr, nullptr};
-    int *ppre = nullptr;
-    GPushCtl *pctl = nullptr;
-    int plist_cap = 0;
+    DevBuf<int> plist[2];
+    DevBuf<int> ppre;
+    DevBuf<GPushCtl> pctl;
     bool converged = false;    // |r| <= conv_eps for every source (state after a completed solve)
     double conv_eps = 0.0;
     double park_eps = 0.0;     // parked rows satisfy |r| <= park_eps
@@ -182,33 +212,33 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     int persist_cap = 0;               // co-resident workgroups of k_pull_resident at the sweep's block size
     int res_slots = 1;                 // 1: resident launches take their edge slots from the sorted slot table (0: CSR order)
     int res_update = 1;                // 1: a whole-batch resident launch applies the batch's records itself (PLAN_UPDATE)
-    double *res_arena = nullptr;       // snapshot vectors of a resident launch (resident_arena)
+    DevBuf<double> res_arena;       // snapshot vectors of a resident launch (resident_arena)
     long long res_arena_stride = 0;    // doubles per vector
     unsigned long long persist_ticks = 5000000ull; // roll-call time limit in 100 MHz ticks (50 ms)
     int persist_rollcall_extra = 0;    // tests: the roll-call waits for a workgroup that does not exist
-    GridBar *bar = nullptr;
+    DevBuf<GridBar> bar;
     // window ring, stream order
-    int *w1 = nullptr, *w2 = nullptr;
+    DevBuf<int> w1, w2;
     int head = 0;
     bool loaded = false;
     bool broken = false; // a renumbering failed half way (HIP error after the host maps changed): every call but dppr_destroy is refused
-    int *outdeg = nullptr;
-    int *hub_slot_of = nullptr; // V, scratch of the CSR build (k_assign_hubs: ~hub slot, or out-degree + 1)
-    int *hub_hist = nullptr;    // 32 + 1 ints (histogram, hub counter)
+    DevBuf<int> outdeg;
+    DevBuf<int> hub_slot_of; // V, scratch of the CSR build (k_assign_hubs: ~hub slot, or out-degree + 1)
+    DevBuf<int> hub_hist;    // 32 + 1 ints (histogram, hub counter)
     int hub_min_degree = HUB_MIN_DEGREE_DEFAULT;
     int big_row = BIG_ROW_DEFAULT;
     int pull_min_frontier = 0; // 0: auto (max(1024, Ed/192)); < 0: never pull; > 0: pull when F >= value
     // CSR build: persistent sorted key arrays (in-orientation dst<<bits|src, out-orientation
     // src<<bits|dst; undirected graphs share one) + scratch of the same size
-    uint64_t *in_sorted = nullptr, *out_sorted = nullptr;
-    uint64_t *keys_a = nullptr, *keys_b = nullptr;
-    void *sort_tmp = nullptr;
+    DevBuf<uint64_t> in_sorted, out_sorted;
+    DevBuf<uint64_t> keys_a, keys_b;
+    DevBuf<unsigned char> sort_tmp;
     size_t sort_tmp_bytes = 0;
-    int *su_grp = nullptr; // hand-written grouping of a large batch (dppr_update.hpp k_su_grp_*): histogram | cursors | bucket starts + slice starts
+    DevBuf<int> su_grp; // hand-written grouping of a large batch (dppr_update.hpp k_su_grp_*): histogram | cursors | bucket starts + slice starts
     // incremental maintenance (f1): batch keys, positions of the retired keys
-    uint64_t *bk[4] = {nullptr, nullptr, nullptr, nullptr}; // del-in, ins-in, del-out, ins-out (unsorted)
-    uint64_t *bks[4] = {nullptr, nullptr, nullptr, nullptr}; // the same, sorted
-    int *delpos = nullptr; // positions of a slide's retired keys in the persistent sorted keys (2 * max_batch)
+    DevBuf<uint64_t> bk[4]; // del-in, ins-in, del-out, ins-out (unsorted)
+    DevBuf<uint64_t> bks[4]; // the same, sorted
+    DevBuf<int> delpos; // positions of a slide's retired keys in the persistent sorted keys (2 * max_batch)
     struct Pre { // dppr_hint_next_batch
         std::future<bool> task;
         const int32_t *src[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -250,15 +280,14 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     long long bin_target_a = 4ll << 20; // ... an A-block (its edges are dealt to workgroups of k_bin_scatter in chunks: large, so that tiles are long runs)
     long long bin_min_ids = 1ll << 19; // (smaller windows run resident or gather: R-MAT window of 2 M edges, ~0.65 M ids, single source: binned 2.66 ms per batch
                                        // against 3.26 gathering; window of 1 M edges, ~0.38 M ids: 2.45 against 1.47 -- tools/r04/midsize_probe.sh)
-    int *bin_vblk_a = nullptr;      // vertex -> A-block (V ints; the B-block of a row is found by bisection, k_bin_keys)
-    unsigned long long *bin_scan = nullptr; // counts and scans of the tables' tail (4 x (Ed / 64 + 3) words)
-    int *bin_small = nullptr;       // quantile vertices | big rows | counter (bin_cut)
+    DevBuf<int> bin_vblk_a;      // vertex -> A-block (V ints; the B-block of a row is found by bisection, k_bin_keys)
+    DevBuf<unsigned long long> bin_scan; // counts and scans of the tables' tail (4 x (Ed / 64 + 3) words)
+    DevBuf<int> bin_small;       // quantile vertices | big rows | counter (bin_cut)
     long long bin_chunk = 32768;    // edges per workgroup of k_bin_scatter
-    double *bin_vals = nullptr;     // the values in B-major order: what pass 1 hands to pass 2 (one loop runs at a time)
+    DevBuf<double> bin_vals;     // the values in B-major order: what pass 1 hands to pass 2 (one loop runs at a time)
     // the tables PATCHED per slide (dppr_binned.hpp, round 5): both orders persistent as sorted words under frozen block cuts
-    uint64_t *bin_wb = nullptr, *bin_wa = nullptr; // B-major / A-major words of the NEWEST epoch (rotate with keys_a / keys_b at a merge)
-    int *bin_first = nullptr;       // B-major run index of every block pair's first run: n_b x n_a ints (scratch of the tables' tail)
-    size_t bin_first_cap = 0;
+    DevBuf<uint64_t> bin_wb, bin_wa; // B-major / A-major words of the NEWEST epoch (rotate with keys_a / keys_b at a merge)
+    DevBuf<int> bin_first;       // B-major run index of every block pair's first run: n_b x n_a ints (scratch of the tables' tail)
     std::vector<int32_t> bin_cut_a, bin_cut_b; // the cuts in use (first vertex of every block; frozen between re-cuts, extended by new ids)
     int bin_abits = 0, bin_bbits = 0;   // width of the block-number fields of the words (with room for appended blocks)
     int bin_cut_ids = 0;            // ids the cuts cover
@@ -270,15 +299,15 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     bool bin_force_full = false;    // the next build sorts afresh (a merge missed a key)
     int bin_miss_host = 0;
     long long bin_patched = 0, bin_rebuilt = 0; // epochs whose tables were patched / built by the sorts
-    void *bin_tmp = nullptr;
+    DevBuf<unsigned char> bin_tmp;
     size_t bin_tmp_bytes = 0;
     bool bin_ready = false;         // scratch allocated, kernels' LDS sizes registered
     std::vector<int32_t> h_tiles_in;
     // stream-update scratch
-    uint32_t *su_k[2] = {nullptr, nullptr}, *su_v[2] = {nullptr, nullptr};
-    double *su_term = nullptr;
-    uint8_t *su_ins = nullptr;
-    void *su_tmp = nullptr;
+    DevBuf<uint32_t> su_k[2], su_v[2];
+    DevBuf<double> su_term;
+    DevBuf<uint8_t> su_ins;
+    DevBuf<unsigned char> su_tmp;
     size_t su_tmp_bytes = 0;
     // staged batch (set_batch before slide)
     std::vector<int32_t> st_b1, st_b2;
@@ -289,9 +318,9 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     int newest = -1; // global id of newest epoch
     std::vector<Slot> slots;
     std::vector<Group> groups;
-    int *pinned = nullptr; // host-pinned readback words
+    PinBuf<int> pinned; // host-pinned readback words
     std::atomic<unsigned long long> heartbeat{0}; // bumped at every read-back of a frontier loop and every stage of a graph build (dppr_heartbeat)
-    char *dump_pin = nullptr;     // host-pinned landing area of dppr_debug_dump's device reads, owned by the engine for its whole life
+    PinBuf<char> dump_pin;     // host-pinned landing area of dppr_debug_dump's device reads, owned by the engine for its whole life
     static constexpr size_t DUMP_PIN_BYTES = sizeof(GridBar) + 4096;
     // vertex compaction: external id <-> internal id (assigned on first appearance), live zone [0, n_int) and parked
     // zone [V - n_parked, V): IdSpace. Renumbering (dppr_builder.hpp) is decided here:
@@ -301,23 +330,19 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     int renumber_next = 0;         // n_int at which the next slide looks at the live count
     int renumberings = 0;
     std::vector<int32_t> mv_src, mv_dst, mv_zero; // row moves of revived vertices being applied (flush_moves)
-    int *mv_idx = nullptr;         // device: src | dst | zero lists
-    size_t mv_idx_cap = 0;
-    double *mv_tmp = nullptr;      // device: the rows in flight
-    size_t mv_tmp_cap = 0;
-    int *d_ext2int = nullptr;  // device copy of ext2int, refreshed on demand
-    double *d_xfer = nullptr;  // V doubles: staging of p / r in external order
+    DevBuf<int> mv_idx;         // device: src | dst | zero lists
+    DevBuf<double> mv_tmp;      // device: the rows in flight
+    DevBuf<int> d_ext2int;  // device copy of ext2int, refreshed on demand
+    DevBuf<double> d_xfer;  // V doubles: staging of p / r in external order
     // queries of a state (dppr_topk.hpp), all allocated on the first query
-    int *d_int2ext = nullptr;          // device copy of int2ext (live and parked zones), refreshed by the queries only
+    DevBuf<int> d_int2ext;          // device copy of int2ext (live and parked zones), refreshed by the queries only
     unsigned i2e_gen_on_device = 0;    // IdSpace::map_gen that copy was taken at
-    unsigned char *tk_ws = nullptr;    // pass-1 and refinement histograms, per-lane control words (zeroed per query)
-    unsigned long long *tk_out_key = nullptr; // [16][DPPR_TOPK_MAX] result lists before ordering
-    int *tk_out_row = nullptr;
-    int *tk_cand = nullptr;            // candidate lists: [n][cap] internal rows
-    size_t tk_cand_cap = 0;            // ints allocated
-    unsigned char *tk_res = nullptr, *tk_pin = nullptr; // ordered results (device / pinned host): counts, ids, p, r
-    int *ra_buf = nullptr;             // point reads: ids, then p and r outputs
-    size_t ra_cap = 0;                 // bytes allocated
+    DevBuf<unsigned char> tk_ws;    // pass-1 and refinement histograms, per-lane control words (zeroed per query)
+    DevBuf<unsigned long long> tk_out_key; // [16][DPPR_TOPK_MAX] result lists before ordering
+    DevBuf<int> tk_out_row;
+    DevBuf<int> tk_cand;            // candidate lists: [n][cap] internal rows
+    DevBuf<unsigned char> tk_res; PinBuf<unsigned char> tk_pin; // ordered results (device / pinned host): counts, ids, p, r
+    DevBuf<unsigned char> ra_buf;   // point reads: ids, then p and r outputs
     std::vector<int32_t> h_tmp1, h_tmp2;
     std::vector<int32_t> h_tiles; // host copy of the tile edge prefix / group table
     int max_iters = 1 << 20;
@@ -331,15 +356,26 @@ inline void set_err(dppr_engine *e, const char *msg) {
     e->err = msg;
 }
 
+// (`call`: a HIP call, or a buffer's alloc / regrow, whose int status is the policy's hipError_t)
 #define HIP_TRY(call)                                                                                   \
     do {                                                                                                \
-        hipError_t _e = (call);                                                                         \
+        const hipError_t _e = static_cast<hipError_t>(call);                                            \
         if (_e != hipSuccess) {                                                                         \
             char _b[512];                                                                               \
             snprintf(_b, sizeof(_b), "%s in %s at line %d", hipGetErrorString(_e), __FILE__, __LINE__); \
             set_err(e, _b);                                                                             \
             return _e == hipErrorOutOfMemory ? DPPR_ERR_NOMEM : DPPR_ERR_HIP;                           \
         }                                                                                               \
+    } while (0)
+
+// the same for calls whose message is "<prefix><HIP's words>" (no file / line): what a caller of those entry points reads today
+#define HIP_TRY_MSG(prefix, call)                                                 \
+    do {                                                                          \
+        const hipError_t _e = static_cast<hipError_t>(call);                      \
+        if (_e != hipSuccess) {                                                   \
+            set_err(e, (std::string(prefix) + hipGetErrorString(_e)).c_str());    \
+            return _e == hipErrorOutOfMemory ? DPPR_ERR_NOMEM : DPPR_ERR_HIP;     \
+        }                                                                         \
     } while (0)
 
 inline int grid_for(int64_t n, int per_block = BLOCK, int cap = 2048) {

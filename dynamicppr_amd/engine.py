@@ -60,7 +60,7 @@ EXPORTS = [
     "dppr_set_renumbering", "dppr_id_space", "dppr_set_group_push", "dppr_set_binned_sweep", "dppr_device_count", "dppr_set_phase_merge", "dppr_init_solve_at", "dppr_group_init_solve_at", "dppr_set_variant", "dppr_set_batch_grouping",
     "dppr_time_batch_grouping", "dppr_debug_dump", "dppr_hint_next_batch",
     "dppr_bench_line_fills", "dppr_bench_stream_copy", "dppr_build_id", "dppr_heartbeat", "dppr_slide_concurrent", "dppr_renumbering_due", "dppr_debug_bin_tables",
-    "dppr_debug_grouping", "dppr_topk", "dppr_group_topk", "dppr_read_at", "dppr_group_read_at",
+    "dppr_debug_grouping", "dppr_topk", "dppr_group_topk", "dppr_read_at", "dppr_group_read_at", "dppr_debug_live_bytes",
 ]
 
 
@@ -147,6 +147,7 @@ def lib():
     L.dppr_group_topk.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, ip, dp, dp, ip]
     L.dppr_read_at.argtypes = [vp, C.c_int32, ip, C.c_int32, dp, dp]
     L.dppr_group_read_at.argtypes = [vp, C.c_int32, ip, C.c_int32, dp, dp]
+    L.dppr_debug_live_bytes.argtypes = [i64p, i64p]
     for name in EXPORTS:
         if name not in ("dppr_strerror", "dppr_last_error", "dppr_destroy", "dppr_build_id", "dppr_heartbeat"):
             getattr(L, name).restype = C.c_int
@@ -544,6 +545,15 @@ def bench_stream_copy(nbytes=1 << 30, reps=5, device=0):
     if rc:
         raise DpprError(f"bench_stream_copy: {lib().dppr_strerror(rc).decode()}")
     return ms.value
+
+
+def live_bytes():
+    """(device bytes, pinned host bytes) this process holds through the library right now (dppr_debug_live_bytes): the leak check."""
+    dev, pin = C.c_int64(0), C.c_int64(0)
+    rc = lib().dppr_debug_live_bytes(C.byref(dev), C.byref(pin))
+    if rc:
+        raise DpprError(f"debug_live_bytes: {lib().dppr_strerror(rc).decode()}")
+    return dev.value, pin.value
 
 
 def build_id():

@@ -460,6 +460,11 @@ int dppr_debug_dump(dppr_engine *e, char *buf, int32_t cap);
 int dppr_debug_bin_tables(dppr_engine *e, int32_t epoch, int32_t *n_a, int32_t *n_b, int32_t *n_edges, int32_t *n_runs, int32_t *n_tiles,
                           int32_t *acut, int32_t *bcut, uint16_t *hl, int32_t *tdelta, int32_t *tb, uint16_t *dl, int32_t *vb,
                           int64_t *patched, int64_t *rebuilt);
+/* Leak check (backward-compatible addition, ABI 6): bytes of device memory and of pinned host memory that THIS PROCESS holds through
+ * the library at the moment of the call, all engines together -- the library's own count, so other tenants of a shared device do
+ * not show in it. Needs no engine; callable from any thread; either pointer may be NULL. After every engine has been destroyed both
+ * are what they were before the first was created (0 in a process that made no other call that is still running). */
+int dppr_debug_live_bytes(int64_t *device_bytes, int64_t *pinned_bytes);
 
 /* A counter that advances at every host read-back of a frontier loop and every stage of a graph build (ABI 4): a watchdog
  * samples it so that ONE long call (the first solve on a large window, a group's from-scratch solve) is told from a hang

@@ -79,3 +79,17 @@ def test_grouping_path_selection(tmp_path, seed):
                            "-Werror", "-o", exe, os.path.join(ROOT, "tests", "native", "grouping_test.cpp")])
     r = subprocess.run([exe, str(seed), "60"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
     assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-2000:]
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3])
+def test_owning_buffer(tmp_path, seed):
+    """dppr_devbuf.hpp under a counting host allocator that can fail the n-th allocation: destruction releases; moves and swaps
+    transfer without allocating, freeing or leaking; regrow releases before it allocates and leaves an empty buffer on failure; a
+    struct of buffers built up to a failing allocation and dropped leaves nothing (the dppr_add_source shape); a vector of such
+    structs grown past its capacity keeps every buffer; random sequences of all of these end at zero live bytes. ASan's leak
+    check is the second witness."""
+    exe = str(tmp_path / "devbuf_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall",
+                           "-Werror", "-o", exe, os.path.join(ROOT, "tests", "native", "devbuf_test.cpp")])
+    r = subprocess.run([exe, str(seed), "20"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-2000:]
