@@ -29,6 +29,7 @@
 #include <rocprim/rocprim.hpp> // device radix sort only (CSR rebuild, batch grouping); no CUB/Thrust in kernels
 
 #include "../../include/dppr.h"
+#include "dppr_churn_plan.hpp"
 #include "dppr_cut.hpp"
 #include "dppr_devbuf.hpp"
 #include "dppr_idspace.hpp"
@@ -787,6 +788,9 @@ int dppr_debug_dump(dppr_engine *e, char *buf, int32_t cap) {
             "pairs in the three rotating rows %lld %lld %lld, multi-sweep status 0x%x\n", i, g.n, g.gw, (int)g.converged, g.last_epoch,
             (long long)g.st.iterations, (long long)g.st.persist_launches, (long long)g.st.persist_aborts, ok ? "" : "(unreadable) ", f[0], f[1], f[2],
             (unsigned)st);
+        std::string srcs; // (the current ones: dppr_group_replace_source / _add_source / _remove_source change them)
+        for (int k = 0; k < std::min(std::max(g.n, 0), GS_MAX); ++k) srcs += " " + std::to_string(g.src_ext[k]) + "(" + std::to_string(g.src.s[k]) + ")";
+        add("group %zu sources, external(internal) in lane order:%s\n", i, srcs.c_str());
     }
     if (side_stuck) add("(a device read did not complete within 2 s: the remaining ones were skipped, the side stream is abandoned)\n");
     if (have_side && !side_stuck) (void)hipStreamDestroy(side);
@@ -1320,6 +1324,120 @@ int dppr_group_read(dppr_engine *e, int32_t group, int32_t index, double *p, dou
         HIP_TRY(hipStreamSynchronize(e->stream));
     }
     return DPPR_OK;
+}
+
+// ---- sources of a running group (dppr_churn_plan.hpp, dppr_churn.hpp, group_solve_column) -------------------------------
+static_assert(CHURN_LANES == GS_MAX, "dppr_churn_plan.hpp plans for the group size of dppr_multi.hpp");
+static constexpr bool churn_geometry_agrees() {
+    for (int n = 1; n <= GS_MAX; ++n)
+        if (churn_row_width(n, false) != row_width(n) || churn_row_spl(row_width(n)) != row_spl(row_width(n)) ||
+            churn_row_width(n, true) != (n > OCT ? 2 * OCT : OCT))
+            return false;
+    return true;
+}
+static_assert(churn_geometry_agrees(), "dppr_churn_plan.hpp restates row_width / row_spl of dppr_multi.hpp");
+
+int dppr_group_sources(dppr_engine *e, int32_t group, int32_t *out_sources, int32_t *out_n) {
+    GET_GROUP(e, group);
+    if (out_sources)
+        for (int s = 0; s < g.n; ++s) out_sources[s] = g.src_ext[s];
+    if (out_n) *out_n = g.n;
+    return DPPR_OK;
+}
+
+// The three changes share one sequence: every check, every new buffer, then the ids (the first step that touches anything),
+// the re-cut of a fresh id or of the first wide group (the builder's work: outside the event bracket), then the device
+// work on the solver stream -- relayout, owners swapped, column init, the column's loop.
+static int group_churn(dppr_engine *e, int32_t group, ChurnOp op, int32_t index, int32_t new_source, int32_t *out_index, float *out_ms) {
+    static const char *const what[3] = {"group_replace_source", "group_add_source", "group_remove_source"};
+    auto refuse = [&](const char *why) { return fail(e, DPPR_ERR_INVALID, (std::string(what[op]) + ": " + why).c_str()); };
+    GET_GROUP(e, group);
+    const ChurnPlan pl = churn_plan(op, g.n, g.gw, index, e->group_full_rows, e->wide_groups);
+    if (!pl.ok) return refuse(op == CHURN_ADD ? "the group holds 16 sources" : op == CHURN_REMOVE && g.n <= 1 ? "the last source of a group cannot be removed" : "bad source index");
+    if (op != CHURN_REMOVE && (new_source < 0 || new_source >= e->V)) return refuse("vertex out of range");
+    if (!g.converged || g.last_epoch < 0) return refuse("the group is not converged (solve or update it first)");
+    Epoch *epp = find_epoch(e, g.last_epoch);
+    if (!epp) return refuse("the epoch the group was last solved on is not resident any more");
+    const Epoch &ep = *epp;
+    HIP_TRY(hipSetDevice(e->device));
+    // every new buffer before anything changes (a failure: the locals go out of scope, the group is as it was)
+    const size_t V = (size_t)e->V;
+    const bool new_x = x_stride(pl.gw) != x_stride(g.gw);
+    DevBuf<double> p2, r2, x_new, x2_new; // after the swap below they own the OLD arrays, released when this call returns
+    if (pl.relayout) {
+        HIP_TRY(p2.alloc((size_t)pl.gw * V));
+        HIP_TRY(r2.alloc((size_t)pl.gw * V));
+    }
+    if (new_x) {
+        HIP_TRY(x_new.alloc((size_t)x_stride(pl.gw) * V));
+        HIP_TRY(x2_new.alloc((size_t)x_stride(pl.gw) * V));
+    }
+    int src_int = -1;
+    if (op != CHURN_REMOVE) { // the id (a vertex outside the window receives one, a parked one is revived), rows moved in the old layout
+        (void)to_int(e, new_source);
+        if (int rc = flush_moves(e)) return rc;
+        src_int = e->ext2int[(size_t)new_source];
+        if (pl.recut) e->wide_groups = true;
+        if (int rc = recut_stale_groups(e)) return rc; // (a fresh id lies beyond every resident epoch's tables; the first wide group halves the sweep groups)
+    }
+    HIP_TRY(hipEventRecord(e->ev0, e->stream));
+    if (pl.relayout) {
+        ColMap cm;
+        for (int s = 0; s < GS_MAX; ++s) cm.m[s] = pl.map[s];
+        const int grid = grid_for((int64_t)e->V, BLOCK / pl.gw);
+        hipLaunchKernelGGL(k_grow_remap, dim3(grid), dim3(BLOCK), 0, e->stream, p2.get(), g.p.get(), e->V, pl.gw, g.gw, cm);
+        hipLaunchKernelGGL(k_grow_remap, dim3(grid), dim3(BLOCK), 0, e->stream, r2.get(), g.r.get(), e->V, pl.gw, g.gw, cm);
+        HIP_TRY(hipGetLastError());
+        g.p.swap(p2);
+        g.r.swap(r2);
+    }
+    if (new_x) { // (both activity bitmaps are clear between loops: nothing of the snapshot rows is carried over)
+        g.x.swap(x_new);
+        g.x2.swap(x2_new);
+    }
+    SrcN src;
+    int src_ext[GS_MAX] = {0};
+    for (int s = 0; s < GS_MAX; ++s) {
+        src.s[s] = s < pl.n && pl.map[s] >= 0 ? g.src.s[pl.map[s]] : -1;
+        src_ext[s] = s < pl.n && pl.map[s] >= 0 ? g.src_ext[pl.map[s]] : 0;
+    }
+    if (pl.lane >= 0) {
+        src.s[pl.lane] = src_int;
+        src_ext[pl.lane] = new_source;
+    }
+    g.src = src;
+    memcpy(g.src_ext, src_ext, sizeof(src_ext));
+    g.n = pl.n;
+    g.gw = pl.gw;
+    g.spl = pl.spl;
+    if (pl.lane >= 0) {
+        // (a padding lane that is taken into use is initialised like any other, not trusted to be zero; the new column is
+        // zero in the parked zone too, which satisfies any park_eps)
+        hipLaunchKernelGGL(k_gcol_init, dim3(grid_for(e->V)), dim3(BLOCK), 0, e->stream, g.p.get(), g.r.get(), e->V, g.gw, pl.lane, src_int);
+        HIP_TRY(hipGetLastError());
+        g.converged = false;
+        if (int rc = group_solve_column(e, g, ep)) return rc;
+    }
+    HIP_TRY(hipEventRecord(e->ev1, e->stream));
+    HIP_TRY(hipEventSynchronize(e->ev1));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+    if (out_ms) *out_ms = ms;
+    if (out_index) *out_index = pl.lane;
+    g.converged = true; // at the same conv_eps, on the same last_epoch: the next dppr_group_update seeds from the batch tails as before
+    return DPPR_OK;
+}
+
+int dppr_group_replace_source(dppr_engine *e, int32_t group, int32_t index, int32_t new_source, float *out_ms) {
+    return group_churn(e, group, CHURN_REPLACE, index, new_source, nullptr, out_ms);
+}
+
+int dppr_group_add_source(dppr_engine *e, int32_t group, int32_t new_source, int32_t *out_index, float *out_ms) {
+    return group_churn(e, group, CHURN_ADD, -1, new_source, out_index, out_ms);
+}
+
+int dppr_group_remove_source(dppr_engine *e, int32_t group, int32_t index) {
+    return group_churn(e, group, CHURN_REMOVE, index, -1, nullptr, nullptr);
 }
 
 // ---- queries of a state (dppr_topk.hpp, dppr_host_query.hpp) -----------------------------------------------------------

@@ -382,6 +382,23 @@ int group_loop(dppr_engine *e, Group &g, const Epoch &ep, int phase, double eps,
     return DPPR_OK;
 }
 
+// One freshly initialised column of an otherwise converged group (dppr_churn.hpp: p = 0, r = e_src in that lane), solved on
+// `ep`: Init + ExecuteMainLoop(0) for that source, as dppr_group_init_solve_at runs them for all. The tolerance is the group's
+// own, so dense seeding finds exactly the one legal vertex -- every other column satisfies |r| <= conv_eps and stays inert in
+// every sweep (the legal-push test is per source). The loop histories size the first chunk of the NEXT UPDATE's loops, and a
+// from-scratch loop is no predictor of those: they are put back.
+int group_solve_column(dppr_engine *e, Group &g, const Epoch &ep) {
+    int hint[2], hist[2][4], dense[2][4];
+    memcpy(hint, g.iter_hint, sizeof(hint));
+    memcpy(hist, g.iter_hist, sizeof(hist));
+    memcpy(dense, g.dense_hist, sizeof(dense));
+    const int rc = group_loop(e, g, ep, 0, g.conv_eps, /*tails=*/false);
+    memcpy(g.iter_hint, hint, sizeof(hint));
+    memcpy(g.iter_hist, hist, sizeof(hist));
+    memcpy(g.dense_hist, dense, sizeof(dense));
+    return rc;
+}
+
 int group_stream_update(dppr_engine *e, Group &g, const Epoch &ep) {
     const int L = ep.L;
     if (L == 0) return DPPR_OK;

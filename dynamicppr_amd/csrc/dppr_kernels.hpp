@@ -22,6 +22,7 @@
 //   dppr_resident.hpp a run of dense iterations as one resident launch (state on chip, data-flow synchronisation)
 //   dppr_update.hpp   IncrementalBatchUpdate (lock-free, batch-index order)
 //   dppr_builder.hpp  sliding-window graph builder (full sort / incremental merge), id translation
+//   dppr_churn.hpp    a source group changes its sources: column init, row re-interleaving
 //   dppr_multi.hpp    multi-source batched sweeps (included separately by the engine)
 #pragma once
 
@@ -31,3 +32,4 @@
 #include "dppr_resident.hpp"
 #include "dppr_update.hpp"
 #include "dppr_builder.hpp"
+#include "dppr_churn.hpp"

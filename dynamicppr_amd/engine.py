@@ -61,6 +61,7 @@ EXPORTS = [
     "dppr_time_batch_grouping", "dppr_debug_dump", "dppr_hint_next_batch",
     "dppr_bench_line_fills", "dppr_bench_stream_copy", "dppr_build_id", "dppr_heartbeat", "dppr_slide_concurrent", "dppr_renumbering_due", "dppr_debug_bin_tables",
     "dppr_debug_grouping", "dppr_topk", "dppr_group_topk", "dppr_read_at", "dppr_group_read_at", "dppr_debug_live_bytes",
+    "dppr_group_sources", "dppr_group_replace_source", "dppr_group_add_source", "dppr_group_remove_source",
 ]
 
 
@@ -148,6 +149,10 @@ def lib():
     L.dppr_read_at.argtypes = [vp, C.c_int32, ip, C.c_int32, dp, dp]
     L.dppr_group_read_at.argtypes = [vp, C.c_int32, ip, C.c_int32, dp, dp]
     L.dppr_debug_live_bytes.argtypes = [i64p, i64p]
+    L.dppr_group_sources.argtypes = [vp, C.c_int32, ip, ip]
+    L.dppr_group_replace_source.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, fp]
+    L.dppr_group_add_source.argtypes = [vp, C.c_int32, C.c_int32, ip, fp]
+    L.dppr_group_remove_source.argtypes = [vp, C.c_int32, C.c_int32]
     for name in EXPORTS:
         if name not in ("dppr_strerror", "dppr_last_error", "dppr_destroy", "dppr_build_id", "dppr_heartbeat"):
             getattr(L, name).restype = C.c_int
@@ -430,6 +435,33 @@ class Engine:
         self._ck(self._L.dppr_group_read(self._h, group, int(index), p.ctypes.data_as(dp), r.ctypes.data_as(dp)),
                  "group_read")
         return p, r
+
+    # ---- sources of a running group (exclusive calls, like add_source_group; include/dppr.h) ----
+    def group_sources(self, group):
+        """The external ids of the group's sources in lane order."""
+        out = np.empty(16, dtype=np.int32)
+        n = C.c_int32(0)
+        self._ck(self._L.dppr_group_sources(self._h, int(group), out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)), "group_sources")
+        self._group_n[group] = n.value
+        return [int(v) for v in out[:n.value]]
+
+    def group_replace_source(self, group, index, source):
+        """Lane `index` of a converged group becomes `source`, solved from scratch at the group's tolerance: ms of the device work."""
+        ms = C.c_float(0)
+        self._ck(self._L.dppr_group_replace_source(self._h, int(group), int(index), int(source), C.byref(ms)), "group_replace_source")
+        return ms.value
+
+    def group_add_source(self, group, source):
+        """One more source for a converged group: (its index, ms of the device work)."""
+        idx, ms = C.c_int32(-1), C.c_float(0)
+        self._ck(self._L.dppr_group_add_source(self._h, int(group), int(source), C.byref(idx), C.byref(ms)), "group_add_source")
+        self._group_n[group] = idx.value + 1
+        return idx.value, ms.value
+
+    def group_remove_source(self, group, index):
+        """Drops source `index`; the sources behind it move down by one."""
+        self._ck(self._L.dppr_group_remove_source(self._h, int(group), int(index)), "group_remove_source")
+        self.group_sources(group)   # (keeps _group_n in step: group_topk / group_read_at size their outputs from it)
 
     # ---- queries of a state (top-k and point reads on the device) ----
     def topk(self, slot, k, min_p=0.0):

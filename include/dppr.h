@@ -322,6 +322,45 @@ int dppr_group_read(dppr_engine *e, int32_t group, int32_t index, double *p, dou
 int dppr_group_stats(dppr_engine *e, int32_t group, dppr_stats_t *out); /* summed over the sources */
 int dppr_group_reset_stats(dppr_engine *e, int32_t group);
 
+/* ---- sources of a running group: replace, add, drop (backward-compatible additions, ABI 6) ----
+ * A group's set of sources may change while the stream runs, without a second group and without re-solving the
+ * sources that stay. The reference has no counterpart (one source per process, gpu/PPRGPU.cuh:24).
+ *
+ * Common contract. The group must be converged (a completed dppr_group_init_solve / dppr_group_update) and the
+ * epoch it was last solved on must still be resident, DPPR_ERR_INVALID otherwise. A new source's column is solved
+ * from scratch ON THAT EPOCH -- Init + ExecuteMainLoop(0) for that source, exactly as dppr_group_init_solve_at runs
+ * them (gpu/PPRCommon.cuh:12-22, gpu/PPRRevPushGPU.cuh:97-131) -- with the tolerance the group is converged to:
+ * there is no eps argument, any other value would either move the other columns or leave the group with two
+ * tolerances. The other sources are not changed by value: p and r as dppr_group_read returns them are equal
+ * before and after, element for element (their columns fail the legal-push test in every sweep of the loop).
+ * Afterwards the group is converged at the same tolerance on the same epoch, and the next dppr_group_update
+ * seeds from the batch tails as before.
+ * EXCLUSIVE calls, like dppr_add_source_group: they assign or revive vertex ids, move state rows and may re-cut
+ * the sweep groups of every resident epoch -- never beside dppr_slide_concurrent or any other call on the engine.
+ * Every argument is checked first and a rejected call touches nothing (no id assigned, no parked vertex revived,
+ * no row moved): a bad group or index, a source outside [0, V), a group that is not converged, an epoch that is
+ * gone, add at 16 sources, remove at 1 source -- all DPPR_ERR_INVALID. Every buffer a call needs is obtained
+ * before anything changes: after DPPR_ERR_NOMEM the group is exactly as before.
+ * *out_ms (may be NULL): hipEvent time of the device work -- the column's init, the re-interleaving of the rows
+ * where the row width changes, the column's frontier loop; the sweep-group re-cut that a fresh vertex id or the
+ * first group of more than 8 sources needs is builder work and stays outside, as everywhere else. dppr_group_stats:
+ * the loop's iterations, sum_F, sum_E, sum_N, inspected and sweep fields are added; batches, records and gpu_ms
+ * describe dppr_group_update and are not. */
+/* The external ids of the group's sources in lane order (the `index` of dppr_group_read) and their number. */
+int dppr_group_sources(dppr_engine *e, int32_t group, int32_t *out_sources /* [16], may be NULL */, int32_t *out_n);
+/* Lane `index` becomes new_source; the row width stays, nothing is re-interleaved. The vertex the lane had before, or
+ * one another lane has, is allowed and means a re-solve of that lane. */
+int dppr_group_replace_source(dppr_engine *e, int32_t group, int32_t index, int32_t new_source, float *out_ms);
+/* One more source; it takes index n (*out_index, may be NULL). An odd group's padding double is taken into use as it
+ * is (re-initialised), otherwise p / r are re-interleaved to rows of two more doubles in one streaming pass each
+ * (the old and the new rows exist side by side during the call). The ninth source makes the group a wide one
+ * (16-byte lanes; sweep groups of at most 512 vertices on this engine from then on). */
+int dppr_group_add_source(dppr_engine *e, int32_t group, int32_t new_source, int32_t *out_index, float *out_ms);
+/* Drops source `index`. The sources behind it move down by one -- the order is kept, THE CALLER'S HIGHER INDICES
+ * DECREASE BY 1 -- and the rows are re-interleaved to the width of n - 1 sources, which gives the memory back.
+ * The dropped vertex no longer counts as in use when the ids are renumbered. No loop runs. */
+int dppr_group_remove_source(dppr_engine *e, int32_t group, int32_t index);
+
 /* ---- queries of a state: top-k and point reads (added in ABI 6, backward compatible) ----
  * The answer a dense dppr_read / dppr_group_read would give, without moving V doubles per source to the
  * host: a radix select runs on the device over the rows that hold a vertex (the live and the parked
