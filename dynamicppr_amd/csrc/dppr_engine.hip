@@ -33,6 +33,7 @@
 #include "dppr_cut.hpp"
 #include "dppr_devbuf.hpp"
 #include "dppr_idspace.hpp"
+#include "dppr_loop_plan.hpp"
 #include "dppr_kernels.hpp"
 #include "dppr_multi.hpp"
 #include "dppr_gpush.hpp"
@@ -1054,14 +1055,8 @@ int dppr_stats(dppr_engine *e, int32_t slot, dppr_stats_t *out) {
     GET_SLOT(e, slot);
     if (!out) return DPPR_ERR_INVALID;
     HIP_TRY(hipSetDevice(e->device));
-    int rc = pull_device_stats(e, s);
+    int rc = pull_device_stats(e, s.dstats, s.st);
     if (rc) return rc;
-    // every enqueued vertex is a frontier member of a later iteration, except the seeds
-    s.st.sum_N = s.st.sum_F;
-    // SURVEY.md 8(d); its Inspect term (8 bytes per vertex and pass) is counted for the passes that RAN:
-    // after a converged solve the frontier is seeded from the batch tails and no vertex is scanned
-    s.st.algorithmic_bytes = 8ll * s.st.inspected + 45ll * s.st.records + 72ll * s.st.sum_F + 24ll * s.st.sum_E +
-                             4ll * s.st.sum_N;
     *out = s.st;
     return DPPR_OK;
 }
@@ -1336,6 +1331,8 @@ static constexpr bool churn_geometry_agrees() {
     return true;
 }
 static_assert(churn_geometry_agrees(), "dppr_churn_plan.hpp restates row_width / row_spl of dppr_multi.hpp");
+static_assert(PLAN_RES_MAX_SWEEPS == RES_MAX_SWEEPS && PLAN_GPUSH_LOG == GPUSH_LOG && PLAN_TINY_N == TINY_N && PLAN_TINY_E == TINY_E,
+              "dppr_loop_plan.hpp restates RES_MAX_SWEEPS of dppr_resident.hpp and GPUSH_LOG / TINY_N / TINY_E of dppr_gpush.hpp");
 
 int dppr_group_sources(dppr_engine *e, int32_t group, int32_t *out_sources, int32_t *out_n) {
     GET_GROUP(e, group);
@@ -1499,19 +1496,8 @@ int dppr_group_stats(dppr_engine *e, int32_t group, dppr_stats_t *out) {
     GET_GROUP(e, group);
     if (!out) return DPPR_ERR_INVALID;
     HIP_TRY(hipSetDevice(e->device));
-    static thread_local IterStats h[2];
-    HIP_TRY(hipMemcpyAsync(h, g.dstats, sizeof(h), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    unsigned long long t = 0, ts = 0;
-    for (int i = 0; i < STAT_SLOTS; ++i) {
-        t += h[0].blk_E[i];
-        ts += h[1].blk_E[i];
-    }
-    g.st.sum_E = (int64_t)(t + ts);
-    g.st.sweep_E = (int64_t)ts;
-    g.st.sum_N = g.st.sum_F;
-    g.st.algorithmic_bytes = 8ll * g.st.inspected + 45ll * g.st.records + 72ll * g.st.sum_F + 24ll * g.st.sum_E +
-                             4ll * g.st.sum_N;
+    int rc = pull_device_stats(e, g.dstats, g.st);
+    if (rc) return rc;
     *out = g.st;
     return DPPR_OK;
 }

@@ -6,20 +6,60 @@ namespace {
 
 // ---------------------------------------------------------------------------- f2: groups
 // The group kernels are instantiated per row width (dppr_multi.hpp: GW = 2, 4, .. 16 doubles; one double per lane of
-// an octet up to 8, two beyond): f(SPL, GW) is called with the two as compile-time constants.
+// an octet up to 8, two beyond), the sweep also per size of a sweep group (nvx vertices: 1024, or 512 once a 16-wide group
+// exists -- a wide row always, a narrow one on an engine that also has a wide group): f(SPL, GW, NVX) is called with the
+// three as compile-time constants.
 template <int N> using IC = std::integral_constant<int, N>;
 template <class F>
-void with_row(int gw, F &&f) {
+void with_row(int gw, int nvx, F &&f) {
+    auto narrow = [&](auto w) {
+        if (nvx == 512) f(IC<1>{}, w, IC<512>{});
+        else f(IC<1>{}, w, IC<1024>{});
+    };
     switch (gw) {
-    case 2: f(IC<1>{}, IC<2>{}); break;
-    case 4: f(IC<1>{}, IC<4>{}); break;
-    case 6: f(IC<1>{}, IC<6>{}); break;
-    case 8: f(IC<1>{}, IC<8>{}); break;
-    case 10: f(IC<2>{}, IC<10>{}); break;
-    case 12: f(IC<2>{}, IC<12>{}); break;
-    case 14: f(IC<2>{}, IC<14>{}); break;
-    default: f(IC<2>{}, IC<16>{}); break;
+    case 2: narrow(IC<2>{}); break;
+    case 4: narrow(IC<4>{}); break;
+    case 6: narrow(IC<6>{}); break;
+    case 8: narrow(IC<8>{}); break;
+    case 10: f(IC<2>{}, IC<10>{}, IC<512>{}); break;
+    case 12: f(IC<2>{}, IC<12>{}, IC<512>{}); break;
+    case 14: f(IC<2>{}, IC<14>{}, IC<512>{}); break;
+    default: f(IC<2>{}, IC<16>{}, IC<512>{}); break;
     }
+}
+template <class F>
+void with_row(int gw, F &&f) { // (kernels that do not depend on the sweep groups: f(SPL, GW))
+    with_row(gw, 512, [&](auto spl, auto w, auto) { f(spl, w); });
+}
+
+// One launch of k_gsweep (dppr_multi.hpp). MULTI: n sweeps behind grid barriers, one workgroup per sweep group, pagerank
+// credited as the launch decides per sweep (CM = 2); otherwise ONE sweep whose crediting is a compile-time constant (CM = `owed`),
+// the sweep groups beyond the grid dealt by the device counter q_take.
+struct GSweepLaunch {
+    int grid;                     // workgroups
+    const int *cnt_in;            // frontier sizes of the live snapshot
+    int *cnt_out, *cnt_zero;      // ... of the one the (last) sweep leaves; a row the launch zeroes for the one after
+    int *log;                     // a row of frontier sizes per sweep
+    int n;                        // sweeps
+    GridBar *bar = nullptr;       // multi-sweep launches: barrier, status word, roll-call limits
+    int *status = nullptr;
+    unsigned long long ticks = 0;
+    int rollcall_extra = 0;
+    int *q_take = nullptr, *q_zero = nullptr; // one-sweep launches: the group counter to take tickets from, the one to zero
+};
+template <bool MULTI>
+void launch_gsweep(dppr_engine *e, Group &g, const Epoch &ep, int phase, double eps, bool owed, const GSweepLaunch &a) {
+    with_row(g.gw, ep.ggrp_max_tiles * WAVE, [&](auto spl, auto gw, auto nvx) {
+        auto go = [&](auto cm) {
+            hipLaunchKernelGGL((k_gsweep<decltype(spl)::value, decltype(gw)::value, decltype(nvx)::value, MULTI, decltype(cm)::value>),
+                               dim3(a.grid), dim3(GNT), 0, e->stream, ep.grp_n_int, ep.gtab, ep.n_ggroups, a.cnt_in, e->gsweep_hot_rows,
+                               ep.out_col, g.x, g.x2, g.act[0], g.act[1], g.r, g.p, a.cnt_out, a.cnt_zero, phase, eps, g.dstats + 1, a.log,
+                               a.n, a.bar, a.status, a.ticks, a.rollcall_extra, owed ? 1 : 0, a.q_take, a.q_zero);
+        };
+        if constexpr (MULTI) go(IC<2>{});
+        else if (owed) go(IC<1>{});
+        else go(IC<0>{});
+    });
 }
 
 // workgroups of the multi-sweep form of k_gsweep that the device holds at once
@@ -74,30 +114,22 @@ int group_push_tail(dppr_engine *e, Group &g, const Epoch &ep, int phase, double
     HIP_TRY(hipGetLastError());
     *entered = true;
     const int credit_first = *owed ? 1 : 0; // (iteration 0 of this mode settles it; every later one credits as it snapshots)
-    // what an iteration may cost here: a sweep's floor is ~0.02 us per sweep group, a returning f64 atomic ~1 / 20 000 us
-    // (round 6: 20 in-edges per sweep group, was 200 -- on the headline's 3 075 groups a push iteration of up to 615 K in-edges x 10 sources cost up
-    // to 540 us where a near-empty sweep costs 50-85: bound 615 K / 150 K / 60 K / 40 K / 20 K -> 12.37 / 12.24 / 12.18 / 12.19 / 12.23 ms per batch,
-    // two runs each on one box; twitter / friendster groups and resident-size windows: unchanged)
-    const long long max_edges = e->gpush_max_edges > 0 ? e->gpush_max_edges : std::max<long long>(4096, 20ll * std::max(ep.n_ggroups, 1));
+    const long long max_edges = gpush_edge_bound(e->gpush_max_edges, ep.n_ggroups);
     const int grid = 256;
     static const bool trace = getenv("DPPR_GROUP_TRACE") != nullptr;
     int it_done = 0;
     long long known_n = pairs_at_entry; // (an upper bound of the frontier's vertices until the first read-back)
     bool tiny_declined = false;
-    long long last_adds = pairs_at_entry <= 64 ? 0 : -1; // edge x source adds of the last iteration run (-1: not known yet)
+    long long last_adds = gpush_adds_at_entry(pairs_at_entry); // edge x source adds of the last iteration run (-1: not known yet)
     for (;;) {
-        if (known_n <= TINY_N && last_adds >= 0 && last_adds <= TINY_E / 2 && !tiny_declined) {
+        if (gpush_take_tiny(known_n, last_adds, tiny_declined)) {
             // a frontier of a few hundred vertices: a run of iterations as ONE single-workgroup launch
             with_row(g.gw, [&](auto spl, auto gw) {
                 hipLaunchKernelGGL((k_gpush_tiny<decltype(spl)::value, decltype(gw)::value>), dim3(1), dim3(1024), 0, e->stream, g.pctl, g.plist[0],
                                    g.plist[1], ep.row_ptr, ep.adj, ep.hub_degp1, g.r, g.p, g.act[0], phase, eps, g.dstats, GPUSH_LOG, credit_first);
             });
         } else {
-        // iterations per chunk (<= GPUSH_LOG): down here the frontier about halves per iteration, so the first chunk is
-        // sized to reach the single-workgroup form (an iteration that finds nothing is three empty dispatches)
-        int m = 2;
-        if (it_done == 0)
-            for (long long f = pairs_at_entry; f > 128 && m < GPUSH_LOG; f >>= 2) ++m;
+        const int m = gpush_chunk(it_done, pairs_at_entry); // iterations of this chunk (<= GPUSH_LOG)
         tiny_declined = false;
         for (int k = 0; k < m; ++k) {
             hipLaunchKernelGGL(k_gpush_scan, dim3(1), dim3(1024), 0, e->stream, g.pctl, g.plist[0], g.plist[1], ep.row_ptr, g.ppre, cap - 1, max_edges);
@@ -114,16 +146,14 @@ int group_push_tail(dppr_engine *e, Group &g, const Epoch &ep, int phase, double
         HIP_TRY(hipMemcpyAsync(&h, g.pctl, sizeof(GPushCtl), hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(loop_wait(e));
         for (int i = it_done; i < h.it; ++i) {
-            long long F = 0;
-            for (int s = 0; s < GWM; ++s) F += h.F[i & (GPUSH_LOG - 1)][s];
+            const long long F = lane_sum(h.F[i & (GPUSH_LOG - 1)]);
             if (F == 0) continue;
-            g.st.iterations++;
-            g.st.sum_F += F;
+            account_iteration(g.st, F, ITER_PUSH);
             ++*iters;
             if (trace)
                 fprintf(stderr, "[gpush ] phase %d iteration +%d  frontier pairs %9lld  adds %lld\n", phase, i, F, h.atomics[i & (GPUSH_LOG - 1)]);
         }
-        if (h.it == it_done && !h.stop && known_n <= TINY_N) tiny_declined = true; // (too many vertices or in-edges for one workgroup)
+        if (gpush_tiny_declined(h.it > it_done, h.stop != 0, known_n)) tiny_declined = true; // (too many vertices or in-edges for one workgroup)
         if (h.it > it_done) last_adds = h.atomics[(h.it - 1) & (GPUSH_LOG - 1)];
         it_done = h.it;
         known_n = h.n[h.it & 1];
@@ -173,11 +203,7 @@ int group_loop(dppr_engine *e, Group &g, const Epoch &ep, int phase, double eps,
     }
     HIP_TRY(hipGetLastError());
     int *log = g.cnt + 5 * GWM;
-    auto any_left = [&](const int *c) {
-        for (int s = 0; s < GWM; ++s)
-            if (c[s] > 0) return true;
-        return false;
-    };
+    auto any_left = [](const int *row) { return lane_sum(row) > 0; };
     HIP_TRY(hipMemcpyAsync(e->pinned, g.cnt + cur * GWM, sizeof(int) * GWM, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(loop_wait(e));
     bool more = any_left(e->pinned);
@@ -188,39 +214,25 @@ int group_loop(dppr_engine *e, Group &g, const Epoch &ep, int phase, double eps,
         e->gsweep_grid_cap = std::min(2 * cus, STAT_SLOTS);
     }
     const int sweep_grid = std::min(std::max(ep.n_ggroups, 1), e->gsweep_grid_cap);
-    int follow = 4; // size of the next follow-up chunk of one-sweep launches
     // pagerank is credited every other sweep (dppr_multi.hpp): the seeding credited its snapshot, so the first sweep defers;
     // `owed` = the live snapshot's share has not been added yet, the next sweep is a crediting one
     bool owed = false;
-    // the tail of the loop as pushes (dppr_gpush.hpp): below push_thr frontier pairs, one-sweep launches only
-    long long push_thr = e->gpush_enter_pairs == 0 ? 0 : e->gpush_enter_pairs > 0 ? e->gpush_enter_pairs : std::max(64, ep.n_ggroups * e->gpush_auto_factor);
-    bool push_gave_up = false;
-    int dense_len = -1; // sweeps of this loop before the frontier was that small
-    const int nvx = ep.ggrp_max_tiles * WAVE; // vertices per sweep group of this epoch's tables: 1024, or 512 once a 16-wide group exists
+    // the tail of the loop as pushes (dppr_gpush.hpp): below plan.push_thr frontier pairs, one-sweep launches only
+    GroupLoopPlan plan;
+    plan.push_thr = group_push_threshold(e->gpush_enter_pairs, ep.n_ggroups, e->gpush_auto_factor);
     for (int it = 0; more;) {
         if (it >= e->max_iters) return fail(e, DPPR_ERR_NOT_CONVERGED, "iteration cap hit");
         // ---- a window whose sweep groups are all resident at once: a run of sweeps as ONE launch (k_gsweep<.., true>)
         const int mcap = e->group_resident && e->persist_mode && e->persist_ok && e->chunk_iters > 1 ? group_multi_capacity(e, g.spl) : 0;
         if (mcap > 0 && ep.n_ggroups > 0 && ep.n_ggroups <= mcap) {
-            int n = g.iter_hint[hp] > it ? g.iter_hint[hp] - it + RESIDENT_MARGIN : 2 * e->chunk_iters;
-            n = std::max(2, std::min(n, GMULTI_MAX));
-            if (e->chunk_explicit) n = std::min(n, std::max(e->chunk_iters, 2)); // (tests: launches that stop mid-loop and are resumed)
+            const int n = group_multi_sweeps(g.hist.hint[hp], it, e->chunk_iters, e->chunk_explicit);
             HIP_TRY(hipMemsetAsync(g.mlog, 0, sizeof(int) * (size_t)(n + 2) * GWM, e->stream));
             HIP_TRY(hipMemsetAsync(e->bar, 0, sizeof(GridBar), e->stream));
             if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[0], e->stream));
-            int *status = g.mlog, *rows = g.mlog + GWM;
-#define DPPR_LAUNCH_GMULTI(SPL, GW, NVX)                                                                                 \
-    hipLaunchKernelGGL((k_gsweep<SPL, GW, NVX, true, 2>), dim3(ep.n_ggroups), dim3(GNT), 0, e->stream, ep.grp_n_int, ep.gtab,   \
-                       ep.n_ggroups, g.cnt + cur * GWM, e->gsweep_hot_rows, ep.out_col, g.x, g.x2, g.act[0], g.act[1], g.r, g.p, \
-                       g.cnt + 3 * GWM, g.cnt + 4 * GWM, phase, eps, g.dstats + 1, rows, n, e->bar, status, e->persist_ticks,    \
-                       e->persist_rollcall_extra, owed ? 1 : 0, (int *)nullptr, (int *)nullptr)
-            with_row(g.gw, [&](auto spl, auto gw) {
-                constexpr int SPL = decltype(spl)::value, GW = decltype(gw)::value;
-                if constexpr (SPL == 2) DPPR_LAUNCH_GMULTI(2, GW, 512);
-                else if (nvx == 512) DPPR_LAUNCH_GMULTI(1, GW, 512); // (a narrow group on an engine that also has a wide one)
-                else DPPR_LAUNCH_GMULTI(1, GW, 1024);
-            });
-#undef DPPR_LAUNCH_GMULTI
+            // (g.mlog: the status word's row, then a row of frontier sizes per sweep)
+            launch_gsweep<true>(e, g, ep, phase, eps, owed,
+                                {ep.n_ggroups, g.cnt + cur * GWM, g.cnt + 3 * GWM, g.cnt + 4 * GWM, g.mlog + GWM, n, e->bar, g.mlog,
+                                 e->persist_ticks, e->persist_rollcall_extra});
             if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[1], e->stream));
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(e->pinned, g.mlog, sizeof(int) * (size_t)(n + 2) * GWM, hipMemcpyDeviceToHost, e->stream));
@@ -235,14 +247,7 @@ int group_loop(dppr_engine *e, Group &g, const Epoch &ep, int phase, double eps,
                 continue;
             }
             const int sweeps = st & GSM_SWEEPS;
-            for (int k = 0; k < sweeps; ++k) {
-                const int *f = e->pinned + GWM + k * GWM;
-                g.st.iterations++;
-                g.st.pull_iterations++;
-                for (int s = 0; s < GWM; ++s) g.st.sum_F += f[s];
-                for (int s = 0; s < GWM; ++s) g.st.sweep_F += f[s];
-                active_iters = it + k + 1;
-            }
+            account_sweeps(g.st, e->pinned + GWM, sweeps, GWM, ITER_SWEEP, it, &active_iters); // (the launch ran no sweep on an empty frontier)
             if (e->profiling) {
                 float ms = 0;
                 HIP_TRY(hipEventElapsedTime(&ms, e->evpool[0], e->evpool[1]));
@@ -263,46 +268,14 @@ int group_loop(dppr_engine *e, Group &g, const Epoch &ep, int phase, double eps,
             more = any_left(e->pinned + GWM + sweeps * GWM);
             continue;
         }
-        // One-sweep launches are enqueued in chunks; a launch that finds every frontier empty returns at once, but it
-        // still costs a dispatch (~4 us + gap). Consecutive batches take about the same number of sweeps, so the first
-        // chunk is the SHORTEST of the last four loops of this phase (almost surely needed in full), and what follows
-        // doubles from 4: a boundary (read-back + relaunch) costs about three empty dispatches.
-        int n;
-        if (it == 0) {
-            int lo = 0;
-            for (int h : (push_thr > 0 ? g.dense_hist : g.iter_hist)[hp]) lo = h > 0 && (lo == 0 || h < lo) ? h : lo;
-            n = lo > 0 ? lo : e->chunk_iters;
-            follow = 4;
-        } else if (push_thr > 0 && !push_gave_up) {
-            // the push form takes over below push_thr pairs and a sweep of the tail costs its floor whatever it finds: go
-            // only as far as the frontier is sure to stay above the threshold (it shrinks by <= ~4x per sweep down there)
-            long long F = 0;
-            for (int s = 0; s < GWM; ++s) F += e->pinned[cur * GWM + s];
-            n = 1;
-            for (long long f = F / 4; f > push_thr && n < e->chunk_iters; f /= 4) ++n;
-        } else {
-            n = std::min(follow, e->chunk_iters);
-            follow *= 2;
-        }
-        if (e->chunk_explicit) n = std::min(n, std::max(e->chunk_iters, 1));
-        n = std::max(1, std::min(n, MAX_CHUNK));
+        // ---- one-sweep launches, enqueued in chunks (GroupLoopPlan::next_chunk); e->pinned holds the live frontier sizes in row `cur`
+        const int n = plan.next_chunk(g.hist, hp, it, lane_sum(e->pinned + cur * GWM), e->chunk_iters, e->chunk_explicit);
         for (int k = 0; k < n; ++k) {
             const int nxt = (cur + 1) % 3, zer = (cur + 2) % 3;
             if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[2 * k], e->stream));
-#define DPPR_LAUNCH_GSWEEP(SPL, GW, NVX) do { if (owed) DPPR_LAUNCH_GSWEEP_CM(SPL, GW, NVX, 1); else DPPR_LAUNCH_GSWEEP_CM(SPL, GW, NVX, 0); } while (0)
-#define DPPR_LAUNCH_GSWEEP_CM(SPL, GW, NVX, CM)                                                                          \
-    hipLaunchKernelGGL((k_gsweep<SPL, GW, NVX, false, CM>), dim3(sweep_grid), dim3(GNT), 0, e->stream, ep.grp_n_int, ep.gtab,  \
-                       ep.n_ggroups, g.cnt + cur * GWM, e->gsweep_hot_rows, ep.out_col, g.x, g.x2, g.act[0], g.act[1], g.r, g.p,  \
-                       g.cnt + nxt * GWM, g.cnt + zer * GWM, phase, eps, g.dstats + 1, log + k * GWM, 1, (GridBar *)nullptr,      \
-                       (int *)nullptr, 0ull, 0, owed ? 1 : 0, g.gq + (g.gq_seq % 3) * GQ_PAD, g.gq + ((g.gq_seq + 1) % 3) * GQ_PAD)
-            with_row(g.gw, [&](auto spl, auto gw) {
-                constexpr int SPL = decltype(spl)::value, GW = decltype(gw)::value;
-                if constexpr (SPL == 2) DPPR_LAUNCH_GSWEEP(2, GW, 512);
-                else if (nvx == 512) DPPR_LAUNCH_GSWEEP(1, GW, 512);
-                else DPPR_LAUNCH_GSWEEP(1, GW, 1024);
-            });
-#undef DPPR_LAUNCH_GSWEEP
-#undef DPPR_LAUNCH_GSWEEP_CM
+            launch_gsweep<false>(e, g, ep, phase, eps, owed,
+                                 {sweep_grid, g.cnt + cur * GWM, g.cnt + nxt * GWM, g.cnt + zer * GWM, log + k * GWM, 1, nullptr, nullptr, 0, 0,
+                                  g.gq + (g.gq_seq % 3) * GQ_PAD, g.gq + ((g.gq_seq + 1) % 3) * GQ_PAD});
             if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[2 * k + 1], e->stream));
             std::swap(g.x, g.x2);
             std::swap(g.act[0], g.act[1]);
@@ -314,19 +287,8 @@ int group_loop(dppr_engine *e, Group &g, const Epoch &ep, int phase, double eps,
         HIP_TRY(hipMemcpyAsync(e->pinned, g.cnt, sizeof(int) * (size_t)(5 * GWM + n * GWM), hipMemcpyDeviceToHost,
                                e->stream));
         HIP_TRY(loop_wait(e));
-        for (int k = 0; k < n; ++k) {
-            const int *f = e->pinned + 5 * GWM + k * GWM;
-            if (!any_left(f)) continue;
-            if (push_thr > 0 && dense_len < 0) { // (the sweep that FOUND the frontier this small could have been a push iteration)
-                long long F = 0;
-                for (int s = 0; s < GWM; ++s) F += f[s];
-                if (F <= push_thr) dense_len = it + k;
-            }
-            g.st.iterations++;
-            g.st.pull_iterations++;
-            for (int s = 0; s < GWM; ++s) g.st.sum_F += f[s];
-            for (int s = 0; s < GWM; ++s) g.st.sweep_F += f[s];
-            active_iters = it + k + 1;
+        int rc = account_sweeps(g.st, e->pinned + 5 * GWM, n, GWM, ITER_SWEEP, it, &active_iters, [&](int k, long long F) -> int {
+            plan.saw_frontier(F, it + k);
             if (e->profiling) {
                 float ms = 0;
                 HIP_TRY(hipEventElapsedTime(&ms, e->evpool[2 * k], e->evpool[2 * k + 1]));
@@ -335,50 +297,37 @@ int group_loop(dppr_engine *e, Group &g, const Epoch &ep, int phase, double eps,
                 g.st.sweep_ms += ms;
                 g.st.sweep_launches++;
                 static const bool trace = getenv("DPPR_GROUP_TRACE") != nullptr; // (diagnostic: one line per sweep)
-                if (trace) {
-                    long long F = 0;
-                    for (int s = 0; s < GWM; ++s) F += f[s];
-                    fprintf(stderr, "[gsweep] phase %d sweep %3d  frontier pairs %9lld  %7.1f us\n", phase, it + k, F, ms * 1e3);
-                }
+                if (trace) fprintf(stderr, "[gsweep] phase %d sweep %3d  frontier pairs %9lld  %7.1f us\n", phase, it + k, F, ms * 1e3);
             }
-        }
-        more = any_left(e->pinned + cur * GWM);
+            return DPPR_OK;
+        });
+        if (rc) return rc;
+        const long long F = lane_sum(e->pinned + cur * GWM);
+        more = F > 0;
         it += n;
-        if (more && push_thr > 0 && !push_gave_up) {
-            long long F = 0;
-            for (int s = 0; s < GWM; ++s) F += e->pinned[cur * GWM + s];
-            if (F <= push_thr) {
-                if (dense_len < 0) dense_len = it;
-                int pushed = 0;
-                bool entered = false, conv = false;
-                int rc = group_push_tail(e, g, ep, phase, eps, F, &pushed, &entered, &conv, &owed);
-                if (rc) return rc;
-                if (entered) {
-                    active_iters = it + pushed;
-                    it += pushed;
-                    if (conv) more = false;
-                    else { // back in sweep form: frontier sizes in row 0; the next try waits for a much smaller frontier
-                        cur = 0;
-                        HIP_TRY(hipMemcpyAsync(e->pinned, g.cnt, sizeof(int) * GWM, hipMemcpyDeviceToHost, e->stream));
-                        HIP_TRY(loop_wait(e));
-                        more = any_left(e->pinned);
-                        push_thr = std::max<long long>(F / 8, 1);
-                        dense_len = -1;
-                    }
-                } else { // (the frontier did not fit the lists)
-                    push_thr = std::max<long long>(F / 8, 1);
-                    dense_len = -1;
+        if (plan.enter_push(more, F)) {
+            plan.saw_frontier(F, it);
+            int pushed = 0;
+            bool entered = false, conv = false;
+            rc = group_push_tail(e, g, ep, phase, eps, F, &pushed, &entered, &conv, &owed);
+            if (rc) return rc;
+            if (entered) {
+                active_iters = it + pushed;
+                it += pushed;
+                if (conv) more = false;
+                else { // back in sweep form: frontier sizes in row 0
+                    cur = 0;
+                    HIP_TRY(hipMemcpyAsync(e->pinned, g.cnt, sizeof(int) * GWM, hipMemcpyDeviceToHost, e->stream));
+                    HIP_TRY(loop_wait(e));
+                    more = any_left(e->pinned);
+                    plan.push_declined(F);
                 }
+            } else { // (the frontier did not fit the lists)
+                plan.push_declined(F);
             }
         }
     }
-    if (push_thr > 0) {
-        for (int k = 3; k > 0; --k) g.dense_hist[hp][k] = g.dense_hist[hp][k - 1];
-        g.dense_hist[hp][0] = dense_len >= 0 ? std::max(dense_len, 1) : std::max(active_iters, 1);
-    }
-    g.iter_hint[hp] = active_iters;
-    for (int k = 3; k > 0; --k) g.iter_hist[hp][k] = g.iter_hist[hp][k - 1];
-    g.iter_hist[hp][0] = active_iters;
+    plan.finish(g.hist, hp, active_iters);
     return DPPR_OK;
 }
 
@@ -388,14 +337,9 @@ int group_loop(dppr_engine *e, Group &g, const Epoch &ep, int phase, double eps,
 // every sweep (the legal-push test is per source). The loop histories size the first chunk of the NEXT UPDATE's loops, and a
 // from-scratch loop is no predictor of those: they are put back.
 int group_solve_column(dppr_engine *e, Group &g, const Epoch &ep) {
-    int hint[2], hist[2][4], dense[2][4];
-    memcpy(hint, g.iter_hint, sizeof(hint));
-    memcpy(hist, g.iter_hist, sizeof(hist));
-    memcpy(dense, g.dense_hist, sizeof(dense));
+    const LoopHistory kept = g.hist;
     const int rc = group_loop(e, g, ep, 0, g.conv_eps, /*tails=*/false);
-    memcpy(g.iter_hint, hint, sizeof(hint));
-    memcpy(g.iter_hist, hist, sizeof(hist));
-    memcpy(g.dense_hist, dense, sizeof(dense));
+    g.hist = kept;
     return rc;
 }
 

@@ -13,6 +13,40 @@ int read_count(dppr_engine *e, const int *dptr, int *out) {
     return DPPR_OK;
 }
 
+// ---- accounting of a read-back log: `width` frontier sizes per logged iteration (a source group: one per source)
+inline long long lane_sum(const int *row, int width = GS_MAX) {
+    long long F = 0;
+    for (int s = 0; s < width; ++s) F += row[s];
+    return F;
+}
+
+enum IterKind { ITER_PUSH, ITER_RESIDENT_SWEEP, ITER_SWEEP }; // (a resident launch's edges are counted with the pushes': no sweep_F)
+
+inline void account_iteration(dppr_stats_t &st, long long F, IterKind kind) {
+    st.iterations++;
+    st.sum_F += F;
+    if (kind != ITER_PUSH) st.pull_iterations++;
+    if (kind == ITER_SWEEP) st.sweep_F += F;
+}
+
+// Every one of the n logged iterations that saw a frontier counts: iterations, sum_F, by kind pull_iterations and sweep_F;
+// *active_iters becomes the loop position after the last of them (the log starts at position `it`). each(k, F) is called for
+// every such iteration (per-launch timings, traces); a status other than DPPR_OK ends the walk and is returned.
+template <class Each>
+int account_sweeps(dppr_stats_t &st, const int *rows, int n, int width, IterKind kind, int it, int *active_iters, Each &&each) {
+    for (int k = 0; k < n; ++k) {
+        const long long F = lane_sum(rows + (size_t)k * width, width);
+        if (F <= 0) continue; // the frontier emptied inside the chunk: the rest were no-ops
+        account_iteration(st, F, kind);
+        *active_iters = it + k + 1;
+        if (int rc = each(k, F)) return rc;
+    }
+    return DPPR_OK;
+}
+inline void account_sweeps(dppr_stats_t &st, const int *rows, int n, int width, IterKind kind, int it, int *active_iters) {
+    account_sweeps(st, rows, n, width, kind, it, active_iters, [](int, long long) -> int { return DPPR_OK; });
+}
+
 // Frontier loop: PPRRevPushGPU::ExecuteOptimized's while(1) (gpu/PPRRevPushGPU.cuh:106-130).
 // On entry s.ft[buf] holds the frontier and s.cnt[cur] its size; cnt[(cur+1)%3] is zero and
 // the dense vectors s.x / s.x2 are all zero (no snapshot taken yet) -- unless `entry` says
@@ -36,8 +70,22 @@ struct LoopEntry {
     bool any_pull = false;
 };
 
-int pull_min_frontier(const dppr_engine *e) {
-    return e->pull_min_frontier > 0 ? e->pull_min_frontier : e->pull_min_frontier < 0 ? 0x7fffffff : std::max(1024, e->Ed / 192);
+int pull_min_frontier(const dppr_engine *e) { return dppr::pull_min_frontier(e->pull_min_frontier, e->Ed); }
+
+// k_pull_resident (dppr_resident.hpp) at the sweep's block size: n sweeps from counter `cur` on; plan: PLAN_* of a whole-batch
+// launch (0: a run of sweeps of one loop), upd: the batch's records if the launch applies them itself
+void launch_resident(dppr_engine *e, Slot &s, const Epoch &ep, double eps, int cur, int phase, int n, int plan, const ResUpdate &upd) {
+#define DPPR_LAUNCH_PERSIST(PB)                                                                                       \
+    hipLaunchKernelGGL(k_pull_resident<PB>, dim3(ep.n_groups), dim3(PB), 0, e->stream, ep.grp_n_int, ep.grp_tile,       \
+                       ep.out_row_ptr, ep.out_col, s.x, e->res_arena, e->res_arena_stride, s.r, s.p, s.cnt, cur, phase, eps, s.dstats, s.log,  \
+                       n, e->bar, s.cnt + 7, e->persist_ticks, e->persist_rollcall_extra, plan,                       \
+                       ep.res_valid ? ep.res_pk : nullptr, upd)
+    switch (sweep_block(e)) {
+    case 256: DPPR_LAUNCH_PERSIST(256); break;
+    case 512: DPPR_LAUNCH_PERSIST(512); break;
+    default: DPPR_LAUNCH_PERSIST(1024); break;
+    }
+#undef DPPR_LAUNCH_PERSIST
 }
 
 int run_frontier_loop(dppr_engine *e, Slot &s, const Epoch &ep, int phase, double eps, int buf, int cur,
@@ -47,7 +95,7 @@ int run_frontier_loop(dppr_engine *e, Slot &s, const Epoch &ep, int phase, doubl
     const bool sync_sched = e->schedule == DPPR_SCHEDULE_SYNC;
     const HubTable hubs{ep.hub_v, ep.hub_degp1, ep.n_hubs};
     // the sparse grid must cover the largest frontier a push chunk can meet
-    const int push_grid = pull_min == 0x7fffffff ? 2048 : std::min(2048, std::max(64, (pull_min * 4 / WAVE + 3) / 4));
+    const int push_grid = pull_min == PULL_NEVER ? 2048 : std::min(2048, std::max(64, (pull_min * 4 / WAVE + 3) / 4));
     // Sweeps on a window that cannot run resident carry the activity bitmap of their snapshot (k_pull_iter<.., true>)
     const int pcap0 = persist_capacity(e);
     const bool binned = ep.bin_valid && ep.bin_n_int <= ep.grp_n_int && (pcap0 <= 0 || ep.n_groups > pcap0 || e->bin_mode == 2);
@@ -97,14 +145,11 @@ int run_frontier_loop(dppr_engine *e, Slot &s, const Epoch &ep, int phase, doubl
         }
         bool pull = F >= pull_min;
         // a window whose iterations cost hundreds of microseconds and more (twitter / friendster size): decisions per iteration
-        const bool costly = binned && !e->chunk_explicit && (s.sweep_us > 0 ? s.sweep_us : 6.5e-6 * (double)ep.Ed) >= 300.0;
+        const bool costly = window_costly(binned, e->chunk_explicit, s.sweep_us, ep.Ed);
         if (costly && e->cost_model && !sync_sched && !s.trace && e->pull_min_frontier == 0) {
-            // Push or sweep by what each would cost. A push is one returning atomic per in-edge of the
-            // frontier, executed at the memory side at ~23.5 G/s chip-wide whatever the locality (profiles/r03_atomics_probe.json);
-            // a sweep of this window costs what the last ones did. The frontier's in-edges are counted by the sweep that left it
-            // (k_bin_reduce) or, for a list, by k_front_degree. (Round 3 switched on the vertex count: a late frontier of 1.7 M
-            // low-degree vertices is pushed in 0.23 ms and was swept for 2.6, the 156 K batch tails -- hubs -- cost a sweep's time.)
-            if (D < 0 && F >= 1024) {
+            // push or sweep by what each would cost (dppr_loop_plan.hpp); the frontier's in-edges are counted by the sweep that left
+            // it (k_bin_reduce) or, for a list, by k_front_degree
+            if (cost_needs_degrees(F, D)) {
                 if (!list_valid && (rc = make_list())) return rc;
                 HIP_TRY(hipMemsetAsync(dsum + cur, 0, sizeof(unsigned long long), e->stream));
                 hipLaunchKernelGGL(k_front_degree, dim3(grid_for(F)), dim3(BLOCK), 0, e->stream, s.ft[buf], s.cnt + cur, ep.row_ptr, dsum + cur);
@@ -115,41 +160,12 @@ int run_frontier_loop(dppr_engine *e, Slot &s, const Epoch &ep, int phase, doubl
                 memcpy(&d, e->pinned, sizeof(d));
                 D = (long long)d;
             }
-            if (D >= 0 || F < 1024) {
-                const double sweep_us = s.sweep_us > 0 ? s.sweep_us : 6.5e-6 * (double)ep.Ed; // (no sweep timed yet: ~6.5 ps per edge)
-                const double push_us = 15.0 + (double)std::max<long long>(D, 0) * s.atomic_ns * 1e-3; // (measured on this slot's own pushes)
-                pull = F >= 1024 && push_us > 0.9 * sweep_us;
-            }
+            if (cost_decides(F, D)) pull = cost_says_sweep(F, D, s.sweep_us, ep.Ed, s.atomic_ns);
         }
-        int n;
-        if (s.trace || e->chunk_iters <= 1) n = 1;
-        else if (costly)
-            // A window on binned sweeps: an iteration costs milliseconds (friendster stand-in: 2.6 ms a sweep, 11-13 ms the push
-            // of a 3-10 M-vertex frontier), a read-back tens of microseconds. Nothing is enqueued blind: round 3 ran the second
-            // iteration of every loop as a push of ten million vertices (decided at 156 K) and ended every loop with three to
-            // seven sweeps over frontiers of a few hundred vertices (enqueued from the last batches' lengths) -- 40 of 183 ms.
-            n = (!pull && F < 4096 && F <= prevF) ? e->chunk_iters : 1;
-        else if (pull) // consecutive batches take almost the same number of iterations: aim just past the end
-            n = s.iter_hint[hp] > it ? s.iter_hint[hp] - it + 1 : e->chunk_iters;
-        else if ((long long)F * 4 >= pull_min) n = 1;          // about to turn dense: re-decide next iteration
-        else n = F > prevF ? 2 : e->chunk_iters;                // growing: short chunks; decaying tail: long
+        int n = single_chunk(s.trace, e->chunk_iters, costly, pull, F, prevF, pull_min, s.hist.hint[hp], it);
         const int pcap = persist_capacity(e);
         const bool resident = pull && n >= 2 && !s.trace && pcap > 0 && ep.n_groups > 0 && ep.n_groups <= pcap && resident_arena(e, ep);
-        if (resident && s.iter_hint[hp] > it) n += RESIDENT_MARGIN - 1;
-        if (!resident && pull && n > 1) {
-            // per-iteration sweeps: a launch that finds the frontier empty is still a dispatch, a chunk boundary (read-back
-            // + relaunch) costs about three of them -- go as far as the SHORTEST of the last four loops of this phase went
-            // (almost surely needed in full), then in chunks that double from 4 (group_loop sizes its chunks the same way)
-            int lo = 0;
-            for (int h : s.iter_hist[hp]) lo = h > 0 && (lo == 0 || h < lo) ? h : lo;
-            if (lo > it) n = lo - it;
-            else if (lo > 0) {
-                n = std::min(follow, e->chunk_iters);
-                follow *= 2;
-            }
-        }
-        n = std::min(n, MAX_CHUNK);
-        if (e->chunk_explicit) n = std::min(n, std::max(e->chunk_iters, 1));
+        n = single_chunk_for_form(n, resident, pull, s.hist, hp, it, follow, e->chunk_iters, e->chunk_explicit);
         if (!pull && !list_valid && (rc = make_list())) return rc;
         if (resident) {
             // ---- a run of dense iterations as ONE resident launch (dppr_resident.hpp)
@@ -159,19 +175,8 @@ int run_frontier_loop(dppr_engine *e, Slot &s, const Epoch &ep, int phase, doubl
                 dense_valid = true;
             }
             HIP_TRY(hipMemsetAsync(e->bar, 0, sizeof(GridBar), e->stream));
-            n = std::min(n, RES_MAX_SWEEPS);
             if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[0], e->stream));
-#define DPPR_LAUNCH_PERSIST(PB)                                                                                       \
-    hipLaunchKernelGGL(k_pull_resident<PB>, dim3(ep.n_groups), dim3(PB), 0, e->stream, ep.grp_n_int, ep.grp_tile,       \
-                       ep.out_row_ptr, ep.out_col, s.x, e->res_arena, e->res_arena_stride, s.r, s.p, s.cnt, cur, phase, eps, s.dstats, s.log,  \
-                       n, e->bar, s.cnt + 7, e->persist_ticks, e->persist_rollcall_extra, 0,                          \
-                       ep.res_valid ? ep.res_pk : nullptr, ResUpdate{})
-            switch (sweep_block(e)) {
-            case 256: DPPR_LAUNCH_PERSIST(256); break;
-            case 512: DPPR_LAUNCH_PERSIST(512); break;
-            default: DPPR_LAUNCH_PERSIST(1024); break;
-            }
-#undef DPPR_LAUNCH_PERSIST
+            launch_resident(e, s, ep, eps, cur, phase, n, 0, ResUpdate{});
             if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[1], e->stream));
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(e->pinned, s.cnt, sizeof(int) * (size_t)(CNT_HDR + n), hipMemcpyDeviceToHost, e->stream));
@@ -187,14 +192,7 @@ int run_frontier_loop(dppr_engine *e, Slot &s, const Epoch &ep, int phase, doubl
                 e->persist_retry = PERSIST_RETRY_BATCHES;
                 continue;
             }
-            for (int k = 0; k < n; ++k) {
-                const int f = e->pinned[CNT_HDR + k];
-                if (f <= 0) continue;
-                s.st.iterations++;
-                s.st.pull_iterations++;
-                s.st.sum_F += f;
-                active_iters = it + k + 1;
-            }
+            account_sweeps(s.st, e->pinned + CNT_HDR, n, 1, ITER_RESIDENT_SWEEP, it, &active_iters);
             if (e->profiling) {
                 float ms = 0;
                 HIP_TRY(hipEventElapsedTime(&ms, e->evpool[0], e->evpool[1]));
@@ -303,15 +301,8 @@ int run_frontier_loop(dppr_engine *e, Slot &s, const Epoch &ep, int phase, doubl
         // one read-back per chunk: the new frontier size and the F of each iteration just run
         HIP_TRY(hipMemcpyAsync(e->pinned, s.cnt, sizeof(int) * (size_t)(CNT_HDR + n), hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(loop_wait(e));
-        for (int k = 0; k < n; ++k) {
-            const int f = e->pinned[CNT_HDR + k];
-            if (f <= 0) continue; // the frontier emptied inside the chunk: the rest were no-ops
-            s.st.iterations++;
-            s.st.sum_F += f;
-            if (pull) s.st.pull_iterations++;
-            if (pull) s.st.sweep_F += f;
+        rc = account_sweeps(s.st, e->pinned + CNT_HDR, n, 1, pull ? ITER_SWEEP : ITER_PUSH, it, &active_iters, [&](int k, long long f) -> int {
             if (pull && binned) s.st.binned_sweeps++;
-            active_iters = it + k + 1;
             if (e->profiling) {
                 float ms = 0;
                 HIP_TRY(hipEventElapsedTime(&ms, e->evpool[2 * k], e->evpool[2 * k + 1]));
@@ -323,15 +314,17 @@ int run_frontier_loop(dppr_engine *e, Slot &s, const Epoch &ep, int phase, doubl
                 }
                 static const bool trace = getenv("DPPR_LOOP_TRACE") != nullptr; // (diagnostic: one line per iteration of a profiled batch)
                 if (trace)
-                    fprintf(stderr, "[loop  ] phase %d iteration %3d  %-6s frontier %9d  %8.1f us\n", phase, it + k,
+                    fprintf(stderr, "[loop  ] phase %d iteration %3d  %-6s frontier %9lld  %8.1f us\n", phase, it + k,
                             pull ? (binned ? "binned" : "sweep") : "push", f, ms * 1e3);
             }
-        }
+            return DPPR_OK;
+        });
+        if (rc) return rc;
         if (costly && n == 1 && e->pinned[CNT_HDR] > 0) { // what a sweep of this window costs / what an atomic of a push does (running means)
             float ms = 0;
             HIP_TRY(hipEventElapsedTime(&ms, e->evpool[0], e->evpool[1]));
-            if (pull) s.sweep_us = s.sweep_us > 0 ? 0.75 * s.sweep_us + 0.25 * ms * 1e3 : ms * 1e3;
-            else if (D >= (1 << 20)) s.atomic_ns = 0.75 * s.atomic_ns + 0.25 * std::min(1.0, std::max(0.02, (ms * 1e6 - 15e3) / (double)D));
+            if (pull) s.sweep_us = mean_sweep_us(s.sweep_us, ms);
+            else s.atomic_ns = mean_atomic_ns(s.atomic_ns, ms, D);
         }
         prevF = F;
         F = e->pinned[cur];
@@ -344,9 +337,7 @@ int run_frontier_loop(dppr_engine *e, Slot &s, const Epoch &ep, int phase, doubl
         }
         it += n;
     }
-    s.iter_hint[hp] = active_iters;
-    for (int k = 3; k > 0; --k) s.iter_hist[hp][k] = s.iter_hist[hp][k - 1];
-    s.iter_hist[hp][0] = active_iters;
+    s.hist.record(hp, active_iters);
     if (any_pull && !x_clean) { // leave both dense vectors all-zero for the next loop
         // only internal ids below n_int are ever written
         HIP_TRY(hipMemsetAsync(s.x, 0, sizeof(double) * (size_t)ep.grp_n_int, e->stream));
@@ -377,9 +368,9 @@ bool can_batch_ahead(const dppr_engine *e, const Slot &s, const Epoch &ep) {
     // launches: with the automatic push/pull threshold a window that can run resident always does.
     // With an explicit threshold (tests) only if the last batch's phases both started above it.
     if (e->merge_phases && e->schedule == DPPR_SCHEDULE_EAGER) // (the merged loop keeps its history in slot 0)
-        return e->pull_min_frontier == 0 || (s.iter_hint[0] > 0 && s.start_dense[0]);
+        return e->pull_min_frontier == 0 || (s.hist.hint[0] > 0 && s.start_dense[0]);
     return e->pull_min_frontier == 0 ||
-           (s.iter_hint[0] > 0 && s.iter_hint[1] > 0 && s.start_dense[0] && s.start_dense[1]);
+           (s.hist.hint[0] > 0 && s.hist.hint[1] > 0 && s.start_dense[0] && s.start_dense[1]);
 }
 
 // stage (out): 0 = phase 0 still open (resume with en0), 1 = phase 0 done, phase 1 open (resume with
@@ -389,32 +380,14 @@ int batch_ahead(dppr_engine *e, Slot &s, const Epoch &ep, double eps, int *stage
     // merged (dppr_set_phase_merge): ONE loop over residuals of both signs -- the launch seeds it (PLAN_SEED) and runs it to the
     // end; stage 0 + en0 if it ran out of sweeps, stage 2 when it converged (histories in slot 0)
     const int pull_min = pull_min_frontier(e);
-    // a resident launch stops by itself when the frontier empties: a generous allowance costs nothing,
-    // a short one costs a read-back and another launch (+1: the step that seeds phase 1)
-    int n = merged ? (s.iter_hint[0] > 0 ? std::min(s.iter_hint[0] + 2 * RESIDENT_MARGIN, 2 * MAX_CHUNK) : 2 * MAX_CHUNK)
-            : s.iter_hint[0] > 0 && s.iter_hint[1] > 0
-                      ? std::min(s.iter_hint[0] + s.iter_hint[1] + 1 + 2 * RESIDENT_MARGIN, 2 * MAX_CHUNK)
-                      : 2 * MAX_CHUNK; // no history yet
-    if (e->chunk_explicit) n = std::min(n, e->chunk_iters); // (tests: launches that stop mid-phase and are resumed)
-    n = std::min(n, RES_MAX_SWEEPS);
-    int *status = s.cnt + 7; // (the GridBar was zeroed by the batch's first kernel, k_su_keys)
+    const int n = batch_ahead_sweeps(merged, s.hist, e->chunk_iters, e->chunk_explicit);
+    // (the launch's status word is s.cnt[7]; the GridBar was zeroed by the batch's first kernel, k_su_keys)
     const ResUpdate upd = !inline_update ? ResUpdate{}
                           : ep.grouped   ? ResUpdate{ep.su_rng, ep.sk, ep.sv, ep.b2, ep.ins, ep.deg_after, s.source, nullptr, 0}
                                          : ResUpdate{nullptr, nullptr, nullptr, ep.b2, ep.ins, nullptr, s.source, ep.b1, ep.L}; // raw records
     const int plan = (merged ? PLAN_SEED : (PLAN_SEED | PLAN_BOTH)) | (inline_update ? PLAN_UPDATE : 0);
     if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[0], e->stream));
-#define DPPR_LAUNCH_PERSIST(PB)                                                                                        \
-    hipLaunchKernelGGL(k_pull_resident<PB>, dim3(ep.n_groups), dim3(PB), 0, e->stream, ep.grp_n_int, ep.grp_tile,        \
-                       ep.out_row_ptr, ep.out_col, s.x, e->res_arena, e->res_arena_stride, s.r, s.p, s.cnt, 0,                  \
-                       merged ? PHASE_BOTH : 0, eps, s.dstats,                                                             \
-                       s.log, n, e->bar, status, e->persist_ticks, e->persist_rollcall_extra,                             \
-                       plan, ep.res_valid ? ep.res_pk : nullptr, upd)
-    switch (sweep_block(e)) {
-    case 256: DPPR_LAUNCH_PERSIST(256); break;
-    case 512: DPPR_LAUNCH_PERSIST(512); break;
-    default: DPPR_LAUNCH_PERSIST(1024); break;
-    }
-#undef DPPR_LAUNCH_PERSIST
+    launch_resident(e, s, ep, eps, 0, merged ? PHASE_BOTH : 0, n, plan, upd);
     if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[1], e->stream));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(e->pinned, s.cnt, sizeof(int) * (size_t)(CNT_HDR + n), hipMemcpyDeviceToHost, e->stream));
@@ -448,24 +421,17 @@ int batch_ahead(dppr_engine *e, Slot &s, const Epoch &ep, double eps, int *stage
         s.st.push_ms += ms;
         s.st.push_launches++;
     }
-    // the log: frontier sizes of phase 0, a zero (phase 0 over), those of phase 1, a zero
-    const int *log = e->pinned + CNT_HDR;
     const int pos = st & PERSIST_SWEEPS; // loop position the launch stopped at
-    int act[2] = {0, 0}, ph = 0;
-    for (int k = 0; k < std::min(pos + 1, n) && ph < 2; ++k) {
-        if (log[k] <= 0) {
-            ++ph;
-            continue;
+    const PhaseLog pl = split_phase_log(e->pinned + CNT_HDR, std::min(pos + 1, n));
+    const int *act = pl.act;
+    for (int ph = 0; ph < 2; ++ph)
+        if (act[ph] > 0) {
+            s.start_dense[ph] = pl.F0[ph] >= pull_min;
+            s.last_F0[ph] = pl.F0[ph];
         }
-        if (act[ph] == 0) {
-            s.start_dense[ph] = log[k] >= pull_min;
-            s.last_F0[ph] = log[k];
-        }
-        s.st.iterations++;
-        s.st.pull_iterations++;
-        s.st.sum_F += log[k];
-        act[ph]++;
-    }
+    s.st.iterations += act[0] + act[1];
+    s.st.pull_iterations += act[0] + act[1];
+    s.st.sum_F += pl.sum_F;
     if (merged) {
         if (!(st & PERSIST_CONVERGED)) { // out of sweeps: the host-driven loop goes on from here
             en0->it = act[0];
@@ -474,9 +440,7 @@ int batch_ahead(dppr_engine *e, Slot &s, const Epoch &ep, double eps, int *stage
             en0->any_pull = true;
             return DPPR_OK;
         }
-        s.iter_hint[0] = act[0];
-        for (int k = 3; k > 0; --k) s.iter_hist[0][k] = s.iter_hist[0][k - 1];
-        s.iter_hist[0][0] = act[0];
+        s.hist.record(0, act[0]);
         if (act[0] == 0) s.start_dense[0] = false;
         *stage = 2;
         return DPPR_OK;
@@ -488,7 +452,7 @@ int batch_ahead(dppr_engine *e, Slot &s, const Epoch &ep, double eps, int *stage
         en0->any_pull = true;
         return DPPR_OK;
     }
-    s.iter_hint[0] = act[0];
+    s.hist.hint[0] = act[0];
     if (act[0] == 0) s.start_dense[0] = false;
     *stage = 1;
     *p1_seeded = true;
@@ -499,7 +463,7 @@ int batch_ahead(dppr_engine *e, Slot &s, const Epoch &ep, double eps, int *stage
         en1->any_pull = true;
         return DPPR_OK;
     }
-    s.iter_hint[1] = act[1];
+    s.hist.hint[1] = act[1];
     if (act[1] == 0) s.start_dense[1] = false;
     *stage = 2;
     return DPPR_OK;
@@ -630,17 +594,23 @@ int stream_update(dppr_engine *e, Slot &s, const Epoch &ep, double eps, bool see
     return DPPR_OK;
 }
 
-int pull_device_stats(dppr_engine *e, Slot &s) {
+// the edge counts the kernels keep (of a slot or of a source group), and what follows from the counters: one place for both
+int pull_device_stats(dppr_engine *e, const IterStats *dstats, dppr_stats_t &st) {
     static thread_local IterStats h[2];
-    HIP_TRY(hipMemcpyAsync(h, s.dstats, sizeof(h), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(h, dstats, sizeof(h), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     unsigned long long t = 0, ts = 0;
     for (int i = 0; i < STAT_SLOTS; ++i) {
         t += h[0].blk_E[i];
         ts += h[1].blk_E[i];
     }
-    s.st.sum_E = (int64_t)(t + ts);
-    s.st.sweep_E = (int64_t)ts;
+    st.sum_E = (int64_t)(t + ts);
+    st.sweep_E = (int64_t)ts;
+    // every enqueued vertex is a frontier member of a later iteration, except the seeds
+    st.sum_N = st.sum_F;
+    // SURVEY.md 8(d); its Inspect term (8 bytes per vertex and pass) is counted for the passes that RAN:
+    // after a converged solve the frontier is seeded from the batch tails and no vertex is scanned
+    st.algorithmic_bytes = 8ll * st.inspected + 45ll * st.records + 72ll * st.sum_F + 24ll * st.sum_E + 4ll * st.sum_N;
     return DPPR_OK;
 }
 

@@ -8,18 +8,15 @@
 // Included by dppr_engine.hip only, after the kernel headers (one translation unit: the kernels are templates).
 #pragma once
 
-static constexpr int MAX_CHUNK = 64;
 // Slot::cnt: [0..2] rotating frontier counters, [3] phase-1 candidates, [4] scratch, [5..6] big-row
 // counters, [7] list scratch / status word of a resident launch; the log of a launch (up to
-// 2 x MAX_CHUNK entries: a whole batch) follows the header
+// 2 x MAX_CHUNK entries, dppr_loop_plan.hpp: a whole batch) follows the header
 static constexpr int CNT_HDR = 16;
 static constexpr int PERSIST_RETRY_BATCHES = 64; // after a failed roll-call: batches on per-iteration launches before the next try
-static constexpr int GMULTI_MAX = 2 * MAX_CHUNK; // sweeps a multi-sweep launch of a source group may run
 static constexpr int GQ_PAD = 32;               // ints between the rotating group counters of k_gsweep (own 128-byte line each)
 static constexpr int BIN_MAX_BLOCKS = 1 << 16, BIN_MAX_BIG = 4096, BIN_SMALL_INTS = BIN_MAX_BLOCKS + BIN_MAX_BIG + 1 + 64; // bin_cut scratch
 static constexpr int SU_SPLIT_MIN = 1 << 16;  // batch records from which IncrementalBatchUpdate runs as k_su_terms + k_su_apply (stream_update)
 static constexpr int MERGE_MISS_WORD = 44; // word of hub_hist (64 ints) that counts the retired keys a slide's merge did not find
-static constexpr int RESIDENT_MARGIN = 8; // sweeps a resident launch is given beyond what the last batch needed
 
 namespace dppr {
 
@@ -121,8 +118,7 @@ struct Slot {
     long long iter_seq = 0; // running iteration number (selects the big-row counter)
     double sweep_us = 0;       // binned windows: running mean of a sweep's time (the push / sweep decision)
     double atomic_ns = 1.0 / 23.5; // ... and of a push iteration's time per in-edge (starts at the chip's rate of returning f64 atomics)
-    int iter_hint[2] = {0, 0}; // iterations the last loop of each phase took (sizes the next chunks)
-    int iter_hist[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}; // ... and the last four
+    LoopHistory hist;          // iterations the last loops of each phase took (sizes the next chunks: dppr_loop_plan.hpp)
     bool start_dense[2] = {false, false}; // the last loop of each phase began with a frontier worth a sweep
     int last_F0[2] = {0, 0};   // ... and its size
     DevBuf<IterStats> dstats; // two blocks: [0] push iterations (and resident launches), [1] dense sweeps -- the roofline of the sweep kernel counts its own edges
@@ -155,9 +151,7 @@ struct Group {
     DevBuf<int> mlog;       // multi-sweep launches: [GS_MAX] status word + padding, then one row of frontier sizes per sweep
     DevBuf<IterStats> dstats; // two blocks: [0] push iterations (and resident launches), [1] dense sweeps -- the roofline of the sweep kernel counts its own edges
     dppr_stats_t st{};
-    int iter_hint[2] = {0, 0};
-    int iter_hist[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}; // sweeps the last four loops of each phase took
-    int dense_hist[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}; // ... before the frontier was small enough for the push form
+    LoopHistory hist;          // sweeps the last loops of each phase took, in all and before the push form took over (dppr_loop_plan.hpp)
     // the tail of a loop as pushes (dppr_gpush.hpp): vertex lists, scan, control block; allocated on first use
     DevBuf<int> plist[2];
     DevBuf<int> ppre;
@@ -270,7 +264,7 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     int gpush_enter_pairs = -1;     // a group's loop switches to the push form below this many frontier pairs (-1: automatic,
                                     // max(64, gpush_auto_factor pairs per sweep group); 0: never) -- dppr_set_group_push
     int gpush_list_cap = 1 << 20;   // vertices a frontier list of that form holds
-    long long gpush_max_edges = 0;  // in-edges one iteration of that form may have (0: from the sweep's floor, 200 per sweep group)
+    long long gpush_max_edges = 0;  // in-edges one iteration of that form may have (0: from the sweep's floor, 20 per sweep group)
     int gpush_auto_factor = 2;      // automatic threshold: this many pairs per sweep group (DPPR_GROUP_PUSH_FACTOR: tuning runs)
     // binned sweep of single-source loops on windows far beyond the L2s (dppr_binned.hpp, dppr_set_binned_sweep)
     int bin_mode = 1;               // 0: never, 1: when a source slot exists and the window has >= bin_min_ids vertices, 2: always

@@ -157,8 +157,9 @@ def test_merged_loop_single_source_bit_exact(tuning):
 
 
 # ------------------------------------------------------------------ source groups
-def run_group(sources, seeding="tails", tuning=None, resident=True, push=None, div=0, batches=BATCHES):
-    """A source group against one oracle state per source: schedule C, or the merged loop at eps / div."""
+def run_group(sources, seeding="tails", tuning=None, resident=True, push=None, div=0, batches=BATCHES, reads=None):
+    """A source group against one oracle state per source: schedule C, or the merged loop at eps / div. `reads`: a list that
+    takes every (p, r) read, in order."""
     V, e1, e2, meta = stream()
     tuning = dict(tuning or {}, **(dict(merge_phases=div) if div else {}))
     e = eng.Engine(V, W, 1, C, **tuning)
@@ -183,7 +184,10 @@ def run_group(sources, seeding="tails", tuning=None, resident=True, push=None, d
                     s.sync_inc_execute(g)
             e.group_update(gid, EPS)
         for i, s in enumerate(states):
-            assert_bits(*e.group_read(gid, i), s, (k, i))
+            p, r = e.group_read(gid, i)
+            assert_bits(p, r, s, (k, i))
+            if reads is not None:
+                reads.append((p.copy(), r.copy()))
     st = e.group_stats(gid)
     assert st["sum_F"] == sum(s.stats()["F"] for s in states) and st["sum_E"] == sum(s.stats()["E"] for s in states)
     e.close()
@@ -213,6 +217,28 @@ def test_source_group_launch_forms(nsrc, mode):
         assert st["persist_launches"] >= 1 and st["persist_aborts"] >= 1
     else:
         assert st["persist_launches"] > 0 and st["persist_aborts"] == 0
+
+
+@pytest.mark.parametrize("resident", [True, False], ids=["resident", "one-sweep"])
+@pytest.mark.parametrize("nsrc", [3, 10])
+def test_source_group_independent_of_chunking(nsrc, resident):
+    """How a loop is cut into chunks (dppr_set_tuning chunk_iters; dppr_loop_plan.hpp sizes every chunk and launch from it and from
+    the loop histories) changes what is launched and nothing else: after a solve and after each of three updates the bits of p and r
+    and (iterations, sum_F, sum_E) are the same for 1, 2, 5 and 24 sweeps per chunk. One sweep per chunk without residency is the
+    smallest shape at which an off-by-one in a chunk size or in a history changes the launches; ten sources run SPL = 2, NVX = 512."""
+    want = None
+    for chunk in (1, 2, 5, 24):
+        reads = []
+        st = run_group(group_sources(nsrc), tuning=dict(chunk_iters=chunk, schedule=eng.SCHEDULE_SYNC), resident=resident, batches=3, reads=reads)
+        assert (st["persist_launches"] > 0) == (resident and chunk > 1), (chunk, st)
+        got = (reads, (st["iterations"], st["sum_F"], st["sum_E"]))
+        if want is None:
+            want = got
+            continue
+        assert got[1] == want[1], (chunk, got[1], want[1])
+        assert len(reads) == len(want[0]) == 4 * nsrc
+        for (p, r), (wp, wr) in zip(reads, want[0]):
+            assert same(p, wp) and same(r, wr), chunk
 
 
 GPUSH_MODES = {"automatic": (-1, 0), "never": (0, 0), "as-early-as-possible": (10**9, 0), "as-early-as-possible-chunk2": (10**9, 0),

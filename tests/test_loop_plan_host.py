@@ -1,0 +1,18 @@
+"""Chunk and launch policy of the frontier loops (dynamicppr_amd/csrc/dppr_loop_plan.hpp, HIP-free): driven on the CPU by
+tests/native/loop_plan_test.cpp against a plain restatement of the expressions the loops held inline before -- every combination of
+the small inputs, seeded random large ones, and whole loops replayed (decaying frontiers with and without a plateau, a push tail that
+gives up, one whose lists overflow); built with the address and undefined-behaviour sanitizers. CPU only."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_loop_plan_equals_its_plain_restatement(tmp_path):
+    """Chunk sizes, thresholds, launch allowances, the push-or-sweep decision and its running means, the split of a whole-batch
+    launch's log, and the histories element for element; a history saved and put back around a loop is bit-equal to before."""
+    exe = str(tmp_path / "loop_plan_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall",
+                           "-Werror", "-o", exe, os.path.join(ROOT, "tests", "native", "loop_plan_test.cpp")])
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-2000:]
