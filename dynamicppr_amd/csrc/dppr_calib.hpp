@@ -1,6 +1,7 @@
 // dppr_calib.hpp -- calibration kernels behind dppr_bench_line_fills / dppr_bench_stream_copy: the two ceilings a sweep of this
 // engine is held against besides the HBM peak (SURVEY.md 8(d) "the harness should also report a calibrated ceiling";
-// bench.py measures them in the run that prints the line: roofline.ceiling_*). Not part of any solve.
+// bench.py measures them in the run that prints the line: roofline.ceiling_*), and the host skeleton the three dppr_bench_* entry
+// points share (calib_device, time_launches; after include/dppr.h). Not part of any solve.
 #pragma once
 
 #include "dppr_common.hpp"
@@ -51,6 +52,32 @@ __global__ __launch_bounds__(1024) void k_bench_copy(const double2 *__restrict__
         dst[i + 3 * stride] = d;
     }
     for (; i < n16; i += stride) dst[i] = src[i];
+}
+
+// ---------------------------------------------------------------------------- host side of the dppr_bench_* entry points
+// the device a calibration runs on: checked and selected (before the caller allocates its tables)
+inline int calib_device(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return DPPR_ERR_NO_DEVICE;
+    return hipSetDevice(device) == hipSuccess ? DPPR_OK : DPPR_ERR_HIP;
+}
+// launch() once to warm up, then `reps` times between two events on the null stream: *ms_per_launch
+template <class Launch>
+int time_launches(int reps, float *ms_per_launch, Launch &&launch) {
+    hipEvent_t a, b;
+    (void)hipEventCreate(&a);
+    (void)hipEventCreate(&b);
+    launch(); // warm-up
+    (void)hipEventRecord(a, 0);
+    for (int i = 0; i < reps; ++i) launch();
+    (void)hipEventRecord(b, 0);
+    const hipError_t err = hipEventSynchronize(b);
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, a, b);
+    *ms_per_launch = ms / reps;
+    (void)hipEventDestroy(a);
+    (void)hipEventDestroy(b);
+    return err == hipSuccess ? DPPR_OK : DPPR_ERR_HIP;
 }
 
 } // namespace dppr

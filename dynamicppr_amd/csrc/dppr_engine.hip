@@ -1,8 +1,10 @@
 // dppr_engine.hip -- host side of libdppr_hip.so: the C ABI of include/dppr.h (the extern "C" entry points), over
 //   dppr_host_state.hpp   what an engine owns: epochs, slots, groups, the solver's and the builder's streams and scratch
 //   dppr_host_graph.hpp   the BUILDER: id space, key merge, CSRs, group cuts + tables, binned tables   (untimed region)
-//   dppr_host_loop.hpp    the single-source SOLVER: IncrementalBatchUpdate + the frontier loop's launch forms (timed region)
-//   dppr_host_group.hpp   source groups: the same loop for up to 16 sources at once
+//   dppr_host_loop.hpp    the single-source SOLVER: IncrementalBatchUpdate + the frontier loop's launch forms, one batch = slot_update (timed region)
+//   dppr_host_group.hpp   source groups: the same loop for up to 16 sources at once, one batch = group_update
+// An entry point checks its arguments, finds its slot / group / epoch, selects the device and calls them. (Still here and due to
+// move: slide_impl, group_churn, the numbering block of dppr_load_window, dppr_debug_dump.)
 // One translation unit (the kernels are templates instantiated by the host code that launches them).
 //
 // Owns device memory (replaces gpu/DeviceMemory.cuh, gpu/GPUEdgeBatch.cuh,
@@ -674,15 +676,13 @@ int dppr_time_batch_grouping(dppr_engine *e, int32_t epoch, int32_t reps, float 
     *out_ms = 0.0f;
     const int L = ep.L;
     if (L <= 0) return DPPR_OK;
-    HIP_TRY(hipEventRecord(e->ev0, e->stream));
+    if (int rc = bracket_open(e)) return rc;
     int *deg_scratch = reinterpret_cast<int *>(e->su_term.get());
     for (int k = 0; k < reps; ++k) // what group_records_by_tail enqueues inside the timed region, the degrees into scratch
         if (int rc = enqueue_grouping(e, ep, deg_scratch, nullptr, 0, nullptr, 0)) return rc;
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(e->ev1, e->stream));
-    HIP_TRY(hipEventSynchronize(e->ev1));
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+    if (int rc = bracket_close(e, &ms)) return rc;
     *out_ms = ms / (float)reps;
     return DPPR_OK;
 }
@@ -809,22 +809,15 @@ int dppr_init_solve_at(dppr_engine *e, int32_t slot, int32_t epoch, double eps, 
     GET_EPOCH(e, epoch);
     if (!(eps > 0)) return fail(e, DPPR_ERR_INVALID, "eps must be positive");
     HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipEventRecord(e->ev0, e->stream));
+    int rc = bracket_open(e);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_init, dim3(grid_for(e->V)), dim3(BLOCK), 0, e->stream, s.p, s.r, e->V, s.source);
     HIP_TRY(hipGetLastError());
     s.converged = false;
     s.park_eps = 0.0; // (parked rows are zero again)
-    int rc = main_loop_inspect(e, s, ep, 0, eps);
+    rc = main_loop_inspect(e, s, ep, 0, eps);
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(e->ev1, e->stream));
-    HIP_TRY(hipEventSynchronize(e->ev1));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-    if (out_ms) *out_ms = ms;
-    s.converged = true;
-    s.conv_eps = eps;
-    s.last_epoch = ep.id;
-    return DPPR_OK;
+    return solve_finished(e, s, eps, ep.id, false, out_ms);
 }
 
 int dppr_incremental_batch_update(dppr_engine *e, int32_t slot, int32_t epoch) {
@@ -871,118 +864,7 @@ int dppr_update(dppr_engine *e, int32_t slot, int32_t epoch, double eps, float *
     if (!(eps > 0)) return fail(e, DPPR_ERR_INVALID, "eps must be positive");
     if (!epoch_in_sequence(s.last_epoch, ep.id)) return fail(e, DPPR_ERR_INVALID, "epoch out of sequence for this source");
     HIP_TRY(hipSetDevice(e->device));
-    if (!e->persist_ok && e->persist_mode && e->persist_retry > 0 && --e->persist_retry == 0)
-        e->persist_ok = true; // a resident launch gave up a while ago (the CUs were shared): try them again
-    s.seed_lists_valid = false;
-    // Seeding from the batch tails is exact only if every |r| <= eps beforehand
-    // (the state a completed solve leaves). Otherwise fall back to full Inspect passes.
-    // Merged loop (dppr_set_phase_merge, eager schedule): residuals of both signs are pushed in ONE loop, to eps / merge_div.
-    const bool merged = e->merge_phases && e->schedule == DPPR_SCHEDULE_EAGER;
-    if (merged) eps = eps / e->merge_div;
-    const bool seeded = s.converged && s.conv_eps <= eps;
-    const bool ahead = seeded && can_batch_ahead(e, s, ep) && resident_arena(e, ep);
-    int rc = settle_parked(e, s.p, s.r, 1, eps, &s.park_eps, &s.st);
-    if (rc) return rc;
-    rc = prepare_epoch(e, ep);
-    if (rc) return rc;
-    if (e->raw_backoff > 0) --e->raw_backoff;
-    HIP_TRY(hipEventRecord(e->ev0, e->stream));
-    // A whole-batch resident launch applies the records itself (PLAN_UPDATE) -- grouped at slide time and cut into the sweep groups'
-    // ranges, or (default accounting) RAW: the launch finds, orders and applies every group's records itself. Only the counters
-    // and the GridBar are cleared here. Should the launch call itself off, nothing was changed and the update runs as its own
-    // kernels after all.
-    const bool raw_ok = !ep.grouped && ep.L > 0 && ep.L <= RES_RAW_STEPS * sweep_block(e) && e->raw_backoff == 0;
-    bool inline_su = ahead && e->res_update && ((ep.su_inline && ep.grouped) || raw_ok);
-    if (inline_su) {
-        hipLaunchKernelGGL(k_su_keys, dim3(1), dim3(BLOCK), 0, e->stream, ep.b1, 0, e->su_k[0], e->su_v[0],
-                           reinterpret_cast<unsigned long long *>(e->bar.get()), (int)(sizeof(GridBar) / sizeof(unsigned long long)), s.cnt, 5);
-        HIP_TRY(hipGetLastError());
-    } else {
-        rc = stream_update(e, s, ep, eps, seeded, ahead);
-    }
-    if (rc) return rc;
-    s.converged = false;
-    auto update_after_abort = [&]() -> int { // (inline_su only) the launch called itself off
-        if (!inline_su) return DPPR_OK;
-        if (e->launch_called_off) {
-            inline_su = false;
-            return stream_update(e, s, ep, eps, seeded, false);
-        }
-        s.st.records += ep.L;
-        return DPPR_OK;
-    };
-    if (merged && ahead) { // a window that runs resident: the whole merged loop as ONE launch that seeds itself
-        int stage = 0;
-        bool p1 = false;
-        LoopEntry en0, en1;
-        rc = batch_ahead(e, s, ep, eps, &stage, &en0, &en1, &p1, true, inline_su);
-        if (rc) return rc;
-        rc = update_after_abort();
-        if (rc) return rc;
-        if (stage != 2) { // out of sweeps, or the roll-call failed (then the update's lists stand: add the negative tails)
-            if (en0.it == 0 && !en0.dense) {
-                hipLaunchKernelGGL(k_filter, dim3(grid_for(std::max(ep.L, 1))), dim3(BLOCK), 0, e->stream, s.neg, s.cnt + 3, s.r, 1, eps,
-                                   s.ft[0], s.cnt + 0);
-                HIP_TRY(hipGetLastError());
-            }
-            rc = run_frontier_loop(e, s, ep, PHASE_BOTH, eps, 0, 0, en0);
-            if (rc) return rc;
-        }
-    } else if (merged) {
-        if (seeded) { // the frontier: the tails the update left above eps (ft[0]) and those it left below -eps (the candidates)
-            hipLaunchKernelGGL(k_filter, dim3(grid_for(std::max(ep.L, 1))), dim3(BLOCK), 0, e->stream, s.neg, s.cnt + 3, s.r, 1, eps,
-                               s.ft[0], s.cnt + 0);
-            HIP_TRY(hipGetLastError());
-            rc = run_frontier_loop(e, s, ep, PHASE_BOTH, eps, 0, 0);
-        } else {
-            rc = main_loop_inspect(e, s, ep, PHASE_BOTH, eps);
-        }
-        if (rc) return rc;
-    } else if (seeded) {
-        int stage = 0;
-        bool p1_seeded = false;
-        LoopEntry en0, en1;
-        if (ahead) {
-            rc = batch_ahead(e, s, ep, eps, &stage, &en0, &en1, &p1_seeded, false, inline_su);
-            if (rc) return rc;
-            rc = update_after_abort();
-            if (rc) return rc;
-        }
-        if (stage == 0) {
-            rc = run_frontier_loop(e, s, ep, 0, eps, 0, 0, en0);
-            if (rc) return rc;
-        }
-        if (stage <= 1 && !p1_seeded && inline_su) {
-            // the update ran inside the launch and recorded no candidates: phase 1 starts from a full Inspect
-            rc = main_loop_inspect(e, s, ep, 1, eps);
-            if (rc) return rc;
-        } else if (stage <= 1) {
-            if (!p1_seeded) { // phase 1: candidates recorded by the update, re-checked now
-                HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(int) * 3, e->stream));
-                hipLaunchKernelGGL(k_filter, dim3(grid_for(std::max(ep.L, 1))), dim3(BLOCK), 0, e->stream, s.neg,
-                                   s.cnt + 3, s.r, 1, eps, s.ft[0], s.cnt + 0);
-                HIP_TRY(hipGetLastError());
-            }
-            rc = run_frontier_loop(e, s, ep, 1, eps, 0, 0, en1);
-            if (rc) return rc;
-        }
-    } else {
-        rc = main_loop_inspect(e, s, ep, 0, eps);
-        if (rc) return rc;
-        rc = main_loop_inspect(e, s, ep, 1, eps);
-        if (rc) return rc;
-    }
-    HIP_TRY(hipEventRecord(e->ev1, e->stream));
-    HIP_TRY(hipEventSynchronize(e->ev1));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-    if (out_ms) *out_ms = ms;
-    s.st.gpu_ms += ms;
-    s.st.batches++;
-    s.converged = true;
-    s.conv_eps = eps; // (the merged loop's eps / merge_div)
-    s.last_epoch = ep.id;
-    return DPPR_OK;
+    return slot_update(e, s, ep, eps, out_ms);
 }
 
 int dppr_read(dppr_engine *e, int32_t slot, double *p, double *r) {
@@ -1055,19 +937,13 @@ int dppr_stats(dppr_engine *e, int32_t slot, dppr_stats_t *out) {
     GET_SLOT(e, slot);
     if (!out) return DPPR_ERR_INVALID;
     HIP_TRY(hipSetDevice(e->device));
-    int rc = pull_device_stats(e, s.dstats, s.st);
-    if (rc) return rc;
-    *out = s.st;
-    return DPPR_OK;
+    return solve_stats(e, s, out);
 }
 
 int dppr_reset_stats(dppr_engine *e, int32_t slot) {
     GET_SLOT(e, slot);
     HIP_TRY(hipSetDevice(e->device));
-    s.st = dppr_stats_t{};
-    HIP_TRY(hipMemsetAsync(s.dstats, 0, 2 * sizeof(IterStats), e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return DPPR_OK;
+    return solve_reset_stats(e, s);
 }
 
 int dppr_inspect(dppr_engine *e, int32_t slot, int phase, double eps, int32_t *out_ids, int32_t *out_count) {
@@ -1244,22 +1120,15 @@ int dppr_group_init_solve_at(dppr_engine *e, int32_t group, int32_t epoch, doubl
     GET_EPOCH(e, epoch);
     if (!(eps > 0)) return fail(e, DPPR_ERR_INVALID, "eps must be positive");
     HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipEventRecord(e->ev0, e->stream));
+    int rc = bracket_open(e);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_ginit, dim3(grid_for((int64_t)e->V * g.gw)), dim3(BLOCK), 0, e->stream, g.p, g.r, e->V, g.gw, g.src);
     HIP_TRY(hipGetLastError());
     g.converged = false;
     g.park_eps = 0.0;
-    int rc = group_loop(e, g, ep, 0, eps, false);
+    rc = group_loop(e, g, ep, 0, eps, false);
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(e->ev1, e->stream));
-    HIP_TRY(hipEventSynchronize(e->ev1));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-    if (out_ms) *out_ms = ms;
-    g.converged = true; // r = e_s >= 0 and phase 0 left every r <= eps: nothing is below -eps
-    g.conv_eps = eps;
-    g.last_epoch = ep.id;
-    return DPPR_OK;
+    return solve_finished(e, g, eps, ep.id, false, out_ms); // r = e_s >= 0 and phase 0 left every r <= eps: nothing is below -eps
 }
 
 int dppr_group_update(dppr_engine *e, int32_t group, int32_t epoch, double eps, float *out_ms) {
@@ -1268,38 +1137,7 @@ int dppr_group_update(dppr_engine *e, int32_t group, int32_t epoch, double eps, 
     if (!(eps > 0)) return fail(e, DPPR_ERR_INVALID, "eps must be positive");
     if (!epoch_in_sequence(g.last_epoch, ep.id)) return fail(e, DPPR_ERR_INVALID, "epoch out of sequence for this group");
     HIP_TRY(hipSetDevice(e->device));
-    // seeding from the batch tails is exact only if every |r| <= eps beforehand (dppr_update has the same rule)
-    const bool merged = e->merge_phases && e->schedule == DPPR_SCHEDULE_EAGER; // (dppr_set_phase_merge)
-    if (merged) eps = eps / e->merge_div;
-    const bool tails = g.converged && g.conv_eps <= eps && e->group_tail_seeding;
-    int rc = settle_parked(e, g.p, g.r, g.gw, eps, &g.park_eps, &g.st);
-    if (rc) return rc;
-    rc = prepare_epoch(e, ep);
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(e->ev0, e->stream));
-    rc = group_stream_update(e, g, ep);
-    if (rc) return rc;
-    g.converged = false;
-    if (merged) {
-        rc = group_loop(e, g, ep, PHASE_BOTH, eps, tails);
-        if (rc) return rc;
-    } else {
-        rc = group_loop(e, g, ep, 0, eps, tails);
-        if (rc) return rc;
-        rc = group_loop(e, g, ep, 1, eps, tails);
-        if (rc) return rc;
-    }
-    HIP_TRY(hipEventRecord(e->ev1, e->stream));
-    HIP_TRY(hipEventSynchronize(e->ev1));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-    if (out_ms) *out_ms = ms;
-    g.st.gpu_ms += ms;
-    g.st.batches++;
-    g.converged = true;
-    g.conv_eps = eps;
-    g.last_epoch = ep.id;
-    return DPPR_OK;
+    return group_update(e, g, ep, eps, out_ms);
 }
 
 int dppr_group_read(dppr_engine *e, int32_t group, int32_t index, double *p, double *r) {
@@ -1333,6 +1171,7 @@ static constexpr bool churn_geometry_agrees() {
 static_assert(churn_geometry_agrees(), "dppr_churn_plan.hpp restates row_width / row_spl of dppr_multi.hpp");
 static_assert(PLAN_RES_MAX_SWEEPS == RES_MAX_SWEEPS && PLAN_GPUSH_LOG == GPUSH_LOG && PLAN_TINY_N == TINY_N && PLAN_TINY_E == TINY_E,
               "dppr_loop_plan.hpp restates RES_MAX_SWEEPS of dppr_resident.hpp and GPUSH_LOG / TINY_N / TINY_E of dppr_gpush.hpp");
+static_assert(LOOP_PHASE_BOTH == PHASE_BOTH, "dppr_loop_plan.hpp restates PHASE_BOTH of dppr_common.hpp");
 
 int dppr_group_sources(dppr_engine *e, int32_t group, int32_t *out_sources, int32_t *out_n) {
     GET_GROUP(e, group);
@@ -1377,7 +1216,7 @@ static int group_churn(dppr_engine *e, int32_t group, ChurnOp op, int32_t index,
         if (pl.recut) e->wide_groups = true;
         if (int rc = recut_stale_groups(e)) return rc; // (a fresh id lies beyond every resident epoch's tables; the first wide group halves the sweep groups)
     }
-    HIP_TRY(hipEventRecord(e->ev0, e->stream));
+    if (int rc = bracket_open(e)) return rc;
     if (pl.relayout) {
         ColMap cm;
         for (int s = 0; s < GS_MAX; ++s) cm.m[s] = pl.map[s];
@@ -1415,10 +1254,8 @@ static int group_churn(dppr_engine *e, int32_t group, ChurnOp op, int32_t index,
         g.converged = false;
         if (int rc = group_solve_column(e, g, ep)) return rc;
     }
-    HIP_TRY(hipEventRecord(e->ev1, e->stream));
-    HIP_TRY(hipEventSynchronize(e->ev1));
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+    if (int rc = bracket_close(e, &ms)) return rc;
     if (out_ms) *out_ms = ms;
     if (out_index) *out_index = pl.lane;
     g.converged = true; // at the same conv_eps, on the same last_epoch: the next dppr_group_update seeds from the batch tails as before
@@ -1486,20 +1323,14 @@ int dppr_group_read_at(dppr_engine *e, int32_t group, const int32_t *ids, int32_
 int dppr_group_reset_stats(dppr_engine *e, int32_t group) {
     GET_GROUP(e, group);
     HIP_TRY(hipSetDevice(e->device));
-    g.st = dppr_stats_t{};
-    HIP_TRY(hipMemsetAsync(g.dstats, 0, 2 * sizeof(IterStats), e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return DPPR_OK;
+    return solve_reset_stats(e, g);
 }
 
 int dppr_group_stats(dppr_engine *e, int32_t group, dppr_stats_t *out) {
     GET_GROUP(e, group);
     if (!out) return DPPR_ERR_INVALID;
     HIP_TRY(hipSetDevice(e->device));
-    int rc = pull_device_stats(e, g.dstats, g.st);
-    if (rc) return rc;
-    *out = g.st;
-    return DPPR_OK;
+    return solve_stats(e, g, out);
 }
 
 #ifdef DPPR_STAMPS
@@ -1516,18 +1347,13 @@ extern "C" int dppr_debug_stamps(unsigned long long *out, int rows) {
 
 int dppr_bench_atomics(int device, int64_t table_elems, int64_t n, int scope, int reps, float *out_ms) {
     if (table_elems <= 0 || (table_elems & (table_elems - 1)) || n <= 0 || reps <= 0 || !out_ms) return DPPR_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return DPPR_ERR_NO_DEVICE;
-    if (hipSetDevice(device) != hipSuccess) return DPPR_ERR_HIP;
+    if (int rc = calib_device(device)) return rc;
     DevBuf<double> table, sink;
-    hipEvent_t a, b;
     if (table.alloc((size_t)table_elems) != 0) return DPPR_ERR_NOMEM;
     (void)sink.alloc(1);
     (void)hipMemset(table, 0, sizeof(double) * (size_t)table_elems);
-    (void)hipEventCreate(&a);
-    (void)hipEventCreate(&b);
     const int grid = 2048;
-    auto launch = [&]() {
+    return time_launches(reps, out_ms, [&]() {
         if (scope == 2) // (calibration only) adds whose result is not used
             hipLaunchKernelGGL(k_bench_scatter<0>, dim3(grid), dim3(BLOCK), 0, 0, table, (uint64_t)table_elems - 1, n);
         else if (scope == 3) // ... and plain scattered 8-byte stores
@@ -1538,77 +1364,38 @@ int dppr_bench_atomics(int device, int64_t table_elems, int64_t n, int scope, in
         else
             hipLaunchKernelGGL(k_bench_atomics<__HIP_MEMORY_SCOPE_WORKGROUP>, dim3(grid), dim3(BLOCK), 0, 0, table,
                                (uint64_t)table_elems - 1, n, sink);
-    };
-    launch(); // warm-up
-    (void)hipEventRecord(a, 0);
-    for (int i = 0; i < reps; ++i) launch();
-    (void)hipEventRecord(b, 0);
-    hipError_t err = hipEventSynchronize(b);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, a, b);
-    *out_ms = ms / reps;
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
-    return err == hipSuccess ? DPPR_OK : DPPR_ERR_HIP;
+    });
 }
 
 int dppr_bench_line_fills(int device, int64_t table_bytes, int64_t lines, int reps, float *out_ms) {
     if (table_bytes < 128 || (table_bytes & (table_bytes - 1)) || lines <= 0 || reps <= 0 || !out_ms) return DPPR_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return DPPR_ERR_NO_DEVICE;
-    if (hipSetDevice(device) != hipSuccess) return DPPR_ERR_HIP;
+    if (int rc = calib_device(device)) return rc;
     DevBuf<double2> table;
     DevBuf<double> sink;
     if (table.alloc((size_t)table_bytes / sizeof(double2)) != 0) return DPPR_ERR_NOMEM; // (a power of two >= 128)
     (void)sink.alloc(1);
     (void)hipMemset(table, 0, (size_t)table_bytes);
-    hipEvent_t a, b;
-    (void)hipEventCreate(&a);
-    (void)hipEventCreate(&b);
     const int grid = 2048; // 2048 x 128 octets
     const int per = (int)std::max<int64_t>(8, (lines + (int64_t)grid * 128 - 1) / ((int64_t)grid * 128) / 8 * 8);
-    auto launch = [&]() {
+    const int rc = time_launches(reps, out_ms, [&]() {
         hipLaunchKernelGGL(k_bench_lines<8>, dim3(grid), dim3(1024), 0, 0, table, (uint64_t)(table_bytes / 128) - 1, per, sink);
-    };
-    launch(); // warm-up
-    (void)hipEventRecord(a, 0);
-    for (int i = 0; i < reps; ++i) launch();
-    (void)hipEventRecord(b, 0);
-    hipError_t err = hipEventSynchronize(b);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, a, b);
+    });
     // per launch, scaled to the number of lines asked for (the launch fetches grid * 128 * per of them)
-    *out_ms = ms / reps * (float)((double)lines / ((double)grid * 128.0 * per));
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
-    return err == hipSuccess ? DPPR_OK : DPPR_ERR_HIP;
+    *out_ms = *out_ms * (float)((double)lines / ((double)grid * 128.0 * per));
+    return rc;
 }
 
 int dppr_bench_stream_copy(int device, int64_t bytes, int reps, float *out_ms) {
     if (bytes < 16 || reps <= 0 || !out_ms) return DPPR_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return DPPR_ERR_NO_DEVICE;
-    if (hipSetDevice(device) != hipSuccess) return DPPR_ERR_HIP;
+    if (int rc = calib_device(device)) return rc;
     DevBuf<unsigned char> src, dst; // (`bytes` need not be a multiple of 16: the kernel copies bytes / 16 double2s)
     if (src.alloc((size_t)bytes) != 0 || dst.alloc((size_t)bytes) != 0) return DPPR_ERR_NOMEM;
     (void)hipMemset(src, 0, (size_t)bytes);
     (void)hipMemset(dst, 0, (size_t)bytes);
-    hipEvent_t a, b;
-    (void)hipEventCreate(&a);
-    (void)hipEventCreate(&b);
-    auto launch = [&]() { hipLaunchKernelGGL(k_bench_copy, dim3(4096), dim3(1024), 0, 0, reinterpret_cast<const double2 *>(src.get()),
-                                            reinterpret_cast<double2 *>(dst.get()), bytes / 16); };
-    launch();
-    (void)hipEventRecord(a, 0);
-    for (int i = 0; i < reps; ++i) launch();
-    (void)hipEventRecord(b, 0);
-    hipError_t err = hipEventSynchronize(b);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, a, b);
-    *out_ms = ms / reps;
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
-    return err == hipSuccess ? DPPR_OK : DPPR_ERR_HIP;
+    return time_launches(reps, out_ms, [&]() {
+        hipLaunchKernelGGL(k_bench_copy, dim3(4096), dim3(1024), 0, 0, reinterpret_cast<const double2 *>(src.get()),
+                           reinterpret_cast<double2 *>(dst.get()), bytes / 16);
+    });
 }
 
 int dppr_debug_bin_tables(dppr_engine *e, int32_t epoch, int32_t *n_a, int32_t *n_b, int32_t *n_edges, int32_t *n_runs, int32_t *n_tiles,

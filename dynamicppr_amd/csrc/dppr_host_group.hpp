@@ -1,5 +1,6 @@
 // dppr_host_group.hpp -- host side, part 4 of 4: source groups (f2). The frontier loop of up to 16 sources solved together:
-// one-sweep and multi-sweep launches of k_gsweep, the push form of a loop's tail (dppr_gpush.hpp), the group's stream update.
+// one-sweep and multi-sweep launches of k_gsweep, the push form of a loop's tail (dppr_gpush.hpp), the group's stream update,
+// and the sequence of one batch (group_update).
 #pragma once
 
 namespace {
@@ -359,6 +360,27 @@ int group_stream_update(dppr_engine *e, Group &g, const Epoch &ep) {
     HIP_TRY(hipGetLastError());
     g.st.records += (int64_t)L * g.n;
     return DPPR_OK;
+}
+
+// One batch of a source group = dppr_group_update: the stream update of every source and the loops, inside the event bracket
+int group_update(dppr_engine *e, Group &g, Epoch &ep, double eps, float *out_ms) {
+    // seeding from the batch tails is exact only if every |r| <= eps beforehand (slot_update has the same rule)
+    const bool merged = e->merge_phases && e->schedule == DPPR_SCHEDULE_EAGER; // (dppr_set_phase_merge)
+    if (merged) eps = eps / e->merge_div;
+    const bool tails = g.converged && g.conv_eps <= eps && e->group_tail_seeding;
+    int rc = settle_parked(e, g.p, g.r, g.gw, eps, &g.park_eps, &g.st);
+    if (rc) return rc;
+    rc = prepare_epoch(e, ep);
+    if (rc) return rc;
+    rc = bracket_open(e);
+    if (rc) return rc;
+    rc = group_stream_update(e, g, ep);
+    if (rc) return rc;
+    g.converged = false;
+    if (merged) rc = group_loop(e, g, ep, PHASE_BOTH, eps, tails);
+    else if (!(rc = group_loop(e, g, ep, 0, eps, tails))) rc = group_loop(e, g, ep, 1, eps, tails);
+    if (rc) return rc;
+    return solve_finished(e, g, eps, ep.id, true, out_ms);
 }
 
 } // namespace

@@ -1,7 +1,8 @@
 // dppr_host_loop.hpp -- host side, part 3 of 4: the single-source SOLVER. IncrementalBatchUpdate's grouping and replay
 // (gpu/StreamUpdate.cuh:7-76), the frontier loop of PPRRevPushGPU::ExecuteOptimized (gpu/PPRRevPushGPU.cuh:97-131) with its launch
 // forms -- push iterations, per-iteration sweeps (gather or binned), resident launches of a run of sweeps or of a whole batch --
-// and the policies that choose between them. Runs on the engine's solver stream.
+// and the sequence of one batch (slot_update). What to launch and what follows a launch is decided in dppr_loop_plan.hpp; the
+// functions here enqueue, read back and account. Runs on the engine's solver stream.
 #pragma once
 
 namespace {
@@ -60,15 +61,8 @@ inline void account_sweeps(dppr_stats_t &st, const int *rows, int n, int width, 
 // atomics; as ONE resident launch for the whole chunk when the epoch's sweep groups fit the chip,
 // dppr_resident.hpp) -- the same sums either way.
 //
-// `entry` describes a loop that is picked up in the middle (after a launch of batch_ahead that
-// ended before the loop did): iterations already done, the frontier size if the host knows it,
-// and whether s.x already holds the frontier's dense snapshot.
-struct LoopEntry {
-    int it = 0;
-    int F = -1; // -1: read cnt[cur]
-    bool dense = false;
-    bool any_pull = false;
-};
+// `entry` (LoopEntry, dppr_loop_plan.hpp) describes a loop that is picked up in the middle (after a
+// launch of batch_ahead that ended before the loop did).
 
 int pull_min_frontier(const dppr_engine *e) { return dppr::pull_min_frontier(e->pull_min_frontier, e->Ed); }
 
@@ -357,7 +351,7 @@ int run_frontier_loop(dppr_engine *e, Slot &s, const Epoch &ep, int phase, doubl
 // of gpu/PPRGPU.cuh:138-164 are one kernel. One copy of the counters, the status word and the log
 // comes back at the end. Whatever did not go as expected (a phase needed more sweeps than the
 // launch was given, the roll-call failed) leaves the state at a well-defined point from which the
-// ordinary host-driven loop resumes (`stage`, `en0`, `en1`).
+// ordinary host-driven loop resumes (AheadOutcome::stage / entry).
 // The reference pays a blocking read-back per ITERATION (gpu/PPRRevPushGPU.cuh:107).
 // ---------------------------------------------------------------------------------------------
 bool can_batch_ahead(const dppr_engine *e, const Slot &s, const Epoch &ep) {
@@ -373,13 +367,11 @@ bool can_batch_ahead(const dppr_engine *e, const Slot &s, const Epoch &ep) {
            (s.hist.hint[0] > 0 && s.hist.hint[1] > 0 && s.start_dense[0] && s.start_dense[1]);
 }
 
-// stage (out): 0 = phase 0 still open (resume with en0), 1 = phase 0 done, phase 1 open (resume with
-// en1; *p1_seeded tells whether its snapshot exists), 2 = both phases done
-int batch_ahead(dppr_engine *e, Slot &s, const Epoch &ep, double eps, int *stage, LoopEntry *en0, LoopEntry *en1,
-                bool *p1_seeded, bool merged = false, bool inline_update = false) {
-    // merged (dppr_set_phase_merge): ONE loop over residuals of both signs -- the launch seeds it (PLAN_SEED) and runs it to the
-    // end; stage 0 + en0 if it ran out of sweeps, stage 2 when it converged (histories in slot 0)
-    const int pull_min = pull_min_frontier(e);
+// What the launch reported comes back as `out` (AheadOutcome, dppr_loop_plan.hpp: decoded and applied to the slot there); a
+// status other than DPPR_OK only for a HIP error or a wait that timed out inside the launch.
+// merged (dppr_set_phase_merge): ONE loop over residuals of both signs -- the launch seeds it (PLAN_SEED) and runs it to the end
+// (histories in slot 0); inline_update: the launch applies the batch's records itself (PLAN_UPDATE)
+int batch_ahead(dppr_engine *e, Slot &s, const Epoch &ep, double eps, bool merged, bool inline_update, AheadOutcome &out) {
     const int n = batch_ahead_sweeps(merged, s.hist, e->chunk_iters, e->chunk_explicit);
     // (the launch's status word is s.cnt[7]; the GridBar was zeroed by the batch's first kernel, k_su_keys)
     const ResUpdate upd = !inline_update ? ResUpdate{}
@@ -393,27 +385,19 @@ int batch_ahead(dppr_engine *e, Slot &s, const Epoch &ep, double eps, int *stage
     HIP_TRY(hipMemcpyAsync(e->pinned, s.cnt, sizeof(int) * (size_t)(CNT_HDR + n), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(loop_wait(e));
 
-    const int st = e->pinned[7];
-    *stage = 0;
-    *p1_seeded = false;
-    *en0 = LoopEntry();
-    *en1 = LoopEntry();
+    out = ahead_outcome(e->pinned[7], e->pinned[4], e->pinned[0], e->pinned + CNT_HDR, n, merged, inline_update, ep.grouped);
     s.st.persist_launches++;
-    if (st & PERSIST_FAULT) return fail(e, DPPR_ERR_HIP, "a wait inside the resident sweep timed out");
-    e->launch_called_off = false;
-    if ((st & PERSIST_ABORTED) && inline_update && !ep.grouped && e->pinned[4] == 1) {
-        // a sweep group owns more of the batch's records than it has threads: the launch called itself off before anything was
-        // changed -- not a residency problem. The caller applies the update with its own kernels; the next batches do so at once.
-        e->launch_called_off = true;
+    switch (out.kind) {
+    case AHEAD_FAULT: return fail(e, DPPR_ERR_HIP, "a wait inside the resident sweep timed out");
+    case AHEAD_CALLED_OFF_RECORDS: // not a residency problem: the caller applies the update with its own kernels, the next batches do so at once
         e->raw_backoff = 16;
         return DPPR_OK;
-    }
-    if (st & PERSIST_ABORTED) { // roll-call failed: nothing was changed, the lists of the stream update stand
+    case AHEAD_CALLED_OFF_ROLLCALL: // nothing was changed, the lists of the stream update stand; per-iteration launches for a while
         s.st.persist_aborts++;
-        e->launch_called_off = true;
         e->persist_ok = false;
         e->persist_retry = PERSIST_RETRY_BATCHES;
         return DPPR_OK;
+    case AHEAD_RAN: break;
     }
     if (e->profiling) {
         float ms = 0;
@@ -421,51 +405,7 @@ int batch_ahead(dppr_engine *e, Slot &s, const Epoch &ep, double eps, int *stage
         s.st.push_ms += ms;
         s.st.push_launches++;
     }
-    const int pos = st & PERSIST_SWEEPS; // loop position the launch stopped at
-    const PhaseLog pl = split_phase_log(e->pinned + CNT_HDR, std::min(pos + 1, n));
-    const int *act = pl.act;
-    for (int ph = 0; ph < 2; ++ph)
-        if (act[ph] > 0) {
-            s.start_dense[ph] = pl.F0[ph] >= pull_min;
-            s.last_F0[ph] = pl.F0[ph];
-        }
-    s.st.iterations += act[0] + act[1];
-    s.st.pull_iterations += act[0] + act[1];
-    s.st.sum_F += pl.sum_F;
-    if (merged) {
-        if (!(st & PERSIST_CONVERGED)) { // out of sweeps: the host-driven loop goes on from here
-            en0->it = act[0];
-            en0->F = e->pinned[0];
-            en0->dense = true;
-            en0->any_pull = true;
-            return DPPR_OK;
-        }
-        s.hist.record(0, act[0]);
-        if (act[0] == 0) s.start_dense[0] = false;
-        *stage = 2;
-        return DPPR_OK;
-    }
-    if (!(st & PERSIST_PHASE1)) { // phase 0 needs more sweeps than the launch had; phase 1 has not started
-        en0->it = act[0];
-        en0->F = e->pinned[0];
-        en0->dense = true;
-        en0->any_pull = true;
-        return DPPR_OK;
-    }
-    s.hist.hint[0] = act[0];
-    if (act[0] == 0) s.start_dense[0] = false;
-    *stage = 1;
-    *p1_seeded = true;
-    if (!(st & PERSIST_CONVERGED)) {
-        en1->it = act[1];
-        en1->F = e->pinned[0];
-        en1->dense = true;
-        en1->any_pull = true;
-        return DPPR_OK;
-    }
-    s.hist.hint[1] = act[1];
-    if (act[1] == 0) s.start_dense[1] = false;
-    *stage = 2;
+    apply_ahead(out, merged, pull_min_frontier(e), s.hist, s.start_dense, s.last_F0, s.st.iterations, s.st.pull_iterations, s.st.sum_F);
     return DPPR_OK;
 }
 
@@ -612,6 +552,79 @@ int pull_device_stats(dppr_engine *e, const IterStats *dstats, dppr_stats_t &st)
     // after a converged solve the frontier is seeded from the batch tails and no vertex is scanned
     st.algorithmic_bytes = 8ll * st.inspected + 45ll * st.records + 72ll * st.sum_F + 24ll * st.sum_E + 4ll * st.sum_N;
     return DPPR_OK;
+}
+
+// dppr_stats / dppr_group_stats and their resets
+int solve_stats(dppr_engine *e, SolveState &o, dppr_stats_t *out) {
+    if (int rc = pull_device_stats(e, o.dstats, o.st)) return rc;
+    *out = o.st;
+    return DPPR_OK;
+}
+int solve_reset_stats(dppr_engine *e, SolveState &o) {
+    o.st = dppr_stats_t{};
+    HIP_TRY(hipMemsetAsync(o.dstats, 0, 2 * sizeof(IterStats), e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return DPPR_OK;
+}
+
+// the candidates the update recorded below -eps (s.neg, cnt[3]), re-checked now, appended to the list in ft[0] / cnt[0]
+// (clear: after cnt[0..2] were zeroed -- the list then holds them alone)
+int filter_negative_tails(dppr_engine *e, Slot &s, const Epoch &ep, double eps, bool clear) {
+    if (clear) HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(int) * 3, e->stream));
+    hipLaunchKernelGGL(k_filter, dim3(grid_for(std::max(ep.L, 1))), dim3(BLOCK), 0, e->stream, s.neg, s.cnt + 3, s.r, 1, eps, s.ft[0], s.cnt + 0);
+    HIP_TRY(hipGetLastError());
+    return DPPR_OK;
+}
+
+// One batch of one source = dppr_update: IncrementalBatchUpdate and both frontier loops (gpu/PPRGPU.cuh:138-164), inside the
+// event bracket. Top to bottom: settle, prepare, open the bracket; the update (or, where a whole-batch launch applies it, the
+// kernel that clears the counters); that launch; after_launch (dppr_loop_plan.hpp) says what follows; at most one redone update,
+// one filter and two loops; close the bracket.
+int slot_update(dppr_engine *e, Slot &s, Epoch &ep, double eps, float *out_ms) {
+    if (!e->persist_ok && e->persist_mode && e->persist_retry > 0 && --e->persist_retry == 0)
+        e->persist_ok = true; // a resident launch gave up a while ago (the CUs were shared): try them again
+    s.seed_lists_valid = false;
+    // Seeding from the batch tails is exact only if every |r| <= eps beforehand
+    // (the state a completed solve leaves). Otherwise fall back to full Inspect passes.
+    // Merged loop (dppr_set_phase_merge, eager schedule): residuals of both signs are pushed in ONE loop, to eps / merge_div.
+    const bool merged = e->merge_phases && e->schedule == DPPR_SCHEDULE_EAGER;
+    if (merged) eps = eps / e->merge_div;
+    const bool seeded = s.converged && s.conv_eps <= eps;
+    const bool ahead = seeded && can_batch_ahead(e, s, ep) && resident_arena(e, ep);
+    int rc = settle_parked(e, s.p, s.r, 1, eps, &s.park_eps, &s.st);
+    if (rc) return rc;
+    rc = prepare_epoch(e, ep);
+    if (rc) return rc;
+    if (e->raw_backoff > 0) --e->raw_backoff;
+    rc = bracket_open(e);
+    if (rc) return rc;
+    // A whole-batch resident launch applies the records itself (PLAN_UPDATE) -- grouped at slide time and cut into the sweep groups'
+    // ranges, or (default accounting) RAW: the launch finds, orders and applies every group's records itself. Only the counters
+    // and the GridBar are cleared here. Should the launch call itself off, nothing was changed and the update runs as its own
+    // kernels after all.
+    const bool raw_ok = !ep.grouped && ep.L > 0 && ep.L <= RES_RAW_STEPS * sweep_block(e) && e->raw_backoff == 0;
+    const bool inline_su = ahead && e->res_update && ((ep.su_inline && ep.grouped) || raw_ok);
+    if (inline_su) {
+        hipLaunchKernelGGL(k_su_keys, dim3(1), dim3(BLOCK), 0, e->stream, ep.b1, 0, e->su_k[0], e->su_v[0],
+                           reinterpret_cast<unsigned long long *>(e->bar.get()), (int)(sizeof(GridBar) / sizeof(unsigned long long)), s.cnt, 5);
+        HIP_TRY(hipGetLastError());
+    } else {
+        rc = stream_update(e, s, ep, eps, seeded, ahead);
+    }
+    if (rc) return rc;
+    s.converged = false;
+    AheadOutcome launched; // (no launch: as constructed)
+    if (ahead && (rc = batch_ahead(e, s, ep, eps, merged, inline_su, launched))) return rc;
+    const AfterLaunch then = after_launch(merged, seeded, ahead, inline_su, launched);
+    if (then.redo_update && (rc = stream_update(e, s, ep, eps, seeded, false))) return rc;
+    if (then.count_records) s.st.records += ep.L;
+    for (int k = 0; k < then.n_loops; ++k) {
+        const LoopStep &l = then.loop[k];
+        if (then.filter && k == then.n_loops - 1 && (rc = filter_negative_tails(e, s, ep, eps, then.filter_clears))) return rc;
+        rc = l.inspect ? main_loop_inspect(e, s, ep, l.phase, eps) : run_frontier_loop(e, s, ep, l.phase, eps, 0, 0, l.entry);
+        if (rc) return rc;
+    }
+    return solve_finished(e, s, eps, ep.id, true, out_ms); // (eps: the merged loop's eps / merge_div)
 }
 
 } // namespace

@@ -1,7 +1,8 @@
 // dppr_host_state.hpp -- host side of libdppr_hip.so, part 1 of 4: what an engine OWNS (replaces gpu/DeviceMemory.cuh,
 // gpu/GPUEdgeBatch.cuh and the members of gpu/SlidingGraphBuilder.cuh) -- the resident graph epochs, the per-source slots and source
-// groups, the two HIP streams (solver / builder) and their scratch -- plus the small helpers every other part uses (error
-// reporting, the bounded stream wait, the id lookahead of dppr_hint_next_batch).
+// groups (what both carry with the same meaning: SolveState), the two HIP streams (solver / builder) and their scratch -- plus the
+// small helpers every other part uses (error reporting, the bounded stream wait, the event bracket of a timed region and the end of
+// a solve, the id lookahead of dppr_hint_next_batch).
 // Every device or pinned-host allocation is a DevBuf / PinBuf (dppr_devbuf.hpp) that is a member of its owner -- Epoch, Slot, Group,
 // dppr_engine -- or a local of the function that needs it: memory goes when its owner goes, dppr_destroy lists nothing, and a call
 // that fails half way leaves nothing behind. The HIP runtime's allocation calls appear in the two policies below and nowhere else.
@@ -102,7 +103,18 @@ struct Epoch {
     bool su_inline = false;     // every group's range fits the launch's workgroup and no tail lies beyond the groups
 };
 
-struct Slot {
+// What a Slot and a Group carry with the same meaning: the state a solve leaves, its statistics and the loops' histories
+struct SolveState {
+    bool converged = false; // |r| <= conv_eps everywhere, for every source (state after a completed solve)
+    double conv_eps = 0.0;
+    double park_eps = 0.0;  // parked rows satisfy |r| <= park_eps (0: they are exactly zero)
+    int last_epoch = -2;    // epoch whose batch was applied last (-2: unknown, e.g. after dppr_write: anything goes)
+    dppr_stats_t st{};
+    LoopHistory hist;       // iterations the last loops of each phase took; groups: also before the push form took over (dppr_loop_plan.hpp)
+    DevBuf<IterStats> dstats; // two blocks: [0] push iterations (and resident launches), [1] dense sweeps -- the roofline of the sweep kernel counts its own edges
+};
+
+struct Slot : SolveState {
     int source = 0;     // internal id
     int source_ext = 0; // id the caller gave
     DevBuf<double> p, r;
@@ -118,25 +130,18 @@ struct Slot {
     long long iter_seq = 0; // running iteration number (selects the big-row counter)
     double sweep_us = 0;       // binned windows: running mean of a sweep's time (the push / sweep decision)
     double atomic_ns = 1.0 / 23.5; // ... and of a push iteration's time per in-edge (starts at the chip's rate of returning f64 atomics)
-    LoopHistory hist;          // iterations the last loops of each phase took (sizes the next chunks: dppr_loop_plan.hpp)
     bool start_dense[2] = {false, false}; // the last loop of each phase began with a frontier worth a sweep
     int last_F0[2] = {0, 0};   // ... and its size
-    DevBuf<IterStats> dstats; // two blocks: [0] push iterations (and resident launches), [1] dense sweeps -- the roofline of the sweep kernel counts its own edges
-    bool converged = false; // |r| <= eps everywhere (state after a completed solve)
-    double conv_eps = 0.0;
-    double park_eps = 0.0;  // parked rows satisfy |r| <= park_eps (0: they are exactly zero)
-    int last_epoch = -2;    // epoch whose batch was applied last (-2: unknown, e.g. after dppr_write: anything goes)
     bool seed_lists_valid = false; // ft[0]/cnt[0] and neg/cnt[3] hold the lists of the last dppr_incremental_batch_update
     bool phase0_done = false; // ExecuteMainLoop(0) completed since the last modification
     double phase0_eps = 0.0;
-    dppr_stats_t st{};
     bool trace = false;
     std::vector<int64_t> trace_off;
     std::vector<int32_t> trace_ids;
 };
 
 // f2: up to 16 sources solved together on interleaved state (dppr_multi.hpp)
-struct Group {
+struct Group : SolveState {
     int n = 0;                 // sources in use (1..16)
     int spl = 1;               // doubles per lane of an octet: 1 (rows of <= 8 doubles) or 2
     int gw = OCT;              // doubles per vertex = row_width(n): 2, 4, .. 16 (dppr_multi.hpp)
@@ -149,17 +154,10 @@ struct Group {
     DevBuf<int> gq;         // one-sweep launches: three rotating group counters (a launch takes tickets from one and zeroes the next), GQ_PAD ints apart
     unsigned gq_seq = 0;       // one-sweep launches enqueued so far
     DevBuf<int> mlog;       // multi-sweep launches: [GS_MAX] status word + padding, then one row of frontier sizes per sweep
-    DevBuf<IterStats> dstats; // two blocks: [0] push iterations (and resident launches), [1] dense sweeps -- the roofline of the sweep kernel counts its own edges
-    dppr_stats_t st{};
-    LoopHistory hist;          // sweeps the last loops of each phase took, in all and before the push form took over (dppr_loop_plan.hpp)
     // the tail of a loop as pushes (dppr_gpush.hpp): vertex lists, scan, control block; allocated on first use
     DevBuf<int> plist[2];
     DevBuf<int> ppre;
     DevBuf<GPushCtl> pctl;
-    bool converged = false;    // |r| <= conv_eps for every source (state after a completed solve)
-    double conv_eps = 0.0;
-    double park_eps = 0.0;     // parked rows satisfy |r| <= park_eps
-    int last_epoch = -2;       // epoch whose batch was applied last (-2: unknown)
 };
 
 } // namespace
@@ -178,7 +176,6 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     int merge_miss_host = 0;        // retired keys the last slide's merge did not find (read back with the build's synchronisations)
     long long merge_fallbacks = 0;  // slides that re-sorted the window because of that
     bool test_force_merge_miss = false; // (test hook, DPPR_TEST_MERGE_MISS=1: every incremental slide takes the fallback)
-    bool launch_called_off = false; // batch_ahead: the last whole-batch launch changed nothing (roll-call failed, or a group had too many records)
     int raw_backoff = 0;         // batches for which a resident launch does not take the records raw (after one called itself off: a group with more records than threads)
     bool merge_phases = false; // dppr_set_phase_merge: one loop for residuals of both signs (eager schedule only)
     int merge_div = 4;         // ... run to eps / merge_div
@@ -412,6 +409,33 @@ inline hipError_t loop_wait(dppr_engine *e) { // a read-back of a frontier loop:
 int fail(dppr_engine *e, int code, const char *msg) {
     if (e) set_err(e, msg);
     return code;
+}
+
+// The event bracket of a timed region on the solver's stream: what is enqueued between the two calls is what *ms reports, after
+// ONE synchronisation at the close. (An error return between them leaves nothing to undo.)
+inline int bracket_open(dppr_engine *e) {
+    HIP_TRY(hipEventRecord(e->ev0, e->stream));
+    return DPPR_OK;
+}
+inline int bracket_close(dppr_engine *e, float *ms) {
+    HIP_TRY(hipEventRecord(e->ev1, e->stream));
+    HIP_TRY(hipEventSynchronize(e->ev1));
+    HIP_TRY(hipEventElapsedTime(ms, e->ev0, e->ev1));
+    return DPPR_OK;
+}
+// ... closed at the end of a solve: converged at eps on that epoch; `counted`: the solve is a batch of the statistics
+inline int solve_finished(dppr_engine *e, SolveState &o, double eps, int epoch_id, bool counted, float *out_ms) {
+    float ms = 0;
+    if (int rc = bracket_close(e, &ms)) return rc;
+    if (out_ms) *out_ms = ms;
+    if (counted) {
+        o.st.gpu_ms += ms;
+        o.st.batches++;
+    }
+    o.converged = true;
+    o.conv_eps = eps;
+    o.last_epoch = epoch_id;
+    return DPPR_OK;
 }
 
 // dppr_hint_next_batch: the lookups of the NEXT batch's ids run on helper threads while dppr_update waits for the device. They

@@ -1,11 +1,14 @@
 // dppr_loop_plan.hpp -- the POLICY of the frontier loops: how many sweeps to enqueue before the next read-back, what a resident or
 // multi-sweep launch is given, when a group's push tail takes over and at what threshold, push or sweep by estimated cost, and the
-// loop histories all of that is sized from. Pure functions of plain integers, without HIP includes: run_frontier_loop / batch_ahead
-// (dppr_host_loop.hpp) and group_loop / group_push_tail (dppr_host_group.hpp) ask here, launch, read back and account;
-// tests/native/loop_plan_test.cpp drives every function on the CPU against a plain restatement, and replays whole loops.
+// loop histories all of that is sized from -- and, one layer above the loops, what a whole-batch launch of a single source
+// reported (AheadOutcome) and what a batch therefore runs after it (AfterLaunch). Pure functions of plain integers, without HIP
+// includes: run_frontier_loop / batch_ahead / slot_update (dppr_host_loop.hpp) and group_loop / group_push_tail
+// (dppr_host_group.hpp) ask here, launch, read back and account; tests/native/loop_plan_test.cpp drives every function on the CPU
+// against a plain restatement, and replays whole loops.
 #pragma once
 
 #include <algorithm>
+#include <cstdint>
 
 namespace dppr {
 
@@ -17,6 +20,13 @@ constexpr int RESIDENT_MARGIN = 8;         // sweeps a resident launch is given 
 constexpr int PLAN_RES_MAX_SWEEPS = 128;   // sweeps of one resident launch at most
 constexpr int PLAN_GPUSH_LOG = 16;         // iterations one chunk of a group's push tail may hold
 constexpr int PLAN_TINY_N = 512, PLAN_TINY_E = 1024; // vertices / in-edges the single-workgroup form of the push tail takes
+// status word of a resident launch (k_pull_resident, dppr_resident.hpp, writes it; ahead_outcome below and run_frontier_loop read it)
+constexpr int PERSIST_ABORTED = 1 << 30;   // the roll-call failed, nothing was changed
+constexpr int PERSIST_FAULT = 1 << 29;     // a wait timed out after a successful roll-call
+constexpr int PERSIST_CONVERGED = 1 << 28; // the frontier emptied; all snapshot vectors are all zero again
+constexpr int PERSIST_PHASE1 = 1 << 26;    // a launch that runs both phases had started phase 1
+constexpr int PERSIST_SWEEPS = (1 << 16) - 1; // low bits: loop position g
+constexpr int LOOP_PHASE_BOTH = 2;         // the merged loop's phase (asserted equal to PHASE_BOTH of dppr_common.hpp in dppr_engine.hip)
 
 // ---------------------------------------------------------------------------- loop histories
 // What the last loops of each phase took (the merged loop uses slot 0): consecutive batches take about the same number of
@@ -241,6 +251,121 @@ inline PhaseLog split_phase_log(const int *log, int entries) {
         pl.act[ph]++;
     }
     return pl;
+}
+
+// ---------------------------------------------------------------------------- a whole batch of a single source (batch_ahead, slot_update)
+// a frontier loop that is picked up in the middle (after a launch of batch_ahead that ended before the loop did): iterations
+// already done, the frontier size if the host knows it, and whether the slot's x already holds the frontier's dense snapshot
+struct LoopEntry {
+    int it = 0;
+    int F = -1; // -1: read cnt[cur]
+    bool dense = false;
+    bool any_pull = false;
+};
+
+// What a whole-batch resident launch reported. A launch that was CALLED OFF changed nothing: a sweep group owned more of the raw
+// records than it has threads (RECORDS: not a residency problem), or the roll-call failed (ROLLCALL: the grid was not co-resident).
+enum AheadKind { AHEAD_FAULT, AHEAD_CALLED_OFF_RECORDS, AHEAD_CALLED_OFF_ROLLCALL, AHEAD_RAN };
+struct AheadOutcome {
+    AheadKind kind = AHEAD_RAN;
+    int stage = 0;          // 0: phase 0 (the merged loop) still open, 1: phase 0 done and phase 1 open, 2: the batch is done
+    bool p1_seeded = false; // phase 1's snapshot exists (the launch seeded it)
+    LoopEntry entry;        // where the open loop of `stage` resumes (as constructed: from its start)
+    PhaseLog log;           // what the launch's log says of each phase
+    bool called_off() const { return kind == AHEAD_CALLED_OFF_RECORDS || kind == AHEAD_CALLED_OFF_ROLLCALL; }
+};
+// status, cnt4, cnt0: words 7 (status word), 4 (1: a group owns too many records) and 0 (the live frontier size) of the counters
+// the launch left; log: its n entries; merged / inline_update: the launch's plan; grouped: the records it took were grouped at slide
+inline AheadOutcome ahead_outcome(int status, int cnt4, int cnt0, const int *log, int n, bool merged, bool inline_update, bool grouped) {
+    AheadOutcome o;
+    if (status & PERSIST_FAULT) o.kind = AHEAD_FAULT;
+    else if (status & PERSIST_ABORTED) o.kind = inline_update && !grouped && cnt4 == 1 ? AHEAD_CALLED_OFF_RECORDS : AHEAD_CALLED_OFF_ROLLCALL;
+    if (o.kind != AHEAD_RAN) return o;
+    const int pos = status & PERSIST_SWEEPS; // loop position the launch stopped at
+    o.log = split_phase_log(log, std::min(pos + 1, n));
+    const bool phase0_done = merged ? (status & PERSIST_CONVERGED) != 0 : (status & PERSIST_PHASE1) != 0;
+    o.stage = !phase0_done ? 0 : merged || (status & PERSIST_CONVERGED) ? 2 : 1;
+    o.p1_seeded = !merged && phase0_done;
+    if (o.stage < 2) o.entry = LoopEntry{o.log.act[o.stage], cnt0, true, true}; // out of sweeps: the host-driven loop goes on from here
+    return o;
+}
+// ... and what a launch that RAN leaves in the slot: the first frontiers of the phases it saw, the iterations it ran, and the
+// histories of the loops it finished. The merged loop records through LoopHistory::record (which also pushes the ring that
+// shortest() reads); the two phases write hint[] alone and leave the ring to the host-driven loops. That asymmetry is deliberate
+// to the refactor that moved these lines here: unchanged, not judged.
+inline void apply_ahead(const AheadOutcome &o, bool merged, int pull_min, LoopHistory &hist, bool (&start_dense)[2], int (&last_F0)[2],
+                        int64_t &iterations, int64_t &pull_iterations, int64_t &sum_F) {
+    if (o.kind != AHEAD_RAN) return;
+    const int *act = o.log.act;
+    for (int ph = 0; ph < 2; ++ph)
+        if (act[ph] > 0) {
+            start_dense[ph] = o.log.F0[ph] >= pull_min;
+            last_F0[ph] = o.log.F0[ph];
+        }
+    iterations += act[0] + act[1];
+    pull_iterations += act[0] + act[1];
+    sum_F += o.log.sum_F;
+    const int finished = merged ? o.stage / 2 : o.stage; // loops the launch ran to their end
+    for (int ph = 0; ph < finished; ++ph) {
+        if (merged) hist.record(0, act[0]);
+        else hist.hint[ph] = act[ph];
+        if (act[ph] == 0) start_dense[ph] = false;
+    }
+}
+
+// What a batch runs after its update (and after the whole-batch launch, if one was made). merged / seeded / ahead / inline_su: the
+// batch runs the merged loop / starts from a converged state (frontiers from the batch's tails) / made a whole-batch launch / that
+// launch was to apply the records itself; o: what it reported (as constructed where none was made).
+struct LoopStep {
+    int phase = 0;        // 0, 1 or LOOP_PHASE_BOTH
+    bool inspect = false; // seed by a full Inspect pass; otherwise enter at `entry`
+    LoopEntry entry;
+};
+struct AfterLaunch {
+    bool redo_update = false;   // the launch called itself off: the update runs as its own kernels after all ...
+    bool count_records = false; // ... or it applied the records: they are counted
+    bool filter = false;        // the update's candidates below -eps join (merged) or become (phase 1) the list the LAST loop starts from
+    bool filter_clears = false; // ... after cnt[0..2] were cleared (phase 1: phase 0 used them)
+    int n_loops = 0;
+    LoopStep loop[2];
+};
+inline AfterLaunch after_launch(bool merged, bool seeded, bool ahead, bool inline_su, const AheadOutcome &o) {
+    AfterLaunch d;
+    auto add = [&d](int phase, bool inspect, LoopEntry entry = LoopEntry()) { d.loop[d.n_loops++] = LoopStep{phase, inspect, entry}; };
+    if (ahead && o.kind == AHEAD_FAULT) return d; // (batch_ahead returned the error)
+    if (ahead && inline_su) {
+        d.redo_update = o.called_off();
+        d.count_records = !d.redo_update;
+        inline_su = !d.redo_update;
+    }
+    if (merged) {
+        if (!seeded) add(LOOP_PHASE_BOTH, true);
+        else if (!ahead || o.stage != 2) {
+            // the frontier: the tails the update left above eps (ft[0]) and those it left below -eps (the candidates). A launch
+            // that ran out of sweeps left a dense snapshot; one that was called off left the update's lists standing
+            d.filter = !ahead || (o.entry.it == 0 && !o.entry.dense);
+            add(LOOP_PHASE_BOTH, false, ahead ? o.entry : LoopEntry());
+        }
+        return d;
+    }
+    if (!seeded) {
+        add(0, true);
+        add(1, true);
+        return d;
+    }
+    const int stage = ahead ? o.stage : 0;
+    if (stage == 0) add(0, false, ahead ? o.entry : LoopEntry());
+    if (stage <= 1) {
+        const bool p1_seeded = ahead && o.p1_seeded;
+        // the update ran inside the launch and recorded no candidates: phase 1 starts from a full Inspect; otherwise from the
+        // candidates the update recorded, re-checked now
+        if (!p1_seeded && inline_su) add(1, true);
+        else {
+            d.filter = d.filter_clears = !p1_seeded;
+            add(1, false, stage == 1 ? o.entry : LoopEntry());
+        }
+    }
+    return d;
 }
 
 } // namespace dppr

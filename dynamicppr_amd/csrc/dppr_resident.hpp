@@ -2,6 +2,7 @@
 #pragma once
 
 #include "dppr_common.hpp"
+#include "dppr_loop_plan.hpp" // PERSIST_*: the status word of a launch
 #include "dppr_pull.hpp" // STAMP (diagnostic builds)
 
 namespace dppr {
@@ -123,12 +124,7 @@ struct GridBar {                          // zeroed by the host before every lau
     BarWord roll[BAR_SUBS];               // roll-call check-ins of the workgroups with blockIdx % BAR_SUBS == s
     BarWord sub[2][BAR_REPS][BAR_SUBS];   // per sweep parity and replica: arrivals << 32 | cumulative legal count
 };
-// status word of a launch
-constexpr int PERSIST_ABORTED = 1 << 30;   // the roll-call failed, nothing was changed
-constexpr int PERSIST_FAULT = 1 << 29;     // a wait timed out after a successful roll-call
-constexpr int PERSIST_CONVERGED = 1 << 28; // the frontier emptied; all snapshot vectors are all zero again
-constexpr int PERSIST_PHASE1 = 1 << 26;    // a launch that runs both phases had started phase 1
-constexpr int PERSIST_SWEEPS = (1 << 16) - 1; // low bits: loop position g
+// status word of a launch: PERSIST_ABORTED / FAULT / CONVERGED / PHASE1 / SWEEPS of dppr_loop_plan.hpp (the host decodes it there)
 // plan of a launch
 constexpr int PLAN_SEED = 1;  // take the first snapshot from the registers: {v : legal(residual[v])} (valid after a converged solve)
 constexpr int PLAN_BOTH = 2;  // when phase 0 is over, seed phase 1 the same way and go on

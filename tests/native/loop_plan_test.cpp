@@ -3,8 +3,13 @@
 // planner existed, transcribed, with the place it stood named (files and lines of commit 21acc1c, "Add, drop and replace sources
 // of a running source group": H = dppr_host_loop.hpp, G = dppr_host_group.hpp). Small discrete inputs exhaustively, large ones
 // seeded at random, and whole loops replayed through the planner's state struct and through the restatement's loose locals.
+// One layer above the loops (commit 36757a9, "Move the frontier loops' chunk and launch policy into a tested planner": H2 =
+// dppr_host_loop.hpp, E2 = dppr_engine.hip): what a whole-batch launch reported (ahead_outcome + apply_ahead against the tail of
+// batch_ahead, H2:396-469) and what a batch runs after it (after_launch against dppr_update, E2:905-974), the latter driven by every
+// outcome the former produces.
 //   loop_plan_test
 #include <algorithm>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -144,6 +149,180 @@ static int r_batch_ahead(bool merged, const RHist &s, int chunk_iters, bool chun
     if (chunk_explicit) n = std::min(n, chunk_iters);
     n = std::min(n, R_RES_MAX_SWEEPS);
     return n;
+}
+
+// ---------------------------------------------------------------------------- restatement: a whole batch of a single source
+static const int R_CNT_HDR = 16;                                                           // dppr_host_state.hpp:14
+static const int R_ABORTED = 1 << 30, R_FAULT = 1 << 29, R_CONVERGED = 1 << 28, R_PHASE1 = 1 << 26, R_SWEEPS = (1 << 16) - 1; // dppr_resident.hpp:127-131
+static const int R_PHASE_BOTH = 2;                                                         // dppr_common.hpp:25
+static const int R_RETRY_BATCHES = 64;                                                     // dppr_host_state.hpp:15
+struct REntry { int it = 0; int F = -1; bool dense = false; bool any_pull = false; };      // H2:66-71
+struct RSlot {                                                                             // what batch_ahead touches of Slot
+    RHist hist;
+    bool start_dense[2];
+    int last_F0[2];
+    long long iterations, pull_iterations, sum_F, persist_launches, persist_aborts;
+};
+struct REngine { bool launch_called_off; int raw_backoff; bool persist_ok; int persist_retry; }; // ... and of dppr_engine
+// H2:396-469 (the profiling block, :418-423, reads HIP events and is left out). Returns 0, or 1 where the function fails.
+static int r_ahead_tail(const int *pinned, int n, bool merged, bool inline_update, bool grouped, int pull_min, RSlot &s, REngine &e, int *stage,
+                        REntry *en0, REntry *en1, bool *p1_seeded) {
+    const int st = pinned[7];
+    *stage = 0;
+    *p1_seeded = false;
+    *en0 = REntry();
+    *en1 = REntry();
+    s.persist_launches++;
+    if (st & R_FAULT) return 1;
+    e.launch_called_off = false;
+    if ((st & R_ABORTED) && inline_update && !grouped && pinned[4] == 1) {
+        e.launch_called_off = true;
+        e.raw_backoff = 16;
+        return 0;
+    }
+    if (st & R_ABORTED) {
+        s.persist_aborts++;
+        e.launch_called_off = true;
+        e.persist_ok = false;
+        e.persist_retry = R_RETRY_BATCHES;
+        return 0;
+    }
+    const int pos = st & R_SWEEPS;
+    int act[2] = {0, 0}, F0[2] = {0, 0}; // (H2:425: split_phase_log, as the loop it replaced -- H:452-468)
+    long long log_sum = 0;
+    for (int k = 0, ph = 0; k < std::min(pos + 1, n) && ph < 2; ++k) {
+        if (pinned[R_CNT_HDR + k] <= 0) {
+            ++ph;
+            continue;
+        }
+        if (act[ph] == 0) F0[ph] = pinned[R_CNT_HDR + k];
+        log_sum += pinned[R_CNT_HDR + k];
+        act[ph]++;
+    }
+    for (int ph = 0; ph < 2; ++ph)
+        if (act[ph] > 0) {
+            s.start_dense[ph] = F0[ph] >= pull_min;
+            s.last_F0[ph] = F0[ph];
+        }
+    s.iterations += act[0] + act[1];
+    s.pull_iterations += act[0] + act[1];
+    s.sum_F += log_sum;
+    if (merged) {
+        if (!(st & R_CONVERGED)) {
+            en0->it = act[0];
+            en0->F = pinned[0];
+            en0->dense = true;
+            en0->any_pull = true;
+            return 0;
+        }
+        r_record(s.hist, 0, act[0]);
+        if (act[0] == 0) s.start_dense[0] = false;
+        *stage = 2;
+        return 0;
+    }
+    if (!(st & R_PHASE1)) {
+        en0->it = act[0];
+        en0->F = pinned[0];
+        en0->dense = true;
+        en0->any_pull = true;
+        return 0;
+    }
+    s.hist.iter_hint[0] = act[0];
+    if (act[0] == 0) s.start_dense[0] = false;
+    *stage = 1;
+    *p1_seeded = true;
+    if (!(st & R_CONVERGED)) {
+        en1->it = act[1];
+        en1->F = pinned[0];
+        en1->dense = true;
+        en1->any_pull = true;
+        return 0;
+    }
+    s.hist.iter_hint[1] = act[1];
+    if (act[1] == 0) s.start_dense[1] = false;
+    *stage = 2;
+    return 0;
+}
+
+// what a batch enqueues after its update, in order
+enum { DO_REDO_UPDATE, DO_COUNT_RECORDS, DO_FILTER, DO_LOOP };
+struct Did {
+    int what, phase; // DO_LOOP: its phase
+    bool flag;       // DO_FILTER: cnt[0..2] cleared first; DO_LOOP: seeded by a full Inspect (main_loop_inspect)
+    REntry en;       // DO_LOOP without Inspect: the entry
+};
+static bool same(const REntry &a, const REntry &b) { return a.it == b.it && a.F == b.F && a.dense == b.dense && a.any_pull == b.any_pull; }
+static bool same(const LoopEntry &a, const REntry &b) { return a.it == b.it && a.F == b.F && a.dense == b.dense && a.any_pull == b.any_pull; }
+static bool same(const std::vector<Did> &a, const std::vector<Did> &b) {
+    if (a.size() != b.size()) return false;
+    for (size_t k = 0; k < a.size(); ++k)
+        if (a[k].what != b[k].what || a[k].phase != b[k].phase || a[k].flag != b[k].flag || !same(a[k].en, b[k].en)) return false;
+    return true;
+}
+// E2:905-974. The launch (made where `ahead`) reported called_off / stage / en0 / en1 / p1: what r_ahead_tail left.
+static std::vector<Did> r_after_launch(bool merged, bool seeded, bool ahead, bool inline_su, bool called_off, int l_stage, REntry l_en0,
+                                       REntry l_en1, bool l_p1) {
+    std::vector<Did> did;
+    auto stream_update = [&]() { did.push_back({DO_REDO_UPDATE, 0, false, REntry()}); };
+    auto k_filter = [&](bool clear) { did.push_back({DO_FILTER, 0, clear, REntry()}); };
+    auto run_frontier_loop = [&](int phase, REntry en = REntry()) { did.push_back({DO_LOOP, phase, false, en}); };
+    auto main_loop_inspect = [&](int phase) { did.push_back({DO_LOOP, phase, true, REntry()}); };
+    auto update_after_abort = [&]() {
+        if (!inline_su) return;
+        if (called_off) {
+            inline_su = false;
+            stream_update();
+            return;
+        }
+        did.push_back({DO_COUNT_RECORDS, 0, false, REntry()});
+    };
+    if (merged && ahead) {
+        int stage = l_stage;
+        REntry en0 = l_en0;
+        update_after_abort();
+        if (stage != 2) {
+            if (en0.it == 0 && !en0.dense) k_filter(false);
+            run_frontier_loop(R_PHASE_BOTH, en0);
+        }
+    } else if (merged) {
+        if (seeded) {
+            k_filter(false);
+            run_frontier_loop(R_PHASE_BOTH);
+        } else {
+            main_loop_inspect(R_PHASE_BOTH);
+        }
+    } else if (seeded) {
+        int stage = 0;
+        bool p1_seeded = false;
+        REntry en0, en1;
+        if (ahead) {
+            stage = l_stage; en0 = l_en0; en1 = l_en1; p1_seeded = l_p1;
+            update_after_abort();
+        }
+        if (stage == 0) run_frontier_loop(0, en0);
+        if (stage <= 1 && !p1_seeded && inline_su) {
+            main_loop_inspect(1);
+        } else if (stage <= 1) {
+            if (!p1_seeded) k_filter(true);
+            run_frontier_loop(1, en1);
+        }
+    } else {
+        main_loop_inspect(0);
+        main_loop_inspect(1);
+    }
+    return did;
+}
+// ... and the same list from the planner's decision, executed as slot_update executes it
+static std::vector<Did> planned_after_launch(const AfterLaunch &d) {
+    std::vector<Did> did;
+    if (d.redo_update) did.push_back({DO_REDO_UPDATE, 0, false, REntry()});
+    if (d.count_records) did.push_back({DO_COUNT_RECORDS, 0, false, REntry()});
+    for (int k = 0; k < d.n_loops; ++k) {
+        const LoopStep &l = d.loop[k];
+        if (d.filter && k == d.n_loops - 1) did.push_back({DO_FILTER, 0, d.filter_clears, REntry()});
+        did.push_back({DO_LOOP, l.phase, l.inspect, l.inspect ? REntry() : REntry{l.entry.it, l.entry.F, l.entry.dense, l.entry.any_pull}});
+    }
+    return did;
 }
 
 // ---------------------------------------------------------------------------- whole loops of a group
@@ -471,6 +650,144 @@ int main() {
             bool lowered = false;
             for (size_t k = 1; k < st.size(); ++k) lowered |= st[k].thr < st[k - 1].thr;
             CHECK(lowered, "script %d never lowered the threshold", script);
+        }
+    }
+    // ---- a whole-batch launch: its outcome, what it leaves in the slot, and what the batch runs after it
+    {
+        CHECK(PERSIST_ABORTED == R_ABORTED && PERSIST_FAULT == R_FAULT && PERSIST_CONVERGED == R_CONVERGED && PERSIST_PHASE1 == R_PHASE1 &&
+                  PERSIST_SWEEPS == R_SWEEPS && LOOP_PHASE_BOTH == R_PHASE_BOTH, "status bits");
+        bool reached[2][2][4][3][2][2][2] = {}; // merged, inline_update, kind, stage, p1_seeded, entry.it == 0, entry.dense
+        long long outcomes = 0;
+        for (int n : {1, 2, 3, 5, 64, 128}) {
+            // the logs: no zero at all; a zero in one position, every position in turn (0: a leading zero); two adjacent zeros,
+            // every position in turn; random ones with a zero in every fourth place or so
+            std::vector<std::vector<int>> logs;
+            auto fresh = [&]() {
+                std::vector<int> l((size_t)n);
+                for (int &v : l) v = 1 + (int)rnd_scaled(1 << 30);
+                return l;
+            };
+            logs.push_back(fresh());
+            for (int z = 0; z < n; ++z) {
+                logs.push_back(fresh());
+                logs.back()[(size_t)z] = 0;
+                if (z + 1 < n) {
+                    logs.push_back(fresh());
+                    logs.back()[(size_t)z] = logs.back()[(size_t)z + 1] = 0;
+                }
+            }
+            for (int k = 0; k < 24; ++k) {
+                logs.push_back(fresh());
+                for (int &v : logs.back())
+                    if (!rnd_below(4)) v = 0;
+            }
+            for (const std::vector<int> &log : logs)
+                for (int bits = 0; bits < 16; ++bits)
+                    for (int pos : {0, 1, 2, n - 1, n, n + 1})
+                        for (int cnt4 = 0; cnt4 < 2; ++cnt4)
+                            for (int flags = 0; flags < 8; ++flags) {
+                                const bool merged = flags & 1, inline_update = flags & 2, grouped = flags & 4;
+                                const int status = pos | (bits & 1 ? R_ABORTED : 0) | (bits & 2 ? R_FAULT : 0) | (bits & 4 ? R_CONVERGED : 0) | (bits & 8 ? R_PHASE1 : 0);
+                                int pinned[R_CNT_HDR + 128];
+                                for (int k = 0; k < R_CNT_HDR; ++k) pinned[k] = (int)rnd_scaled(1 << 30);
+                                pinned[7] = status;
+                                pinned[4] = cnt4;
+                                memcpy(pinned + R_CNT_HDR, log.data(), sizeof(int) * (size_t)n);
+                                const int pull_min = rnd_below(3) ? (int)rnd_scaled(1 << 30) : 0x7fffffff;
+                                // the slot as some earlier batches left it, the same on both sides
+                                LoopHistory hist;
+                                RSlot rs;
+                                fill(hist, rs.hist, (int)rnd_below(3), (int)rnd_below(2), 1 + (int)rnd_below(69));
+                                bool start_dense[2];
+                                int last_F0[2];
+                                for (int ph = 0; ph < 2; ++ph) {
+                                    start_dense[ph] = rs.start_dense[ph] = rnd_below(2);
+                                    last_F0[ph] = rs.last_F0[ph] = (int)rnd_scaled(1 << 30);
+                                }
+                                int64_t iterations = rnd_scaled(1ll << 40), pull_iterations = rnd_scaled(1ll << 40), sum_F = rnd_scaled(1ll << 50);
+                                const int64_t iterations0 = iterations, sum_F0 = sum_F;
+                                rs.iterations = iterations; rs.pull_iterations = pull_iterations; rs.sum_F = sum_F;
+                                rs.persist_launches = rs.persist_aborts = 0;
+                                REngine re{false, 0, true, 0};
+                                int stage = -1;
+                                bool p1 = true;
+                                REntry en0, en1;
+                                const int rc = r_ahead_tail(pinned, n, merged, inline_update, grouped, pull_min, rs, re, &stage, &en0, &en1, &p1);
+
+                                const AheadOutcome o = ahead_outcome(pinned[7], pinned[4], pinned[0], pinned + R_CNT_HDR, n, merged, inline_update, grouped);
+                                apply_ahead(o, merged, pull_min, hist, start_dense, last_F0, iterations, pull_iterations, sum_F);
+                                ++outcomes;
+                                // the kind against the four ways out of the transcription
+                                const AheadKind want = rc ? AHEAD_FAULT : !re.launch_called_off ? AHEAD_RAN : rs.persist_aborts ? AHEAD_CALLED_OFF_ROLLCALL : AHEAD_CALLED_OFF_RECORDS;
+                                CHECK(o.kind == want, "kind %d / %d (status 0x%x cnt4 %d flags %d)", (int)o.kind, (int)want, (unsigned)status, cnt4, flags);
+                                CHECK(o.called_off() == (!rc && re.launch_called_off), "called off");
+                                CHECK((o.kind == AHEAD_CALLED_OFF_RECORDS) == (re.raw_backoff == 16) && (o.kind == AHEAD_CALLED_OFF_ROLLCALL) == (!re.persist_ok && re.persist_retry == R_RETRY_BATCHES),
+                                      "a records call-off backs the raw records off and counts no abort; a failed roll-call counts one and re-arms later");
+                                CHECK(o.stage == stage && o.p1_seeded == p1, "stage %d / %d, p1_seeded %d / %d (status 0x%x n %d flags %d)", o.stage, stage, (int)o.p1_seeded, (int)p1,
+                                      (unsigned)status, n, flags);
+                                // the one entry to resume with is that of the open loop; the transcription's other one is as constructed
+                                CHECK(same(o.entry, stage == 1 ? en1 : en0) && same(stage == 1 ? en0 : en1, REntry()) && (stage < 2 || same(en0, REntry())),
+                                      "entry it %d F %d (stage %d status 0x%x n %d flags %d)", o.entry.it, o.entry.F, stage, (unsigned)status, n, flags);
+                                CHECK(same(hist, rs.hist), "histories (status 0x%x n %d flags %d)", (unsigned)status, n, flags);
+                                CHECK(!memcmp(start_dense, rs.start_dense, sizeof(start_dense)) && !memcmp(last_F0, rs.last_F0, sizeof(last_F0)), "start_dense / last_F0");
+                                CHECK(iterations == rs.iterations && pull_iterations == rs.pull_iterations && sum_F == rs.sum_F, "iterations / pull_iterations / sum_F");
+                                // the log it carries is the one it was applied from; a launch that did not run carries none
+                                CHECK(iterations - iterations0 == o.log.act[0] + o.log.act[1] && sum_F - sum_F0 == o.log.sum_F && (o.kind == AHEAD_RAN || o.log.act[0] + o.log.act[1] == 0), "log");
+                                reached[merged][inline_update][o.kind][o.stage][o.p1_seeded][o.entry.it == 0][o.entry.dense] = true;
+                                if (rc) continue; // (dppr_update returned the error)
+                                // what the batch runs after this launch: a launch is made from a converged state only (ahead => seeded),
+                                // and only a launch applies the records itself (inline_su => ahead)
+                                const std::vector<Did> want_did = r_after_launch(merged, true, true, inline_update, re.launch_called_off, stage, en0, en1, p1);
+                                const std::vector<Did> got_did = planned_after_launch(after_launch(merged, true, true, inline_update, o));
+                                CHECK(same(got_did, want_did) && !want_did.empty() == (stage != 2 || inline_update), "after the launch: %zu / %zu steps (status 0x%x n %d flags %d)",
+                                      got_did.size(), want_did.size(), (unsigned)status, n, flags);
+                            }
+        }
+        CHECK(outcomes > 500000, "%lld outcomes", outcomes);
+        // ... and without a launch
+        for (int flags = 0; flags < 4; ++flags) {
+            const bool merged = flags & 1, seeded = flags & 2;
+            const std::vector<Did> want_did = r_after_launch(merged, seeded, false, false, false, 0, REntry(), REntry(), false);
+            CHECK(same(planned_after_launch(after_launch(merged, seeded, false, false, AheadOutcome())), want_did) && want_did.size() >= 1, "no launch, flags %d", flags);
+        }
+        // what the enumeration reached of merged x inline_update x kind x stage x p1_seeded x (entry.it == 0) x entry.dense: every kind
+        // in every plan; a merged launch stops at stage 0 or 2 and seeds no phase 1; an entry is dense exactly where a launch ran out
+        // of sweeps, and then may well be at position 0 (a launch that was given one sweep)
+        int n_reached = 0;
+        for (int m = 0; m < 2; ++m)
+            for (int iu = 0; iu < 2; ++iu)
+                for (int kind = 0; kind < 4; ++kind)
+                    for (int stage = 0; stage < 3; ++stage)
+                        for (int p1 = 0; p1 < 2; ++p1)
+                            for (int it0 = 0; it0 < 2; ++it0)
+                                for (int dense = 0; dense < 2; ++dense) {
+                                    if (!reached[m][iu][kind][stage][p1][it0][dense]) continue;
+                                    ++n_reached;
+                                    CHECK(kind == AHEAD_RAN || (stage == 0 && !p1 && it0 && !dense), "a launch that did not run leaves stage 0 and no entry");
+                                    CHECK(!m || (stage != 1 && !p1), "a merged launch has no phase 1");
+                                    CHECK(m || p1 == (stage >= 1), "two phases: phase 1 is seeded by the launch that finished phase 0");
+                                    CHECK(kind != AHEAD_RAN || dense == (stage < 2), "the entry of an open loop holds its snapshot");
+                                    CHECK(kind != AHEAD_CALLED_OFF_RECORDS || iu, "only a launch that applies the records calls itself off over them");
+                                }
+        for (int m = 0; m < 2; ++m) {
+            for (int iu = 0; iu < 2; ++iu) {
+                CHECK(reached[m][iu][AHEAD_FAULT][0][0][1][0] && reached[m][iu][AHEAD_CALLED_OFF_ROLLCALL][0][0][1][0], "fault and failed roll-call, merged %d inline %d", m, iu);
+                CHECK(reached[m][iu][AHEAD_RAN][0][0][0][1] && reached[m][iu][AHEAD_RAN][0][0][1][1] && reached[m][iu][AHEAD_RAN][2][!m][1][0], "out of sweeps / done, merged %d inline %d", m, iu);
+            }
+            CHECK(reached[m][1][AHEAD_CALLED_OFF_RECORDS][0][0][1][0], "records call-off, merged %d", m);
+        }
+        CHECK(reached[0][0][AHEAD_RAN][1][1][0][1] && reached[0][0][AHEAD_RAN][1][1][1][1], "phase 1 open");
+        // fault and failed roll-call in each of the four plans, the records call-off in the two that apply them: 10; the merged loop
+        // open at position 0 / further on, or done, in its two plans: 6; phase 0 open (twice), phase 1 open (twice), done, in two plans: 10
+        CHECK(n_reached == 10 + 6 + 10, "%d combinations reached", n_reached);
+        // the branch no GPU test drove before: the merged loop after a records call-off is the update's own kernels, the negative
+        // tails added WITHOUT clearing the counters, and the loop over both signs from its start
+        {
+            const int log1[1] = {0};
+            const AheadOutcome o = ahead_outcome(R_ABORTED, 1, 0, log1, 1, true, true, false);
+            const AfterLaunch d = after_launch(true, true, true, true, o);
+            CHECK(o.kind == AHEAD_CALLED_OFF_RECORDS && d.redo_update && !d.count_records && d.filter && !d.filter_clears && d.n_loops == 1 &&
+                      d.loop[0].phase == LOOP_PHASE_BOTH && !d.loop[0].inspect && same(d.loop[0].entry, REntry()), "merged loop after a records call-off");
         }
     }
     printf("%lld checks, %d failures\n", checked, fails);
