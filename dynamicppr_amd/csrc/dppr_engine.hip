@@ -16,6 +16,7 @@
 // DPPR_ERR_NO_DEVICE.
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -42,6 +43,7 @@
 #include "dppr_binned.hpp"
 #include "dppr_calib.hpp"
 #include "dppr_topk.hpp"
+#include "dppr_wquery.hpp"
 
 using namespace dppr;
 
@@ -1318,6 +1320,40 @@ int dppr_group_read_at(dppr_engine *e, int32_t group, const int32_t *ids, int32_
     if (m == 0 || (!out_p && !out_r)) return DPPR_OK;
     std::lock_guard<std::mutex> map_lk(e->map_mu);
     return run_read_at(e, g.p, g.r, g.gw, g.n, ids, m, out_p, out_r);
+}
+
+// weights [q][n]: q in [1, 16], every entry finite
+static bool weights_ok(const double *w, int32_t q, int n) {
+    if (!w || q < 1 || q > GS_MAX) return false;
+    for (int i = 0; i < q * n; ++i)
+        if (!std::isfinite(w[i])) return false;
+    return true;
+}
+
+int dppr_group_topk_weighted(dppr_engine *e, int32_t group, const double *weights, int32_t q, int32_t k, double min_score,
+                             int32_t *out_ids, double *out_score, int32_t *out_counts) {
+    GET_GROUP(e, group);
+    if (!weights_ok(weights, q, g.n) || !topk_args_ok(k, min_score, out_ids, out_score, out_counts))
+        return fail(e, DPPR_ERR_INVALID,
+                    "group_topk_weighted: q in [1, 16], finite weights, k in [1, DPPR_TOPK_MAX], min_score >= 0, non-null ids / score / counts");
+    std::lock_guard<std::mutex> map_lk(e->map_mu);
+    return run_topk_weighted(e, g.p, g.gw, g.n, weights, q, k, min_score, out_ids, out_score, out_counts);
+}
+
+int dppr_group_score_at(dppr_engine *e, int32_t group, const double *weights, int32_t q, const int32_t *ids, int32_t m,
+                        double *out_score) {
+    GET_GROUP(e, group);
+    if (!weights_ok(weights, q, g.n) || !out_score || !read_at_args_ok(e, ids, m))
+        return fail(e, DPPR_ERR_INVALID, "group_score_at: q in [1, 16], finite weights, ids in [0, V), non-null score");
+    if (m == 0) return DPPR_OK;
+    std::lock_guard<std::mutex> map_lk(e->map_mu);
+    return run_score_at(e, g.p, g.gw, g.n, weights, q, ids, m, out_score);
+}
+
+int dppr_debug_query_ms(dppr_engine *e, float *out_ms) {
+    if (!e || !out_ms) return DPPR_ERR_INVALID;
+    *out_ms = e->query_ms;
+    return DPPR_OK;
 }
 
 int dppr_group_reset_stats(dppr_engine *e, int32_t group) {

@@ -1,5 +1,6 @@
-// dppr_host_query.hpp -- host side of the state queries (dppr_topk / dppr_group_topk / dppr_read_at / dppr_group_read_at):
-// workspace, the device copy of int2ext and the launch sequence of dppr_topk.hpp. Called with map_mu held, on the solver
+// dppr_host_query.hpp -- host side of the state queries (dppr_topk / dppr_group_topk / dppr_read_at / dppr_group_read_at, and
+// dppr_group_topk_weighted / dppr_group_score_at): workspace, the device copy of int2ext and the launch sequences of dppr_topk.hpp
+// and dppr_wquery.hpp. Called with map_mu held, on the solver
 // stream; nothing here is reached from the update path.
 #pragma once
 
@@ -48,22 +49,13 @@ int topk_workspace(dppr_engine *e, int n, size_t rows) {
     return DPPR_OK;
 }
 
-// Top k of every lane of a state (p / r rows gw doubles wide, n lanes). Results are lane-major: [n][k].
-int run_topk(dppr_engine *e, const double *p, const double *r, int gw, int n, int k, double min_p, int32_t *out_ids,
-             double *out_p, double *out_r, int32_t *out_counts) {
-    HIP_TRY(hipSetDevice(e->device));
-    TkState st;
-    st.p = p;
-    st.r = r;
-    st.gw = gw;
-    st.n = n;
-    st.n_int = e->n_int;
-    st.lo_parked = e->V - e->n_parked;
-    st.rows = e->n_int + e->n_parked;
-    int rc = sync_int2ext(e);
-    if (rc) return rc;
-    rc = topk_workspace(e, n, (size_t)st.rows);
-    if (rc) return rc;
+// The selection of dppr_topk.hpp over a state whose workspace is in place (topk_workspace). i2e: the external id of every row of
+// `st`. Results are lane-major: [n][k]. With dppr_set_profiling on, the device time from the first to the last kernel is kept
+// (query_ms; `opened`: the caller recorded the opening event before kernels of its own).
+int run_select(dppr_engine *e, const TkState &st, const int *i2e, int k, double min_p, int32_t *out_ids, double *out_p,
+               double *out_r, int32_t *out_counts, bool opened = false) {
+    const int n = st.n;
+    if (e->profiling && !opened) HIP_TRY(hipEventRecord(e->evpool[0], e->stream));
     unsigned *hist1 = reinterpret_cast<unsigned *>(e->tk_ws.get()), *hist2 = hist1 + GS_MAX * TK_BINS1;
     TkLane *ctl = reinterpret_cast<TkLane *>(hist2 + GS_MAX * TK_BINS2);
     const int cand_cap = (int)std::max<size_t>(st.rows, 1);
@@ -77,25 +69,89 @@ int run_topk(dppr_engine *e, const double *p, const double *r, int gw, int n, in
     const int grid2 = std::min(std::max(st.rows / 4096, 1), 64);
     for (int round = 0; round < TK_ROUNDS; ++round) {
         const int s = TK_SHIFT1 - TK_DIGIT * (round + 1);
-        hipLaunchKernelGGL(k_tk_hist2, dim3(grid2, n), dim3(256), 0, e->stream, st, e->d_int2ext, ctl, e->tk_cand, cand_cap, s, hist2);
+        hipLaunchKernelGGL(k_tk_hist2, dim3(grid2, n), dim3(256), 0, e->stream, st, i2e, ctl, e->tk_cand, cand_cap, s, hist2);
         hipLaunchKernelGGL(k_tk_select2, dim3(n), dim3(256), 0, e->stream, hist2, s, ctl);
     }
-    hipLaunchKernelGGL(k_tk_take, dim3(grid2, n), dim3(256), 0, e->stream, st, e->d_int2ext, ctl, e->tk_cand, cand_cap, k,
+    hipLaunchKernelGGL(k_tk_take, dim3(grid2, n), dim3(256), 0, e->stream, st, i2e, ctl, e->tk_cand, cand_cap, k,
                        e->tk_out_key, e->tk_out_row);
     const size_t nk = (size_t)n * (size_t)k;
     int *res_cnt = reinterpret_cast<int *>(e->tk_res.get()), *res_id = reinterpret_cast<int *>(e->tk_res.get() + TK_RES_IDS);
     const size_t off_p = TK_RES_IDS + ((sizeof(int) * nk + 7) & ~(size_t)7), off_r = off_p + sizeof(double) * nk;
     double *res_p = reinterpret_cast<double *>(e->tk_res + off_p), *res_r = reinterpret_cast<double *>(e->tk_res + off_r);
-    hipLaunchKernelGGL(k_tk_rank, dim3((k + 255) / 256, n), dim3(256), 0, e->stream, st, e->d_int2ext, ctl, k, e->tk_out_key,
+    hipLaunchKernelGGL(k_tk_rank, dim3((k + 255) / 256, n), dim3(256), 0, e->stream, st, i2e, ctl, k, e->tk_out_key,
                        e->tk_out_row, res_cnt, res_id, res_p, res_r);
     HIP_TRY(hipGetLastError());
+    if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[1], e->stream));
     HIP_TRY(hipMemcpyAsync(e->tk_pin, e->tk_res, tk_res_bytes(n, k, out_r != nullptr), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
+    if (e->profiling) HIP_TRY(hipEventElapsedTime(&e->query_ms, e->evpool[0], e->evpool[1]));
     memcpy(out_counts, e->tk_pin, sizeof(int) * (size_t)n);
     memcpy(out_ids, e->tk_pin + TK_RES_IDS, sizeof(int) * nk);
     memcpy(out_p, e->tk_pin + off_p, sizeof(double) * nk);
     if (out_r) memcpy(out_r, e->tk_pin + off_r, sizeof(double) * nk);
     return DPPR_OK;
+}
+
+TkState tk_state(const dppr_engine *e, const double *p, const double *r, int gw, int n) {
+    TkState st;
+    st.p = p;
+    st.r = r;
+    st.gw = gw;
+    st.n = n;
+    st.n_int = e->n_int;
+    st.lo_parked = e->V - e->n_parked;
+    st.rows = e->n_int + e->n_parked;
+    return st;
+}
+
+// Top k of every lane of a state (p / r rows gw doubles wide, n lanes). Results are lane-major: [n][k].
+int run_topk(dppr_engine *e, const double *p, const double *r, int gw, int n, int k, double min_p, int32_t *out_ids,
+             double *out_p, double *out_r, int32_t *out_counts) {
+    HIP_TRY(hipSetDevice(e->device));
+    const TkState st = tk_state(e, p, r, gw, n);
+    int rc = sync_int2ext(e);
+    if (rc) return rc;
+    rc = topk_workspace(e, n, (size_t)st.rows);
+    if (rc) return rc;
+    return run_select(e, st, e->d_int2ext, k, min_p, out_ids, out_p, out_r, out_counts);
+}
+
+// ---- a group as a weighted set of targets (dppr_wquery.hpp) ---------------------------------------------------------------
+// the weights of a call on the device: [q][n] (one small upload; wq_w is in place)
+int wq_upload(dppr_engine *e, const double *weights, int q, int n) {
+    HIP_TRY(hipMemcpyAsync(e->wq_w, weights, sizeof(double) * (size_t)q * (size_t)n, hipMemcpyHostToDevice, e->stream));
+    return DPPR_OK;
+}
+
+// Top k of q weighted combinations of a group's lanes (weights [q][n], validated by the caller). Results are query-major: [q][k].
+// Every buffer is in place before the first kernel; the scratch state is 8 q + 4 bytes per occupied row.
+int run_topk_weighted(dppr_engine *e, const double *p, int gw, int n, const double *weights, int q, int k, double min_score,
+                      int32_t *out_ids, double *out_score, int32_t *out_counts) {
+    HIP_TRY(hipSetDevice(e->device));
+    const TkState st = tk_state(e, p, p, gw, n);
+    int rc = sync_int2ext(e);
+    if (rc) return rc;
+    rc = topk_workspace(e, q, (size_t)st.rows);
+    if (rc) return rc;
+    const size_t rows = std::max<size_t>((size_t)st.rows, 1);
+    if (e->wq_score.capacity() < rows * (size_t)q || e->wq_ext.capacity() < rows) {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        if (e->wq_score.capacity() < rows * (size_t)q) HIP_TRY(e->wq_score.regrow(rows * (size_t)q + rows * (size_t)q / 4));
+        if (e->wq_ext.capacity() < rows) HIP_TRY(e->wq_ext.regrow(rows + rows / 4));
+    }
+    if (!e->wq_w) HIP_TRY(e->wq_w.alloc((size_t)GS_MAX * GS_MAX));
+    rc = wq_upload(e, weights, q, n);
+    if (rc) return rc;
+    if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[0], e->stream));
+    const int n_tiles = std::max((st.rows + WQ_ROWS - 1) / WQ_ROWS, 1);
+    hipLaunchKernelGGL(k_wq_scores, dim3(std::min(n_tiles, 2048)), dim3(WQ_BLOCK), 0, e->stream, st, e->d_int2ext, e->wq_w, q,
+                       e->wq_score, e->wq_ext);
+    HIP_TRY(hipGetLastError());
+    TkState sc; // the scratch: q lanes, rows q doubles wide, compacted (no parked zone)
+    sc.p = sc.r = e->wq_score;
+    sc.gw = sc.n = q;
+    sc.n_int = sc.lo_parked = sc.rows = st.rows;
+    return run_select(e, sc, e->wq_ext, k, min_score, out_ids, out_score, nullptr, out_counts, true);
 }
 
 // p / r at m external ids (validated by the caller), [m][n]
@@ -118,6 +174,32 @@ int run_read_at(dppr_engine *e, const double *p, const double *r, int gw, int n,
     HIP_TRY(hipGetLastError());
     if (out_p) HIP_TRY(hipMemcpyAsync(out_p, d_p, sizeof(double) * mn, hipMemcpyDeviceToHost, e->stream));
     if (out_r) HIP_TRY(hipMemcpyAsync(out_r, d_r, sizeof(double) * mn, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return DPPR_OK;
+}
+
+// scores of q weighted combinations at m external ids (ids and weights validated by the caller, m > 0), [m][q]
+int run_score_at(dppr_engine *e, const double *p, int gw, int n, const double *weights, int q, const int32_t *ids, int m,
+                 double *out_score) {
+    HIP_TRY(hipSetDevice(e->device));
+    int rc = sync_map(e);
+    if (rc) return rc;
+    const size_t mq = (size_t)m * (size_t)q;
+    const size_t ids_bytes = (sizeof(int) * (size_t)m + 7) & ~(size_t)7, need = ids_bytes + sizeof(double) * mq;
+    if (e->ra_buf.capacity() < need) {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(e->ra_buf.regrow(need));
+    }
+    if (!e->wq_w) HIP_TRY(e->wq_w.alloc((size_t)GS_MAX * GS_MAX));
+    rc = wq_upload(e, weights, q, n);
+    if (rc) return rc;
+    int *d_ids = reinterpret_cast<int *>(e->ra_buf.get());
+    double *d_out = reinterpret_cast<double *>(e->ra_buf + ids_bytes);
+    HIP_TRY(hipMemcpyAsync(d_ids, ids, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(k_score_at, dim3(grid_for((int64_t)mq, WQ_BLOCK)), dim3(WQ_BLOCK), 0, e->stream, p, gw, n, e->d_ext2int, d_ids,
+                       m, e->wq_w, q, d_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out_score, d_out, sizeof(double) * mq, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return DPPR_OK;
 }

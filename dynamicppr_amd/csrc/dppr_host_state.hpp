@@ -333,7 +333,12 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     DevBuf<int> tk_out_row;
     DevBuf<int> tk_cand;            // candidate lists: [n][cap] internal rows
     DevBuf<unsigned char> tk_res; PinBuf<unsigned char> tk_pin; // ordered results (device / pinned host): counts, ids, p, r
-    DevBuf<unsigned char> ra_buf;   // point reads: ids, then p and r outputs
+    DevBuf<unsigned char> ra_buf;   // point reads: ids, then p and r outputs (dppr_group_score_at: ids, then the scores)
+    // a group as a weighted set of targets (dppr_wquery.hpp), allocated on the first such query and grown on demand
+    DevBuf<double> wq_w;            // [16][16] weights of the call
+    DevBuf<double> wq_score;        // scratch state: [occupied rows][q] scores
+    DevBuf<int> wq_ext;             // ... and the external id of every row of it
+    float query_ms = -1.0f;         // dppr_set_profiling: device time of the last top-k query, first to last kernel (dppr_debug_query_ms)
     std::vector<int32_t> h_tmp1, h_tmp2;
     std::vector<int32_t> h_tiles; // host copy of the tile edge prefix / group table
     int max_iters = 1 << 20;

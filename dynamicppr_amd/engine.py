@@ -62,6 +62,7 @@ EXPORTS = [
     "dppr_bench_line_fills", "dppr_bench_stream_copy", "dppr_build_id", "dppr_heartbeat", "dppr_slide_concurrent", "dppr_renumbering_due", "dppr_debug_bin_tables",
     "dppr_debug_grouping", "dppr_topk", "dppr_group_topk", "dppr_read_at", "dppr_group_read_at", "dppr_debug_live_bytes",
     "dppr_group_sources", "dppr_group_replace_source", "dppr_group_add_source", "dppr_group_remove_source",
+    "dppr_group_topk_weighted", "dppr_group_score_at", "dppr_debug_query_ms",
 ]
 
 
@@ -153,6 +154,9 @@ def lib():
     L.dppr_group_replace_source.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, fp]
     L.dppr_group_add_source.argtypes = [vp, C.c_int32, C.c_int32, ip, fp]
     L.dppr_group_remove_source.argtypes = [vp, C.c_int32, C.c_int32]
+    L.dppr_group_topk_weighted.argtypes = [vp, C.c_int32, dp, C.c_int32, C.c_int32, C.c_double, ip, dp, ip]
+    L.dppr_group_score_at.argtypes = [vp, C.c_int32, dp, C.c_int32, ip, C.c_int32, dp]
+    L.dppr_debug_query_ms.argtypes = [vp, fp]
     for name in EXPORTS:
         if name not in ("dppr_strerror", "dppr_last_error", "dppr_destroy", "dppr_build_id", "dppr_heartbeat"):
             getattr(L, name).restype = C.c_int
@@ -504,6 +508,49 @@ class Engine:
         self._ck(self._L.dppr_group_read_at(self._h, int(group), pa, len(a), p.ctypes.data_as(dp), r.ctypes.data_as(dp)),
                  "group_read_at")
         return p, r
+
+    # ---- a group as a weighted set of targets ----
+    def _weights(self, group, weights, what):
+        """weights as a contiguous [q][n] array, checked here (before the library is called)."""
+        w = np.array(weights, dtype=np.float64, order="C", ndmin=2)
+        n = self._group_n.get(group, 1)
+        if w.ndim != 2 or w.shape[1] != n:
+            raise DpprError(f"{what}: weights must be [n] or [q][n] with n = {n} sources, got shape {np.shape(weights)}")
+        if not 1 <= w.shape[0] <= 16:
+            raise DpprError(f"{what}: 1 to 16 weight vectors per call, got {w.shape[0]}")
+        if not np.all(np.isfinite(w)):
+            raise DpprError(f"{what}: weights must be finite")
+        return w
+
+    def group_topk_weighted(self, group, weights, k, min_score=0.0):
+        """The k vertices of largest score = sum_i w_i * p_i (folded in lane order, include/dppr.h) with score > min_score, by score
+        descending then id ascending, for every weight vector: a list of (ids, scores), trimmed to the counts. `weights` is [n] or [q][n]."""
+        w = self._weights(group, weights, "group_topk_weighted")
+        q, kk = w.shape[0], max(int(k), 1)
+        ids = np.empty((q, kk), dtype=np.int32)
+        sc = np.empty((q, kk), dtype=np.float64)
+        cnt = np.empty(q, dtype=np.int32)
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        self._ck(self._L.dppr_group_topk_weighted(self._h, int(group), w.ctypes.data_as(dp), q, int(k), float(min_score),
+                                                  ids.ctypes.data_as(ip), sc.ctypes.data_as(dp), cnt.ctypes.data_as(ip)),
+                 "group_topk_weighted")
+        return [(ids[j, :c].copy(), sc[j, :c].copy()) for j, c in enumerate(cnt)]
+
+    def group_score_at(self, group, weights, ids):
+        """The scores of every weight vector at the given external ids: a [len(ids)][q] array."""
+        w = self._weights(group, weights, "group_score_at")
+        a, pa = _i32(ids)
+        out = np.empty((len(a), w.shape[0]), dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        self._ck(self._L.dppr_group_score_at(self._h, int(group), w.ctypes.data_as(dp), w.shape[0], pa, len(a),
+                                             out.ctypes.data_as(dp)), "group_score_at")
+        return out
+
+    def query_ms(self):
+        """With set_profiling on: device ms of the last top-k query, first to last kernel (dppr_debug_query_ms)."""
+        ms = C.c_float(0)
+        self._ck(self._L.dppr_debug_query_ms(self._h, C.byref(ms)), "debug_query_ms")
+        return ms.value
 
     def group_stats(self, group):
         st = Stats()

@@ -3,11 +3,13 @@
 // of an out-of-bounds read (util/CommandLine.h:52-55), and -a is range-checked exactly.
 #pragma once
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
 #include <string>
+#include <vector>
 
 #include "../../include/dppr.h" // (DPPR_TOPK_MAX)
 #include "meta.hpp"
@@ -45,6 +47,19 @@ inline double as_double(int argc, char **argv, const char *flag, double dflt) {
     }
     return x;
 }
+// "w1,w2,..": finite numbers separated by commas; anything else gives an empty list (rejected by ArgumentsChecker)
+inline std::vector<double> parse_weights(const char *v) {
+    std::vector<double> w;
+    for (const char *p = v;;) {
+        char *end = nullptr;
+        const double x = std::strtod(p, &end);
+        if (end == p || !std::isfinite(x)) return {};
+        w.push_back(x);
+        if (*end == '\0') return w;
+        if (*end != ',') return {};
+        p = end + 1;
+    }
+}
 } // namespace args_detail
 
 inline void PrintUsage() {
@@ -60,6 +75,9 @@ inline void PrintUsage() {
               << "--dump <path>: write pagerank/residual of every source after the last batch\n"
               << "--topk <K>: after the last batch print the K vertices of largest pagerank of every source (1 <= K <= 8192),\n"
               << "            one line each, in source order: topk <source> <rank from 1> <vertex> <pagerank>\n"
+              << "--topk-weights <w1,w2,...>: with --topk and all sources in one group (one GPU, 2 to 16 sources, no --no-groups / --split),\n"
+              << "            one finite weight per source: after the topk lines, the K vertices of largest sum_i w_i * pagerank_i,\n"
+              << "            one line each: topkw <rank from 1> <vertex> <score>\n"
               << "--validate: residual bound + power-iteration check after every solve\n"
               << "--split: drive each batch through IncrementalBatchUpdate/ExecuteMainLoop(0)/(1)\n"
               << "--sync: synchronous (deterministic) push schedule\n"
@@ -99,6 +117,7 @@ inline void ArgumentsChecker() {
     }
     if (gVariant < 0 || gVariant >= kVariantTypeSize) ok = false;
     if (gTopK < 0 || gTopK > DPPR_TOPK_MAX) ok = false;
+    if (gTopKWeightsGiven && (gTopK == 0 || gTopKWeights.empty())) ok = false; // (the count is checked against the sources in main)
     if (!ok) {
         std::cout << "invalid arguments" << std::endl;
         PrintUsage();
@@ -126,6 +145,10 @@ inline void ArgumentsParser(int argc, char **argv) {
     if (const char *f = find(argc, argv, "--sources")) gSourcesFile = f;
     if (const char *f = find(argc, argv, "--dump")) gDumpPath = f;
     gTopK = as_int(argc, argv, "--topk", 0);
+    if (const char *w = find(argc, argv, "--topk-weights")) {
+        gTopKWeightsGiven = true;
+        gTopKWeights = parse_weights(w);
+    }
     gValidate = has(argc, argv, "--validate");
     gSplitInterface = has(argc, argv, "--split");
     gSchedule = has(argc, argv, "--sync") ? 1 : 0;

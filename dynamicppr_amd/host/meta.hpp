@@ -7,6 +7,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <vector>
 
 using IndexType = int32_t; // Meta.h:26
 using ValueType = double;  // Meta.h:25
@@ -40,6 +41,8 @@ inline int gNumGpus = 1;              // -g : devices; sources are dealt round-r
 inline std::string gSourcesFile;      // --sources : file with one source vertex id per line
 inline std::string gDumpPath;         // --dump : write p/r of every source after the last batch
 inline int gTopK = 0;                 // --topk K : print the K vertices of largest p of every source after the last batch (0: off)
+inline std::vector<double> gTopKWeights; // --topk-weights w1,w2,.. : also rank the weighted combination of the sources (one weight per source, all in one group)
+inline bool gTopKWeightsGiven = false;
 inline bool gValidate = false;        // --validate : the reference's -DVALIDATE checks at run time
 inline bool gShareDevice = false;     // --share-device (or DPPR_DEVICE_ALIAS=1): the -g N device threads share the devices that exist (d % count)
 inline bool gPushOnly = false;        // --push-only : no pull sweeps (the ablation of the -o variants times their push mechanisms)

@@ -42,6 +42,13 @@ int main(int argc, char *argv[]) {
     PrintArguments();
     const std::vector<IndexType> sources = LoadSources();
     const int ngpu = std::min<int>(gNumGpus, (int)sources.size());
+    // --topk-weights ranks ONE group's sources as a set: all of them on one device, solved as one group, one weight each
+    if (gTopKWeightsGiven && (ngpu != 1 || sources.size() < 2 || sources.size() > PPRGPU::kGroupMax || gNoGroups || gSplitInterface ||
+                              gTopKWeights.size() != sources.size())) {
+        std::cout << "invalid arguments" << std::endl;
+        PrintUsage();
+        return -1;
+    }
 
     // Every device thread streams the same file through its own SlidingGraphVec (a position in
     // a shared read-only mapping of the page cache) and owns one engine.
@@ -139,6 +146,13 @@ int main(int argc, char *argv[]) {
             const auto &list = top[j % (size_t)ngpu][j / (size_t)ngpu];
             for (size_t t = 0; t < list.size(); ++t) {
                 std::snprintf(line, sizeof(line), "topk %d %zu %d %.17g", (int)sources[j], t + 1, (int)list[t].vertex, list[t].p);
+                std::cout << line << "\n";
+            }
+        }
+        if (gTopKWeightsGiven) {
+            const auto list = drivers[0]->TopKWeighted(gTopK, gTopKWeights);
+            for (size_t t = 0; t < list.size(); ++t) {
+                std::snprintf(line, sizeof(line), "topkw %zu %d %.17g", t + 1, (int)list[t].vertex, list[t].p);
                 std::cout << line << "\n";
             }
         }

@@ -97,7 +97,8 @@ public:
         use_groups = source_vertex_ids.size() > 1 && !gSplitInterface && !gNoGroups;
         // two or three sources on a large window: one after the other on the single-source path (binned sweeps) beats a group, whose
         // sweep costs about the same for 2 as for 8 sources (friendster stand-in, 3 sources: 422 ms per batch as a group, 3 x 100 in series)
-        if (use_groups && source_vertex_ids.size() <= 3 && graph->sliding_window_size >= 4000000) use_groups = false;
+        // (--topk-weights asks for the group)
+        if (use_groups && source_vertex_ids.size() <= 3 && graph->sliding_window_size >= 4000000 && !gTopKWeightsGiven) use_groups = false;
         if (gProfile) DPPR_CHECK(engine, dppr_set_profiling(engine, 1));
         if (!quiet_) std::cout << "start..." << std::endl;
         if (use_groups) {
@@ -446,6 +447,17 @@ public:
             for (size_t j = 0; j < n; ++j)
                 for (int32_t t = 0; t < cnt[j]; ++t) out[first + j].push_back({ids[j * (size_t)k + t], p[j * (size_t)k + t]});
         }
+        return out;
+    }
+
+    // --topk-weights: the k vertices of largest sum_i w_i * p_i over this device's sources, which are one group (checked in main)
+    std::vector<TopEntry> TopKWeighted(int k, const std::vector<double> &w) {
+        std::vector<int32_t> ids((size_t)k, -1);
+        std::vector<double> score((size_t)k, 0.0);
+        int32_t cnt = 0;
+        DPPR_CHECK(engine, dppr_group_topk_weighted(engine, groups[0], w.data(), 1, k, 0.0, ids.data(), score.data(), &cnt));
+        std::vector<TopEntry> out;
+        for (int32_t t = 0; t < cnt; ++t) out.push_back({ids[(size_t)t], score[(size_t)t]});
         return out;
     }
 

@@ -394,6 +394,49 @@ int dppr_read_at(dppr_engine *e, int32_t slot, const int32_t *ids, int32_t m, do
 int dppr_group_read_at(dppr_engine *e, int32_t group, const int32_t *ids, int32_t m,
                        double *out_p /* [m][n] */, double *out_r /* [m][n] */); /* either output may be NULL */
 
+/* ---- a source group as a weighted set of targets (backward-compatible additions, ABI 6) ----
+ * PPR is linear in the target: with p_i[v] the PPR of v towards source s_i, sum_i w_i * p_i[v] is the PPR of v
+ * towards the weighted target set {(s_i, w_i)}. These two calls rank and read that combination on the device,
+ * for up to 16 weight vectors at once, instead of dppr_group_read of every column and host arithmetic.
+ *
+ * weights is [q][n], q in [1, 16]; n is the group's current source count and the columns follow its lane order,
+ * as dppr_group_sources reports both. Weights may be negative (contrast queries) or zero.
+ *
+ * THE SCORE of query j at vertex v is defined exactly. With p_i[v] exactly what dppr_group_read returns:
+ *     acc = w[j][0] * p_0[v];
+ *     for i = 1 .. n-1 in that order: acc = acc + w[j][i] * p_i[v];
+ * Every product and every sum is rounded to double (round to nearest even); nothing is fused into a
+ * multiply-add. A vertex without an internal id takes part with all p_i = 0.0 (its score is +0.0 or -0.0 as
+ * the signs of the weights make it). Two consequences: a one-hot weight vector (w[j][i] = 1.0, the rest 0.0)
+ * gives, bit for bit, the ids and values dppr_group_topk returns for source i; and the same loop over the dense
+ * reads on the host reproduces every score bit for bit.
+ *
+ * dppr_group_topk_weighted: the qualifying vertices of query j are the external ids with score > min_score
+ * (min_score >= 0), ordered by score descending, then external id ascending; the first min(k, #qualifying) are
+ * returned with their count, entries past the count hold id -1 and 0.0. Outputs are query-major: ids [q][k],
+ * scores [q][k], counts [q]. A NaN score (an overflow of opposite signs can make one) never qualifies, nor a
+ * negative or zero one; +inf orders above every finite score.
+ *
+ * dppr_group_score_at: the q scores at m caller-given external ids, vertex-major [m][q]. m == 0 is a valid no-op.
+ *
+ * Rejected with DPPR_ERR_INVALID before any device work, nothing written: q outside [1, 16], k outside
+ * [1, DPPR_TOPK_MAX], min_score negative or NaN, a weight that is NaN or infinite, a NULL weights, out_ids,
+ * out_score or out_counts, a bad group; for dppr_group_score_at a NULL ids with m > 0, m < 0, or an id outside
+ * [0, V). Both hold the id-map lock as dppr_read does (safe beside dppr_slide_concurrent), run on the solver
+ * stream, work on any state (converged or not), scan the live and the parked zone, and are never part of the
+ * update path. The top-k query keeps a device scratch of 8 q + 4 bytes per row that holds a vertex (not per V),
+ * obtained -- like every other buffer of the call -- before anything is written: after DPPR_ERR_NOMEM the states
+ * and the engine are as before. */
+int dppr_group_topk_weighted(dppr_engine *e, int32_t group, const double *weights /* [q][n] */, int32_t q /* 1..16 */,
+                             int32_t k, double min_score, int32_t *out_ids /* [q][k] */, double *out_score /* [q][k] */,
+                             int32_t *out_counts /* [q] */);
+int dppr_group_score_at(dppr_engine *e, int32_t group, const double *weights /* [q][n] */, int32_t q,
+                        const int32_t *ids, int32_t m, double *out_score /* [m][q] */);
+/* Measurement aid: with dppr_set_profiling on, *out_ms is the device time of the last dppr_topk / dppr_group_topk /
+ * dppr_group_topk_weighted call on this engine, from the first to the last kernel (the copy back not included);
+ * -1 before the first such call. */
+int dppr_debug_query_ms(dppr_engine *e, float *out_ms);
+
 /* Windows whose sweep groups are all resident at once run a frontier loop of a source group as
  * multi-sweep launches (grid barrier between sweeps, row tables kept in LDS; dppr_multi.hpp). on by
  * default; 0 = one launch per sweep everywhere. The roll-call / time-out rules are those of
