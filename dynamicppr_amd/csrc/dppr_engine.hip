@@ -44,6 +44,7 @@
 #include "dppr_calib.hpp"
 #include "dppr_topk.hpp"
 #include "dppr_wquery.hpp"
+#include "dppr_changes.hpp"
 
 using namespace dppr;
 
@@ -1218,6 +1219,7 @@ static int group_churn(dppr_engine *e, int32_t group, ChurnOp op, int32_t index,
         if (pl.recut) e->wide_groups = true;
         if (int rc = recut_stale_groups(e)) return rc; // (a fresh id lies beyond every resident epoch's tables; the first wide group halves the sweep groups)
     }
+    g.mark.reset(); // (the lanes change meaning: a mark does not survive a change of the sources)
     if (int rc = bracket_open(e)) return rc;
     if (pl.relayout) {
         ColMap cm;
@@ -1348,6 +1350,54 @@ int dppr_group_score_at(dppr_engine *e, int32_t group, const double *weights, in
     if (m == 0) return DPPR_OK;
     std::lock_guard<std::mutex> map_lk(e->map_mu);
     return run_score_at(e, g.p, g.gw, g.n, weights, q, ids, m, out_score);
+}
+
+// ---- what a batch moved: marks and the top k of |p - mark| (dppr_changes.hpp, dppr_host_query.hpp) ---------------------------
+int dppr_mark(dppr_engine *e, int32_t slot) {
+    GET_SLOT(e, slot);
+    std::lock_guard<std::mutex> map_lk(e->map_mu);
+    return run_mark(e, s.p, 1, s.mark);
+}
+
+int dppr_group_mark(dppr_engine *e, int32_t group) {
+    GET_GROUP(e, group);
+    std::lock_guard<std::mutex> map_lk(e->map_mu);
+    return run_mark(e, g.p, g.gw, g.mark);
+}
+
+// (a release waits for the device: whatever still reads the mark has finished by then)
+int dppr_unmark(dppr_engine *e, int32_t slot) {
+    GET_SLOT(e, slot);
+    HIP_TRY(hipSetDevice(e->device));
+    s.mark.reset();
+    return DPPR_OK;
+}
+
+int dppr_group_unmark(dppr_engine *e, int32_t group) {
+    GET_GROUP(e, group);
+    HIP_TRY(hipSetDevice(e->device));
+    g.mark.reset();
+    return DPPR_OK;
+}
+
+int dppr_changes(dppr_engine *e, int32_t slot, int32_t k, double min_delta, int remark, int32_t *out_ids, double *out_delta,
+                 double *out_p, int32_t *out_count, int32_t *out_moved) {
+    GET_SLOT(e, slot);
+    if (!ch_args_ok(k, min_delta, out_ids, out_delta, out_count))
+        return fail(e, DPPR_ERR_INVALID, "changes: k in [1, DPPR_TOPK_MAX], min_delta >= 0, non-null ids / delta / count");
+    if (!s.mark) return fail(e, DPPR_ERR_INVALID, "changes: the slot has no mark (dppr_mark)");
+    std::lock_guard<std::mutex> map_lk(e->map_mu);
+    return run_changes(e, s.p, 1, 1, s.mark, k, min_delta, remark, out_ids, out_delta, out_p, out_count, out_moved);
+}
+
+int dppr_group_changes(dppr_engine *e, int32_t group, int32_t k, double min_delta, int remark, int32_t *out_ids, double *out_delta,
+                       double *out_p, int32_t *out_counts, int32_t *out_moved) {
+    GET_GROUP(e, group);
+    if (!ch_args_ok(k, min_delta, out_ids, out_delta, out_counts))
+        return fail(e, DPPR_ERR_INVALID, "group_changes: k in [1, DPPR_TOPK_MAX], min_delta >= 0, non-null ids / delta / counts");
+    if (!g.mark) return fail(e, DPPR_ERR_INVALID, "group_changes: the group has no mark (dppr_group_mark; a change of the sources drops it)");
+    std::lock_guard<std::mutex> map_lk(e->map_mu);
+    return run_changes(e, g.p, g.gw, g.n, g.mark, k, min_delta, remark, out_ids, out_delta, out_p, out_counts, out_moved);
 }
 
 int dppr_debug_query_ms(dppr_engine *e, float *out_ms) {

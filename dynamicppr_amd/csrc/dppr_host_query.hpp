@@ -1,6 +1,6 @@
 // dppr_host_query.hpp -- host side of the state queries (dppr_topk / dppr_group_topk / dppr_read_at / dppr_group_read_at, and
-// dppr_group_topk_weighted / dppr_group_score_at): workspace, the device copy of int2ext and the launch sequences of dppr_topk.hpp
-// and dppr_wquery.hpp. Called with map_mu held, on the solver
+// dppr_group_topk_weighted / dppr_group_score_at, dppr_mark / dppr_changes and their group forms): workspace, the device copy of
+// int2ext and the launch sequences of dppr_topk.hpp, dppr_wquery.hpp and dppr_changes.hpp. Called with map_mu held, on the solver
 // stream; nothing here is reached from the update path.
 #pragma once
 
@@ -49,13 +49,11 @@ int topk_workspace(dppr_engine *e, int n, size_t rows) {
     return DPPR_OK;
 }
 
-// The selection of dppr_topk.hpp over a state whose workspace is in place (topk_workspace). i2e: the external id of every row of
-// `st`. Results are lane-major: [n][k]. With dppr_set_profiling on, the device time from the first to the last kernel is kept
-// (query_ms; `opened`: the caller recorded the opening event before kernels of its own).
-int run_select(dppr_engine *e, const TkState &st, const int *i2e, int k, double min_p, int32_t *out_ids, double *out_p,
-               double *out_r, int32_t *out_counts, bool opened = false) {
+// The kernels of one selection of dppr_topk.hpp over a state whose workspace is in place (topk_workspace), enqueued. i2e: the
+// external id of every row of `st`. Ordered counts, ids, p and r of all lanes, lane-major [n][k], go where the four res_ pointers say.
+int select_enqueue(dppr_engine *e, const TkState &st, const int *i2e, int k, double min_p, int *res_cnt, int *res_id, double *res_p,
+                   double *res_r) {
     const int n = st.n;
-    if (e->profiling && !opened) HIP_TRY(hipEventRecord(e->evpool[0], e->stream));
     unsigned *hist1 = reinterpret_cast<unsigned *>(e->tk_ws.get()), *hist2 = hist1 + GS_MAX * TK_BINS1;
     TkLane *ctl = reinterpret_cast<TkLane *>(hist2 + GS_MAX * TK_BINS2);
     const int cand_cap = (int)std::max<size_t>(st.rows, 1);
@@ -74,13 +72,23 @@ int run_select(dppr_engine *e, const TkState &st, const int *i2e, int k, double 
     }
     hipLaunchKernelGGL(k_tk_take, dim3(grid2, n), dim3(256), 0, e->stream, st, i2e, ctl, e->tk_cand, cand_cap, k,
                        e->tk_out_key, e->tk_out_row);
+    hipLaunchKernelGGL(k_tk_rank, dim3((k + 255) / 256, n), dim3(256), 0, e->stream, st, i2e, ctl, k, e->tk_out_key,
+                       e->tk_out_row, res_cnt, res_id, res_p, res_r);
+    HIP_TRY(hipGetLastError());
+    return DPPR_OK;
+}
+
+// The selection and its copy to the host. With dppr_set_profiling on, the device time from the first to the last kernel is kept
+// (query_ms; `opened`: the caller recorded the opening event before kernels of its own).
+int run_select(dppr_engine *e, const TkState &st, const int *i2e, int k, double min_p, int32_t *out_ids, double *out_p,
+               double *out_r, int32_t *out_counts, bool opened = false) {
+    const int n = st.n;
+    if (e->profiling && !opened) HIP_TRY(hipEventRecord(e->evpool[0], e->stream));
     const size_t nk = (size_t)n * (size_t)k;
     int *res_cnt = reinterpret_cast<int *>(e->tk_res.get()), *res_id = reinterpret_cast<int *>(e->tk_res.get() + TK_RES_IDS);
     const size_t off_p = TK_RES_IDS + ((sizeof(int) * nk + 7) & ~(size_t)7), off_r = off_p + sizeof(double) * nk;
     double *res_p = reinterpret_cast<double *>(e->tk_res + off_p), *res_r = reinterpret_cast<double *>(e->tk_res + off_r);
-    hipLaunchKernelGGL(k_tk_rank, dim3((k + 255) / 256, n), dim3(256), 0, e->stream, st, i2e, ctl, k, e->tk_out_key,
-                       e->tk_out_row, res_cnt, res_id, res_p, res_r);
-    HIP_TRY(hipGetLastError());
+    if (int rc = select_enqueue(e, st, i2e, k, min_p, res_cnt, res_id, res_p, res_r)) return rc;
     if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[1], e->stream));
     HIP_TRY(hipMemcpyAsync(e->tk_pin, e->tk_res, tk_res_bytes(n, k, out_r != nullptr), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -201,6 +209,86 @@ int run_score_at(dppr_engine *e, const double *p, int gw, int n, const double *w
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out_score, d_out, sizeof(double) * mq, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
+    return DPPR_OK;
+}
+
+// ---- what a batch moved (dppr_changes.hpp) ---------------------------------------------------------------------------------
+static_assert(CH_LANES == GS_MAX && CH_K_MAX == DPPR_TOPK_MAX, "dppr_changes_plan.hpp restates GS_MAX and DPPR_TOPK_MAX");
+
+// mark = p of every source as it is now, by external id ([V][gw]). The buffer is obtained before anything is written; a second
+// mark of the same width overwrites the first in place.
+int run_mark(dppr_engine *e, const double *p, int gw, DevBuf<double> &mark) {
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t need = (size_t)e->V * (size_t)gw;
+    DevBuf<double> fresh;
+    if (mark.capacity() != need) HIP_TRY(fresh.alloc(need));
+    int rc = sync_map(e);
+    if (rc) return rc;
+    if (fresh) mark.swap(fresh); // (what `fresh` holds now goes when this call returns, after the stream has drained)
+    hipLaunchKernelGGL(k_ch_mark, dim3(grid_for((int64_t)need, CH_BLOCK)), dim3(CH_BLOCK), 0, e->stream, p, gw, e->d_ext2int.get(), e->V,
+                       mark.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return DPPR_OK;
+}
+
+// Top k of |p - mark| of every lane (arguments validated by the caller, the mark exists and is [V][gw]). Results are lane-major:
+// [n][k]. Every buffer is in place before the first kernel; the scratch is 16 n + 4 bytes per occupied row; nothing is read back
+// between the kernels and one copy brings counts, moved, ids, deltas and p to the host.
+int run_changes(dppr_engine *e, const double *p, int gw, int n, double *mark, int k, double min_delta, int remark, int32_t *out_ids,
+                double *out_delta, double *out_p, int32_t *out_counts, int32_t *out_moved) {
+    HIP_TRY(hipSetDevice(e->device));
+    const TkState st = tk_state(e, p, p, gw, n);
+    int rc = sync_int2ext(e);
+    if (rc) return rc;
+    rc = sync_map(e);
+    if (rc) return rc;
+    rc = topk_workspace(e, n, (size_t)st.rows);
+    if (rc) return rc;
+    const size_t rows = std::max<size_t>((size_t)st.rows, 1);
+    if (e->ch_abs.capacity() < rows * (size_t)n || e->ch_d.capacity() < rows * (size_t)n || e->ch_ext.capacity() < rows) {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        const size_t want = rows * (size_t)n + rows * (size_t)n / 4;
+        if (e->ch_abs.capacity() < rows * (size_t)n) HIP_TRY(e->ch_abs.regrow(want));
+        if (e->ch_d.capacity() < rows * (size_t)n) HIP_TRY(e->ch_d.regrow(want));
+        if (e->ch_ext.capacity() < rows) HIP_TRY(e->ch_ext.regrow(rows + rows / 4));
+    }
+    if (!e->ch_pin) { // (the last of the pair: one that failed half way is made again)
+        HIP_TRY(e->ch_res.regrow(ch_layout(GS_MAX, DPPR_TOPK_MAX).total_bytes));
+        HIP_TRY(e->ch_pin.regrow(ch_layout(GS_MAX, DPPR_TOPK_MAX).copy_bytes));
+    }
+    const ChLayout lay = ch_layout(n, k);
+    unsigned char *res = e->ch_res.get();
+    int *res_cnt = reinterpret_cast<int *>(res + lay.off_cnt), *res_moved = reinterpret_cast<int *>(res + lay.off_moved);
+    int *res_id = reinterpret_cast<int *>(res + lay.off_ids);
+    double *res_d = reinterpret_cast<double *>(res + lay.off_delta), *res_p = reinterpret_cast<double *>(res + lay.off_p);
+    double *res_abs = reinterpret_cast<double *>(res + lay.off_abs);
+    if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[0], e->stream));
+    HIP_TRY(hipMemsetAsync(res_moved, 0, sizeof(int) * GS_MAX, e->stream));
+    const int n_tiles = std::max((st.rows + CH_ROWS - 1) / CH_ROWS, 1);
+    hipLaunchKernelGGL(k_ch_delta, dim3(std::min(n_tiles, 2048)), dim3(CH_BLOCK), 0, e->stream, st, e->d_int2ext.get(), mark, e->V,
+                       min_delta, remark, e->ch_abs.get(), e->ch_d.get(), e->ch_ext.get(), res_moved);
+    HIP_TRY(hipGetLastError());
+    TkState sc; // the scratch: n lanes, rows n doubles wide, compacted (no parked zone); p = |d|, r = d
+    sc.p = e->ch_abs;
+    sc.r = e->ch_d;
+    sc.gw = sc.n = n;
+    sc.n_int = sc.lo_parked = sc.rows = st.rows;
+    rc = select_enqueue(e, sc, e->ch_ext, k, min_delta, res_cnt, res_id, res_abs, res_d);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_ch_gather, dim3(grid_for((int64_t)n * k, CH_BLOCK)), dim3(CH_BLOCK), 0, e->stream, p, gw, n, k,
+                       e->d_ext2int.get(), res_id, res_p);
+    HIP_TRY(hipGetLastError());
+    if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[1], e->stream));
+    HIP_TRY(hipMemcpyAsync(e->ch_pin, e->ch_res, lay.copy_bytes, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (e->profiling) HIP_TRY(hipEventElapsedTime(&e->query_ms, e->evpool[0], e->evpool[1]));
+    const size_t nk = (size_t)n * (size_t)k;
+    memcpy(out_counts, e->ch_pin + lay.off_cnt, sizeof(int) * (size_t)n);
+    if (out_moved) memcpy(out_moved, e->ch_pin + lay.off_moved, sizeof(int) * (size_t)n);
+    memcpy(out_ids, e->ch_pin + lay.off_ids, sizeof(int) * nk);
+    memcpy(out_delta, e->ch_pin + lay.off_delta, sizeof(double) * nk);
+    if (out_p) memcpy(out_p, e->ch_pin + lay.off_p, sizeof(double) * nk);
     return DPPR_OK;
 }
 

@@ -118,6 +118,7 @@ struct Slot : SolveState {
     int source = 0;     // internal id
     int source_ext = 0; // id the caller gave
     DevBuf<double> p, r;
+    DevBuf<double> mark;  // dppr_mark: p as it was then, [V] by EXTERNAL id (empty: no mark; dppr_changes.hpp)
     DevBuf<double> x, x2; // dense per-iteration push amounts (x) and pull output (x2)
     DevBuf<uint32_t> act[2]; // activity bitmaps of x / x2 for sweeps on windows that cannot run resident
     size_t act_bytes = 0;
@@ -148,6 +149,7 @@ struct Group : SolveState {
     int src_ext[GS_MAX] = {0}; // ids the caller gave
     SrcN src{};                // internal ids, -1 = unused lane
     DevBuf<double> p, r, x, x2; // [V][gw]
+    DevBuf<double> mark;       // dppr_group_mark: p as it was then, [V][gw] by EXTERNAL id (empty: no mark; dropped when the sources change)
     DevBuf<uint32_t> act[2]; // activity bitmaps that go with x / x2
     size_t act_bytes = 0;
     DevBuf<int> cnt;        // [3][GS_MAX] rotating frontier sizes, then the per-chunk log [MAX][GS_MAX]
@@ -338,6 +340,10 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     DevBuf<double> wq_w;            // [16][16] weights of the call
     DevBuf<double> wq_score;        // scratch state: [occupied rows][q] scores
     DevBuf<int> wq_ext;             // ... and the external id of every row of it
+    // what a batch moved (dppr_changes.hpp), allocated on the first dppr_changes and grown on demand
+    DevBuf<double> ch_abs, ch_d;    // scratch states: [occupied rows][n] |p - mark| and p - mark
+    DevBuf<int> ch_ext;             // ... and the external id of every row of them
+    DevBuf<unsigned char> ch_res; PinBuf<unsigned char> ch_pin; // counts, moved, ids, deltas, p (dppr_changes_plan.hpp): device / pinned host
     float query_ms = -1.0f;         // dppr_set_profiling: device time of the last top-k query, first to last kernel (dppr_debug_query_ms)
     std::vector<int32_t> h_tmp1, h_tmp2;
     std::vector<int32_t> h_tiles; // host copy of the tile edge prefix / group table

@@ -63,6 +63,7 @@ EXPORTS = [
     "dppr_debug_grouping", "dppr_topk", "dppr_group_topk", "dppr_read_at", "dppr_group_read_at", "dppr_debug_live_bytes",
     "dppr_group_sources", "dppr_group_replace_source", "dppr_group_add_source", "dppr_group_remove_source",
     "dppr_group_topk_weighted", "dppr_group_score_at", "dppr_debug_query_ms",
+    "dppr_mark", "dppr_group_mark", "dppr_unmark", "dppr_group_unmark", "dppr_changes", "dppr_group_changes",
 ]
 
 
@@ -157,6 +158,10 @@ def lib():
     L.dppr_group_topk_weighted.argtypes = [vp, C.c_int32, dp, C.c_int32, C.c_int32, C.c_double, ip, dp, ip]
     L.dppr_group_score_at.argtypes = [vp, C.c_int32, dp, C.c_int32, ip, C.c_int32, dp]
     L.dppr_debug_query_ms.argtypes = [vp, fp]
+    for name in ("dppr_mark", "dppr_group_mark", "dppr_unmark", "dppr_group_unmark"):
+        getattr(L, name).argtypes = [vp, C.c_int32]
+    L.dppr_changes.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int, ip, dp, dp, ip, ip]
+    L.dppr_group_changes.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int, ip, dp, dp, ip, ip]
     for name in EXPORTS:
         if name not in ("dppr_strerror", "dppr_last_error", "dppr_destroy", "dppr_build_id", "dppr_heartbeat"):
             getattr(L, name).restype = C.c_int
@@ -546,8 +551,48 @@ class Engine:
                                              out.ctypes.data_as(dp)), "group_score_at")
         return out
 
+    # ---- what a batch moved: marks and the top k of |p - mark| ----
+    def mark(self, slot):
+        """Keep a copy of the slot's p as it is now (one mark per slot; marking again overwrites it)."""
+        self._ck(self._L.dppr_mark(self._h, int(slot)), "mark")
+
+    def group_mark(self, group):
+        """Keep a copy of p of every source of the group as it is now (dropped when the group's sources change)."""
+        self._ck(self._L.dppr_group_mark(self._h, int(group)), "group_mark")
+
+    def unmark(self, slot):
+        self._ck(self._L.dppr_unmark(self._h, int(slot)), "unmark")
+
+    def group_unmark(self, group):
+        self._ck(self._L.dppr_group_unmark(self._h, int(group)), "group_unmark")
+
+    def changes(self, slot, k, min_delta=0.0, remark=False):
+        """The k vertices of largest |d|, d = p - mark, with |d| > min_delta, by |d| descending then id ascending:
+        (ids, delta, p, moved), the arrays trimmed to the count; moved is the number of qualifying vertices whatever k is.
+        remark=True: the mark is the current p afterwards (the per-batch feed)."""
+        ids, d, p, cnt, moved = self._changes(self._L.dppr_changes, slot, 1, k, min_delta, remark, "changes")
+        return ids[0, :cnt[0]].copy(), d[0, :cnt[0]].copy(), p[0, :cnt[0]].copy(), int(moved[0])
+
+    def group_changes(self, group, k, min_delta=0.0, remark=False):
+        """changes for every source of a group at once: a list of (ids, delta, p, moved), one per source in group order."""
+        ids, d, p, cnt, moved = self._changes(self._L.dppr_group_changes, group, self._group_n.get(group, 1), k, min_delta, remark,
+                                              "group_changes")
+        return [(ids[i, :c].copy(), d[i, :c].copy(), p[i, :c].copy(), int(moved[i])) for i, c in enumerate(cnt)]
+
+    def _changes(self, fn, which, n, k, min_delta, remark, what):
+        kk = max(int(k), 1)
+        ids = np.empty((n, kk), dtype=np.int32)
+        d = np.empty((n, kk), dtype=np.float64)
+        p = np.empty((n, kk), dtype=np.float64)
+        cnt = np.zeros(n, dtype=np.int32)
+        moved = np.zeros(n, dtype=np.int32)
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        self._ck(fn(self._h, int(which), int(k), float(min_delta), int(bool(remark)), ids.ctypes.data_as(ip), d.ctypes.data_as(dp),
+                    p.ctypes.data_as(dp), cnt.ctypes.data_as(ip), moved.ctypes.data_as(ip)), what)
+        return ids, d, p, cnt, moved
+
     def query_ms(self):
-        """With set_profiling on: device ms of the last top-k query, first to last kernel (dppr_debug_query_ms)."""
+        """With set_profiling on: device ms of the last top-k or changes query, first to last kernel (dppr_debug_query_ms)."""
         ms = C.c_float(0)
         self._ck(self._L.dppr_debug_query_ms(self._h, C.byref(ms)), "debug_query_ms")
         return ms.value

@@ -78,6 +78,9 @@ inline void PrintUsage() {
               << "--topk-weights <w1,w2,...>: with --topk and all sources in one group (one GPU, 2 to 16 sources, no --no-groups / --split),\n"
               << "            one finite weight per source: after the topk lines, the K vertices of largest sum_i w_i * pagerank_i,\n"
               << "            one line each: topkw <rank from 1> <vertex> <score>\n"
+              << "--changes <K> [--changes-min <D>]: after every batch print, per source in source order, what the batch moved (1 <= K <= 8192, D >= 0):\n"
+              << "            moved <batch> <source> <vertices with |delta pagerank| > D>, then the K largest of them by |delta|, one line each:\n"
+              << "            changes <batch> <source> <rank from 1> <vertex> <delta> <pagerank>\n"
               << "--validate: residual bound + power-iteration check after every solve\n"
               << "--split: drive each batch through IncrementalBatchUpdate/ExecuteMainLoop(0)/(1)\n"
               << "--sync: synchronous (deterministic) push schedule\n"
@@ -117,6 +120,7 @@ inline void ArgumentsChecker() {
     }
     if (gVariant < 0 || gVariant >= kVariantTypeSize) ok = false;
     if (gTopK < 0 || gTopK > DPPR_TOPK_MAX) ok = false;
+    if (gChangesK < 0 || gChangesK > DPPR_TOPK_MAX || !(gChangesMin >= 0.0) || (gChangesMinGiven && gChangesK == 0)) ok = false;
     if (gTopKWeightsGiven && (gTopK == 0 || gTopKWeights.empty())) ok = false; // (the count is checked against the sources in main)
     if (!ok) {
         std::cout << "invalid arguments" << std::endl;
@@ -149,6 +153,9 @@ inline void ArgumentsParser(int argc, char **argv) {
         gTopKWeightsGiven = true;
         gTopKWeights = parse_weights(w);
     }
+    gChangesK = as_int(argc, argv, "--changes", 0);
+    gChangesMinGiven = find(argc, argv, "--changes-min") != nullptr;
+    gChangesMin = as_double(argc, argv, "--changes-min", 0.0);
     gValidate = has(argc, argv, "--validate");
     gSplitInterface = has(argc, argv, "--split");
     gSchedule = has(argc, argv, "--sync") ? 1 : 0;

@@ -43,6 +43,9 @@ inline std::string gDumpPath;         // --dump : write p/r of every source afte
 inline int gTopK = 0;                 // --topk K : print the K vertices of largest p of every source after the last batch (0: off)
 inline std::vector<double> gTopKWeights; // --topk-weights w1,w2,.. : also rank the weighted combination of the sources (one weight per source, all in one group)
 inline bool gTopKWeightsGiven = false;
+inline int gChangesK = 0;             // --changes K : after every batch print, per source, how many vertices moved and the K largest |delta p| (0: off)
+inline double gChangesMin = 0.0;      // --changes-min D : only vertices with |delta p| > D count and are printed
+inline bool gChangesMinGiven = false;
 inline bool gValidate = false;        // --validate : the reference's -DVALIDATE checks at run time
 inline bool gShareDevice = false;     // --share-device (or DPPR_DEVICE_ALIAS=1): the -g N device threads share the devices that exist (d % count)
 inline bool gPushOnly = false;        // --push-only : no pull sweeps (the ablation of the -o variants times their push mechanisms)

@@ -19,6 +19,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -130,6 +131,10 @@ public:
                 if (!quiet_) std::cout << "elapsed time=" << ms << "ms" << std::endl;
                 if (gValidate) ValidateResult(i);
             }
+        }
+        if (gChangesK > 0) { // --changes: the from-scratch solution is the first mark
+            for (int32_t gid : groups) DPPR_CHECK(engine, dppr_group_mark(engine, gid));
+            for (int32_t sl : slots) DPPR_CHECK(engine, dppr_mark(engine, sl));
         }
         prof.End(HostProfile::INIT_GRAPH_CALC);
         prof.Start(HostProfile::DYNA_GRAPH_CALC);
@@ -248,6 +253,7 @@ public:
                 const int ahead_rc = ahead_task.get();
                 DPPR_CHECK(engine, ahead_rc);
             }
+            if (gChangesK > 0) PrintChanges(stream_batch_count);
         }
         batches_done = stream_batch_count - 1;
         if (!quiet_) Report(stream_batch_count);
@@ -339,6 +345,7 @@ public:
                 prof.End(HostProfile::EXCLUDE_GRAPH_UPDATE);
                 build_beside_ms += nxt.ms;
             }
+            if (gChangesK > 0) PrintChanges(stream_batch_count);
         }
         batches_done = stream_batch_count - 1;
         if (!quiet_) Report(stream_batch_count);
@@ -448,6 +455,43 @@ public:
                 for (int32_t t = 0; t < cnt[j]; ++t) out[first + j].push_back({ids[j * (size_t)k + t], p[j * (size_t)k + t]});
         }
         return out;
+    }
+
+    // --changes: what batch `batch` (from 1) moved, per source of this device in this device's source order, and the new mark in the
+    // same pass (dppr_changes / dppr_group_changes with remark = 1). Outside the timed region: ppr_time is the hipEvent time the
+    // update calls return. One device's lines of a batch are printed as one block (-g N: the device threads take turns).
+    void PrintChanges(size_t batch) {
+        const int k = gChangesK;
+        const size_t n_src = source_vertex_ids.size();
+        std::vector<int32_t> ids, cnt, moved;
+        std::vector<double> d, p;
+        std::string out;
+        char line[200];
+        for (size_t first = 0; first < n_src; first += use_groups ? kGroupMax : 1) {
+            const size_t n = use_groups ? std::min(kGroupMax, n_src - first) : 1;
+            ids.assign(n * (size_t)k, -1);
+            d.assign(n * (size_t)k, 0.0);
+            p.assign(n * (size_t)k, 0.0);
+            cnt.assign(n, 0);
+            moved.assign(n, 0);
+            if (use_groups)
+                DPPR_CHECK(engine, dppr_group_changes(engine, groups[first / kGroupMax], k, gChangesMin, 1, ids.data(), d.data(), p.data(), cnt.data(), moved.data()));
+            else
+                DPPR_CHECK(engine, dppr_changes(engine, slots[first], k, gChangesMin, 1, ids.data(), d.data(), p.data(), cnt.data(), moved.data()));
+            for (size_t j = 0; j < n; ++j) {
+                std::snprintf(line, sizeof(line), "moved %zu %d %d\n", batch, (int)source_vertex_ids[first + j], (int)moved[j]);
+                out += line;
+                for (int32_t t = 0; t < cnt[j]; ++t) {
+                    const size_t at = j * (size_t)k + (size_t)t;
+                    std::snprintf(line, sizeof(line), "changes %zu %d %d %d %.17g %.17g\n", batch, (int)source_vertex_ids[first + j], (int)t + 1, (int)ids[at], d[at], p[at]);
+                    out += line;
+                }
+            }
+        }
+        progress++;
+        static std::mutex print_mu;
+        std::lock_guard<std::mutex> lk(print_mu);
+        std::cout << out << std::flush;
     }
 
     // --topk-weights: the k vertices of largest sum_i w_i * p_i over this device's sources, which are one group (checked in main)

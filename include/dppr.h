@@ -349,16 +349,19 @@ int dppr_group_reset_stats(dppr_engine *e, int32_t group);
 /* The external ids of the group's sources in lane order (the `index` of dppr_group_read) and their number. */
 int dppr_group_sources(dppr_engine *e, int32_t group, int32_t *out_sources /* [16], may be NULL */, int32_t *out_n);
 /* Lane `index` becomes new_source; the row width stays, nothing is re-interleaved. The vertex the lane had before, or
- * one another lane has, is allowed and means a re-solve of that lane. */
+ * one another lane has, is allowed and means a re-solve of that lane. Drops the group's mark (dppr_group_mark): a
+ * lane changes meaning. */
 int dppr_group_replace_source(dppr_engine *e, int32_t group, int32_t index, int32_t new_source, float *out_ms);
 /* One more source; it takes index n (*out_index, may be NULL). An odd group's padding double is taken into use as it
  * is (re-initialised), otherwise p / r are re-interleaved to rows of two more doubles in one streaming pass each
  * (the old and the new rows exist side by side during the call). The ninth source makes the group a wide one
- * (16-byte lanes; sweep groups of at most 512 vertices on this engine from then on). */
+ * (16-byte lanes; sweep groups of at most 512 vertices on this engine from then on). Drops the group's mark
+ * (dppr_group_mark): the rows change width. */
 int dppr_group_add_source(dppr_engine *e, int32_t group, int32_t new_source, int32_t *out_index, float *out_ms);
 /* Drops source `index`. The sources behind it move down by one -- the order is kept, THE CALLER'S HIGHER INDICES
  * DECREASE BY 1 -- and the rows are re-interleaved to the width of n - 1 sources, which gives the memory back.
- * The dropped vertex no longer counts as in use when the ids are renumbered. No loop runs. */
+ * The dropped vertex no longer counts as in use when the ids are renumbered. No loop runs. Drops the group's mark
+ * (dppr_group_mark): the lanes behind the dropped one change meaning. */
 int dppr_group_remove_source(dppr_engine *e, int32_t group, int32_t index);
 
 /* ---- queries of a state: top-k and point reads (added in ABI 6, backward compatible) ----
@@ -436,6 +439,60 @@ int dppr_group_score_at(dppr_engine *e, int32_t group, const double *weights /* 
  * dppr_group_topk_weighted call on this engine, from the first to the last kernel (the copy back not included);
  * -1 before the first such call. */
 int dppr_debug_query_ms(dppr_engine *e, float *out_ms);
+
+/* ---- what a batch moved: marks and per-source top-k of |delta p| (backward-compatible additions, ABI 6) ----
+ * The question a consumer of a DYNAMIC PPR asks after a batch -- which vertices moved, by how much, how many moved by
+ * more than min_delta -- answered on the device instead of by two dense reads per source and a diff on the host.
+ *
+ * MARK. dppr_mark / dppr_group_mark keep a copy of p of every source of the slot / group as it is now, exactly
+ * what dppr_read / dppr_group_read would return. There is one mark per slot or group; marking again overwrites
+ * it. A vertex that has no internal id at mark time has mark 0.0. The mark belongs to EXTERNAL vertex ids (it is
+ * stored by external id, V doubles per row lane): a renumbering of the id space, the parking of a vertex or its
+ * revival between mark and query changes no result. dppr_write leaves a mark alone.
+ *
+ * DELTA. For source i and external id v: d_i[v] = p_i[v] - mark_i[v], p_i being exactly what dppr_read /
+ * dppr_group_read returns now (0.0 for a vertex without an id) -- ONE double subtraction, rounded to nearest even,
+ * so the same subtraction over two dense reads on the host reproduces every value bit for bit.
+ *
+ * dppr_changes / dppr_group_changes: the qualifying vertices of source i are the external ids v with
+ * |d_i[v]| > min_delta (min_delta >= 0, so a delta of +0.0 or -0.0 never qualifies, nor a NaN). They are ordered by
+ * |d| descending, then external id ascending, and the first min(k, #qualifying) are returned:
+ *     out_ids   [n][k]  the vertices
+ *     out_delta [n][k]  d, signed
+ *     out_p     [n][k]  the current p at those vertices (may be NULL)
+ *     out_counts [n]    min(k, moved_i); entries of a row past its count hold id -1 and 0.0 (delta and p)
+ *     out_moved  [n]    the number of qualifying vertices of source i, whatever k is (may be NULL)
+ * Group outputs are source-major (lane order, as dppr_group_sources reports it); a slot is n = 1.
+ *
+ * RE-MARK. With remark != 0 the mark equals the current p once the call returns, as if dppr_mark / dppr_group_mark
+ * had followed -- done in the same pass over the state, without another buffer. Calling with remark != 0 after
+ * every batch is the per-batch feed: each call reports what that batch moved. (If a call with remark != 0 fails
+ * with DPPR_ERR_HIP the mark is undefined: mark again.)
+ *
+ * UNMARK. dppr_unmark / dppr_group_unmark release the mark's memory (8 V bytes per row lane). Unmarking something
+ * that has no mark returns DPPR_OK. A mark also goes with its engine, and dppr_group_replace_source,
+ * dppr_group_add_source and dppr_group_remove_source drop the group's mark.
+ *
+ * Rejected with DPPR_ERR_INVALID before any device work, nothing written: a slot or group without a mark, k
+ * outside [1, DPPR_TOPK_MAX], min_delta negative or NaN, a NULL out_ids, out_delta or out_counts, a bad slot /
+ * group. Every buffer a call needs -- the mark itself (dppr_mark), the scratch of 16 n + 4 bytes per row that
+ * holds a vertex and the result block (dppr_changes) -- is obtained before anything is written: after
+ * DPPR_ERR_NOMEM the state and any earlier mark are as before.
+ * Threading and stream as dppr_topk: mark and query hold the id-map lock as dppr_read does (safe beside
+ * dppr_slide_concurrent), run on the solver stream, work on any state (converged or not, or set by dppr_write),
+ * scan the live and the parked zone and are never part of the update path or of a timed region. With
+ * dppr_set_profiling on, dppr_debug_query_ms also reports the device time of the last dppr_changes /
+ * dppr_group_changes, first to last kernel. */
+int dppr_mark(dppr_engine *e, int32_t slot);
+int dppr_group_mark(dppr_engine *e, int32_t group);
+int dppr_unmark(dppr_engine *e, int32_t slot);
+int dppr_group_unmark(dppr_engine *e, int32_t group);
+int dppr_changes(dppr_engine *e, int32_t slot, int32_t k, double min_delta, int remark,
+                 int32_t *out_ids, double *out_delta, double *out_p /* may be NULL */, int32_t *out_count,
+                 int32_t *out_moved /* may be NULL */);
+int dppr_group_changes(dppr_engine *e, int32_t group, int32_t k, double min_delta, int remark,
+                       int32_t *out_ids /* [n][k] */, double *out_delta /* [n][k] */, double *out_p /* [n][k] or NULL */,
+                       int32_t *out_counts /* [n] */, int32_t *out_moved /* [n] or NULL */);
 
 /* Windows whose sweep groups are all resident at once run a frontier loop of a source group as
  * multi-sweep launches (grid barrier between sweeps, row tables kept in LDS; dppr_multi.hpp). on by
