@@ -45,6 +45,7 @@
 #include "dppr_topk.hpp"
 #include "dppr_wquery.hpp"
 #include "dppr_changes.hpp"
+#include "dppr_export.hpp"
 
 using namespace dppr;
 
@@ -1398,6 +1399,39 @@ int dppr_group_changes(dppr_engine *e, int32_t group, int32_t k, double min_delt
     if (!g.mark) return fail(e, DPPR_ERR_INVALID, "group_changes: the group has no mark (dppr_group_mark; a change of the sources drops it)");
     std::lock_guard<std::mutex> map_lk(e->map_mu);
     return run_changes(e, g.p, g.gw, g.n, g.mark, k, min_delta, remark, out_ids, out_delta, out_p, out_counts, out_moved);
+}
+
+// ---- the state leaves the engine: sparse vectors and dense device copies (dppr_export.hpp, dppr_host_query.hpp) -------------
+int dppr_support(dppr_engine *e, int32_t slot, double min_p, int64_t *out_count) {
+    GET_SLOT(e, slot);
+    return support_call(e, s.p, 1, 1, min_p, out_count);
+}
+
+int dppr_group_support(dppr_engine *e, int32_t group, double min_p, int64_t *out_counts) {
+    GET_GROUP(e, group);
+    return support_call(e, g.p, g.gw, g.n, min_p, out_counts);
+}
+
+int dppr_export_sparse(dppr_engine *e, int32_t slot, double min_p, int64_t cap, int dest, int64_t *out_offsets, int32_t *out_ids,
+                       double *out_p, double *out_r) {
+    GET_SLOT(e, slot);
+    return export_sparse_call(e, s.p, s.r, 1, 1, min_p, cap, dest, out_offsets, out_ids, out_p, out_r);
+}
+
+int dppr_group_export_sparse(dppr_engine *e, int32_t group, double min_p, int64_t cap, int dest, int64_t *out_offsets,
+                             int32_t *out_ids, double *out_p, double *out_r) {
+    GET_GROUP(e, group);
+    return export_sparse_call(e, g.p, g.r, g.gw, g.n, min_p, cap, dest, out_offsets, out_ids, out_p, out_r);
+}
+
+int dppr_export_dense_dev(dppr_engine *e, int32_t slot, int which, int dtype, void *dst_device) {
+    GET_SLOT(e, slot);
+    return export_dense_call(e, s.p, s.r, 1, 1, which, dtype, DPPR_VERTEX_MAJOR, dst_device);
+}
+
+int dppr_group_export_dense_dev(dppr_engine *e, int32_t group, int which, int dtype, int layout, void *dst_device) {
+    GET_GROUP(e, group);
+    return export_dense_call(e, g.p, g.r, g.gw, g.n, which, dtype, layout, dst_device);
 }
 
 int dppr_debug_query_ms(dppr_engine *e, float *out_ms) {

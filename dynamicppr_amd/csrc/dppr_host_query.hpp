@@ -1,6 +1,7 @@
 // dppr_host_query.hpp -- host side of the state queries (dppr_topk / dppr_group_topk / dppr_read_at / dppr_group_read_at, and
-// dppr_group_topk_weighted / dppr_group_score_at, dppr_mark / dppr_changes and their group forms): workspace, the device copy of
-// int2ext and the launch sequences of dppr_topk.hpp, dppr_wquery.hpp and dppr_changes.hpp. Called with map_mu held, on the solver
+// dppr_group_topk_weighted / dppr_group_score_at, dppr_mark / dppr_changes, dppr_support / dppr_export_sparse /
+// dppr_export_dense_dev and their group forms): workspace, the device copy of int2ext, the check of a caller's device pointer and
+// the launch sequences of dppr_topk.hpp, dppr_wquery.hpp, dppr_changes.hpp and dppr_export.hpp. Called with map_mu held, on the solver
 // stream; nothing here is reached from the update path.
 #pragma once
 
@@ -290,6 +291,160 @@ int run_changes(dppr_engine *e, const double *p, int gw, int n, double *mark, in
     memcpy(out_delta, e->ch_pin + lay.off_delta, sizeof(double) * nk);
     if (out_p) memcpy(out_p, e->ch_pin + lay.off_p, sizeof(double) * nk);
     return DPPR_OK;
+}
+
+// ---- the exports (dppr_export.hpp, dppr_export_plan.hpp) --------------------------------------------------------------------
+static_assert(EX_LANES == GS_MAX, "dppr_export_plan.hpp restates GS_MAX");
+static_assert(EX_DEST_HOST == DPPR_DEST_HOST && EX_DEST_DEVICE == DPPR_DEST_DEVICE && EX_DENSE_P == DPPR_DENSE_P &&
+                  EX_DENSE_R == DPPR_DENSE_R && EX_F64 == DPPR_F64 && EX_F32 == DPPR_F32 && EX_VERTEX_MAJOR == DPPR_VERTEX_MAJOR &&
+                  EX_SOURCE_MAJOR == DPPR_SOURCE_MAJOR,
+              "dppr_export_plan.hpp restates the constants of include/dppr.h");
+
+// A destination in the caller's device memory: device memory of the engine's device, [ptr, ptr + bytes) inside one allocation,
+// aligned. Asked of the runtime's tables alone: no device work, and a pointer the runtime does not know is a `false`, not an error.
+bool ex_dev_dest_ok(const dppr_engine *e, const void *ptr, size_t bytes, size_t align) {
+    if (!ptr || ((uintptr_t)ptr & (uintptr_t)(align - 1))) return false;
+    hipPointerAttribute_t a;
+    memset(&a, 0, sizeof(a));
+    if (hipPointerGetAttributes(&a, ptr) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    if (a.type != hipMemoryTypeDevice || a.device != e->device) return false;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(ptr)) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return ex_range_ok((uintptr_t)ptr, bytes, align, (uintptr_t)base, size);
+}
+
+// The three arrays of a sparse export to the device (cap > 0; out_r may be NULL)
+bool ex_sparse_dest_ok(const dppr_engine *e, int64_t cap, const int32_t *ids, const double *p, const double *r) {
+    return ex_dev_dest_ok(e, ids, sizeof(int32_t) * (size_t)cap, sizeof(int32_t)) &&
+           ex_dev_dest_ok(e, p, sizeof(double) * (size_t)cap, sizeof(double)) &&
+           (!r || ex_dev_dest_ok(e, r, sizeof(double) * (size_t)cap, sizeof(double)));
+}
+
+// workspace by V, the block by what the call copies back: in place before anything is written
+int export_workspace(dppr_engine *e, size_t block_bytes) {
+    const ExWork w = ex_workspace(e->V);
+    if (e->ex_mask.capacity() >= w.mask_elems && e->ex_cnt.capacity() >= w.cnt_elems && e->ex_base.capacity() >= w.base_elems &&
+        e->ex_blk.capacity() >= block_bytes && e->ex_pin.capacity() >= block_bytes)
+        return DPPR_OK;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (e->ex_mask.capacity() < w.mask_elems) HIP_TRY(e->ex_mask.regrow(w.mask_elems));
+    if (e->ex_cnt.capacity() < w.cnt_elems) HIP_TRY(e->ex_cnt.regrow(w.cnt_elems));
+    if (e->ex_base.capacity() < w.base_elems) HIP_TRY(e->ex_base.regrow(w.base_elems));
+    if (e->ex_blk.capacity() < block_bytes) HIP_TRY(e->ex_blk.regrow(block_bytes));
+    if (e->ex_pin.capacity() < block_bytes) HIP_TRY(e->ex_pin.regrow(block_bytes));
+    return DPPR_OK;
+}
+
+// The sparse vectors of every lane of a state (arguments and a device destination validated by the caller). cap = 0: the counts
+// alone (dppr_support, the size query). The offsets are decided on the device and so is whether the fill runs: nothing is read
+// back between the kernels; one copy brings the head -- and a host destination's ids, p and r -- back.
+int run_export_sparse(dppr_engine *e, const double *p, const double *r, int gw, int n, double min_p, int64_t cap, int dest,
+                      int64_t *out_offsets, int32_t *out_ids, double *out_p, double *out_r) {
+    HIP_TRY(hipSetDevice(e->device));
+    int rc = sync_map(e);
+    if (rc) return rc;
+    const bool host = dest == DPPR_DEST_HOST;
+    const int64_t capc = ex_cap_clamped(cap, e->V, n);
+    const ExLayout lay = ex_layout(host ? capc : 0, host && out_r);
+    rc = export_workspace(e, lay.total_bytes);
+    if (rc) return rc;
+    unsigned char *blk = e->ex_blk.get();
+    ExHead *head = reinterpret_cast<ExHead *>(blk);
+    int *d_ids = host ? reinterpret_cast<int *>(blk + lay.off_ids) : out_ids;
+    double *d_p = host ? reinterpret_cast<double *>(blk + lay.off_p) : out_p;
+    double *d_r = !out_r ? nullptr : host ? reinterpret_cast<double *>(blk + lay.off_r) : out_r;
+    const int tiles = (int)ex_tiles(e->V), grid = std::min(tiles, 2048);
+    if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[0], e->stream));
+    hipLaunchKernelGGL(k_ex_mask, dim3(grid), dim3(EX_TILE), 0, e->stream, p, gw, n, e->d_ext2int.get(), e->V, min_p,
+                       e->ex_mask.get(), e->ex_cnt.get());
+    hipLaunchKernelGGL(k_ex_scan, dim3(1), dim3(EX_LANES * WAVE), 0, e->stream, e->ex_cnt.get(), n, tiles, (long long)capc,
+                       e->ex_base.get(), head);
+    if (capc > 0)
+        hipLaunchKernelGGL(k_ex_fill, dim3(grid), dim3(EX_TILE), 0, e->stream, p, r, gw, n, e->d_ext2int.get(), e->V,
+                           e->ex_mask.get(), e->ex_base.get(), head, d_ids, d_p, d_r);
+    HIP_TRY(hipGetLastError());
+    if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[1], e->stream));
+    HIP_TRY(hipMemcpyAsync(e->ex_pin, e->ex_blk, lay.total_bytes, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream)); // (a device destination is complete here: any stream of the caller may read it)
+    if (e->profiling) HIP_TRY(hipEventElapsedTime(&e->query_ms, e->evpool[0], e->evpool[1]));
+    const ExHead *h = reinterpret_cast<const ExHead *>(e->ex_pin.get());
+    for (int i = 0; i <= n; ++i) out_offsets[i] = h->offsets[i];
+    const size_t total = (size_t)h->offsets[n];
+    if (host && capc > 0 && h->go && total > 0) {
+        memcpy(out_ids, e->ex_pin + lay.off_ids, sizeof(int32_t) * total);
+        memcpy(out_p, e->ex_pin + lay.off_p, sizeof(double) * total);
+        if (out_r) memcpy(out_r, e->ex_pin + lay.off_r, sizeof(double) * total);
+    }
+    return DPPR_OK;
+}
+
+// p or r of every lane by external id into the caller's device memory (arguments and the destination validated by the caller)
+int run_export_dense(dppr_engine *e, const double *src, int gw, int n, int dtype, int layout, void *dst) {
+    HIP_TRY(hipSetDevice(e->device));
+    int rc = sync_map(e);
+    if (rc) return rc;
+    const int V = e->V;
+    const int *x2i = e->d_ext2int.get();
+    if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[0], e->stream));
+    if (layout == DPPR_SOURCE_MAJOR) {
+        const dim3 grid(std::min((int)ex_tiles(V), 2048)), block(EX_TILE);
+        if (dtype == DPPR_F32)
+            hipLaunchKernelGGL((k_ex_dense<float, true>), grid, block, 0, e->stream, src, gw, n, x2i, V, static_cast<float *>(dst));
+        else
+            hipLaunchKernelGGL((k_ex_dense<double, true>), grid, block, 0, e->stream, src, gw, n, x2i, V, static_cast<double *>(dst));
+    } else {
+        const dim3 grid(grid_for((int64_t)V * n, EX_TILE)), block(EX_TILE);
+        if (dtype == DPPR_F32)
+            hipLaunchKernelGGL((k_ex_dense<float, false>), grid, block, 0, e->stream, src, gw, n, x2i, V, static_cast<float *>(dst));
+        else
+            hipLaunchKernelGGL((k_ex_dense<double, false>), grid, block, 0, e->stream, src, gw, n, x2i, V, static_cast<double *>(dst));
+    }
+    HIP_TRY(hipGetLastError());
+    if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[1], e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (e->profiling) HIP_TRY(hipEventElapsedTime(&e->query_ms, e->evpool[0], e->evpool[1]));
+    return DPPR_OK;
+}
+
+// What the six entry points share: the checks that need no device and those of a device destination, the id-map lock, the run.
+int export_sparse_call(dppr_engine *e, const double *p, const double *r, int gw, int n, double min_p, int64_t cap, int dest,
+                       int64_t *out_offsets, int32_t *out_ids, double *out_p, double *out_r) {
+    if (!ex_sparse_args_ok(min_p, cap, dest, out_offsets, out_ids, out_p))
+        return fail(e, DPPR_ERR_INVALID, "export_sparse: min_p >= 0, cap >= 0, dest 0 or 1, non-null offsets, non-null ids / p when cap > 0");
+    HIP_TRY(hipSetDevice(e->device));
+    if (cap > 0 && dest == DPPR_DEST_DEVICE && !ex_sparse_dest_ok(e, ex_cap_clamped(cap, e->V, n), out_ids, out_p, out_r))
+        return fail(e, DPPR_ERR_INVALID, "export_sparse: ids / p / r must be aligned device memory of the engine's device, cap entries inside one allocation");
+    std::lock_guard<std::mutex> map_lk(e->map_mu); // (as dppr_read)
+    return run_export_sparse(e, p, r, gw, n, min_p, cap, dest, out_offsets, out_ids, out_p, out_r);
+}
+
+int support_call(dppr_engine *e, const double *p, int gw, int n, double min_p, int64_t *out_counts) {
+    if (!ex_support_args_ok(min_p, out_counts)) return fail(e, DPPR_ERR_INVALID, "support: min_p >= 0, non-null counts");
+    int64_t offsets[GS_MAX + 1];
+    int rc;
+    {
+        std::lock_guard<std::mutex> map_lk(e->map_mu);
+        rc = run_export_sparse(e, p, nullptr, gw, n, min_p, 0, DPPR_DEST_HOST, offsets, nullptr, nullptr, nullptr);
+    }
+    if (rc) return rc;
+    for (int i = 0; i < n; ++i) out_counts[i] = offsets[i + 1] - offsets[i];
+    return DPPR_OK;
+}
+
+int export_dense_call(dppr_engine *e, const double *p, const double *r, int gw, int n, int which, int dtype, int layout, void *dst) {
+    if (!ex_dense_args_ok(which, dtype, layout)) return fail(e, DPPR_ERR_INVALID, "export_dense_dev: which 0 or 1, dtype 0 or 1, layout 0 or 1");
+    HIP_TRY(hipSetDevice(e->device));
+    if (!ex_dev_dest_ok(e, dst, ex_dense_bytes(dtype, n, e->V), ex_elem_bytes(dtype)))
+        return fail(e, DPPR_ERR_INVALID, "export_dense_dev: dst must be aligned device memory of the engine's device, n x V elements inside one allocation");
+    std::lock_guard<std::mutex> map_lk(e->map_mu);
+    return run_export_dense(e, which == DPPR_DENSE_R ? r : p, gw, n, dtype, layout, dst);
 }
 
 } // namespace

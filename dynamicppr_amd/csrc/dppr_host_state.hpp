@@ -344,7 +344,12 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     DevBuf<double> ch_abs, ch_d;    // scratch states: [occupied rows][n] |p - mark| and p - mark
     DevBuf<int> ch_ext;             // ... and the external id of every row of them
     DevBuf<unsigned char> ch_res; PinBuf<unsigned char> ch_pin; // counts, moved, ids, deltas, p (dppr_changes_plan.hpp): device / pinned host
-    float query_ms = -1.0f;         // dppr_set_profiling: device time of the last top-k query, first to last kernel (dppr_debug_query_ms)
+    // the exports (dppr_export.hpp, dppr_export_plan.hpp), allocated on the first export; the block grows with a host destination's cap
+    DevBuf<unsigned short> ex_mask; // [V] which lanes qualify at every external id
+    DevBuf<int> ex_cnt;             // [tiles][16] qualifying ids per tile and lane
+    DevBuf<long long> ex_base;      // [tiles][16] first output position of a tile's entries of a lane
+    DevBuf<unsigned char> ex_blk; PinBuf<unsigned char> ex_pin; // head (offsets, go), then ids / p / r of a host destination: device / pinned host
+    float query_ms = -1.0f;         // dppr_set_profiling: device time of the last top-k, changes or export call, first to last kernel (dppr_debug_query_ms)
     std::vector<int32_t> h_tmp1, h_tmp2;
     std::vector<int32_t> h_tiles; // host copy of the tile edge prefix / group table
     int max_iters = 1 << 20;

@@ -64,7 +64,14 @@ EXPORTS = [
     "dppr_group_sources", "dppr_group_replace_source", "dppr_group_add_source", "dppr_group_remove_source",
     "dppr_group_topk_weighted", "dppr_group_score_at", "dppr_debug_query_ms",
     "dppr_mark", "dppr_group_mark", "dppr_unmark", "dppr_group_unmark", "dppr_changes", "dppr_group_changes",
+    "dppr_support", "dppr_group_support", "dppr_export_sparse", "dppr_group_export_sparse", "dppr_export_dense_dev",
+    "dppr_group_export_dense_dev",
 ]
+
+DEST_HOST, DEST_DEVICE = 0, 1
+DENSE_P, DENSE_R = 0, 1
+F64, F32 = 0, 1
+VERTEX_MAJOR, SOURCE_MAJOR = 0, 1
 
 
 def lib():
@@ -162,6 +169,13 @@ def lib():
         getattr(L, name).argtypes = [vp, C.c_int32]
     L.dppr_changes.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int, ip, dp, dp, ip, ip]
     L.dppr_group_changes.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int, ip, dp, dp, ip, ip]
+    L.dppr_support.argtypes = [vp, C.c_int32, C.c_double, i64p]
+    L.dppr_group_support.argtypes = [vp, C.c_int32, C.c_double, i64p]
+    # (ids / p / r as plain addresses: host arrays or device memory, as `dest` says)
+    L.dppr_export_sparse.argtypes = [vp, C.c_int32, C.c_double, C.c_int64, C.c_int, i64p, vp, vp, vp]
+    L.dppr_group_export_sparse.argtypes = [vp, C.c_int32, C.c_double, C.c_int64, C.c_int, i64p, vp, vp, vp]
+    L.dppr_export_dense_dev.argtypes = [vp, C.c_int32, C.c_int, C.c_int, vp]
+    L.dppr_group_export_dense_dev.argtypes = [vp, C.c_int32, C.c_int, C.c_int, C.c_int, vp]
     for name in EXPORTS:
         if name not in ("dppr_strerror", "dppr_last_error", "dppr_destroy", "dppr_build_id", "dppr_heartbeat"):
             getattr(L, name).restype = C.c_int
@@ -192,6 +206,7 @@ class Engine:
         self._batch_len, self._staged_len = {0: 0}, 0
         self._group_n = {}  # group -> number of sources
         self.V, self.W, self.directed, self.c = int(V), int(W), int(directed), int(max_batch)
+        self.device = int(device)
         rc = self._L.dppr_create(C.byref(self._h), int(device), self.V, self.W, self.directed, self.c, int(n_epochs))
         if rc:
             self._h = C.c_void_p()
@@ -591,8 +606,70 @@ class Engine:
                     p.ctypes.data_as(dp), cnt.ctypes.data_as(ip), moved.ctypes.data_as(ip)), what)
         return ids, d, p, cnt, moved
 
+    # ---- the state leaves the engine: sparse vectors and dense device copies ----
+    def support(self, slot, min_p=0.0):
+        """How many vertices of the slot have p > min_p."""
+        cnt = C.c_int64(-1)
+        self._ck(self._L.dppr_support(self._h, int(slot), float(min_p), C.byref(cnt)), "support")
+        return cnt.value
+
+    def group_support(self, group, min_p=0.0):
+        """How many vertices of every source of the group have p > min_p: an int64 array in lane order."""
+        cnt = np.zeros(self._group_n.get(group, 1), dtype=np.int64)
+        self._ck(self._L.dppr_group_support(self._h, int(group), float(min_p), cnt.ctypes.data_as(C.POINTER(C.c_int64))), "group_support")
+        return cnt
+
+    def export_sparse(self, slot, min_p=0.0, with_r=False):
+        """Every vertex of the slot with p > min_p, by id ascending: (offsets [2], ids, p[, r])."""
+        return self._export_sparse(self._L.dppr_export_sparse, slot, 1, min_p, with_r, "export_sparse")
+
+    def group_export_sparse(self, group, min_p=0.0, with_r=False):
+        """The sparse vectors of every source of a group as one CSR over the sources: (offsets [n + 1], ids, p[, r]); source i's
+        entries are [offsets[i], offsets[i + 1]), by id ascending."""
+        return self._export_sparse(self._L.dppr_group_export_sparse, group, self._group_n.get(group, 1), min_p, with_r, "group_export_sparse")
+
+    def _export_sparse(self, fn, which, n, min_p, with_r, what):
+        i64p = C.POINTER(C.c_int64)
+        off = np.zeros(n + 1, dtype=np.int64)
+        self._ck(fn(self._h, int(which), float(min_p), 0, DEST_HOST, off.ctypes.data_as(i64p), None, None, None), what)   # the size call
+        total = int(off[n])
+        ids = np.empty(total, dtype=np.int32)
+        p = np.empty(total, dtype=np.float64)
+        r = np.empty(total, dtype=np.float64) if with_r else None
+        if total:   # the fill (the state does not change between the two calls of one thread)
+            self._ck(fn(self._h, int(which), float(min_p), total, DEST_HOST, off.ctypes.data_as(i64p), ids.ctypes.data,
+                        p.ctypes.data, r.ctypes.data if with_r else None), what)
+            if int(off[n]) != total:
+                raise DpprError(f"{what}: the state changed between the size call and the fill")
+        return (off, ids, p, r) if with_r else (off, ids, p)
+
+    def export_sparse_dev(self, slot, min_p, cap, ids_ptr, p_ptr, r_ptr=None):
+        """dppr_export_sparse into device memory at the given raw addresses (cap entries each; r_ptr may be None): the host
+        offsets [2]. Nothing is written if offsets[1] > cap."""
+        return self._export_sparse_dev(self._L.dppr_export_sparse, slot, 1, min_p, cap, ids_ptr, p_ptr, r_ptr, "export_sparse_dev")
+
+    def group_export_sparse_dev(self, group, min_p, cap, ids_ptr, p_ptr, r_ptr=None):
+        """dppr_group_export_sparse into device memory at the given raw addresses: the host offsets [n + 1]."""
+        return self._export_sparse_dev(self._L.dppr_group_export_sparse, group, self._group_n.get(group, 1), min_p, cap, ids_ptr, p_ptr,
+                                       r_ptr, "group_export_sparse_dev")
+
+    def _export_sparse_dev(self, fn, which, n, min_p, cap, ids_ptr, p_ptr, r_ptr, what):
+        off = np.zeros(n + 1, dtype=np.int64)
+        self._ck(fn(self._h, int(which), float(min_p), int(cap), DEST_DEVICE, off.ctypes.data_as(C.POINTER(C.c_int64)),
+                    ids_ptr or None, p_ptr or None, r_ptr or None), what)
+        return off
+
+    def export_dense_dev(self, slot, dst_ptr, which=DENSE_P, dtype=F64):
+        """p (or r) of the slot by external id, V elements of `dtype`, into device memory at the raw address dst_ptr."""
+        self._ck(self._L.dppr_export_dense_dev(self._h, int(slot), int(which), int(dtype), dst_ptr or None), "export_dense_dev")
+
+    def group_export_dense_dev(self, group, dst_ptr, which=DENSE_P, dtype=F64, layout=VERTEX_MAJOR):
+        """p (or r) of every source of the group by external id, [V][n] or [n][V] elements of `dtype`, into device memory at dst_ptr."""
+        self._ck(self._L.dppr_group_export_dense_dev(self._h, int(group), int(which), int(dtype), int(layout), dst_ptr or None),
+                 "group_export_dense_dev")
+
     def query_ms(self):
-        """With set_profiling on: device ms of the last top-k or changes query, first to last kernel (dppr_debug_query_ms)."""
+        """With set_profiling on: device ms of the last top-k, changes or export call, first to last kernel (dppr_debug_query_ms)."""
         ms = C.c_float(0)
         self._ck(self._L.dppr_debug_query_ms(self._h, C.byref(ms)), "debug_query_ms")
         return ms.value

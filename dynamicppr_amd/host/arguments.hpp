@@ -81,6 +81,9 @@ inline void PrintUsage() {
               << "--changes <K> [--changes-min <D>]: after every batch print, per source in source order, what the batch moved (1 <= K <= 8192, D >= 0):\n"
               << "            moved <batch> <source> <vertices with |delta pagerank| > D>, then the K largest of them by |delta|, one line each:\n"
               << "            changes <batch> <source> <rank from 1> <vertex> <delta> <pagerank>\n"
+              << "--sparse-min <P> [--sparse-out <file>]: after the last batch print, per source in source order, the number of vertices\n"
+              << "            with pagerank > P (P >= 0): support <source> <count>; with --sparse-out also write them to <file>,\n"
+              << "            one line each, by source then vertex id: <source> <vertex> <pagerank>\n"
               << "--validate: residual bound + power-iteration check after every solve\n"
               << "--split: drive each batch through IncrementalBatchUpdate/ExecuteMainLoop(0)/(1)\n"
               << "--sync: synchronous (deterministic) push schedule\n"
@@ -121,6 +124,7 @@ inline void ArgumentsChecker() {
     if (gVariant < 0 || gVariant >= kVariantTypeSize) ok = false;
     if (gTopK < 0 || gTopK > DPPR_TOPK_MAX) ok = false;
     if (gChangesK < 0 || gChangesK > DPPR_TOPK_MAX || !(gChangesMin >= 0.0) || (gChangesMinGiven && gChangesK == 0)) ok = false;
+    if ((gSparseGiven && !(gSparseMin >= 0.0)) || (!gSparseOut.empty() && !gSparseGiven)) ok = false;
     if (gTopKWeightsGiven && (gTopK == 0 || gTopKWeights.empty())) ok = false; // (the count is checked against the sources in main)
     if (!ok) {
         std::cout << "invalid arguments" << std::endl;
@@ -156,6 +160,9 @@ inline void ArgumentsParser(int argc, char **argv) {
     gChangesK = as_int(argc, argv, "--changes", 0);
     gChangesMinGiven = find(argc, argv, "--changes-min") != nullptr;
     gChangesMin = as_double(argc, argv, "--changes-min", 0.0);
+    gSparseGiven = find(argc, argv, "--sparse-min") != nullptr;
+    gSparseMin = as_double(argc, argv, "--sparse-min", 0.0);
+    if (const char *f = find(argc, argv, "--sparse-out")) gSparseOut = f;
     gValidate = has(argc, argv, "--validate");
     gSplitInterface = has(argc, argv, "--split");
     gSchedule = has(argc, argv, "--sync") ? 1 : 0;

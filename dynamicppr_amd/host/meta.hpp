@@ -45,6 +45,9 @@ inline std::vector<double> gTopKWeights; // --topk-weights w1,w2,.. : also rank 
 inline bool gTopKWeightsGiven = false;
 inline int gChangesK = 0;             // --changes K : after every batch print, per source, how many vertices moved and the K largest |delta p| (0: off)
 inline double gChangesMin = 0.0;      // --changes-min D : only vertices with |delta p| > D count and are printed
+inline bool gSparseGiven = false;     // --sparse-min P : after the last batch print, per source, how many vertices have pagerank > P (support <source> <count>)
+inline double gSparseMin = 0.0;
+inline std::string gSparseOut;        // --sparse-out FILE : ... and write them, one text line `source id pagerank` each, by source then id
 inline bool gChangesMinGiven = false;
 inline bool gValidate = false;        // --validate : the reference's -DVALIDATE checks at run time
 inline bool gShareDevice = false;     // --share-device (or DPPR_DEVICE_ALIAS=1): the -g N device threads share the devices that exist (d % count)

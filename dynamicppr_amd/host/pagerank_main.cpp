@@ -158,6 +158,23 @@ int main(int argc, char *argv[]) {
         }
         std::cout << std::flush;
     }
+    if (gSparseGiven) { // (not a line of the reference) as --topk: source j is device j % ngpu's source j / ngpu
+        std::vector<std::vector<PPRGPU::SparseVec>> sparse((size_t)ngpu);
+        for (int d = 0; d < ngpu; ++d) sparse[(size_t)d] = drivers[(size_t)d]->SparseExport(gSparseMin);
+        std::FILE *f = nullptr;
+        if (!gSparseOut.empty() && !(f = std::fopen(gSparseOut.c_str(), "w"))) {
+            std::cout << "cannot write " << gSparseOut << std::endl;
+            return -1;
+        }
+        for (size_t j = 0; j < sources.size(); ++j) {
+            const auto &v = sparse[j % (size_t)ngpu][j / (size_t)ngpu];
+            std::cout << "support " << sources[j] << " " << v.ids.size() << "\n";
+            if (f)
+                for (size_t t = 0; t < v.ids.size(); ++t) std::fprintf(f, "%d %d %.17g\n", (int)sources[j], (int)v.ids[t], v.p[t]);
+        }
+        if (f) std::fclose(f);
+        std::cout << std::flush;
+    }
     if (!gDumpPath.empty())
         for (int d = 0; d < ngpu; ++d) drivers[(size_t)d]->Dump(gDumpPath + (ngpu > 1 ? "." + std::to_string(d) : ""));
     return 0;

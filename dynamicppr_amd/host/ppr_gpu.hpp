@@ -457,6 +457,38 @@ public:
         return out;
     }
 
+    // --sparse-min: every vertex with p > min_p of every source of this device, in this device's source order and by id, through
+    // the device-side compaction (dppr_export_sparse / dppr_group_export_sparse: the size call, then the fill)
+    struct SparseVec {
+        std::vector<int32_t> ids;
+        std::vector<double> p;
+    };
+    std::vector<SparseVec> SparseExport(double min_p) {
+        const size_t n_src = source_vertex_ids.size();
+        std::vector<SparseVec> out(n_src);
+        std::vector<int32_t> ids;
+        std::vector<double> p;
+        for (size_t first = 0; first < n_src; first += use_groups ? kGroupMax : 1) {
+            const size_t n = use_groups ? std::min(kGroupMax, n_src - first) : 1;
+            std::vector<int64_t> off(n + 1, 0);
+            auto call = [&](int64_t cap) {
+                if (use_groups)
+                    DPPR_CHECK(engine, dppr_group_export_sparse(engine, groups[first / kGroupMax], min_p, cap, DPPR_DEST_HOST, off.data(), ids.data(), p.data(), nullptr));
+                else
+                    DPPR_CHECK(engine, dppr_export_sparse(engine, slots[first], min_p, cap, DPPR_DEST_HOST, off.data(), ids.data(), p.data(), nullptr));
+            };
+            call(0);
+            ids.assign((size_t)off[n] + 1, -1);
+            p.assign((size_t)off[n] + 1, 0.0);
+            if (off[n] > 0) call(off[n]);
+            for (size_t j = 0; j < n; ++j) {
+                out[first + j].ids.assign(ids.begin() + off[j], ids.begin() + off[j + 1]);
+                out[first + j].p.assign(p.begin() + off[j], p.begin() + off[j + 1]);
+            }
+        }
+        return out;
+    }
+
     // --changes: what batch `batch` (from 1) moved, per source of this device in this device's source order, and the new mark in the
     // same pass (dppr_changes / dppr_group_changes with remark = 1). Outside the timed region: ppr_time is the hipEvent time the
     // update calls return. One device's lines of a batch are printed as one block (-g N: the device threads take turns).

@@ -494,6 +494,65 @@ int dppr_group_changes(dppr_engine *e, int32_t group, int32_t k, double min_delt
                        int32_t *out_ids /* [n][k] */, double *out_delta /* [n][k] */, double *out_p /* [n][k] or NULL */,
                        int32_t *out_counts /* [n] */, int32_t *out_moved /* [n] or NULL */);
 
+/* ---- the state leaves the engine: thresholded sparse vectors and dense device copies (backward-compatible additions, ABI 6) ----
+ * What a consumer takes beyond "the best k": the whole support of every source above a threshold, in id order (a CSR over the
+ * sources: PPR-sparsified adjacency, candidate generation, a join), and p / r by external id in device memory the caller owns.
+ *
+ * SPARSE (dppr_support / dppr_group_support / dppr_export_sparse / dppr_group_export_sparse).
+ * Qualifying entries: for source i (lane order as dppr_group_sources reports it) the external ids v with p_i[v] > min_p,
+ * min_p >= 0, p_i[v] exactly what dppr_group_read returns. A vertex without an internal id, a negative p, -0.0 and NaN never
+ * qualify (the rule of dppr_topk).
+ * Order: by external id ascending.
+ * Layout: source i's entries occupy [offsets[i], offsets[i + 1]) of out_ids, out_p and out_r; offsets[0] = 0. Values are the
+ * stored doubles bit for bit; out_r holds r at the same vertices. A slot is n = 1 (out_offsets [2]).
+ * Offsets: out_offsets is always HOST memory and is always written with the TRUE counts. dppr_support / dppr_group_support
+ * return the differences offsets[i + 1] - offsets[i] alone.
+ * Capacity: if offsets[n] > cap nothing is written to out_ids, out_p or out_r and the call still returns DPPR_OK -- the caller
+ * compares offsets[n] with cap. cap = 0 with NULL arrays is the size query; the pattern is two calls, the second with
+ * cap = offsets[n] of the first (a host destination is staged and copied by cap entries: an exact cap copies nothing spare).
+ * Determinism: the result is a function of the state alone; it does not depend on grid size or scheduling, and no output
+ * position comes from an atomic.
+ * dest: where out_ids, out_p and out_r live. For DPPR_DEST_DEVICE the call returns after the solver stream has finished
+ * writing, so any stream of the caller may read afterwards.
+ *
+ * DENSE (dppr_export_dense_dev / dppr_group_export_dense_dev): dst[v * n + i] (DPPR_VERTEX_MAJOR) or dst[i * V + v]
+ * (DPPR_SOURCE_MAJOR) is p_i[v] (DPPR_DENSE_P) or r_i[v] (DPPR_DENSE_R) for every external id v in [0, V), 0.0 for a vertex
+ * without an id. DPPR_F64: bit for bit. DPPR_F32: converted with round-to-nearest-even, what numpy's astype(float32) of the
+ * dense read gives. A slot is n = 1. There is no host destination: dppr_read and dppr_group_read are that.
+ *
+ * A device destination is checked before any device work (hipPointerGetAttributes, hipMemGetAddressRange): the pointer must
+ * be device memory on the ENGINE'S device, [dst, dst + bytes needed) must lie wholly inside one allocation (sparse: cap
+ * entries of each array, cap taken as at most n * V; dense: n * V elements) and it must be aligned to its element size.
+ * Anything else is DPPR_ERR_INVALID with nothing written: a wrong pointer is a rejected call, never a fault.
+ * Also rejected with DPPR_ERR_INVALID before any device work, nothing written: min_p negative or NaN, cap < 0, a NULL
+ * out_offsets / out_counts, cap > 0 with a NULL out_ids or out_p, dest / which / dtype / layout outside its values, a bad
+ * slot / group.
+ *
+ * Threading and stream as dppr_topk: every call holds the id-map lock as dppr_read does (safe beside dppr_slide_concurrent),
+ * runs on the solver stream, works on any state (converged or not, or set by dppr_write), sees the live and the parked zone
+ * and is never part of the update path or of a timed region. The work space is 2 bytes per external id plus 192 bytes per
+ * 256 external ids, and the block of a host destination 12 (20 with out_r) bytes per entry of cap, device and pinned host;
+ * all of it is the engine's, obtained before anything is written, grown on demand and released with the engine: after
+ * DPPR_ERR_NOMEM the state and the engine are as before. With dppr_set_profiling on, dppr_debug_query_ms also reports
+ * the device time of the last of these calls, first to last kernel. */
+#define DPPR_DEST_HOST 0
+#define DPPR_DEST_DEVICE 1
+#define DPPR_DENSE_P 0
+#define DPPR_DENSE_R 1
+#define DPPR_F64 0
+#define DPPR_F32 1
+#define DPPR_VERTEX_MAJOR 0 /* [V][n] */
+#define DPPR_SOURCE_MAJOR 1 /* [n][V] */
+int dppr_support(dppr_engine *e, int32_t slot, double min_p, int64_t *out_count);
+int dppr_group_support(dppr_engine *e, int32_t group, double min_p, int64_t *out_counts /* [n] */);
+int dppr_export_sparse(dppr_engine *e, int32_t slot, double min_p, int64_t cap, int dest, int64_t *out_offsets /* [2], HOST */,
+                       int32_t *out_ids, double *out_p, double *out_r /* may be NULL */);
+int dppr_group_export_sparse(dppr_engine *e, int32_t group, double min_p, int64_t cap, int dest,
+                             int64_t *out_offsets /* [n + 1], HOST */, int32_t *out_ids, double *out_p,
+                             double *out_r /* may be NULL */);
+int dppr_export_dense_dev(dppr_engine *e, int32_t slot, int which, int dtype, void *dst_device);
+int dppr_group_export_dense_dev(dppr_engine *e, int32_t group, int which, int dtype, int layout, void *dst_device);
+
 /* Windows whose sweep groups are all resident at once run a frontier loop of a source group as
  * multi-sweep launches (grid barrier between sweeps, row tables kept in LDS; dppr_multi.hpp). on by
  * default; 0 = one launch per sweep everywhere. The roll-call / time-out rules are those of
