@@ -46,6 +46,7 @@
 #include "dppr_wquery.hpp"
 #include "dppr_changes.hpp"
 #include "dppr_export.hpp"
+#include "dppr_dot.hpp"
 
 using namespace dppr;
 
@@ -1432,6 +1433,31 @@ int dppr_export_dense_dev(dppr_engine *e, int32_t slot, int which, int dtype, vo
 int dppr_group_export_dense_dev(dppr_engine *e, int32_t group, int which, int dtype, int layout, void *dst_device) {
     GET_GROUP(e, group);
     return export_dense_call(e, g.p, g.r, g.gw, g.n, which, dtype, layout, dst_device);
+}
+
+// ---- the state folded over the vertex axis: h . p for any seed distribution (dppr_dot.hpp, dppr_host_query.hpp) ------------
+int dppr_dot_dense_dev(dppr_engine *e, int32_t slot, int which, const void *h_device, int dtype, int h_layout, int32_t F, int dest,
+                       double *out) {
+    GET_SLOT(e, slot);
+    return dot_dense_call(e, s.p, s.r, 1, 1, which, h_device, dtype, h_layout, F, dest, out);
+}
+
+int dppr_group_dot_dense_dev(dppr_engine *e, int32_t group, int which, const void *h_device, int dtype, int h_layout, int32_t F,
+                             int dest, double *out) {
+    GET_GROUP(e, group);
+    return dot_dense_call(e, g.p, g.r, g.gw, g.n, which, h_device, dtype, h_layout, F, dest, out);
+}
+
+int dppr_dot_sparse(dppr_engine *e, int32_t slot, int which, const int64_t *offsets, const int32_t *ids, const double *w, int src,
+                    int32_t F, int dest, double *out) {
+    GET_SLOT(e, slot);
+    return dot_sparse_call(e, s.p, s.r, 1, 1, which, offsets, ids, w, src, F, dest, out);
+}
+
+int dppr_group_dot_sparse(dppr_engine *e, int32_t group, int which, const int64_t *offsets, const int32_t *ids, const double *w,
+                          int src, int32_t F, int dest, double *out) {
+    GET_GROUP(e, group);
+    return dot_sparse_call(e, g.p, g.r, g.gw, g.n, which, offsets, ids, w, src, F, dest, out);
 }
 
 int dppr_debug_query_ms(dppr_engine *e, float *out_ms) {

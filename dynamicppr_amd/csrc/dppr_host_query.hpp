@@ -1,7 +1,7 @@
 // dppr_host_query.hpp -- host side of the state queries (dppr_topk / dppr_group_topk / dppr_read_at / dppr_group_read_at, and
 // dppr_group_topk_weighted / dppr_group_score_at, dppr_mark / dppr_changes, dppr_support / dppr_export_sparse /
-// dppr_export_dense_dev and their group forms): workspace, the device copy of int2ext, the check of a caller's device pointer and
-// the launch sequences of dppr_topk.hpp, dppr_wquery.hpp, dppr_changes.hpp and dppr_export.hpp. Called with map_mu held, on the solver
+// dppr_export_dense_dev and their group forms, dppr_dot_dense_dev / dppr_dot_sparse and theirs): workspace, the device copy of int2ext, the check of a caller's device pointer and
+// the launch sequences of dppr_topk.hpp, dppr_wquery.hpp, dppr_changes.hpp, dppr_export.hpp and dppr_dot.hpp. Called with map_mu held, on the solver
 // stream; nothing here is reached from the update path.
 #pragma once
 
@@ -445,6 +445,157 @@ int export_dense_call(dppr_engine *e, const double *p, const double *r, int gw, 
         return fail(e, DPPR_ERR_INVALID, "export_dense_dev: dst must be aligned device memory of the engine's device, n x V elements inside one allocation");
     std::lock_guard<std::mutex> map_lk(e->map_mu);
     return run_export_dense(e, which == DPPR_DENSE_R ? r : p, gw, n, dtype, layout, dst);
+}
+
+// ---- the state folded over the vertex axis (dppr_dot.hpp, dppr_dot_plan.hpp) ----------------------------------------------------
+static_assert(DOT_LANES == GS_MAX && DOT_MAX_F == DPPR_DOT_MAX_F, "dppr_dot_plan.hpp restates GS_MAX and DPPR_DOT_MAX_F");
+static_assert(DOT_DEST_HOST == DPPR_DEST_HOST && DOT_DEST_DEVICE == DPPR_DEST_DEVICE && DOT_P == DPPR_DENSE_P && DOT_R == DPPR_DENSE_R &&
+                  DOT_F64 == DPPR_F64 && DOT_F32 == DPPR_F32 && DOT_FEATURE_MAJOR == DPPR_H_FEATURE_MAJOR &&
+                  DOT_VERTEX_MAJOR == DPPR_H_VERTEX_MAJOR,
+              "dppr_dot_plan.hpp restates the constants of include/dppr.h");
+
+// partials, the device input of a sparse call, the block and its pinned twin: in place before the first kernel
+int dot_workspace(dppr_engine *e, size_t part_elems, size_t in_bytes, size_t block_bytes) {
+    if (!e->dot_lds_set) { // (the widest dense pass stages more than the 64 KiB a kernel has without asking)
+        const int lds = (int)dot_lds_bytes(GS_MAX, DOT_FCHUNK);
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_dot_dense<double, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_dot_dense<double, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_dot_dense<float, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_dot_dense<float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        e->dot_lds_set = true;
+    }
+    part_elems = std::max<size_t>(part_elems, 1);
+    if (e->dot_part.capacity() >= part_elems && e->dot_in.capacity() >= in_bytes && e->dot_blk.capacity() >= block_bytes &&
+        e->dot_pin.capacity() >= block_bytes)
+        return DPPR_OK;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (e->dot_part.capacity() < part_elems) HIP_TRY(e->dot_part.regrow(part_elems));
+    if (e->dot_in.capacity() < in_bytes) HIP_TRY(e->dot_in.regrow(in_bytes));
+    if (e->dot_blk.capacity() < block_bytes) HIP_TRY(e->dot_blk.regrow(block_bytes));
+    if (e->dot_pin.capacity() < block_bytes) HIP_TRY(e->dot_pin.regrow(block_bytes));
+    return DPPR_OK;
+}
+
+// the end of both runs: one copy brings the head -- and a host destination's results -- back; a raised head is a rejected call
+int dot_finish(dppr_engine *e, size_t block_bytes, size_t out_bytes, int dest, double *out) {
+    if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[1], e->stream));
+    HIP_TRY(hipMemcpyAsync(e->dot_pin, e->dot_blk, block_bytes, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream)); // (a device destination is complete here: any stream of the caller may read it)
+    if (e->profiling) HIP_TRY(hipEventElapsedTime(&e->query_ms, e->evpool[0], e->evpool[1]));
+    if (reinterpret_cast<const DotHead *>(e->dot_pin.get())->bad) return fail(e, DPPR_ERR_INVALID, "dot_sparse: an id in device memory lies outside [0, V)");
+    if (dest == DPPR_DEST_HOST) memcpy(out, e->dot_pin + DOT_HEAD_BYTES, out_bytes);
+    return DPPR_OK;
+}
+
+// out[f][i] over dense h in the caller's device memory (arguments, h and a device destination validated by the caller)
+int run_dot_dense(dppr_engine *e, const double *x, int gw, int n, const void *h, int dtype, int layout, int F, int dest, double *out) {
+    HIP_TRY(hipSetDevice(e->device));
+    int rc = sync_map(e);
+    if (rc) return rc;
+    const int V = e->V;
+    const size_t blk_bytes = dot_block_bytes(F, n, dest), part_elems = dot_dense_part_elems(V, n, F);
+    rc = dot_workspace(e, part_elems, 0, blk_bytes);
+    if (rc) return rc;
+    DotHead *head = reinterpret_cast<DotHead *>(e->dot_blk.get());
+    double *d_out = dest == DPPR_DEST_HOST ? reinterpret_cast<double *>(e->dot_blk + DOT_HEAD_BYTES) : out;
+    const long long stride = dot_cols(V);
+    const int per_launch = dot_launch_features(V, n, F);
+    const int *x2i = e->d_ext2int.get();
+    if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[0], e->stream));
+    HIP_TRY(hipMemsetAsync(head, 0, DOT_HEAD_BYTES, e->stream));
+    HIP_TRY(hipMemsetAsync(e->dot_part, 0, sizeof(double) * part_elems, e->stream)); // (+0.0: the tiles of padding)
+    for (int f0 = 0; f0 < F; f0 += per_launch) {
+        const int f1 = std::min(F, f0 + per_launch), fcm = std::min(DOT_FCHUNK, f1 - f0);
+        const dim3 grid((unsigned)std::min<int64_t>(dot_tiles(V), 2048), (unsigned)((f1 - f0 + DOT_FCHUNK - 1) / DOT_FCHUNK)), block(DOT_TILE);
+        const size_t lds = dot_lds_bytes(gw, fcm);
+        const bool vm = layout == DPPR_H_VERTEX_MAJOR;
+        if (dtype == DPPR_F32) {
+            const float *hf = static_cast<const float *>(h);
+            if (vm) hipLaunchKernelGGL((k_dot_dense<float, true>), grid, block, lds, e->stream, x, gw, n, x2i, V, hf, F, f0, f1, fcm, e->dot_part.get(), stride);
+            else hipLaunchKernelGGL((k_dot_dense<float, false>), grid, block, lds, e->stream, x, gw, n, x2i, V, hf, F, f0, f1, fcm, e->dot_part.get(), stride);
+        } else {
+            const double *hd = static_cast<const double *>(h);
+            if (vm) hipLaunchKernelGGL((k_dot_dense<double, true>), grid, block, lds, e->stream, x, gw, n, x2i, V, hd, F, f0, f1, fcm, e->dot_part.get(), stride);
+            else hipLaunchKernelGGL((k_dot_dense<double, false>), grid, block, lds, e->stream, x, gw, n, x2i, V, hd, F, f0, f1, fcm, e->dot_part.get(), stride);
+        }
+        const int nout = (f1 - f0) * n;
+        hipLaunchKernelGGL(k_dot_combine, dim3((nout + DOT_CB_WAVES - 1) / DOT_CB_WAVES), dim3(DOT_CB_WAVES * WAVE), 0, e->stream,
+                           e->dot_part.get(), (const long long *)nullptr, stride, nout, n, head, d_out + (size_t)f0 * n);
+        HIP_TRY(hipGetLastError());
+    }
+    return dot_finish(e, blk_bytes, dot_out_bytes(F, n), dest, out);
+}
+
+// out[f][i] over the CSR of F queries (arguments, host ids, device ids' / w's range and a device destination validated by the caller)
+int run_dot_sparse(dppr_engine *e, const double *x, int gw, int n, const int64_t *offsets, const int32_t *ids, const double *w, int src,
+                   int F, int dest, double *out) {
+    HIP_TRY(hipSetDevice(e->device));
+    int rc = sync_map(e);
+    if (rc) return rc;
+    const bool host_src = src == DPPR_DEST_HOST;
+    const int64_t m = offsets[F];
+    dot_tile_table(offsets, F, e->dot_tb);
+    const long long n_tiles = (long long)e->dot_tb.tiles.size(), cols = e->dot_tb.cols();
+    const DotSparseWork wk = dot_sparse_work(n_tiles, F, m, host_src);
+    const size_t blk_bytes = dot_block_bytes(F, n, dest), part_elems = std::max<size_t>((size_t)cols * (size_t)n, 1);
+    rc = dot_workspace(e, part_elems, wk.bytes, blk_bytes);
+    if (rc) return rc;
+    unsigned char *in = e->dot_in.get();
+    DotTile *d_tiles = reinterpret_cast<DotTile *>(in);
+    long long *d_col = reinterpret_cast<long long *>(in + wk.off_col);
+    const int *d_ids = host_src ? reinterpret_cast<const int *>(in + wk.off_ids) : ids;
+    const double *d_w = host_src ? reinterpret_cast<const double *>(in + wk.off_w) : w;
+    DotHead *head = reinterpret_cast<DotHead *>(e->dot_blk.get());
+    double *d_out = dest == DPPR_DEST_HOST ? reinterpret_cast<double *>(e->dot_blk + DOT_HEAD_BYTES) : out;
+    if (n_tiles > 0) HIP_TRY(hipMemcpyAsync(d_tiles, e->dot_tb.tiles.data(), sizeof(DotTile) * (size_t)n_tiles, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(d_col, e->dot_tb.col.data(), sizeof(long long) * ((size_t)F + 1), hipMemcpyHostToDevice, e->stream));
+    if (host_src && m > 0) {
+        HIP_TRY(hipMemcpyAsync(in + wk.off_ids, ids, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(in + wk.off_w, w, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, e->stream));
+    }
+    if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[0], e->stream));
+    HIP_TRY(hipMemsetAsync(head, 0, DOT_HEAD_BYTES, e->stream));
+    HIP_TRY(hipMemsetAsync(e->dot_part, 0, sizeof(double) * part_elems, e->stream)); // (+0.0: the tiles of padding)
+    if (n_tiles > 0)
+        hipLaunchKernelGGL(k_dot_sparse, dim3((unsigned)std::min<long long>(n_tiles, 2048)), dim3(DOT_TILE), dot_lds_bytes(gw, 1), e->stream, x,
+                           gw, n, e->d_ext2int.get(), e->V, d_ids, d_w, d_tiles, n_tiles, head, e->dot_part.get(), cols);
+    const int nout = F * n;
+    hipLaunchKernelGGL(k_dot_combine, dim3((nout + DOT_CB_WAVES - 1) / DOT_CB_WAVES), dim3(DOT_CB_WAVES * WAVE), 0, e->stream,
+                       e->dot_part.get(), (const long long *)d_col, cols, nout, n, head, d_out);
+    HIP_TRY(hipGetLastError());
+    return dot_finish(e, blk_bytes, dot_out_bytes(F, n), dest, out);
+}
+
+// What the four entry points share: the checks that need no device, those of the device pointers, the id-map lock, the run.
+int dot_dense_call(dppr_engine *e, const double *p, const double *r, int gw, int n, int which, const void *h, int dtype, int layout,
+                   int F, int dest, double *out) {
+    if (!dot_dense_args_ok(which, h, dtype, layout, F, dest, out))
+        return fail(e, DPPR_ERR_INVALID, "dot_dense_dev: which 0 or 1, dtype 0 or 1, h_layout 0 or 1, F in [1, DPPR_DOT_MAX_F], dest 0 or 1, non-null h / out");
+    HIP_TRY(hipSetDevice(e->device));
+    if (!ex_dev_dest_ok(e, h, dot_dense_h_bytes(dtype, F, e->V), dot_elem_bytes(dtype)))
+        return fail(e, DPPR_ERR_INVALID, "dot_dense_dev: h must be aligned device memory of the engine's device, F x V elements inside one allocation");
+    if (dest == DPPR_DEST_DEVICE && !ex_dev_dest_ok(e, out, dot_out_bytes(F, n), sizeof(double)))
+        return fail(e, DPPR_ERR_INVALID, "dot_dense_dev: out must be aligned device memory of the engine's device, F x n doubles inside one allocation");
+    std::lock_guard<std::mutex> map_lk(e->map_mu); // (as dppr_read)
+    return run_dot_dense(e, which == DPPR_DENSE_R ? r : p, gw, n, h, dtype, layout, F, dest, out);
+}
+
+int dot_sparse_call(dppr_engine *e, const double *p, const double *r, int gw, int n, int which, const int64_t *offsets, const int32_t *ids,
+                    const double *w, int src, int F, int dest, double *out) {
+    if (!dot_sparse_args_ok(which, offsets, ids, w, src, F, dest, out))
+        return fail(e, DPPR_ERR_INVALID, "dot_sparse: which 0 or 1, src 0 or 1, F in [1, DPPR_DOT_MAX_F], dest 0 or 1, non-null ids / w / out, offsets[0] = 0 and non-decreasing");
+    HIP_TRY(hipSetDevice(e->device));
+    const int64_t m = offsets[F];
+    if (src == DPPR_DEST_DEVICE) {
+        if (!ex_dev_dest_ok(e, ids, sizeof(int32_t) * (size_t)m, sizeof(int32_t)) || !ex_dev_dest_ok(e, w, sizeof(double) * (size_t)m, sizeof(double)))
+            return fail(e, DPPR_ERR_INVALID, "dot_sparse: ids / w must be aligned device memory of the engine's device, offsets[F] entries inside one allocation");
+    } else if (!dot_ids_ok(ids, m, e->V)) {
+        return fail(e, DPPR_ERR_INVALID, "dot_sparse: ids in [0, V)");
+    }
+    if (dest == DPPR_DEST_DEVICE && !ex_dev_dest_ok(e, out, dot_out_bytes(F, n), sizeof(double)))
+        return fail(e, DPPR_ERR_INVALID, "dot_sparse: out must be aligned device memory of the engine's device, F x n doubles inside one allocation");
+    std::lock_guard<std::mutex> map_lk(e->map_mu);
+    return run_dot_sparse(e, which == DPPR_DENSE_R ? r : p, gw, n, offsets, ids, w, src, F, dest, out);
 }
 
 } // namespace

@@ -349,7 +349,13 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     DevBuf<int> ex_cnt;             // [tiles][16] qualifying ids per tile and lane
     DevBuf<long long> ex_base;      // [tiles][16] first output position of a tile's entries of a lane
     DevBuf<unsigned char> ex_blk; PinBuf<unsigned char> ex_pin; // head (offsets, go), then ids / p / r of a host destination: device / pinned host
-    float query_ms = -1.0f;         // dppr_set_profiling: device time of the last top-k, changes or export call, first to last kernel (dppr_debug_query_ms)
+    // the state folded over the vertex axis (dppr_dot.hpp, dppr_dot_plan.hpp), allocated on the first such call and grown on demand
+    DevBuf<double> dot_part;        // one partial per (tile, output), output-major
+    DevBuf<unsigned char> dot_in;   // a sparse call: its tile table and columns, and the ids / w of a host source
+    DevBuf<unsigned char> dot_blk; PinBuf<unsigned char> dot_pin; // head (the flag), then the results of a host destination: device / pinned host
+    dppr::DotTable dot_tb;          // host side of the tile table (kept for its capacity)
+    bool dot_lds_set = false;       // the dense pass was given its dynamic LDS limit
+    float query_ms = -1.0f;         // dppr_set_profiling: device time of the last top-k, changes, export or dot call, first to last kernel (dppr_debug_query_ms)
     std::vector<int32_t> h_tmp1, h_tmp2;
     std::vector<int32_t> h_tiles; // host copy of the tile edge prefix / group table
     int max_iters = 1 << 20;

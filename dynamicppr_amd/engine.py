@@ -66,12 +66,15 @@ EXPORTS = [
     "dppr_mark", "dppr_group_mark", "dppr_unmark", "dppr_group_unmark", "dppr_changes", "dppr_group_changes",
     "dppr_support", "dppr_group_support", "dppr_export_sparse", "dppr_group_export_sparse", "dppr_export_dense_dev",
     "dppr_group_export_dense_dev",
+    "dppr_dot_dense_dev", "dppr_group_dot_dense_dev", "dppr_dot_sparse", "dppr_group_dot_sparse",
 ]
 
 DEST_HOST, DEST_DEVICE = 0, 1
 DENSE_P, DENSE_R = 0, 1
 F64, F32 = 0, 1
 VERTEX_MAJOR, SOURCE_MAJOR = 0, 1
+DOT_MAX_F = 4096
+H_FEATURE_MAJOR, H_VERTEX_MAJOR = 0, 1
 
 
 def lib():
@@ -176,6 +179,10 @@ def lib():
     L.dppr_group_export_sparse.argtypes = [vp, C.c_int32, C.c_double, C.c_int64, C.c_int, i64p, vp, vp, vp]
     L.dppr_export_dense_dev.argtypes = [vp, C.c_int32, C.c_int, C.c_int, vp]
     L.dppr_group_export_dense_dev.argtypes = [vp, C.c_int32, C.c_int, C.c_int, C.c_int, vp]
+    L.dppr_dot_dense_dev.argtypes = [vp, C.c_int32, C.c_int, vp, C.c_int, C.c_int, C.c_int32, C.c_int, vp]
+    L.dppr_group_dot_dense_dev.argtypes = [vp, C.c_int32, C.c_int, vp, C.c_int, C.c_int, C.c_int32, C.c_int, vp]
+    L.dppr_dot_sparse.argtypes = [vp, C.c_int32, C.c_int, i64p, vp, vp, C.c_int, C.c_int32, C.c_int, vp]
+    L.dppr_group_dot_sparse.argtypes = [vp, C.c_int32, C.c_int, i64p, vp, vp, C.c_int, C.c_int32, C.c_int, vp]
     for name in EXPORTS:
         if name not in ("dppr_strerror", "dppr_last_error", "dppr_destroy", "dppr_build_id", "dppr_heartbeat"):
             getattr(L, name).restype = C.c_int
@@ -667,6 +674,63 @@ class Engine:
         """p (or r) of every source of the group by external id, [V][n] or [n][V] elements of `dtype`, into device memory at dst_ptr."""
         self._ck(self._L.dppr_group_export_dense_dev(self._h, int(group), int(which), int(dtype), int(layout), dst_ptr or None),
                  "group_export_dense_dev")
+
+    # ---- the sources scored under a seed distribution: h . p over the vertex axis ----
+    def dot_dense_dev(self, slot, h_ptr, F, which=DENSE_P, dtype=F64, layout=H_FEATURE_MAJOR, out_ptr=None):
+        """dppr_dot_dense_dev: h ([F][V] or [V][F] elements of `dtype`) in device memory at the raw address h_ptr. The scores [F]
+        as a numpy array, or, with out_ptr (a raw device address of F doubles), written there (returns None)."""
+        return self._dot_dense(self._L.dppr_dot_dense_dev, slot, 1, h_ptr, F, which, dtype, layout, out_ptr, True, "dot_dense_dev")
+
+    def group_dot_dense_dev(self, group, h_ptr, F, which=DENSE_P, dtype=F64, layout=H_FEATURE_MAJOR, out_ptr=None):
+        """dppr_group_dot_dense_dev: the scores [F][n] of every source of the group, as dot_dense_dev."""
+        return self._dot_dense(self._L.dppr_group_dot_dense_dev, group, self._group_n.get(group, 1), h_ptr, F, which, dtype, layout,
+                               out_ptr, False, "group_dot_dense_dev")
+
+    def _dot_dense(self, fn, handle, n, h_ptr, F, which, dtype, layout, out_ptr, flat, what):
+        if out_ptr is not None:
+            self._ck(fn(self._h, int(handle), int(which), h_ptr or None, int(dtype), int(layout), int(F), DEST_DEVICE, out_ptr or None), what)
+            return None
+        out = np.empty((max(int(F), 0), n), dtype=np.float64)
+        self._ck(fn(self._h, int(handle), int(which), h_ptr or None, int(dtype), int(layout), int(F), DEST_HOST, out.ctypes.data), what)
+        return out[:, 0] if flat else out
+
+    def dot_sparse(self, slot, offsets, ids, w, which=DENSE_P, out_ptr=None):
+        """dppr_dot_sparse over a CSR of seed sets in host memory (offsets [F + 1], external ids, weights): the scores [F], or, with
+        out_ptr (a raw device address of F doubles), written there (returns None)."""
+        return self._dot_sparse(self._L.dppr_dot_sparse, slot, 1, offsets, ids, w, which, out_ptr, True, "dot_sparse")
+
+    def group_dot_sparse(self, group, offsets, ids, w, which=DENSE_P, out_ptr=None):
+        """dppr_group_dot_sparse: the scores [F][n] of every source of the group, as dot_sparse."""
+        return self._dot_sparse(self._L.dppr_group_dot_sparse, group, self._group_n.get(group, 1), offsets, ids, w, which, out_ptr, False,
+                                "group_dot_sparse")
+
+    def dot_sparse_dev(self, slot, offsets, ids_ptr, w_ptr, which=DENSE_P, out_ptr=None):
+        """dot_sparse with ids (int32) and w (f64) in device memory at raw addresses; the offsets stay a host array."""
+        return self._dot_sparse(self._L.dppr_dot_sparse, slot, 1, offsets, ids_ptr, w_ptr, which, out_ptr, True, "dot_sparse_dev", DEST_DEVICE)
+
+    def group_dot_sparse_dev(self, group, offsets, ids_ptr, w_ptr, which=DENSE_P, out_ptr=None):
+        """group_dot_sparse with ids (int32) and w (f64) in device memory at raw addresses; the offsets stay a host array."""
+        return self._dot_sparse(self._L.dppr_group_dot_sparse, group, self._group_n.get(group, 1), offsets, ids_ptr, w_ptr, which, out_ptr,
+                                False, "group_dot_sparse_dev", DEST_DEVICE)
+
+    def _dot_sparse(self, fn, handle, n, offsets, ids, w, which, out_ptr, flat, what, src=DEST_HOST):
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        F = len(off) - 1
+        if src == DEST_HOST:
+            ids = np.ascontiguousarray(ids, dtype=np.int32)
+            w = np.ascontiguousarray(w, dtype=np.float64)
+            if len(off) == 0 or len(ids) != len(w) or len(ids) < int(off[-1]):
+                raise DpprError(f"{what}: offsets [F + 1]; ids and w must hold offsets[F] entries each")
+            ids_ptr, w_ptr = ids.ctypes.data, w.ctypes.data  # (ids and w stay alive until the call returns)
+        else:
+            ids_ptr, w_ptr = ids or None, w or None
+        offp = off.ctypes.data_as(C.POINTER(C.c_int64))
+        if out_ptr is not None:
+            self._ck(fn(self._h, int(handle), int(which), offp, ids_ptr, w_ptr, int(src), F, DEST_DEVICE, out_ptr or None), what)
+            return None
+        out = np.empty((max(F, 0), n), dtype=np.float64)
+        self._ck(fn(self._h, int(handle), int(which), offp, ids_ptr, w_ptr, int(src), F, DEST_HOST, out.ctypes.data), what)
+        return out[:, 0] if flat else out
 
     def query_ms(self):
         """With set_profiling on: device ms of the last top-k, changes or export call, first to last kernel (dppr_debug_query_ms)."""

@@ -3,11 +3,15 @@
 // of an out-of-bounds read (util/CommandLine.h:52-55), and -a is range-checked exactly.
 #pragma once
 
+#include <cerrno>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <iostream>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -60,6 +64,36 @@ inline std::vector<double> parse_weights(const char *v) {
         p = end + 1;
     }
 }
+// --seeds: every line of `path` is one seed set `id[:weight] id[:weight] ...` (weight 1 where none is given; a blank line is an
+// empty set). false: unreadable, no line at all, or a token that is not a non-negative id with an optional finite weight.
+inline bool load_seeds(const char *path, std::vector<int64_t> &off, std::vector<int32_t> &ids, std::vector<double> &w) {
+    std::ifstream in(path);
+    if (!in) return false;
+    off.assign(1, 0);
+    ids.clear();
+    w.clear();
+    std::string line, tok;
+    while (std::getline(in, line)) {
+        std::istringstream ls(line);
+        while (ls >> tok) {
+            char *end = nullptr;
+            errno = 0;
+            const long long id = std::strtoll(tok.c_str(), &end, 10);
+            if (end == tok.c_str() || errno || id < 0 || id > INT32_MAX) return false;
+            double weight = 1.0;
+            if (*end == ':') {
+                const char *ws = end + 1;
+                weight = std::strtod(ws, &end);
+                if (end == ws || !std::isfinite(weight)) return false;
+            }
+            if (*end != '\0') return false;
+            ids.push_back((int32_t)id);
+            w.push_back(weight);
+        }
+        off.push_back((int64_t)ids.size());
+    }
+    return off.size() > 1;
+}
 } // namespace args_detail
 
 inline void PrintUsage() {
@@ -84,6 +118,9 @@ inline void PrintUsage() {
               << "--sparse-min <P> [--sparse-out <file>]: after the last batch print, per source in source order, the number of vertices\n"
               << "            with pagerank > P (P >= 0): support <source> <count>; with --sparse-out also write them to <file>,\n"
               << "            one line each, by source then vertex id: <source> <vertex> <pagerank>\n"
+              << "--seeds <file>: every line of <file> is one seed set `id[:weight] id[:weight] ...` (weight 1 by default, ids in [0, V));\n"
+              << "            after the last batch print, per line (from 1) and per source in source order, the source's PPR under that seed\n"
+              << "            distribution, sum_v weight[v] * pagerank_source[v]: seedscore <line> <source> <score>\n"
               << "--validate: residual bound + power-iteration check after every solve\n"
               << "--split: drive each batch through IncrementalBatchUpdate/ExecuteMainLoop(0)/(1)\n"
               << "--sync: synchronous (deterministic) push schedule\n"
@@ -125,6 +162,7 @@ inline void ArgumentsChecker() {
     if (gTopK < 0 || gTopK > DPPR_TOPK_MAX) ok = false;
     if (gChangesK < 0 || gChangesK > DPPR_TOPK_MAX || !(gChangesMin >= 0.0) || (gChangesMinGiven && gChangesK == 0)) ok = false;
     if ((gSparseGiven && !(gSparseMin >= 0.0)) || (!gSparseOut.empty() && !gSparseGiven)) ok = false;
+    if (gSeedsBad) ok = false;
     if (gTopKWeightsGiven && (gTopK == 0 || gTopKWeights.empty())) ok = false; // (the count is checked against the sources in main)
     if (!ok) {
         std::cout << "invalid arguments" << std::endl;
@@ -163,6 +201,10 @@ inline void ArgumentsParser(int argc, char **argv) {
     gSparseGiven = find(argc, argv, "--sparse-min") != nullptr;
     gSparseMin = as_double(argc, argv, "--sparse-min", 0.0);
     if (const char *f = find(argc, argv, "--sparse-out")) gSparseOut = f;
+    if (const char *f = find(argc, argv, "--seeds")) {
+        gSeedsFile = f;
+        gSeedsBad = !load_seeds(f, gSeedOff, gSeedIds, gSeedW);
+    }
     gValidate = has(argc, argv, "--validate");
     gSplitInterface = has(argc, argv, "--split");
     gSchedule = has(argc, argv, "--sync") ? 1 : 0;

@@ -49,6 +49,11 @@ inline bool gSparseGiven = false;     // --sparse-min P : after the last batch p
 inline double gSparseMin = 0.0;
 inline std::string gSparseOut;        // --sparse-out FILE : ... and write them, one text line `source id pagerank` each, by source then id
 inline bool gChangesMinGiven = false;
+inline std::string gSeedsFile;        // --seeds FILE : every line one seed set `id[:weight] ...`; after the last batch print seedscore <line> <source> <score>
+inline bool gSeedsBad = false;        //   FILE could not be read, holds no line, or a token is not id[:weight] with id >= 0
+inline std::vector<int64_t> gSeedOff; //   the seed sets as one CSR over the lines: offsets [lines + 1], external ids, weights
+inline std::vector<int32_t> gSeedIds;
+inline std::vector<double> gSeedW;
 inline bool gValidate = false;        // --validate : the reference's -DVALIDATE checks at run time
 inline bool gShareDevice = false;     // --share-device (or DPPR_DEVICE_ALIAS=1): the -g N device threads share the devices that exist (d % count)
 inline bool gPushOnly = false;        // --push-only : no pull sweeps (the ablation of the -o variants times their push mechanisms)

@@ -67,6 +67,13 @@ int main(int argc, char *argv[]) {
             }
         }
         graphs[(size_t)d].reset(new SlidingGraphVec(gDataFileName, gIsDirected != 0));
+        if (d == 0) // --seeds: an id the graph does not have is an argument error, found before any device work
+            for (int32_t v : gSeedIds)
+                if (v >= (int32_t)graphs[0]->vertex_count) {
+                    std::cout << "invalid arguments" << std::endl;
+                    PrintUsage();
+                    return -1;
+                }
         drivers[(size_t)d].reset(new PPRRevPushGPU(graphs[(size_t)d].get(), present ? d % present : d, mine, /*quiet=*/d != 0 && ngpu > 1));
     }
     // DPPR_WATCHDOG_S=<seconds>: a thread that ends the process -- after printing dppr_debug_dump of every engine -- when no
@@ -173,6 +180,17 @@ int main(int argc, char *argv[]) {
                 for (size_t t = 0; t < v.ids.size(); ++t) std::fprintf(f, "%d %d %.17g\n", (int)sources[j], (int)v.ids[t], v.p[t]);
         }
         if (f) std::fclose(f);
+        std::cout << std::flush;
+    }
+    if (!gSeedsFile.empty()) { // (not a line of the reference) as --topk: source j is device j % ngpu's source j / ngpu
+        std::vector<std::vector<std::vector<double>>> score((size_t)ngpu);
+        for (int d = 0; d < ngpu; ++d) score[(size_t)d] = drivers[(size_t)d]->SeedScores(gSeedOff, gSeedIds, gSeedW);
+        char line[160];
+        for (size_t l = 0; l + 1 < gSeedOff.size(); ++l)
+            for (size_t j = 0; j < sources.size(); ++j) {
+                std::snprintf(line, sizeof(line), "seedscore %zu %d %.17g", l + 1, (int)sources[j], score[j % (size_t)ngpu][j / (size_t)ngpu][l]);
+                std::cout << line << "\n";
+            }
         std::cout << std::flush;
     }
     if (!gDumpPath.empty())

@@ -489,6 +489,35 @@ public:
         return out;
     }
 
+    // --seeds: the score of every source of this device under every seed set (one CSR over the lines, host memory), through the
+    // device-side fold (dppr_dot_sparse / dppr_group_dot_sparse), DPPR_DOT_MAX_F lines a call: [source of this device][line]
+    std::vector<std::vector<double>> SeedScores(const std::vector<int64_t> &off, const std::vector<int32_t> &ids, const std::vector<double> &w) {
+        const size_t n_src = source_vertex_ids.size(), lines = off.size() - 1;
+        std::vector<std::vector<double>> out(n_src, std::vector<double>(lines, 0.0));
+        const int32_t none_id = 0;
+        const double none_w = 0.0;
+        std::vector<int64_t> rel;
+        std::vector<double> res;
+        for (size_t first = 0; first < n_src; first += use_groups ? kGroupMax : 1) {
+            const size_t n = use_groups ? std::min(kGroupMax, n_src - first) : 1;
+            for (size_t l0 = 0; l0 < lines; l0 += DPPR_DOT_MAX_F) {
+                const size_t F = std::min<size_t>(DPPR_DOT_MAX_F, lines - l0);
+                rel.resize(F + 1);
+                for (size_t f = 0; f <= F; ++f) rel[f] = off[l0 + f] - off[l0];
+                const int32_t *pi = ids.empty() ? &none_id : ids.data() + off[l0]; // (a file of blank lines: no entry, and no NULL)
+                const double *pw = w.empty() ? &none_w : w.data() + off[l0];
+                res.assign(F * n, 0.0);
+                if (use_groups)
+                    DPPR_CHECK(engine, dppr_group_dot_sparse(engine, groups[first / kGroupMax], DPPR_DENSE_P, rel.data(), pi, pw, DPPR_DEST_HOST, (int32_t)F, DPPR_DEST_HOST, res.data()));
+                else
+                    DPPR_CHECK(engine, dppr_dot_sparse(engine, slots[first], DPPR_DENSE_P, rel.data(), pi, pw, DPPR_DEST_HOST, (int32_t)F, DPPR_DEST_HOST, res.data()));
+                for (size_t f = 0; f < F; ++f)
+                    for (size_t j = 0; j < n; ++j) out[first + j][l0 + f] = res[f * n + j];
+            }
+        }
+        return out;
+    }
+
     // --changes: what batch `batch` (from 1) moved, per source of this device in this device's source order, and the new mark in the
     // same pass (dppr_changes / dppr_group_changes with remark = 1). Outside the timed region: ppr_time is the hipEvent time the
     // update calls return. One device's lines of a batch are printed as one block (-g N: the device threads take turns).

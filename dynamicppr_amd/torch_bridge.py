@@ -92,3 +92,46 @@ def group_dense(engine, gid, which="p", dtype=torch.float64, layout="source_majo
     torch.cuda.synchronize(out.device)
     engine.group_export_dense_dev(gid, out.data_ptr(), _WHICH[which], _DTYPES[dtype], _LAYOUTS[layout])
     return out
+
+
+_H_LAYOUTS = {"feature_major": _eng.H_FEATURE_MAJOR, "vertex_major": _eng.H_VERTEX_MAJOR}
+
+
+def group_dot(engine, gid, H, which="p", layout="feature_major"):
+    """The sources of group `gid` scored under F seed distributions (dppr_group_dot_dense_dev / dppr_group_dot_sparse): a float64
+    tensor [F, n] on the engine's device, written in place. H is a dense float64 / float32 tensor on the engine's device, [F, V]
+    (feature_major) or [V, F] (vertex_major), or a torch.sparse_csr_tensor of shape [F, V] with int32 col_indices and float64
+    values there (its crow_indices go to the host as the offsets). Anything else raises DpprError."""
+    if not isinstance(H, torch.Tensor) or which not in _WHICH or layout not in _H_LAYOUTS:
+        raise _eng.DpprError(f"group_dot: H a tensor, which in {sorted(_WHICH)}, layout in {sorted(_H_LAYOUTS)}")
+    dev = _device(engine)
+    n = len(engine.group_sources(gid))
+    if H.layout == torch.sparse_csr:
+        crow, col, val = H.crow_indices(), H.col_indices(), H.values()
+        if H.dim() != 2 or H.shape[1] != engine.V or not 1 <= H.shape[0] <= _eng.DOT_MAX_F:
+            raise _eng.DpprError(f"group_dot: a sparse H is [F, V] with 1 <= F <= {_eng.DOT_MAX_F} and V = {engine.V}, not {tuple(H.shape)}")
+        if col.dtype != torch.int32 or val.dtype != torch.float64:
+            raise _eng.DpprError(f"group_dot: a sparse H has int32 col_indices and float64 values, not {col.dtype} / {val.dtype}")
+        if col.device != dev or val.device != dev:
+            raise _eng.DpprError(f"group_dot: H must be on the engine's device {dev}, not {col.device}")
+        col, val = col.contiguous(), val.contiguous()
+        off = crow.to("cpu", torch.int64).numpy()
+        out = torch.empty((H.shape[0], n), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)   # (H and out are torch's; nothing of torch's is in flight on them when the engine reads and writes)
+        engine.group_dot_sparse_dev(gid, off, col.data_ptr(), val.data_ptr(), _WHICH[which], out_ptr=out.data_ptr())
+        return out
+    if H.layout != torch.strided or H.dtype not in _DTYPES:
+        raise _eng.DpprError(f"group_dot: H is dense float64 / float32 or sparse CSR, not {H.layout} of {H.dtype}")
+    if H.device != dev:
+        raise _eng.DpprError(f"group_dot: H must be on the engine's device {dev}, not {H.device}")
+    vdim = 1 if layout == "feature_major" else 0   # (the axis of the vertices)
+    if H.dim() != 2 or H.shape[vdim] != engine.V:
+        raise _eng.DpprError(f"group_dot: a {layout} H is {'[F, V]' if vdim else '[V, F]'} with V = {engine.V}, not {tuple(H.shape)}")
+    F = H.shape[1 - vdim]
+    if not 1 <= F <= _eng.DOT_MAX_F:
+        raise _eng.DpprError(f"group_dot: 1 <= F <= {_eng.DOT_MAX_F}, not {F}")
+    H = H.contiguous()
+    out = torch.empty((F, n), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize(dev)
+    engine.group_dot_dense_dev(gid, H.data_ptr(), F, _WHICH[which], _DTYPES[H.dtype], _H_LAYOUTS[layout], out_ptr=out.data_ptr())
+    return out

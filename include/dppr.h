@@ -553,6 +553,63 @@ int dppr_group_export_sparse(dppr_engine *e, int32_t group, double min_p, int64_
 int dppr_export_dense_dev(dppr_engine *e, int32_t slot, int which, int dtype, void *dst_device);
 int dppr_group_export_dense_dev(dppr_engine *e, int32_t group, int which, int dtype, int layout, void *dst_device);
 
+/* ---- the sources scored under any seed distribution: h . p over the vertex axis (backward-compatible additions, ABI 6) ----
+ * p_i[v] approximates pi_v(s_i), the PPR a walk started at v gives to the tracked source s_i, and PPR is linear in the start
+ * distribution: for a seed distribution h over the vertices, pi_h(s_i) = sum_v h[v] pi_v(s_i) ~ sum_v h[v] p_i[v], with an error
+ * of at most max|r_i| * |h|_1. One dot product scores a tracked source under any personalisation (a follow set, a set of
+ * flagged accounts, a column of a feature matrix) without leaving the device: this is the dual of dppr_group_topk_weighted,
+ * which folds over the sources.
+ *
+ *     out[f][i] = fold_j ( h_f[slot j] (x) x_i[vertex of slot j] )        f in [0, F), i in [0, n); out is [F][n], a slot is n = 1
+ * x_i[v] is p_i[v] (DPPR_DENSE_P) or r_i[v] (DPPR_DENSE_R) by EXTERNAL id, exactly what dppr_group_read returns, +0.0 for a
+ * vertex without a row. The padding lane of an odd group never reaches a result.
+ *
+ * THE FOLD. The result is a function of the state and of h alone: equal on every run, and reproducible bit for bit.
+ * Slots.  Dense: slot j is external id j, j = 0 .. V - 1; h is [F][V] (DPPR_H_FEATURE_MAJOR) or [V][F] (DPPR_H_VERTEX_MAJOR) in
+ *         DEVICE memory of the caller, DPPR_F64 or DPPR_F32 (f32 is widened to f64, exactly, before anything else).
+ *         Sparse: one CSR over the F queries; slot j of query f is its j-th entry, at offsets[f] + j: external id ids[..],
+ *         weight w[..]. Ids may repeat and come in any order; every occurrence is a slot of its own.
+ * Term.   t_j = h_j * x_i[v_j], rounded to double, never fused with an addition. The product is computed even where x is +0.0
+ *         for want of a row: a negative h gives -0.0 there.
+ * Block.  Slots are taken in blocks of 2^16 consecutive slots, the last one padded with +0.0. A block is summed by the
+ *         balanced binary tree that adds neighbours: level 1 is t_{2j} + t_{2j+1}, level 2 adds neighbouring level-1 sums, and
+ *         so on for 16 levels, every sum rounded to double. Padding is added as +0.0 (-0.0 + +0.0 = +0.0).
+ * Blocks. acc = B_0, then acc = acc + B_b for b = 1, 2, .. in ascending order. A query without slots is +0.0.
+ * The order does not depend on grid size, on F, on n or on any internal chunking. In numpy, over terms t[..., slots]:
+ *         pad to whole blocks, reshape to [..., blocks, 65536], y = y[..., 0::2] + y[..., 1::2] until one column is left, then
+ *         add the columns from left to right.
+ * A one-hot h therefore returns x_i[v] bit for bit. Non-finite h is outside this contract: IEEE arithmetic decides.
+ *
+ * Sparse offsets [F + 1] are always HOST memory: int64, offsets[0] = 0, non-decreasing. ids and w lie where `src` says
+ * (DPPR_DEST_HOST or DPPR_DEST_DEVICE); out lies where `dest` says. For DPPR_DEST_DEVICE the call returns after the solver
+ * stream has finished writing, so any stream of the caller may read afterwards.
+ *
+ * Rejected with DPPR_ERR_INVALID, nothing written and nothing read through a bad pointer: F outside [1, DPPR_DOT_MAX_F];
+ * which / dtype / h_layout / src / dest outside its values; a NULL pointer; offsets that do not begin at 0 or decrease; a
+ * pointer given as device memory (h, ids / w with src = DPPR_DEST_DEVICE, out with dest = DPPR_DEST_DEVICE) that is not device
+ * memory of the ENGINE'S device, whose needed bytes (F * V elements; offsets[F] entries; F * n doubles) do not lie wholly
+ * inside one allocation, or that is not aligned to its element; a sparse id outside [0, V) -- ids in host memory are checked
+ * before any device work, ids in device memory by the kernel that gathers them, which then keeps the result from being
+ * written: either way the call returns DPPR_ERR_INVALID with out untouched; a bad slot / group.
+ *
+ * Threading and stream as dppr_export_dense_dev: the id-map lock of dppr_read, the solver stream, any state, live and parked
+ * zone, never part of the update path or of a timed region. Work space: at most 1 byte per external id and 16 features of a
+ * launch (64 MiB at the most: a launch takes fewer features instead), 8 n bytes per 2048 entries of a sparse call plus the ids
+ * and weights of a host source, and the block of a host destination (8 F n bytes, device and pinned host); all of it is the
+ * engine's, obtained before the first kernel, grown on demand and released with the engine. With dppr_set_profiling on,
+ * dppr_debug_query_ms also reports the device time of the last of these calls, first to last kernel. */
+#define DPPR_DOT_MAX_F 4096
+#define DPPR_H_FEATURE_MAJOR 0 /* h[f][v], F rows of V */
+#define DPPR_H_VERTEX_MAJOR 1  /* h[v][f], V rows of F */
+int dppr_dot_dense_dev(dppr_engine *e, int32_t slot, int which, const void *h_device, int dtype, int h_layout, int32_t F, int dest,
+                       double *out /* [F] */);
+int dppr_group_dot_dense_dev(dppr_engine *e, int32_t group, int which, const void *h_device, int dtype, int h_layout, int32_t F,
+                             int dest, double *out /* [F][n] */);
+int dppr_dot_sparse(dppr_engine *e, int32_t slot, int which, const int64_t *offsets /* [F + 1], HOST */, const int32_t *ids,
+                    const double *w, int src, int32_t F, int dest, double *out /* [F] */);
+int dppr_group_dot_sparse(dppr_engine *e, int32_t group, int which, const int64_t *offsets /* [F + 1], HOST */, const int32_t *ids,
+                          const double *w, int src, int32_t F, int dest, double *out /* [F][n] */);
+
 /* Windows whose sweep groups are all resident at once run a frontier loop of a source group as
  * multi-sweep launches (grid barrier between sweeps, row tables kept in LDS; dppr_multi.hpp). on by
  * default; 0 = one launch per sweep everywhere. The roll-call / time-out rules are those of
