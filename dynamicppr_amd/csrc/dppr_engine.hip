@@ -47,6 +47,7 @@
 #include "dppr_changes.hpp"
 #include "dppr_export.hpp"
 #include "dppr_dot.hpp"
+#include "dppr_walk.hpp"
 
 using namespace dppr;
 
@@ -1458,6 +1459,40 @@ int dppr_group_dot_sparse(dppr_engine *e, int32_t group, int which, const int64_
                           int src, int32_t F, int dest, double *out) {
     GET_GROUP(e, group);
     return dot_sparse_call(e, g.p, g.r, g.gw, g.n, which, offsets, ids, w, src, F, dest, out);
+}
+
+// ---- forward walks over an epoch's out-CSR and the refinement of point queries (dppr_walk.hpp, dppr_host_query.hpp) -----------
+int dppr_walks(dppr_engine *e, int32_t epoch, const int32_t *starts, int32_t m, int32_t W, uint64_t seed, int dest, int32_t *out_ends) {
+    if (!e || e->broken) return fail(e, DPPR_ERR_INVALID, "walks: no usable engine");
+    GET_EPOCH(e, epoch);
+    return walks_call(e, ep, starts, m, W, seed, dest, out_ends);
+}
+
+int dppr_refine_at(dppr_engine *e, int32_t slot, int32_t epoch, const int32_t *ids, int32_t m, int32_t W, uint64_t seed, double *out_est,
+                   double *out_corr, double *out_sumsq) {
+    GET_SLOT(e, slot);
+    GET_EPOCH(e, epoch);
+    return refine_call(e, s, ep, s.p, s.r, 1, 1, ids, m, W, seed, out_est, out_corr, out_sumsq);
+}
+
+int dppr_group_refine_at(dppr_engine *e, int32_t group, int32_t epoch, const int32_t *ids, int32_t m, int32_t W, uint64_t seed,
+                         double *out_est, double *out_corr, double *out_sumsq) {
+    GET_GROUP(e, group);
+    GET_EPOCH(e, epoch);
+    return refine_call(e, g, ep, g.p, g.r, g.gw, g.n, ids, m, W, seed, out_est, out_corr, out_sumsq);
+}
+
+int dppr_debug_id_map(dppr_engine *e, int32_t *out_ext2int) {
+    if (!e || e->broken || !out_ext2int) return fail(e, DPPR_ERR_INVALID, "debug_id_map: non-null out_ext2int");
+    std::lock_guard<std::mutex> map_lk(e->map_mu);
+    memcpy(out_ext2int, e->ext2int.data(), sizeof(int32_t) * (size_t)e->V);
+    return DPPR_OK;
+}
+
+int dppr_debug_walk_form(dppr_engine *e, int form) {
+    if (!e || (form != 0 && form != 1)) return fail(e, DPPR_ERR_INVALID, "debug_walk_form: 0 (lane refill) or 1 (one walk per thread)");
+    e->walk_form = form;
+    return DPPR_OK;
 }
 
 int dppr_debug_query_ms(dppr_engine *e, float *out_ms) {

@@ -1,7 +1,8 @@
 // dppr_host_query.hpp -- host side of the state queries (dppr_topk / dppr_group_topk / dppr_read_at / dppr_group_read_at, and
 // dppr_group_topk_weighted / dppr_group_score_at, dppr_mark / dppr_changes, dppr_support / dppr_export_sparse /
-// dppr_export_dense_dev and their group forms, dppr_dot_dense_dev / dppr_dot_sparse and theirs): workspace, the device copy of int2ext, the check of a caller's device pointer and
-// the launch sequences of dppr_topk.hpp, dppr_wquery.hpp, dppr_changes.hpp, dppr_export.hpp and dppr_dot.hpp. Called with map_mu held, on the solver
+// dppr_export_dense_dev and their group forms, dppr_dot_dense_dev / dppr_dot_sparse and theirs, dppr_walks / dppr_refine_at /
+// dppr_group_refine_at): workspace, the device copy of int2ext, the check of a caller's device pointer and
+// the launch sequences of dppr_topk.hpp, dppr_wquery.hpp, dppr_changes.hpp, dppr_export.hpp, dppr_dot.hpp and dppr_walk.hpp. Called with map_mu held, on the solver
 // stream; nothing here is reached from the update path.
 #pragma once
 
@@ -596,6 +597,129 @@ int dot_sparse_call(dppr_engine *e, const double *p, const double *r, int gw, in
         return fail(e, DPPR_ERR_INVALID, "dot_sparse: out must be aligned device memory of the engine's device, F x n doubles inside one allocation");
     std::lock_guard<std::mutex> map_lk(e->map_mu);
     return run_dot_sparse(e, which == DPPR_DENSE_R ? r : p, gw, n, offsets, ids, w, src, F, dest, out);
+}
+
+// ---- forward walks and the refinement of point queries (dppr_walk.hpp, dppr_walk_plan.hpp) ------------------------------------------
+static_assert(WALK_MAX_M == DPPR_WALK_MAX_M && WALK_MAX_W == DPPR_WALK_MAX_W && WALK_DEST_HOST == DPPR_DEST_HOST &&
+                  WALK_DEST_DEVICE == DPPR_DEST_DEVICE,
+              "dppr_walk_plan.hpp restates the constants of include/dppr.h");
+
+// starts, endpoints and the results of a refine call: in place before the first kernel
+int walk_workspace(dppr_engine *e, size_t m, size_t ends_elems, size_t res_elems) {
+    if (e->wk_starts.capacity() >= m && e->wk_ends.capacity() >= ends_elems && e->wk_res.capacity() >= res_elems) return DPPR_OK;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (e->wk_starts.capacity() < m) HIP_TRY(e->wk_starts.regrow(m));
+    if (e->wk_ends.capacity() < ends_elems) HIP_TRY(e->wk_ends.regrow(ends_elems));
+    if (e->wk_res.capacity() < res_elems) HIP_TRY(e->wk_res.regrow(res_elems));
+    return DPPR_OK;
+}
+
+// the walk kernel in the engine's form over the m starts in wk_starts (both id maps are on the device)
+int walk_enqueue(dppr_engine *e, const Epoch &ep, int m, int W, uint64_t seed, int *d_ends) {
+    const long long total = walk_total(m, W), per_wave = walk_per_wave(total);
+    const unsigned k0 = (unsigned)(seed & 0xffffffffu), k1 = (unsigned)(seed >> 32);
+    if (e->walk_form == 0)
+        hipLaunchKernelGGL(k_walk<true>, dim3((unsigned)walk_blocks_refill(total)), dim3(WALK_BLOCK), 0, e->stream, ep.out_row_ptr.get(),
+                           ep.out_col.get(), e->d_ext2int.get(), e->d_int2ext.get(), e->wk_starts.get(), (unsigned)W, total, per_wave, k0, k1, d_ends);
+    else
+        hipLaunchKernelGGL(k_walk<false>, dim3((unsigned)walk_blocks_simple(total)), dim3(WALK_BLOCK), 0, e->stream, ep.out_row_ptr.get(),
+                           ep.out_col.get(), e->d_ext2int.get(), e->d_int2ext.get(), e->wk_starts.get(), (unsigned)W, total, per_wave, k0, k1, d_ends);
+    HIP_TRY(hipGetLastError());
+    return DPPR_OK;
+}
+
+// the endpoints of W walks from each of m starts (arguments, ids and a device destination validated by the caller), [m][W]
+int run_walks(dppr_engine *e, const Epoch &ep, const int32_t *starts, int m, int W, uint64_t seed, int dest, int32_t *out_ends) {
+    HIP_TRY(hipSetDevice(e->device));
+    int rc = sync_map(e);
+    if (rc) return rc;
+    rc = sync_int2ext(e);
+    if (rc) return rc;
+    const bool host = dest == DPPR_DEST_HOST;
+    rc = walk_workspace(e, (size_t)m, host ? (size_t)walk_total(m, W) : 0, 0);
+    if (rc) return rc;
+    int *d_ends = host ? e->wk_ends.get() : out_ends;
+    HIP_TRY(hipMemcpyAsync(e->wk_starts, starts, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, e->stream));
+    if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[0], e->stream));
+    rc = walk_enqueue(e, ep, m, W, seed, d_ends);
+    if (rc) return rc;
+    if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[1], e->stream));
+    if (host) HIP_TRY(hipMemcpyAsync(out_ends, d_ends, walk_ends_bytes(m, W), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream)); // (a device destination is complete here: any stream of the caller may read it)
+    if (e->profiling) HIP_TRY(hipEventElapsedTime(&e->query_ms, e->evpool[0], e->evpool[1]));
+    return DPPR_OK;
+}
+
+// est / corr / sumsq at m ids, [m][n]: the walks, the fold of r at their endpoints over the pieces of the dot products, the finish
+int run_refine(dppr_engine *e, const Epoch &ep, const double *p, const double *r, int gw, int n, const int32_t *ids, int m, int W,
+               uint64_t seed, double *out_est, double *out_corr, double *out_sumsq) {
+    HIP_TRY(hipSetDevice(e->device));
+    int rc = sync_map(e);
+    if (rc) return rc;
+    rc = sync_int2ext(e);
+    if (rc) return rc;
+    e->wk_off.resize((size_t)m + 1);
+    for (int q = 0; q <= m; ++q) e->wk_off[(size_t)q] = (int64_t)q * W;
+    dot_tile_table(e->wk_off.data(), m, e->dot_tb);
+    const long long n_tiles = (long long)e->dot_tb.tiles.size(), cols = e->dot_tb.cols();
+    const DotSparseWork wk = dot_sparse_work(n_tiles, m, 0, false);
+    const size_t mn = (size_t)m * (size_t)n, part_elems = (size_t)cols * 2 * (size_t)n;
+    rc = walk_workspace(e, (size_t)m, (size_t)walk_total(m, W), 2 * mn + walk_result_elems(m, n));
+    if (rc) return rc;
+    rc = dot_workspace(e, part_elems, wk.bytes, DOT_HEAD_BYTES);
+    if (rc) return rc;
+    unsigned char *in = e->dot_in.get();
+    DotTile *d_tiles = reinterpret_cast<DotTile *>(in);
+    long long *d_col = reinterpret_cast<long long *>(in + wk.off_col);
+    DotHead *head = reinterpret_cast<DotHead *>(e->dot_blk.get());
+    double *d_folded = e->wk_res.get(), *d_res = d_folded + 2 * mn;
+    HIP_TRY(hipMemcpyAsync(e->wk_starts, ids, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(d_tiles, e->dot_tb.tiles.data(), sizeof(DotTile) * (size_t)n_tiles, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(d_col, e->dot_tb.col.data(), sizeof(long long) * ((size_t)m + 1), hipMemcpyHostToDevice, e->stream));
+    if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[0], e->stream));
+    rc = walk_enqueue(e, ep, m, W, seed, e->wk_ends.get());
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(head, 0, DOT_HEAD_BYTES, e->stream));
+    HIP_TRY(hipMemsetAsync(e->dot_part, 0, sizeof(double) * part_elems, e->stream)); // (+0.0: the tiles of padding)
+    hipLaunchKernelGGL(k_walk_fold, dim3((unsigned)std::min<long long>(n_tiles, 2048)), dim3(DOT_TILE), dot_lds_bytes(gw, 1), e->stream, r, gw, n,
+                       e->d_ext2int.get(), e->wk_ends.get(), d_tiles, n_tiles, e->dot_part.get(), cols);
+    const int nout = m * 2 * n;
+    hipLaunchKernelGGL(k_dot_combine, dim3((nout + DOT_CB_WAVES - 1) / DOT_CB_WAVES), dim3(DOT_CB_WAVES * WAVE), 0, e->stream,
+                       e->dot_part.get(), (const long long *)d_col, cols, nout, 2 * n, head, d_folded);
+    hipLaunchKernelGGL(k_refine_finish, dim3(grid_for((int64_t)mn)), dim3(BLOCK), 0, e->stream, p, gw, n, e->d_ext2int.get(),
+                       e->wk_starts.get(), m, W, d_folded, d_res);
+    HIP_TRY(hipGetLastError());
+    if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[1], e->stream));
+    HIP_TRY(hipMemcpyAsync(out_est, d_res, sizeof(double) * mn, hipMemcpyDeviceToHost, e->stream));
+    if (out_corr) HIP_TRY(hipMemcpyAsync(out_corr, d_res + mn, sizeof(double) * mn, hipMemcpyDeviceToHost, e->stream));
+    if (out_sumsq) HIP_TRY(hipMemcpyAsync(out_sumsq, d_res + 2 * mn, sizeof(double) * mn, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (e->profiling) HIP_TRY(hipEventElapsedTime(&e->query_ms, e->evpool[0], e->evpool[1]));
+    return DPPR_OK;
+}
+
+// What the entry points share: the checks that need no device, that of a device destination, the id-map lock, the run.
+int walks_call(dppr_engine *e, const Epoch &ep, const int32_t *starts, int32_t m, int32_t W, uint64_t seed, int dest, int32_t *out_ends) {
+    if (!walk_args_ok(starts, m, W, dest, out_ends))
+        return fail(e, DPPR_ERR_INVALID, "walks: m in [1, DPPR_WALK_MAX_M], W in [1, DPPR_WALK_MAX_W], m * W <= 2^26, dest 0 or 1, non-null starts / out_ends");
+    if (!walk_ids_ok(starts, m, e->V)) return fail(e, DPPR_ERR_INVALID, "walks: starts in [0, V)");
+    HIP_TRY(hipSetDevice(e->device));
+    if (dest == DPPR_DEST_DEVICE && !ex_dev_dest_ok(e, out_ends, walk_ends_bytes(m, W), sizeof(int32_t)))
+        return fail(e, DPPR_ERR_INVALID, "walks: out_ends must be aligned device memory of the engine's device, m x W ints inside one allocation");
+    std::lock_guard<std::mutex> map_lk(e->map_mu); // (as dppr_read)
+    return run_walks(e, ep, starts, m, W, seed, dest, out_ends);
+}
+
+int refine_call(dppr_engine *e, const SolveState &st, const Epoch &ep, const double *p, const double *r, int gw, int n, const int32_t *ids,
+                int32_t m, int32_t W, uint64_t seed, double *out_est, double *out_corr, double *out_sumsq) {
+    if (!refine_args_ok(ids, m, W, out_est))
+        return fail(e, DPPR_ERR_INVALID, "refine_at: m in [1, DPPR_WALK_MAX_M], W in [1, DPPR_WALK_MAX_W], m * W <= 2^26, non-null ids / out_est");
+    if (!walk_ids_ok(ids, m, e->V)) return fail(e, DPPR_ERR_INVALID, "refine_at: ids in [0, V)");
+    if (!st.converged) return fail(e, DPPR_ERR_INVALID, "refine_at: the state is not converged (solve or update it first)");
+    if (!refine_epoch_ok(st.last_epoch, ep.id))
+        return fail(e, DPPR_ERR_INVALID, "refine_at: the state stands on another epoch than the one given: walks over another graph would give a biased estimate");
+    std::lock_guard<std::mutex> map_lk(e->map_mu); // (as dppr_read)
+    return run_refine(e, ep, p, r, gw, n, ids, m, W, seed, out_est, out_corr, out_sumsq);
 }
 
 } // namespace

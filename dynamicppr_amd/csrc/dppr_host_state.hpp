@@ -355,6 +355,12 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     DevBuf<unsigned char> dot_blk; PinBuf<unsigned char> dot_pin; // head (the flag), then the results of a host destination: device / pinned host
     dppr::DotTable dot_tb;          // host side of the tile table (kept for its capacity)
     bool dot_lds_set = false;       // the dense pass was given its dynamic LDS limit
+    // forward walks and the refinement of point queries (dppr_walk.hpp, dppr_walk_plan.hpp), allocated on the first such call and grown on demand
+    DevBuf<int> wk_starts;          // [m] the starts / queried ids of the call
+    DevBuf<int> wk_ends;            // [m][W] endpoints of a host destination and of a refine call
+    DevBuf<double> wk_res;          // a refine call: folded [m][2 n], then est | corr | sumsq [m][n] each
+    std::vector<int64_t> wk_off;    // a refine call: the offsets q * W of its m queries (kept for its capacity)
+    int walk_form = 0;              // 0: lane refill, 1: one walk per thread (dppr_debug_walk_form)
     float query_ms = -1.0f;         // dppr_set_profiling: device time of the last top-k, changes, export or dot call, first to last kernel (dppr_debug_query_ms)
     std::vector<int32_t> h_tmp1, h_tmp2;
     std::vector<int32_t> h_tiles; // host copy of the tile edge prefix / group table

@@ -67,6 +67,7 @@ EXPORTS = [
     "dppr_support", "dppr_group_support", "dppr_export_sparse", "dppr_group_export_sparse", "dppr_export_dense_dev",
     "dppr_group_export_dense_dev",
     "dppr_dot_dense_dev", "dppr_group_dot_dense_dev", "dppr_dot_sparse", "dppr_group_dot_sparse",
+    "dppr_walks", "dppr_refine_at", "dppr_group_refine_at", "dppr_debug_id_map", "dppr_debug_walk_form",
 ]
 
 DEST_HOST, DEST_DEVICE = 0, 1
@@ -75,6 +76,8 @@ F64, F32 = 0, 1
 VERTEX_MAJOR, SOURCE_MAJOR = 0, 1
 DOT_MAX_F = 4096
 H_FEATURE_MAJOR, H_VERTEX_MAJOR = 0, 1
+WALK_MAX_M, WALK_MAX_W, WALK_MAX_TOTAL = 4096, 1 << 20, 1 << 26
+WALK_REFILL, WALK_PER_THREAD = 0, 1
 
 
 def lib():
@@ -183,6 +186,12 @@ def lib():
     L.dppr_group_dot_dense_dev.argtypes = [vp, C.c_int32, C.c_int, vp, C.c_int, C.c_int, C.c_int32, C.c_int, vp]
     L.dppr_dot_sparse.argtypes = [vp, C.c_int32, C.c_int, i64p, vp, vp, C.c_int, C.c_int32, C.c_int, vp]
     L.dppr_group_dot_sparse.argtypes = [vp, C.c_int32, C.c_int, i64p, vp, vp, C.c_int, C.c_int32, C.c_int, vp]
+    # (out_ends as a plain address: a host array or device memory, as `dest` says; corr / sumsq may be NULL)
+    L.dppr_walks.argtypes = [vp, C.c_int32, ip, C.c_int32, C.c_int32, C.c_uint64, C.c_int, vp]
+    L.dppr_refine_at.argtypes = [vp, C.c_int32, C.c_int32, ip, C.c_int32, C.c_int32, C.c_uint64, vp, vp, vp]
+    L.dppr_group_refine_at.argtypes = [vp, C.c_int32, C.c_int32, ip, C.c_int32, C.c_int32, C.c_uint64, vp, vp, vp]
+    L.dppr_debug_id_map.argtypes = [vp, ip]
+    L.dppr_debug_walk_form.argtypes = [vp, C.c_int]
     for name in EXPORTS:
         if name not in ("dppr_strerror", "dppr_last_error", "dppr_destroy", "dppr_build_id", "dppr_heartbeat"):
             getattr(L, name).restype = C.c_int
@@ -731,6 +740,44 @@ class Engine:
         out = np.empty((max(F, 0), n), dtype=np.float64)
         self._ck(fn(self._h, int(handle), int(which), offp, ids_ptr, w_ptr, int(src), F, DEST_HOST, out.ctypes.data), what)
         return out[:, 0] if flat else out
+
+    def walks(self, starts, W, seed=0, epoch=-1):
+        """Endpoints of W forward walks from each of the external ids `starts` over the out-CSR of `epoch` (dppr_walks):
+        int32 [m][W], an external id or -1 for a walk that died. A walk is a function of (start, walk number, seed) alone."""
+        a, pa = _i32(starts)
+        out = np.empty((len(a), max(int(W), 0)), dtype=np.int32)
+        self._ck(self._L.dppr_walks(self._h, int(epoch), pa, len(a), int(W), int(seed), DEST_HOST, out.ctypes.data), "walks")
+        return out
+
+    def walks_dev(self, starts, W, seed, out_ptr, epoch=-1):
+        """... into device memory of the caller: m * W int32 at the raw address out_ptr."""
+        a, pa = _i32(starts)
+        self._ck(self._L.dppr_walks(self._h, int(epoch), pa, len(a), int(W), int(seed), DEST_DEVICE, out_ptr), "walks")
+
+    def refine_at(self, slot, ids, W, seed=0, epoch=-1, corr=True, sumsq=True):
+        """p refined by W walks from each of `ids` (dppr_refine_at): (est, corr, sumsq), each [m]; corr / sumsq None when not asked for.
+        est = p[v] + corr is an unbiased estimate of the fixed point; its standard error is sqrt((sumsq / W - corr^2) / (W - 1))."""
+        return self._refine(self._L.dppr_refine_at, slot, 1, ids, W, seed, epoch, corr, sumsq, True, "refine_at")
+
+    def group_refine_at(self, group, ids, W, seed=0, epoch=-1, corr=True, sumsq=True):
+        """... for every source of a group from ONE set of walks: each [m][n]."""
+        return self._refine(self._L.dppr_group_refine_at, group, self._group_n[group], ids, W, seed, epoch, corr, sumsq, False, "group_refine_at")
+
+    def _refine(self, fn, handle, n, ids, W, seed, epoch, corr, sumsq, flat, what):
+        a, pa = _i32(ids)
+        outs = [np.empty((len(a), n), dtype=np.float64) if want else None for want in (True, corr, sumsq)]
+        self._ck(fn(self._h, int(handle), int(epoch), pa, len(a), int(W), int(seed), *[None if o is None else o.ctypes.data for o in outs]), what)
+        return tuple(None if o is None else (o[:, 0] if flat else o) for o in outs)
+
+    def id_map(self):
+        """Test hook (dppr_debug_id_map): the internal id of every external id, -1 without one."""
+        out = np.empty(self.V, dtype=np.int32)
+        self._ck(self._L.dppr_debug_id_map(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))), "debug_id_map")
+        return out
+
+    def set_walk_form(self, form):
+        """Test hook (dppr_debug_walk_form): WALK_REFILL (default) or WALK_PER_THREAD; the same results bit for bit."""
+        self._ck(self._L.dppr_debug_walk_form(self._h, int(form)), "debug_walk_form")
 
     def query_ms(self):
         """With set_profiling on: device ms of the last top-k, changes or export call, first to last kernel (dppr_debug_query_ms)."""

@@ -94,6 +94,21 @@ inline bool load_seeds(const char *path, std::vector<int64_t> &off, std::vector<
     }
     return off.size() > 1;
 }
+// --refine: one external vertex id per line (blank lines are skipped). false: unreadable, no id, or a token that is not an id >= 0.
+inline bool load_ids(const char *path, std::vector<int32_t> &ids) {
+    std::ifstream in(path);
+    if (!in) return false;
+    ids.clear();
+    std::string tok;
+    while (in >> tok) {
+        char *end = nullptr;
+        errno = 0;
+        const long long id = std::strtoll(tok.c_str(), &end, 10);
+        if (end == tok.c_str() || *end != '\0' || errno || id < 0 || id > INT32_MAX) return false;
+        ids.push_back((int32_t)id);
+    }
+    return !ids.empty();
+}
 } // namespace args_detail
 
 inline void PrintUsage() {
@@ -121,6 +136,9 @@ inline void PrintUsage() {
               << "--seeds <file>: every line of <file> is one seed set `id[:weight] id[:weight] ...` (weight 1 by default, ids in [0, V));\n"
               << "            after the last batch print, per line (from 1) and per source in source order, the source's PPR under that seed\n"
               << "            distribution, sum_v weight[v] * pagerank_source[v]: seedscore <line> <source> <score>\n"
+              << "--refine <file> --walks <W> [--walk-seed <S>]: <file> holds one vertex id per line (ids in [0, V), at most 4096, W in [1, 2^20],\n"
+              << "            ids x W <= 2^26); after every batch print, per id and per source (index from 0, in source order), the pagerank\n"
+              << "            refined by W random walks, its correction and its standard error: refined <vertex> <source index> <est> <corr> <stderr>\n"
               << "--validate: residual bound + power-iteration check after every solve\n"
               << "--split: drive each batch through IncrementalBatchUpdate/ExecuteMainLoop(0)/(1)\n"
               << "--sync: synchronous (deterministic) push schedule\n"
@@ -163,6 +181,10 @@ inline void ArgumentsChecker() {
     if (gChangesK < 0 || gChangesK > DPPR_TOPK_MAX || !(gChangesMin >= 0.0) || (gChangesMinGiven && gChangesK == 0)) ok = false;
     if ((gSparseGiven && !(gSparseMin >= 0.0)) || (!gSparseOut.empty() && !gSparseGiven)) ok = false;
     if (gSeedsBad) ok = false;
+    if (gRefineBad || gRefineFile.empty() != !gWalksGiven) ok = false;
+    if (!gRefineFile.empty() && !gRefineBad &&
+        (gWalks < 1 || gWalks > DPPR_WALK_MAX_W || gRefineIds.size() > (size_t)DPPR_WALK_MAX_M || (long long)gRefineIds.size() * gWalks > (1ll << 26)))
+        ok = false;
     if (gTopKWeightsGiven && (gTopK == 0 || gTopKWeights.empty())) ok = false; // (the count is checked against the sources in main)
     if (!ok) {
         std::cout << "invalid arguments" << std::endl;
@@ -205,6 +227,13 @@ inline void ArgumentsParser(int argc, char **argv) {
         gSeedsFile = f;
         gSeedsBad = !load_seeds(f, gSeedOff, gSeedIds, gSeedW);
     }
+    if (const char *f = find(argc, argv, "--refine")) {
+        gRefineFile = f;
+        gRefineBad = !load_ids(f, gRefineIds);
+    }
+    gWalksGiven = find(argc, argv, "--walks") != nullptr;
+    gWalks = as_int(argc, argv, "--walks", 0);
+    if (const char *v = find(argc, argv, "--walk-seed")) gWalkSeed = std::strtoull(v, nullptr, 0);
     gValidate = has(argc, argv, "--validate");
     gSplitInterface = has(argc, argv, "--split");
     gSchedule = has(argc, argv, "--sync") ? 1 : 0;

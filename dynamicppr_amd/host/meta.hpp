@@ -54,6 +54,12 @@ inline bool gSeedsBad = false;        //   FILE could not be read, holds no line
 inline std::vector<int64_t> gSeedOff; //   the seed sets as one CSR over the lines: offsets [lines + 1], external ids, weights
 inline std::vector<int32_t> gSeedIds;
 inline std::vector<double> gSeedW;
+inline std::string gRefineFile;       // --refine FILE : one external vertex id per line; after every batch print refined <v> <source index> <est> <corr> <stderr>
+inline bool gRefineBad = false;       //   FILE could not be read, holds no id, or a token is not an id >= 0
+inline std::vector<int32_t> gRefineIds;
+inline int gWalks = 0;                // --walks W : walks per refined vertex (with --refine)
+inline bool gWalksGiven = false;
+inline unsigned long long gWalkSeed = 0; // --walk-seed S
 inline bool gValidate = false;        // --validate : the reference's -DVALIDATE checks at run time
 inline bool gShareDevice = false;     // --share-device (or DPPR_DEVICE_ALIAS=1): the -g N device threads share the devices that exist (d % count)
 inline bool gPushOnly = false;        // --push-only : no pull sweeps (the ablation of the -o variants times their push mechanisms)

@@ -67,13 +67,16 @@ int main(int argc, char *argv[]) {
             }
         }
         graphs[(size_t)d].reset(new SlidingGraphVec(gDataFileName, gIsDirected != 0));
-        if (d == 0) // --seeds: an id the graph does not have is an argument error, found before any device work
-            for (int32_t v : gSeedIds)
-                if (v >= (int32_t)graphs[0]->vertex_count) {
-                    std::cout << "invalid arguments" << std::endl;
-                    PrintUsage();
-                    return -1;
-                }
+        if (d == 0) { // --seeds, --refine: an id the graph does not have is an argument error, found before any device work
+            bool ok = true;
+            for (int32_t v : gSeedIds) ok = ok && v < (int32_t)graphs[0]->vertex_count;
+            for (int32_t v : gRefineIds) ok = ok && v < (int32_t)graphs[0]->vertex_count;
+            if (!ok) {
+                std::cout << "invalid arguments" << std::endl;
+                PrintUsage();
+                return -1;
+            }
+        }
         drivers[(size_t)d].reset(new PPRRevPushGPU(graphs[(size_t)d].get(), present ? d % present : d, mine, /*quiet=*/d != 0 && ngpu > 1));
     }
     // DPPR_WATCHDOG_S=<seconds>: a thread that ends the process -- after printing dppr_debug_dump of every engine -- when no

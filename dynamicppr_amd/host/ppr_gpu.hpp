@@ -254,6 +254,7 @@ public:
                 DPPR_CHECK(engine, ahead_rc);
             }
             if (gChangesK > 0) PrintChanges(stream_batch_count);
+            if (!gRefineIds.empty()) PrintRefined(-1);
         }
         batches_done = stream_batch_count - 1;
         if (!quiet_) Report(stream_batch_count);
@@ -346,6 +347,7 @@ public:
                 build_beside_ms += nxt.ms;
             }
             if (gChangesK > 0) PrintChanges(stream_batch_count);
+            if (!gRefineIds.empty()) PrintRefined(epoch); // (the epoch the states stand on: the helper may have built the next one)
         }
         batches_done = stream_batch_count - 1;
         if (!quiet_) Report(stream_batch_count);
@@ -548,6 +550,39 @@ public:
                     out += line;
                 }
             }
+        }
+        progress++;
+        static std::mutex print_mu;
+        std::lock_guard<std::mutex> lk(print_mu);
+        std::cout << out << std::flush;
+    }
+
+    // --refine: after a batch, the pagerank of every listed vertex towards every source of this device refined by gWalks forward
+    // walks over `epoch` (dppr_refine_at / dppr_group_refine_at: one set of walks serves all sources of a group), with the
+    // standard error a caller derives from sumsq. Outside the timed region, printed as one block like --changes.
+    void PrintRefined(int32_t epoch) {
+        const size_t n_src = source_vertex_ids.size(), m = gRefineIds.size();
+        const double W = (double)gWalks;
+        std::vector<double> est, corr, sumsq;
+        std::string out;
+        char line[200];
+        for (size_t first = 0; first < n_src; first += use_groups ? kGroupMax : 1) {
+            const size_t n = use_groups ? std::min(kGroupMax, n_src - first) : 1;
+            est.assign(m * n, 0.0);
+            corr.assign(m * n, 0.0);
+            sumsq.assign(m * n, 0.0);
+            if (use_groups)
+                DPPR_CHECK(engine, dppr_group_refine_at(engine, groups[first / kGroupMax], epoch, gRefineIds.data(), (int32_t)m, gWalks, gWalkSeed, est.data(), corr.data(), sumsq.data()));
+            else
+                DPPR_CHECK(engine, dppr_refine_at(engine, slots[first], epoch, gRefineIds.data(), (int32_t)m, gWalks, gWalkSeed, est.data(), corr.data(), sumsq.data()));
+            for (size_t q = 0; q < m; ++q)
+                for (size_t j = 0; j < n; ++j) {
+                    const size_t at = q * n + j;
+                    const double var = std::max(sumsq[at] / W - corr[at] * corr[at], 0.0);
+                    const double se = gWalks > 1 ? std::sqrt(var / (W - 1.0)) : std::nan("");
+                    std::snprintf(line, sizeof(line), "refined %d %zu %.17g %.17g %.17g\n", (int)gRefineIds[q], first + j, est[at], corr[at], se);
+                    out += line;
+                }
         }
         progress++;
         static std::mutex print_mu;

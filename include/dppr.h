@@ -610,6 +610,74 @@ int dppr_dot_sparse(dppr_engine *e, int32_t slot, int which, const int64_t *offs
 int dppr_group_dot_sparse(dppr_engine *e, int32_t group, int which, const int64_t *offsets /* [F + 1], HOST */, const int32_t *ids,
                           const double *w, int src, int32_t F, int dest, double *out /* [F][n] */);
 
+/* ---- point queries refined by random walks on the device: unbiased pi beyond eps (backward-compatible additions, ABI 6) ----
+ * Every other query is bounded by the solve tolerance: p_i[v] is within about max|r_i| of pi_v(s_i). The state is one half of a
+ * bidirectional estimator. With pi^ the fixed point the loop invariant defines (cpu/PPRCPUPowVec.h),
+ *     pi^[u] = ALPHA [u == s] + (1 - ALPHA) / (outdeg(u) + 1) * sum_{x in out(u)} pi^[x],
+ * the error e = pi^ - p satisfies e[u] = ALPHA r[u] + (1 - ALPHA) / (outdeg(u) + 1) * sum_{x in out(u)} e[x], so e[v] = E[t], t the
+ * residual at the endpoint of a short forward walk from v (0 for a walk that dies): p_i[v] + mean_w r_i[X_w] is an unbiased
+ * estimate of pi^_v(s_i) whose error shrinks as max|r_i| / sqrt(W), and ONE set of walks from v serves every source of a group,
+ * because a walk does not depend on the source. The endpoints are also samples of the forward PPR distribution of v.
+ *
+ * THE WALK is identified by (start EXTERNAL id v, walk number w, seed) and by nothing else: not by the grid, the lane that ran it,
+ * the position of v in the call, m or W. It runs over the out-CSR of the given epoch, the one the pull sweep reads.
+ * Random numbers: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85; a round is
+ *     c' = (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)), then the key is incremented).
+ * Step t = 0 .. 255 at internal vertex u (u_0 the internal id of v):
+ *     1. (x0, x1, x2, x3) = philox(counter = (w, v, t, 0), key = (seed & 0xffffffff, seed >> 32)).
+ *     2. x0 < 0x26666666 = floor(0.15 * 2^32): the walk STOPS; its endpoint is the external id of u.
+ *     3. d = out_row_ptr[u + 1] - out_row_ptr[u] in that epoch; d = 0 for a vertex with no row there, a parked vertex, and a
+ *        start without an internal id (which stops at itself or dies).
+ *     4. j = floor(((x1 * 2^32 + x2) * (d + 1)) / 2^64).
+ *     5. j == d: the walk DIES (the `+ 1` of the reference's denominator is this slot); its endpoint is -1.
+ *        Otherwise u = out_col[out_row_ptr[u] + j].
+ *     6. A walk still alive after step 255 dies.
+ * Row order: the row the device holds -- neighbours by ascending INTERNAL id, duplicates kept. Results are reproducible for a
+ * given engine history and seed. A renumbering of the id space changes which neighbour an index j selects, NOT the
+ * distribution; it invalidates every older epoch, so a resident epoch is always in the current numbering.
+ * Bias: the stop probability is 0.15 - 9.3e-11, a neighbour's probability is off by at most d / 2^64, truncation at 256 steps
+ * loses at most 0.85^256 = 8.5e-19. With about 6.7 expected steps the endpoint distribution is within 1e-8 of the ideal one in
+ * total variation: the bias of an estimate is at most 1e-8 * max|r_i|.
+ *
+ * dppr_walks: out_ends[q * W + w] = endpoint (external id, or -1) of walk w from starts[q]; starts are HOST memory and may
+ * repeat; out_ends lies where dest says (DPPR_DEST_HOST / DPPR_DEST_DEVICE; a device pointer is checked as a destination of
+ * dppr_export_dense_dev is). The epoch must be resident (-1: the newest).
+ *
+ * dppr_refine_at / dppr_group_refine_at, for source i (lane order) and query q, v = ids[q]; outputs [m][n], a slot is n = 1:
+ *     t_w   = r_i[X_w] by external id, exactly what dppr_group_read returns (+0.0 without a row); +0.0 for a walk that died
+ *     S     = fold_w t_w: THE FOLD of dppr_dot_dense_dev above over the slots w = 0 .. W - 1 (blocks of 2^16, the balanced tree
+ *             that adds neighbours, padding +0.0, blocks added in ascending order)
+ *     corr  = S / (double)W                  one division, rounded to nearest
+ *     est   = p_i[v] + corr                  one addition; p_i[v] what dppr_group_read returns (+0.0 without a row)
+ *     sumsq = fold_w (t_w * t_w)             every product rounded to double, never fused
+ * out_corr and out_sumsq may be NULL. The standard error of est is sqrt((sumsq / W - corr^2) / (W - 1)).
+ * The state must be converged, and if the epoch it stands on is known (anything but a state set by dppr_write) that must be
+ * the epoch given: against another graph the estimate is biased, and the call is refused.
+ *
+ * Rejected with DPPR_ERR_INVALID, nothing written: m outside [1, DPPR_WALK_MAX_M], W outside [1, DPPR_WALK_MAX_W], m * W > 2^26;
+ * a NULL starts / ids / out_ends / out_est; a start outside [0, V) (checked on the host before any launch); a bad dest; a device
+ * pointer that is not aligned device memory of the engine's device with m * W ints inside one allocation; a bad slot / group;
+ * an epoch that is not resident; for the refine calls a state that is not converged or stands on another epoch.
+ * Threading and stream as dppr_dot_sparse: the id-map lock of dppr_read (safe beside dppr_slide_concurrent), the solver stream,
+ * live and parked zone, never part of the update path or of a timed region. Work space: 4 bytes per walk for a host destination
+ * and for a refine call, whose fold adds 16 n bytes per 2048 walks (at least 512 n bytes per query); all of it is the engine's,
+ * obtained before the first kernel, grown on demand and released with the engine. With dppr_set_profiling on,
+ * dppr_debug_query_ms also reports the device time of the last of these calls, first to last kernel. */
+#define DPPR_WALK_MAX_M 4096
+#define DPPR_WALK_MAX_W (1 << 20)
+int dppr_walks(dppr_engine *e, int32_t epoch, const int32_t *starts /* [m] external, HOST */, int32_t m, int32_t W, uint64_t seed,
+               int dest, int32_t *out_ends /* [m][W] external id or -1 */);
+int dppr_refine_at(dppr_engine *e, int32_t slot, int32_t epoch, const int32_t *ids, int32_t m, int32_t W, uint64_t seed,
+                   double *out_est /* [m] */, double *out_corr /* [m], may be NULL */, double *out_sumsq /* [m], may be NULL */);
+int dppr_group_refine_at(dppr_engine *e, int32_t group, int32_t epoch, const int32_t *ids, int32_t m, int32_t W, uint64_t seed,
+                         double *out_est /* [m][n] */, double *out_corr /* [m][n], may be NULL */,
+                         double *out_sumsq /* [m][n], may be NULL */);
+/* Test hooks. dppr_debug_id_map: the internal id of every external id ([V]; -1 without one), with which a test rebuilds the
+ * rows the walks index from dppr_read_out_graph. dppr_debug_walk_form: 0 (default) the lane-refill kernel, 1 one walk per
+ * thread -- the same results bit for bit, kept for the measurement (tools/walk_times.py). */
+int dppr_debug_id_map(dppr_engine *e, int32_t *out_ext2int /* [V], -1 without an internal id */);
+int dppr_debug_walk_form(dppr_engine *e, int form);
+
 /* Windows whose sweep groups are all resident at once run a frontier loop of a source group as
  * multi-sweep launches (grid barrier between sweeps, row tables kept in LDS; dppr_multi.hpp). on by
  * default; 0 = one launch per sweep everywhere. The roll-call / time-out rules are those of
