@@ -1,5 +1,5 @@
 // dppr_changes_plan.hpp -- the result block of dppr_changes / dppr_group_changes and the checks of their arguments. Pure host code
-// without HIP includes (dppr_host_query.hpp lays the device and the pinned block out with it, dppr_engine.hip checks a call with
+// without HIP includes (dppr_host_query.hpp lays the device and the pinned block out with it and checks a call with
 // it; tests/native/changes_test.cpp drives it on the CPU against a plain restatement).
 //
 // One block holds everything a call returns, so that one copy brings it to the host:
@@ -7,12 +7,12 @@
 //     [|delta| n x k]                                                             <- device only (k_tk_rank writes it; not returned)
 #pragma once
 
-#include <cstddef>
+#include "dppr_query_plan.hpp"
 
 namespace dppr {
 
-constexpr int CH_LANES = 16;       // sources of a group (GS_MAX of dppr_multi.hpp, asserted equal in dppr_host_query.hpp)
-constexpr int CH_K_MAX = 8192;     // DPPR_TOPK_MAX of include/dppr.h (asserted equal in dppr_host_query.hpp)
+constexpr int CH_LANES = Q_LANES;      // (the name the kernels of dppr_changes.hpp know the lane count by)
+constexpr int CH_K_MAX = DPPR_TOPK_MAX; // (... and tests/native/changes_test.cpp the largest k)
 
 struct ChLayout {
     size_t off_cnt = 0, off_moved = 0, off_ids = 0, off_delta = 0, off_p = 0, off_abs = 0;
@@ -26,7 +26,7 @@ constexpr ChLayout ch_layout(int n, int k) {
     l.off_cnt = 0;
     l.off_moved = l.off_cnt + sizeof(int) * CH_LANES;
     l.off_ids = l.off_moved + sizeof(int) * CH_LANES;
-    l.off_delta = l.off_ids + ((sizeof(int) * nk + 7) & ~(size_t)7);
+    l.off_delta = l.off_ids + pad8(sizeof(int) * nk);
     l.off_p = l.off_delta + sizeof(double) * nk;
     l.off_abs = l.off_p + sizeof(double) * nk;
     l.copy_bytes = l.off_abs;

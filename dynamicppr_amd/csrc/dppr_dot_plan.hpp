@@ -16,31 +16,23 @@
 // BLOCK of a call: [DotHead][out F x n doubles, only for a host destination]; device and pinned host.
 #pragma once
 
-#include <cstddef>
-#include <cstdint>
 #include <vector>
+
+#include "dppr_query_plan.hpp"
 
 namespace dppr {
 
-constexpr int DOT_LANES = 16;                        // sources of a group (GS_MAX, asserted equal in dppr_host_query.hpp)
 constexpr int DOT_TILE = 256;                        // slots of a subtile = threads of a workgroup of dppr_dot.hpp
 constexpr int DOT_SUB = 8;                           // subtiles of a tile
 constexpr int DOT_WG_SLOTS = DOT_TILE * DOT_SUB;     // slots of a tile: 2048
 constexpr int64_t DOT_BLOCK = 1 << 16;               // slots of a block of the fold
 constexpr int DOT_TPB = (int)(DOT_BLOCK / DOT_WG_SLOTS); // tiles of a block: 32
 constexpr int DOT_FCHUNK = 16;                       // features one workgroup folds against a gathered row
-constexpr int DOT_MAX_F = 4096;                      // DPPR_DOT_MAX_F
 constexpr size_t DOT_PART_BUDGET = (size_t)64 << 20; // bytes of partials one dense launch may fill (a launch takes fewer features instead)
 constexpr size_t DOT_HEAD_BYTES = 8;
 static_assert((DOT_TILE & (DOT_TILE - 1)) == 0 && (DOT_SUB & (DOT_SUB - 1)) == 0 && (DOT_TPB & (DOT_TPB - 1)) == 0 &&
                   (int64_t)DOT_TILE * DOT_SUB * DOT_TPB == DOT_BLOCK,
               "subtile, tile and block are powers of two of one another: the pieces are one balanced tree");
-
-// the values of include/dppr.h (asserted equal in dppr_host_query.hpp)
-constexpr int DOT_DEST_HOST = 0, DOT_DEST_DEVICE = 1;
-constexpr int DOT_P = 0, DOT_R = 1;
-constexpr int DOT_F64 = 0, DOT_F32 = 1;
-constexpr int DOT_FEATURE_MAJOR = 0, DOT_VERTEX_MAJOR = 1;
 
 struct DotHead {
     int bad; // 1: an id of a sparse call in device memory lay outside [0, V): the combine launch wrote nothing
@@ -62,14 +54,14 @@ constexpr int64_t dot_blocks(int64_t slots) { return (slots + DOT_BLOCK - 1) / D
 // partial columns of `slots` slots: whole blocks
 constexpr int64_t dot_cols(int64_t slots) { return dot_blocks(slots) * DOT_TPB; }
 
-constexpr size_t dot_elem_bytes(int dtype) { return dtype == DOT_F32 ? 4 : 8; }
+constexpr size_t dot_elem_bytes(int dtype) { return dtype == DPPR_F32 ? 4 : 8; }
 constexpr size_t dot_dense_h_bytes(int dtype, int F, int64_t V) { return dot_elem_bytes(dtype) * (size_t)F * (size_t)V; }
 constexpr size_t dot_h_index(int layout, int F, int64_t V, int f, int64_t v) {
-    return layout == DOT_VERTEX_MAJOR ? (size_t)v * (size_t)F + (size_t)f : (size_t)f * (size_t)V + (size_t)v;
+    return layout == DPPR_H_VERTEX_MAJOR ? (size_t)v * (size_t)F + (size_t)f : (size_t)f * (size_t)V + (size_t)v;
 }
 constexpr size_t dot_out_bytes(int F, int n) { return sizeof(double) * (size_t)F * (size_t)n; }
 // the block: the head, and the results of a host destination
-constexpr size_t dot_block_bytes(int F, int n, int dest) { return DOT_HEAD_BYTES + (dest == DOT_DEST_HOST ? dot_out_bytes(F, n) : 0); }
+constexpr size_t dot_block_bytes(int F, int n, int dest) { return DOT_HEAD_BYTES + (dest == DPPR_DEST_HOST ? dot_out_bytes(F, n) : 0); }
 
 // features of one dense launch: whole chunks of DOT_FCHUNK, as many as the budget of partials holds, one chunk at the least
 constexpr int dot_launch_features(int64_t V, int n, int F) {
@@ -94,12 +86,12 @@ constexpr size_t dot_lds_bytes(int gw, int fc) {
 }
 
 inline bool dot_enums_ok(int which, int dest) {
-    return (which == DOT_P || which == DOT_R) && (dest == DOT_DEST_HOST || dest == DOT_DEST_DEVICE);
+    return (which == DPPR_DENSE_P || which == DPPR_DENSE_R) && (dest == DPPR_DEST_HOST || dest == DPPR_DEST_DEVICE);
 }
-inline bool dot_f_ok(int F) { return F >= 1 && F <= DOT_MAX_F; }
+inline bool dot_f_ok(int F) { return F >= 1 && F <= DPPR_DOT_MAX_F; }
 inline bool dot_dense_args_ok(int which, const void *h, int dtype, int layout, int F, int dest, const void *out) {
-    return dot_enums_ok(which, dest) && dot_f_ok(F) && h && out && (dtype == DOT_F64 || dtype == DOT_F32) &&
-           (layout == DOT_FEATURE_MAJOR || layout == DOT_VERTEX_MAJOR);
+    return dot_enums_ok(which, dest) && dot_f_ok(F) && h && out && (dtype == DPPR_F64 || dtype == DPPR_F32) &&
+           (layout == DPPR_H_FEATURE_MAJOR || layout == DPPR_H_VERTEX_MAJOR);
 }
 // offsets [F + 1]: offsets[0] = 0, non-decreasing
 inline bool dot_offsets_ok(const int64_t *offsets, int F) {
@@ -110,13 +102,8 @@ inline bool dot_offsets_ok(const int64_t *offsets, int F) {
 }
 inline bool dot_sparse_args_ok(int which, const int64_t *offsets, const void *ids, const void *w, int src, int F, int dest,
                                const void *out) {
-    return dot_enums_ok(which, dest) && dot_f_ok(F) && (src == DOT_DEST_HOST || src == DOT_DEST_DEVICE) && ids && w && out &&
+    return dot_enums_ok(which, dest) && dot_f_ok(F) && (src == DPPR_DEST_HOST || src == DPPR_DEST_DEVICE) && ids && w && out &&
            dot_offsets_ok(offsets, F);
-}
-inline bool dot_ids_ok(const int32_t *ids, int64_t m, int64_t V) {
-    for (int64_t e = 0; e < m; ++e)
-        if (ids[e] < 0 || ids[e] >= V) return false;
-    return true;
 }
 
 // The tile table of a sparse call from its (checked) host offsets: col[f] .. col[f + 1] are query f's partial columns (whole blocks:
@@ -169,7 +156,7 @@ constexpr DotSparseWork dot_sparse_work(long long n_tiles, int F, int64_t m, boo
     DotSparseWork w;
     w.off_col = sizeof(DotTile) * (size_t)n_tiles;
     w.off_ids = w.off_col + sizeof(long long) * ((size_t)F + 1);
-    w.off_w = w.off_ids + (host_src ? (sizeof(int32_t) * (size_t)m + 7) & ~(size_t)7 : 0);
+    w.off_w = w.off_ids + (host_src ? pad8(sizeof(int32_t) * (size_t)m) : 0);
     w.bytes = w.off_w + (host_src ? sizeof(double) * (size_t)m : 0);
     if (w.bytes < 8) w.bytes = 8;
     return w;

@@ -37,6 +37,7 @@
 #include "dppr_devbuf.hpp"
 #include "dppr_idspace.hpp"
 #include "dppr_loop_plan.hpp"
+#include "dppr_query_plan.hpp"
 #include "dppr_kernels.hpp"
 #include "dppr_multi.hpp"
 #include "dppr_gpush.hpp"
@@ -1281,91 +1282,50 @@ int dppr_group_remove_source(dppr_engine *e, int32_t group, int32_t index) {
     return group_churn(e, group, CHURN_REMOVE, index, -1, nullptr, nullptr);
 }
 
-// ---- queries of a state (dppr_topk.hpp, dppr_host_query.hpp) -----------------------------------------------------------
-// Arguments are checked before any device work and before anything is written.
-static bool topk_args_ok(int32_t k, double min_p, const void *ids, const void *p, const void *cnt) {
-    return k >= 1 && k <= DPPR_TOPK_MAX && min_p >= 0.0 && ids && p && cnt; // (min_p >= 0 is false for NaN)
-}
-static bool read_at_args_ok(const dppr_engine *e, const int32_t *ids, int32_t m) {
-    if (m < 0 || (m > 0 && !ids)) return false;
-    for (int32_t i = 0; i < m; ++i)
-        if (ids[i] < 0 || ids[i] >= e->V) return false;
-    return true;
-}
-
+// ---- queries of a state (dppr_host_query.hpp): an entry point finds its state and hands a view of it to the family's call, which
+// checks the arguments before any device work and before anything is written --------------------------------------------------
 int dppr_topk(dppr_engine *e, int32_t slot, int32_t k, double min_p, int32_t *out_ids, double *out_p, double *out_r,
               int32_t *out_count) {
     GET_SLOT(e, slot);
-    if (!topk_args_ok(k, min_p, out_ids, out_p, out_count))
-        return fail(e, DPPR_ERR_INVALID, "topk: k in [1, DPPR_TOPK_MAX], min_p >= 0, non-null ids / p / count");
-    std::lock_guard<std::mutex> map_lk(e->map_mu); // (as dppr_read: one state of the id space for the whole query)
-    return run_topk(e, s.p, s.r, 1, 1, k, min_p, out_ids, out_p, out_r, out_count);
+    return topk_call(e, view(s), k, min_p, out_ids, out_p, out_r, out_count);
 }
 
 int dppr_group_topk(dppr_engine *e, int32_t group, int32_t k, double min_p, int32_t *out_ids, double *out_p, double *out_r,
                     int32_t *out_counts) {
     GET_GROUP(e, group);
-    if (!topk_args_ok(k, min_p, out_ids, out_p, out_counts))
-        return fail(e, DPPR_ERR_INVALID, "group_topk: k in [1, DPPR_TOPK_MAX], min_p >= 0, non-null ids / p / counts");
-    std::lock_guard<std::mutex> map_lk(e->map_mu);
-    return run_topk(e, g.p, g.r, g.gw, g.n, k, min_p, out_ids, out_p, out_r, out_counts);
+    return topk_call(e, view(g), k, min_p, out_ids, out_p, out_r, out_counts);
 }
 
 int dppr_read_at(dppr_engine *e, int32_t slot, const int32_t *ids, int32_t m, double *out_p, double *out_r) {
     GET_SLOT(e, slot);
-    if (!read_at_args_ok(e, ids, m)) return fail(e, DPPR_ERR_INVALID, "read_at: ids in [0, V)");
-    if (m == 0 || (!out_p && !out_r)) return DPPR_OK;
-    std::lock_guard<std::mutex> map_lk(e->map_mu);
-    return run_read_at(e, s.p, s.r, 1, 1, ids, m, out_p, out_r);
+    return read_at_call(e, view(s), ids, m, out_p, out_r);
 }
 
 int dppr_group_read_at(dppr_engine *e, int32_t group, const int32_t *ids, int32_t m, double *out_p, double *out_r) {
     GET_GROUP(e, group);
-    if (!read_at_args_ok(e, ids, m)) return fail(e, DPPR_ERR_INVALID, "group_read_at: ids in [0, V)");
-    if (m == 0 || (!out_p && !out_r)) return DPPR_OK;
-    std::lock_guard<std::mutex> map_lk(e->map_mu);
-    return run_read_at(e, g.p, g.r, g.gw, g.n, ids, m, out_p, out_r);
-}
-
-// weights [q][n]: q in [1, 16], every entry finite
-static bool weights_ok(const double *w, int32_t q, int n) {
-    if (!w || q < 1 || q > GS_MAX) return false;
-    for (int i = 0; i < q * n; ++i)
-        if (!std::isfinite(w[i])) return false;
-    return true;
+    return read_at_call(e, view(g), ids, m, out_p, out_r);
 }
 
 int dppr_group_topk_weighted(dppr_engine *e, int32_t group, const double *weights, int32_t q, int32_t k, double min_score,
                              int32_t *out_ids, double *out_score, int32_t *out_counts) {
     GET_GROUP(e, group);
-    if (!weights_ok(weights, q, g.n) || !topk_args_ok(k, min_score, out_ids, out_score, out_counts))
-        return fail(e, DPPR_ERR_INVALID,
-                    "group_topk_weighted: q in [1, 16], finite weights, k in [1, DPPR_TOPK_MAX], min_score >= 0, non-null ids / score / counts");
-    std::lock_guard<std::mutex> map_lk(e->map_mu);
-    return run_topk_weighted(e, g.p, g.gw, g.n, weights, q, k, min_score, out_ids, out_score, out_counts);
+    return topk_weighted_call(e, view(g), weights, q, k, min_score, out_ids, out_score, out_counts);
 }
 
 int dppr_group_score_at(dppr_engine *e, int32_t group, const double *weights, int32_t q, const int32_t *ids, int32_t m,
                         double *out_score) {
     GET_GROUP(e, group);
-    if (!weights_ok(weights, q, g.n) || !out_score || !read_at_args_ok(e, ids, m))
-        return fail(e, DPPR_ERR_INVALID, "group_score_at: q in [1, 16], finite weights, ids in [0, V), non-null score");
-    if (m == 0) return DPPR_OK;
-    std::lock_guard<std::mutex> map_lk(e->map_mu);
-    return run_score_at(e, g.p, g.gw, g.n, weights, q, ids, m, out_score);
+    return score_at_call(e, view(g), weights, q, ids, m, out_score);
 }
 
-// ---- what a batch moved: marks and the top k of |p - mark| (dppr_changes.hpp, dppr_host_query.hpp) ---------------------------
 int dppr_mark(dppr_engine *e, int32_t slot) {
     GET_SLOT(e, slot);
-    std::lock_guard<std::mutex> map_lk(e->map_mu);
-    return run_mark(e, s.p, 1, s.mark);
+    return mark_call(e, view(s));
 }
 
 int dppr_group_mark(dppr_engine *e, int32_t group) {
     GET_GROUP(e, group);
-    std::lock_guard<std::mutex> map_lk(e->map_mu);
-    return run_mark(e, g.p, g.gw, g.mark);
+    return mark_call(e, view(g));
 }
 
 // (a release waits for the device: whatever still reads the mark has finished by then)
@@ -1386,82 +1346,71 @@ int dppr_group_unmark(dppr_engine *e, int32_t group) {
 int dppr_changes(dppr_engine *e, int32_t slot, int32_t k, double min_delta, int remark, int32_t *out_ids, double *out_delta,
                  double *out_p, int32_t *out_count, int32_t *out_moved) {
     GET_SLOT(e, slot);
-    if (!ch_args_ok(k, min_delta, out_ids, out_delta, out_count))
-        return fail(e, DPPR_ERR_INVALID, "changes: k in [1, DPPR_TOPK_MAX], min_delta >= 0, non-null ids / delta / count");
-    if (!s.mark) return fail(e, DPPR_ERR_INVALID, "changes: the slot has no mark (dppr_mark)");
-    std::lock_guard<std::mutex> map_lk(e->map_mu);
-    return run_changes(e, s.p, 1, 1, s.mark, k, min_delta, remark, out_ids, out_delta, out_p, out_count, out_moved);
+    return changes_call(e, view(s), k, min_delta, remark, out_ids, out_delta, out_p, out_count, out_moved);
 }
 
 int dppr_group_changes(dppr_engine *e, int32_t group, int32_t k, double min_delta, int remark, int32_t *out_ids, double *out_delta,
                        double *out_p, int32_t *out_counts, int32_t *out_moved) {
     GET_GROUP(e, group);
-    if (!ch_args_ok(k, min_delta, out_ids, out_delta, out_counts))
-        return fail(e, DPPR_ERR_INVALID, "group_changes: k in [1, DPPR_TOPK_MAX], min_delta >= 0, non-null ids / delta / counts");
-    if (!g.mark) return fail(e, DPPR_ERR_INVALID, "group_changes: the group has no mark (dppr_group_mark; a change of the sources drops it)");
-    std::lock_guard<std::mutex> map_lk(e->map_mu);
-    return run_changes(e, g.p, g.gw, g.n, g.mark, k, min_delta, remark, out_ids, out_delta, out_p, out_counts, out_moved);
+    return changes_call(e, view(g), k, min_delta, remark, out_ids, out_delta, out_p, out_counts, out_moved);
 }
 
-// ---- the state leaves the engine: sparse vectors and dense device copies (dppr_export.hpp, dppr_host_query.hpp) -------------
 int dppr_support(dppr_engine *e, int32_t slot, double min_p, int64_t *out_count) {
     GET_SLOT(e, slot);
-    return support_call(e, s.p, 1, 1, min_p, out_count);
+    return support_call(e, view(s), min_p, out_count);
 }
 
 int dppr_group_support(dppr_engine *e, int32_t group, double min_p, int64_t *out_counts) {
     GET_GROUP(e, group);
-    return support_call(e, g.p, g.gw, g.n, min_p, out_counts);
+    return support_call(e, view(g), min_p, out_counts);
 }
 
 int dppr_export_sparse(dppr_engine *e, int32_t slot, double min_p, int64_t cap, int dest, int64_t *out_offsets, int32_t *out_ids,
                        double *out_p, double *out_r) {
     GET_SLOT(e, slot);
-    return export_sparse_call(e, s.p, s.r, 1, 1, min_p, cap, dest, out_offsets, out_ids, out_p, out_r);
+    return export_sparse_call(e, view(s), min_p, cap, dest, out_offsets, out_ids, out_p, out_r);
 }
 
 int dppr_group_export_sparse(dppr_engine *e, int32_t group, double min_p, int64_t cap, int dest, int64_t *out_offsets,
                              int32_t *out_ids, double *out_p, double *out_r) {
     GET_GROUP(e, group);
-    return export_sparse_call(e, g.p, g.r, g.gw, g.n, min_p, cap, dest, out_offsets, out_ids, out_p, out_r);
+    return export_sparse_call(e, view(g), min_p, cap, dest, out_offsets, out_ids, out_p, out_r);
 }
 
 int dppr_export_dense_dev(dppr_engine *e, int32_t slot, int which, int dtype, void *dst_device) {
     GET_SLOT(e, slot);
-    return export_dense_call(e, s.p, s.r, 1, 1, which, dtype, DPPR_VERTEX_MAJOR, dst_device);
+    return export_dense_call(e, view(s), which, dtype, DPPR_VERTEX_MAJOR, dst_device);
 }
 
 int dppr_group_export_dense_dev(dppr_engine *e, int32_t group, int which, int dtype, int layout, void *dst_device) {
     GET_GROUP(e, group);
-    return export_dense_call(e, g.p, g.r, g.gw, g.n, which, dtype, layout, dst_device);
+    return export_dense_call(e, view(g), which, dtype, layout, dst_device);
 }
 
-// ---- the state folded over the vertex axis: h . p for any seed distribution (dppr_dot.hpp, dppr_host_query.hpp) ------------
 int dppr_dot_dense_dev(dppr_engine *e, int32_t slot, int which, const void *h_device, int dtype, int h_layout, int32_t F, int dest,
                        double *out) {
     GET_SLOT(e, slot);
-    return dot_dense_call(e, s.p, s.r, 1, 1, which, h_device, dtype, h_layout, F, dest, out);
+    return dot_dense_call(e, view(s), which, h_device, dtype, h_layout, F, dest, out);
 }
 
 int dppr_group_dot_dense_dev(dppr_engine *e, int32_t group, int which, const void *h_device, int dtype, int h_layout, int32_t F,
                              int dest, double *out) {
     GET_GROUP(e, group);
-    return dot_dense_call(e, g.p, g.r, g.gw, g.n, which, h_device, dtype, h_layout, F, dest, out);
+    return dot_dense_call(e, view(g), which, h_device, dtype, h_layout, F, dest, out);
 }
 
 int dppr_dot_sparse(dppr_engine *e, int32_t slot, int which, const int64_t *offsets, const int32_t *ids, const double *w, int src,
                     int32_t F, int dest, double *out) {
     GET_SLOT(e, slot);
-    return dot_sparse_call(e, s.p, s.r, 1, 1, which, offsets, ids, w, src, F, dest, out);
+    return dot_sparse_call(e, view(s), which, offsets, ids, w, src, F, dest, out);
 }
 
 int dppr_group_dot_sparse(dppr_engine *e, int32_t group, int which, const int64_t *offsets, const int32_t *ids, const double *w,
                           int src, int32_t F, int dest, double *out) {
     GET_GROUP(e, group);
-    return dot_sparse_call(e, g.p, g.r, g.gw, g.n, which, offsets, ids, w, src, F, dest, out);
+    return dot_sparse_call(e, view(g), which, offsets, ids, w, src, F, dest, out);
 }
 
-// ---- forward walks over an epoch's out-CSR and the refinement of point queries (dppr_walk.hpp, dppr_host_query.hpp) -----------
 int dppr_walks(dppr_engine *e, int32_t epoch, const int32_t *starts, int32_t m, int32_t W, uint64_t seed, int dest, int32_t *out_ends) {
     if (!e || e->broken) return fail(e, DPPR_ERR_INVALID, "walks: no usable engine");
     GET_EPOCH(e, epoch);
@@ -1472,14 +1421,14 @@ int dppr_refine_at(dppr_engine *e, int32_t slot, int32_t epoch, const int32_t *i
                    double *out_corr, double *out_sumsq) {
     GET_SLOT(e, slot);
     GET_EPOCH(e, epoch);
-    return refine_call(e, s, ep, s.p, s.r, 1, 1, ids, m, W, seed, out_est, out_corr, out_sumsq);
+    return refine_call(e, view(s), ep, ids, m, W, seed, out_est, out_corr, out_sumsq);
 }
 
 int dppr_group_refine_at(dppr_engine *e, int32_t group, int32_t epoch, const int32_t *ids, int32_t m, int32_t W, uint64_t seed,
                          double *out_est, double *out_corr, double *out_sumsq) {
     GET_GROUP(e, group);
     GET_EPOCH(e, epoch);
-    return refine_call(e, g, ep, g.p, g.r, g.gw, g.n, ids, m, W, seed, out_est, out_corr, out_sumsq);
+    return refine_call(e, view(g), ep, ids, m, W, seed, out_est, out_corr, out_sumsq);
 }
 
 int dppr_debug_id_map(dppr_engine *e, int32_t *out_ext2int) {

@@ -1,6 +1,6 @@
 // dppr_export_plan.hpp -- the sizes, the result block and the argument checks of the exports (dppr_support / dppr_export_sparse /
 // dppr_export_dense_dev and their group forms). Pure host code without HIP includes (dppr_export.hpp takes the tile from it,
-// dppr_host_query.hpp lays the workspace and the staging block out with it, dppr_engine.hip checks a call with it;
+// dppr_host_query.hpp lays the workspace and the staging block out with it and checks a call with it;
 // tests/native/export_plan_test.cpp drives it on the CPU against a plain restatement).
 //
 // WORKSPACE, by the number of external ids V alone (every lane count fits):
@@ -12,20 +12,13 @@
 //     [ids cap x int32, padded to 8 bytes][p cap x double][r cap x double, if asked for]
 #pragma once
 
-#include <cstddef>
-#include <cstdint>
+#include "dppr_query_plan.hpp"
 
 namespace dppr {
 
-constexpr int EX_LANES = 16;   // sources of a group (GS_MAX of dppr_multi.hpp, asserted equal in dppr_host_query.hpp)
+constexpr int EX_LANES = Q_LANES; // (the name the kernels of dppr_export.hpp know the lane count by)
 constexpr int EX_TILE = 256;   // external ids per tile = threads of a workgroup of dppr_export.hpp (4 waves)
 constexpr size_t EX_HEAD_BYTES = 8 * (EX_LANES + 1) + 8;
-
-// the values of include/dppr.h (asserted equal in dppr_host_query.hpp)
-constexpr int EX_DEST_HOST = 0, EX_DEST_DEVICE = 1;
-constexpr int EX_DENSE_P = 0, EX_DENSE_R = 1;
-constexpr int EX_F64 = 0, EX_F32 = 1;
-constexpr int EX_VERTEX_MAJOR = 0, EX_SOURCE_MAJOR = 1;
 
 struct ExHead {
     long long offsets[EX_LANES + 1]; // offsets[i] .. offsets[i + 1]: source i; entries past n repeat offsets[n]
@@ -63,7 +56,7 @@ constexpr ExLayout ex_layout(int64_t cap, bool with_r) {
     ExLayout l;
     const size_t c = (size_t)(cap > 0 ? cap : 0);
     l.off_ids = EX_HEAD_BYTES;
-    l.off_p = l.off_ids + ((sizeof(int32_t) * c + 7) & ~(size_t)7);
+    l.off_p = l.off_ids + pad8(sizeof(int32_t) * c);
     l.off_r = l.off_p + sizeof(double) * c;
     l.total_bytes = l.off_r + (with_r ? sizeof(double) * c : 0);
     return l;
@@ -75,22 +68,22 @@ constexpr int64_t ex_cap_clamped(int64_t cap, int64_t V, int n) { return cap < V
 // the arguments of a sparse export that need no device: min_p >= 0 (false for NaN), cap >= 0, a known dest, offsets, and ids / p
 // wherever something could be written
 inline bool ex_sparse_args_ok(double min_p, int64_t cap, int dest, const void *offsets, const void *ids, const void *p) {
-    if (!(min_p >= 0.0) || cap < 0 || (dest != EX_DEST_HOST && dest != EX_DEST_DEVICE) || !offsets) return false;
+    if (!(min_p >= 0.0) || cap < 0 || (dest != DPPR_DEST_HOST && dest != DPPR_DEST_DEVICE) || !offsets) return false;
     return cap == 0 || (ids && p);
 }
 inline bool ex_support_args_ok(double min_p, const void *counts) { return min_p >= 0.0 && counts; }
 
 inline bool ex_dense_args_ok(int which, int dtype, int layout) {
-    return (which == EX_DENSE_P || which == EX_DENSE_R) && (dtype == EX_F64 || dtype == EX_F32) &&
-           (layout == EX_VERTEX_MAJOR || layout == EX_SOURCE_MAJOR);
+    return (which == DPPR_DENSE_P || which == DPPR_DENSE_R) && (dtype == DPPR_F64 || dtype == DPPR_F32) &&
+           (layout == DPPR_VERTEX_MAJOR || layout == DPPR_SOURCE_MAJOR);
 }
 
-constexpr size_t ex_elem_bytes(int dtype) { return dtype == EX_F32 ? 4 : 8; }
+constexpr size_t ex_elem_bytes(int dtype) { return dtype == DPPR_F32 ? 4 : 8; }
 // bytes a dense destination must hold, and its alignment (the element size); the same for both layouts
 constexpr size_t ex_dense_bytes(int dtype, int n, int64_t V) { return ex_elem_bytes(dtype) * (size_t)n * (size_t)V; }
 // element index of (vertex v, source i)
 constexpr size_t ex_dense_index(int layout, int n, int64_t V, int64_t v, int i) {
-    return layout == EX_SOURCE_MAJOR ? (size_t)i * (size_t)V + (size_t)v : (size_t)v * (size_t)n + (size_t)i;
+    return layout == DPPR_SOURCE_MAJOR ? (size_t)i * (size_t)V + (size_t)v : (size_t)v * (size_t)n + (size_t)i;
 }
 
 // [ptr, ptr + bytes) lies inside the allocation [base, base + size) and ptr is aligned to `align` (a power of two)

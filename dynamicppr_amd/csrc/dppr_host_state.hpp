@@ -162,6 +162,61 @@ struct Group : SolveState {
     DevBuf<GPushCtl> pctl;
 };
 
+// What a query needs of a state, slot or group alike (dppr_host_query.hpp): p / r rows gw doubles wide, n lanes, the state's mark
+// and what its last solve left
+struct StateView {
+    const double *p, *r;
+    int gw, n;
+    DevBuf<double> &mark;
+    const SolveState &st;
+    bool group; // (the words of a rejection name a slot or a group)
+};
+inline StateView view(Slot &s) { return {s.p, s.r, 1, 1, s.mark, s, false}; }
+inline StateView view(Group &g) { return {g.p, g.r, g.gw, g.n, g.mark, g, true}; }
+
+// The workspace of the state queries, family by family: all of it allocated on a family's first call and grown on demand
+struct QueryWork {
+    struct TopK { // dppr_topk.hpp
+        DevBuf<unsigned char> ws;           // pass-1 and refinement histograms, per-lane control words (zeroed per query)
+        DevBuf<unsigned long long> out_key; // [16][DPPR_TOPK_MAX] result lists before ordering
+        DevBuf<int> out_row;
+        DevBuf<int> cand;                   // candidate lists: [n][cap] internal rows
+        DevBuf<unsigned char> res; PinBuf<unsigned char> pin; // ordered results (device / pinned host): counts, ids, p, r
+    } tk;
+    struct ReadAt {
+        DevBuf<unsigned char> buf; // point reads: ids, then p and r outputs (dppr_group_score_at: ids, then the scores)
+    } ra;
+    struct Weighted { // a group as a weighted set of targets (dppr_wquery.hpp)
+        DevBuf<double> w;     // [16][16] weights of the call
+        DevBuf<double> score; // scratch state: [occupied rows][q] scores
+        DevBuf<int> ext;      // ... and the external id of every row of it
+    } wq;
+    struct Changes { // what a batch moved (dppr_changes.hpp)
+        DevBuf<double> abs, d; // scratch states: [occupied rows][n] |p - mark| and p - mark
+        DevBuf<int> ext;       // ... and the external id of every row of them
+        DevBuf<unsigned char> res; PinBuf<unsigned char> pin; // counts, moved, ids, deltas, p (dppr_changes_plan.hpp): device / pinned host
+    } ch;
+    struct Export { // dppr_export.hpp, dppr_export_plan.hpp; the block grows with a host destination's cap
+        DevBuf<unsigned short> mask; // [V] which lanes qualify at every external id
+        DevBuf<int> cnt;             // [tiles][16] qualifying ids per tile and lane
+        DevBuf<long long> base;      // [tiles][16] first output position of a tile's entries of a lane
+        DevBuf<unsigned char> blk; PinBuf<unsigned char> pin; // head (offsets, go), then ids / p / r of a host destination: device / pinned host
+    } ex;
+    struct Dot { // the state folded over the vertex axis (dppr_dot.hpp, dppr_dot_plan.hpp)
+        DevBuf<double> part;      // one partial per (tile, output), output-major
+        DevBuf<unsigned char> in; // a sparse call: its tile table and columns, and the ids / w of a host source
+        DevBuf<unsigned char> blk; PinBuf<unsigned char> pin; // head (the flag), then the results of a host destination: device / pinned host
+        dppr::DotTable tb;        // host side of the tile table (kept for its capacity)
+        bool lds_set = false;     // the dense pass was given its dynamic LDS limit
+    } dot;
+    struct Walk { // forward walks and the refinement of point queries (dppr_walk.hpp, dppr_walk_plan.hpp)
+        DevBuf<int> starts;       // [m] the starts / queried ids of the call
+        DevBuf<int> ends;         // [m][W] endpoints of a host destination and of a refine call
+        DevBuf<double> res;       // a refine call: folded [m][2 n], then est | corr | sumsq [m][n] each
+        std::vector<int64_t> off; // a refine call: the offsets q * W of its m queries (kept for its capacity)
+    } wk;
+};
+
 } // namespace
 
 struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pending row moves: dppr_idspace.hpp)
@@ -327,39 +382,10 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     DevBuf<double> mv_tmp;      // device: the rows in flight
     DevBuf<int> d_ext2int;  // device copy of ext2int, refreshed on demand
     DevBuf<double> d_xfer;  // V doubles: staging of p / r in external order
-    // queries of a state (dppr_topk.hpp), all allocated on the first query
+    // queries of a state (dppr_host_query.hpp)
     DevBuf<int> d_int2ext;          // device copy of int2ext (live and parked zones), refreshed by the queries only
     unsigned i2e_gen_on_device = 0;    // IdSpace::map_gen that copy was taken at
-    DevBuf<unsigned char> tk_ws;    // pass-1 and refinement histograms, per-lane control words (zeroed per query)
-    DevBuf<unsigned long long> tk_out_key; // [16][DPPR_TOPK_MAX] result lists before ordering
-    DevBuf<int> tk_out_row;
-    DevBuf<int> tk_cand;            // candidate lists: [n][cap] internal rows
-    DevBuf<unsigned char> tk_res; PinBuf<unsigned char> tk_pin; // ordered results (device / pinned host): counts, ids, p, r
-    DevBuf<unsigned char> ra_buf;   // point reads: ids, then p and r outputs (dppr_group_score_at: ids, then the scores)
-    // a group as a weighted set of targets (dppr_wquery.hpp), allocated on the first such query and grown on demand
-    DevBuf<double> wq_w;            // [16][16] weights of the call
-    DevBuf<double> wq_score;        // scratch state: [occupied rows][q] scores
-    DevBuf<int> wq_ext;             // ... and the external id of every row of it
-    // what a batch moved (dppr_changes.hpp), allocated on the first dppr_changes and grown on demand
-    DevBuf<double> ch_abs, ch_d;    // scratch states: [occupied rows][n] |p - mark| and p - mark
-    DevBuf<int> ch_ext;             // ... and the external id of every row of them
-    DevBuf<unsigned char> ch_res; PinBuf<unsigned char> ch_pin; // counts, moved, ids, deltas, p (dppr_changes_plan.hpp): device / pinned host
-    // the exports (dppr_export.hpp, dppr_export_plan.hpp), allocated on the first export; the block grows with a host destination's cap
-    DevBuf<unsigned short> ex_mask; // [V] which lanes qualify at every external id
-    DevBuf<int> ex_cnt;             // [tiles][16] qualifying ids per tile and lane
-    DevBuf<long long> ex_base;      // [tiles][16] first output position of a tile's entries of a lane
-    DevBuf<unsigned char> ex_blk; PinBuf<unsigned char> ex_pin; // head (offsets, go), then ids / p / r of a host destination: device / pinned host
-    // the state folded over the vertex axis (dppr_dot.hpp, dppr_dot_plan.hpp), allocated on the first such call and grown on demand
-    DevBuf<double> dot_part;        // one partial per (tile, output), output-major
-    DevBuf<unsigned char> dot_in;   // a sparse call: its tile table and columns, and the ids / w of a host source
-    DevBuf<unsigned char> dot_blk; PinBuf<unsigned char> dot_pin; // head (the flag), then the results of a host destination: device / pinned host
-    dppr::DotTable dot_tb;          // host side of the tile table (kept for its capacity)
-    bool dot_lds_set = false;       // the dense pass was given its dynamic LDS limit
-    // forward walks and the refinement of point queries (dppr_walk.hpp, dppr_walk_plan.hpp), allocated on the first such call and grown on demand
-    DevBuf<int> wk_starts;          // [m] the starts / queried ids of the call
-    DevBuf<int> wk_ends;            // [m][W] endpoints of a host destination and of a refine call
-    DevBuf<double> wk_res;          // a refine call: folded [m][2 n], then est | corr | sumsq [m][n] each
-    std::vector<int64_t> wk_off;    // a refine call: the offsets q * W of its m queries (kept for its capacity)
+    QueryWork q;                    // their workspace
     int walk_form = 0;              // 0: lane refill, 1: one walk per thread (dppr_debug_walk_form)
     float query_ms = -1.0f;         // dppr_set_profiling: device time of the last top-k, changes, export or dot call, first to last kernel (dppr_debug_query_ms)
     std::vector<int32_t> h_tmp1, h_tmp2;

@@ -16,8 +16,7 @@
 // A wave of the lane-refill kernel owns walk_range(total, wave): contiguous, whole multiples of 64 but for the last.
 #pragma once
 
-#include <cstddef>
-#include <cstdint>
+#include "dppr_query_plan.hpp"
 
 #if defined(__HIPCC__)
 #define WALK_HD __host__ __device__ __forceinline__
@@ -27,11 +26,7 @@
 
 namespace dppr {
 
-// the values of include/dppr.h (asserted equal in dppr_host_query.hpp)
-constexpr int WALK_MAX_M = 4096;
-constexpr int WALK_MAX_W = 1 << 20;
-constexpr int64_t WALK_MAX_TOTAL = (int64_t)1 << 26;
-constexpr int WALK_DEST_HOST = 0, WALK_DEST_DEVICE = 1;
+constexpr int64_t WALK_MAX_TOTAL = (int64_t)1 << 26; // walks of one call (the limits of m and W: include/dppr.h)
 
 constexpr int WALK_MAX_STEPS = 256;
 constexpr uint32_t WALK_STOP_BELOW = 0x26666666u; // floor(0.15 * 2^32)
@@ -139,18 +134,15 @@ WALK_HD void walk_range(int64_t total, int64_t per_wave, int64_t wave, int64_t *
 
 // ---- argument checks ------------------------------------------------------------------------------------------------------------
 inline bool walk_sizes_ok(int64_t m, int64_t W) {
-    return m >= 1 && m <= WALK_MAX_M && W >= 1 && W <= WALK_MAX_W && m * W <= WALK_MAX_TOTAL;
+    return m >= 1 && m <= DPPR_WALK_MAX_M && W >= 1 && W <= DPPR_WALK_MAX_W && m * W <= WALK_MAX_TOTAL;
 }
-inline bool walk_dest_ok(int dest) { return dest == WALK_DEST_HOST || dest == WALK_DEST_DEVICE; }
+inline bool walk_dest_ok(int dest) { return dest == DPPR_DEST_HOST || dest == DPPR_DEST_DEVICE; }
 inline bool walk_args_ok(const void *starts, int64_t m, int64_t W, int dest, const void *out_ends) {
     return walk_sizes_ok(m, W) && walk_dest_ok(dest) && starts && out_ends;
 }
 inline bool refine_args_ok(const void *ids, int64_t m, int64_t W, const void *out_est) { return walk_sizes_ok(m, W) && ids && out_est; }
-inline bool walk_ids_ok(const int32_t *ids, int64_t m, int64_t V) {
-    for (int64_t i = 0; i < m; ++i)
-        if (ids[i] < 0 || ids[i] >= V) return false;
-    return true;
-}
+// (the name tests/native/walk_plan_test.cpp checks it by)
+inline bool walk_ids_ok(const int32_t *ids, int64_t m, int64_t V) { return ids_in_range(ids, m, V); }
 // the state of a refine call: converged, and standing on the epoch the walks run over (-2: set by dppr_write, anything goes)
 inline bool refine_epoch_ok(int last_epoch, int epoch_id) { return last_epoch == -2 || last_epoch == epoch_id; }
 

@@ -106,7 +106,7 @@ static double fold_pieces(const double *t, int64_t m, int G) {
 
 int main() {
     long cases = 0;
-    static_assert(DOT_TILE == 256 && DOT_WG_SLOTS == 2048 && DOT_BLOCK == 65536 && DOT_TPB == 32 && DOT_MAX_F == 4096, "the constants of the contract");
+    static_assert(DOT_TILE == 256 && DOT_WG_SLOTS == 2048 && DOT_BLOCK == 65536 && DOT_TPB == 32 && DPPR_DOT_MAX_F == 4096, "the constants of the contract");
     const int64_t Ms[] = {0, 1, 255, 256, 257, 65535, 65536, 65537, (int64_t)1 << 22};
     // tile, block and column counts
     for (int64_t m : Ms) {
@@ -119,12 +119,12 @@ int main() {
     }
     CHECK(dot_tiles(((int64_t)1 << 33) + 1) == ((int64_t)1 << 22) + 1, "tile count past 2^31 slots");
     CHECK(dot_cols(((int64_t)1 << 33) + 1) == (((int64_t)1 << 17) + 1) * 32, "column count past 2^31 slots");
-    CHECK(dot_dense_h_bytes(DOT_F64, 4096, ((int64_t)1 << 31) - 1) == (size_t)8 * 4096 * (size_t)(((int64_t)1 << 31) - 1), "h bytes past 2^31");
-    CHECK(dot_dense_h_bytes(DOT_F32, 3, 1000) == 12000 && dot_elem_bytes(DOT_F32) == 4 && dot_elem_bytes(DOT_F64) == 8, "element sizes");
-    CHECK(dot_h_index(DOT_FEATURE_MAJOR, 4096, (int64_t)1 << 30, 4095, ((int64_t)1 << 30) - 1) == ((size_t)1 << 42) - 1, "last element, feature-major");
-    CHECK(dot_h_index(DOT_VERTEX_MAJOR, 4096, (int64_t)1 << 30, 4095, ((int64_t)1 << 30) - 1) == ((size_t)1 << 42) - 1, "last element, vertex-major");
-    CHECK(dot_h_index(DOT_FEATURE_MAJOR, 7, 100, 2, 5) == 205 && dot_h_index(DOT_VERTEX_MAJOR, 7, 100, 2, 5) == 37, "strides");
-    CHECK(dot_out_bytes(4096, 16) == 524288 && dot_block_bytes(3, 10, DOT_DEST_HOST) == 8 + 240 && dot_block_bytes(3, 10, DOT_DEST_DEVICE) == 8, "block");
+    CHECK(dot_dense_h_bytes(DPPR_F64, 4096, ((int64_t)1 << 31) - 1) == (size_t)8 * 4096 * (size_t)(((int64_t)1 << 31) - 1), "h bytes past 2^31");
+    CHECK(dot_dense_h_bytes(DPPR_F32, 3, 1000) == 12000 && dot_elem_bytes(DPPR_F32) == 4 && dot_elem_bytes(DPPR_F64) == 8, "element sizes");
+    CHECK(dot_h_index(DPPR_H_FEATURE_MAJOR, 4096, (int64_t)1 << 30, 4095, ((int64_t)1 << 30) - 1) == ((size_t)1 << 42) - 1, "last element, feature-major");
+    CHECK(dot_h_index(DPPR_H_VERTEX_MAJOR, 4096, (int64_t)1 << 30, 4095, ((int64_t)1 << 30) - 1) == ((size_t)1 << 42) - 1, "last element, vertex-major");
+    CHECK(dot_h_index(DPPR_H_FEATURE_MAJOR, 7, 100, 2, 5) == 205 && dot_h_index(DPPR_H_VERTEX_MAJOR, 7, 100, 2, 5) == 37, "strides");
+    CHECK(dot_out_bytes(4096, 16) == 524288 && dot_block_bytes(3, 10, DPPR_DEST_HOST) == 8 + 240 && dot_block_bytes(3, 10, DPPR_DEST_DEVICE) == 8, "block");
     // the dense workspace: whole chunks inside the budget, one chunk at the least, never more features than asked for
     for (int64_t V : {(int64_t)1, (int64_t)257, (int64_t)65536 + 257, (int64_t)1 << 22, ((int64_t)1 << 31) - 1})
         for (int n : {1, 3, 10, 16})
@@ -219,7 +219,7 @@ int main() {
                   !dot_sparse_args_ok(0, good, P, P, 0, 4097, 0, P) && !dot_sparse_args_ok(0, good, P, P, 0, 4, 2, P) && !dot_sparse_args_ok(0, good, P, P, 0, 4, 0, nullptr),
               "bad sparse calls");
         const int32_t ids[] = {0, 9, 4, 9}, lo[] = {0, -1, 3}, hi[] = {0, 10, 3};
-        CHECK(dot_ids_ok(ids, 4, 10) && !dot_ids_ok(lo, 3, 10) && !dot_ids_ok(hi, 3, 10) && dot_ids_ok(hi, 0, 10), "ids");
+        CHECK(ids_in_range(ids, 4, 10) && !ids_in_range(lo, 3, 10) && !ids_in_range(hi, 3, 10) && ids_in_range(hi, 0, 10), "ids");
     }
 
     // the fold

@@ -42,12 +42,12 @@ int main() {
     static_assert(EX_TILE <= 256 && EX_TILE % 64 == 0, "a tile is whole waves, at most 256 ids");
     static_assert(EX_HEAD_BYTES % 8 == 0, "the sections start aligned");
     // dense destinations
-    for (int dtype : {EX_F64, EX_F32})
-        for (int layout : {EX_VERTEX_MAJOR, EX_SOURCE_MAJOR})
+    for (int dtype : {DPPR_F64, DPPR_F32})
+        for (int layout : {DPPR_VERTEX_MAJOR, DPPR_SOURCE_MAJOR})
             for (int n = 1; n <= EX_LANES; ++n)
                 for (int64_t V : Vs) {
                     ++cases;
-                    const size_t el = dtype == EX_F32 ? 4 : 8;
+                    const size_t el = dtype == DPPR_F32 ? 4 : 8;
                     CHECK(ex_elem_bytes(dtype) == el, "dtype %d", dtype);
                     const size_t bytes = ex_dense_bytes(dtype, n, V);
                     CHECK(bytes == el * (uint64_t)n * (uint64_t)V, "dtype %d n %d V %lld", dtype, n, (long long)V);
@@ -57,11 +57,11 @@ int main() {
                     CHECK((last + 1) * el == bytes, "the last element ends the destination");
                     if (V > 1) {
                         const size_t a = ex_dense_index(layout, n, V, 1, 0);
-                        CHECK(a == (layout == EX_SOURCE_MAJOR ? (size_t)1 : (size_t)n), "vertex stride");
+                        CHECK(a == (layout == DPPR_SOURCE_MAJOR ? (size_t)1 : (size_t)n), "vertex stride");
                     }
                     if (n > 1) {
                         const size_t a = ex_dense_index(layout, n, V, 0, 1);
-                        CHECK(a == (layout == EX_SOURCE_MAJOR ? (size_t)V : (size_t)1), "source stride");
+                        CHECK(a == (layout == DPPR_SOURCE_MAJOR ? (size_t)V : (size_t)1), "source stride");
                     }
                     if (V <= 257) { // every (v, i) once
                         std::vector<unsigned char> seen((size_t)n * (size_t)V, 0);
@@ -76,9 +76,9 @@ int main() {
     {
         ++cases;
         const int64_t V = ((int64_t)1 << 28) + 3;
-        CHECK(ex_dense_bytes(EX_F64, 16, V) == (size_t)8 * 16 * (size_t)V, "bytes past 2^35");
-        CHECK(ex_dense_index(EX_SOURCE_MAJOR, 16, V, V - 1, 15) == (size_t)16 * (size_t)V - 1, "index past 2^31");
-        CHECK(ex_dense_index(EX_VERTEX_MAJOR, 16, V, V - 1, 15) == (size_t)16 * (size_t)V - 1, "index past 2^31");
+        CHECK(ex_dense_bytes(DPPR_F64, 16, V) == (size_t)8 * 16 * (size_t)V, "bytes past 2^35");
+        CHECK(ex_dense_index(DPPR_SOURCE_MAJOR, 16, V, V - 1, 15) == (size_t)16 * (size_t)V - 1, "index past 2^31");
+        CHECK(ex_dense_index(DPPR_VERTEX_MAJOR, 16, V, V - 1, 15) == (size_t)16 * (size_t)V - 1, "index past 2^31");
         CHECK(ex_cap_clamped(std::numeric_limits<int64_t>::max(), V, 16) == 16 * V, "cap clamps to V * n in 64 bits");
         CHECK(ex_cap_clamped(5, V, 16) == 5, "a small cap stays");
         const ExLayout l = ex_layout(16 * V, true);
