@@ -10,7 +10,6 @@ namespace {
 // an octet up to 8, two beyond), the sweep also per size of a sweep group (nvx vertices: 1024, or 512 once a 16-wide group
 // exists -- a wide row always, a narrow one on an engine that also has a wide group): f(SPL, GW, NVX) is called with the
 // three as compile-time constants.
-template <int N> using IC = std::integral_constant<int, N>;
 template <class F>
 void with_row(int gw, int nvx, F &&f) {
     auto narrow = [&](auto w) {
@@ -77,20 +76,22 @@ int group_multi_capacity(dppr_engine *e, int spl) {
     return cap;
 }
 
-// One frontier loop of a source group. `tails`: the state was converged before the batch's stream
-// update, so only the batch tails (grouped in batch_tails: each tail one run, dppr_grouping.hpp) can be legal -- no pass over all vertices.
+// What group_push_tail reports: whether it took the frontier and how it ended, the iterations it ran (already in the group's
+// statistics), and -- in and out -- whether the snapshot at hand still owes its pagerank share
+struct PushTail {
+    enum How { NOT_ENTERED, CONVERGED, GAVE_BACK } how = NOT_ENTERED;
+    int iters = 0;
+    bool owed = false;
+};
+
 // The tail of a group's loop in push form (dppr_gpush.hpp). Called between two chunks of sweeps when the frontier is
-// small: g.act[0] / g.x hold the frontier the last sweep left. Returns with *converged set (the loop is over; state as
-// a finished loop leaves it) or cleared (the mode gave up -- an iteration too large for it -- and put the frontier back
-// in sweep form: g.act[0], g.x, frontier sizes in row 0 of g.cnt, the other rows zero), or with *entered false if it
-// did not start (nothing changed). Iterations run are added to *iters and to the group's statistics.
-// *owed: the handed-over snapshot's pagerank share is still to be credited (the last sweep was a deferring one,
+// small: g.act[0] / g.x hold the frontier the last sweep left. Returns CONVERGED (the loop is over; state as
+// a finished loop leaves it) or GAVE_BACK (the mode gave up -- an iteration too large for it -- and put the frontier back
+// in sweep form: g.act[0], g.x, frontier sizes in row 0 of g.cnt, the other rows zero), or NOT_ENTERED if it
+// did not start (nothing changed). Iterations run are counted in t->iters and in the group's statistics.
+// t->owed: the handed-over snapshot's pagerank share is still to be credited (the last sweep was a deferring one,
 // dppr_multi.hpp); on a return in sweep form it says the same about the snapshot handed back.
-int group_push_tail(dppr_engine *e, Group &g, const Epoch &ep, int phase, double eps, long long pairs_at_entry, int *iters, bool *entered,
-                    bool *converged, bool *owed) {
-    *entered = false;
-    *converged = false;
-    const int GWM = GS_MAX;
+int group_push_tail(dppr_engine *e, Group &g, const Epoch &ep, int phase, double eps, long long pairs_at_entry, PushTail *t) {
     const int cap = std::max(1024, std::min(e->gpush_list_cap, e->V));
     if (g.plist[0].capacity() != (size_t)cap || !g.pctl) { // (pctl comes last: a set that failed half way is made again)
         HIP_TRY(loop_wait(e));
@@ -100,7 +101,6 @@ int group_push_tail(dppr_engine *e, Group &g, const Epoch &ep, int phase, double
         HIP_TRY(g.ppre.alloc((size_t)cap + 1));
         HIP_TRY(g.pctl.alloc(1));
     }
-    static thread_local GPushCtl h;
     // no host round trip on the way in: a list that does not fit (overflow) moves nothing and makes the first scan call
     // the mode off, which the read-back of the first chunk shows
     HIP_TRY(hipMemsetAsync(g.pctl, 0, sizeof(GPushCtl), e->stream));
@@ -113,8 +113,8 @@ int group_push_tail(dppr_engine *e, Group &g, const Epoch &ep, int phase, double
                            g.pctl, 0, g.x, g.r, false);
     });
     HIP_TRY(hipGetLastError());
-    *entered = true;
-    const int credit_first = *owed ? 1 : 0; // (iteration 0 of this mode settles it; every later one credits as it snapshots)
+    static thread_local GPushCtl h;
+    const int credit_first = t->owed ? 1 : 0; // (iteration 0 of this mode settles it; every later one credits as it snapshots)
     const long long max_edges = gpush_edge_bound(e->gpush_max_edges, ep.n_ggroups);
     const int grid = 256;
     static const bool trace = getenv("DPPR_GROUP_TRACE") != nullptr;
@@ -144,13 +144,14 @@ int group_push_tail(dppr_engine *e, Group &g, const Epoch &ep, int phase, double
         }
         }
         HIP_TRY(hipGetLastError());
+        // (not read_back: the chunk's control block and log come back into this function's own GPushCtl, not into e->pinned)
         HIP_TRY(hipMemcpyAsync(&h, g.pctl, sizeof(GPushCtl), hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(loop_wait(e));
         for (int i = it_done; i < h.it; ++i) {
             const long long F = lane_sum(h.F[i & (GPUSH_LOG - 1)]);
             if (F == 0) continue;
             account_iteration(g.st, F, ITER_PUSH);
-            ++*iters;
+            ++t->iters;
             if (trace)
                 fprintf(stderr, "[gpush ] phase %d iteration +%d  frontier pairs %9lld  adds %lld\n", phase, i, F, h.atomics[i & (GPUSH_LOG - 1)]);
         }
@@ -158,177 +159,183 @@ int group_push_tail(dppr_engine *e, Group &g, const Epoch &ep, int phase, double
         if (h.it > it_done) last_adds = h.atomics[(h.it - 1) & (GPUSH_LOG - 1)];
         it_done = h.it;
         known_n = h.n[h.it & 1];
-        if (h.stop && h.it == 0 && h.overflow) { // the frontier did not fit the lists: nothing was moved, the sweeps go on
-            *entered = false;
-            return DPPR_OK;
-        }
+        if (h.stop && h.it == 0 && h.overflow) return DPPR_OK; // the frontier did not fit the lists: nothing was moved, the sweeps go on (NOT_ENTERED)
         if (h.stop) { // an iteration too large for this form: the queued vertices go back to sweep form
             if (trace) fprintf(stderr, "[gpush ] phase %d: an iteration of %d vertices called itself off after %d iterations\n", phase, h.n[h.it & 1], h.it);
-            HIP_TRY(hipMemsetAsync(g.cnt, 0, sizeof(int) * 3 * GWM, e->stream));
+            HIP_TRY(hipMemsetAsync(g.cnt, 0, sizeof(int) * 3 * GS_MAX, e->stream));
             with_row(g.gw, [&](auto spl, auto gw) {
                 hipLaunchKernelGGL((k_gpush_leave<decltype(spl)::value, decltype(gw)::value>), dim3(grid_for(ep.grp_n_int, BLOCK / OCT)), dim3(BLOCK), 0,
                                    e->stream, ep.grp_n_int, g.act[0], g.x, g.r, g.p, h.it > 0 ? 1 : 0, phase, eps, g.cnt);
             });
             HIP_TRY(hipGetLastError());
-            if (h.it > 0) *owed = false; // (iteration 0 settled the hand-over, k_gpush_leave credited what it queued)
+            if (h.it > 0) t->owed = false; // (iteration 0 settled the hand-over, k_gpush_leave credited what it queued)
+            t->how = PushTail::GAVE_BACK;
             return DPPR_OK;
         }
         if (h.n[h.it & 1] == 0) {
-            *converged = true;
+            t->how = PushTail::CONVERGED;
             return DPPR_OK;
         }
         if (it_done >= e->max_iters) return fail(e, DPPR_ERR_NOT_CONVERGED, "iteration cap hit");
     }
 }
 
-int group_loop(dppr_engine *e, Group &g, const Epoch &ep, int phase, double eps, bool tails) {
+// One frontier loop of a source group: what its chunks share and hand to each other. Each chunk below says what it requires
+// and what it leaves.
+struct GroupLoop {
+    dppr_engine *const e;
+    Group &g;
+    const Epoch &ep;
+    const int phase;
+    const double eps;
     const int hp = phase == PHASE_BOTH ? 0 : phase; // (loop histories: the merged loop uses slot 0)
-    int cur = 0;
-    const int GWM = GS_MAX;
-    HIP_TRY(hipMemsetAsync(g.cnt, 0, sizeof(int) * 3 * GWM, e->stream));
+    CounterRing ring;  // row of g.cnt that holds the live frontier sizes, one per source
+    // pagerank is credited every other sweep (dppr_multi.hpp): the seeding credited its snapshot, so the first sweep defers;
+    // `owed` = the live snapshot's share has not been added yet, the next sweep is a crediting one
+    bool owed = false;
+    int it = 0, active_iters = 0; // loop position; the position after the last iteration that saw a frontier
+    bool more = false; // a frontier is left
+    long long F = 0;   // ... of this many pairs, as the last chunk of one-sweep launches read them back
+    // the tail of the loop as pushes (dppr_gpush.hpp): below plan.push_thr frontier pairs, one-sweep launches only
+    GroupLoopPlan plan;
+    int sweep_grid = 1; // workgroups of a one-sweep launch
+    int *row(int k) const { return g.cnt + k * GS_MAX; }
+
+    // requires a window whose sweep groups are all resident at once; leaves a run of sweeps done as ONE launch (k_gsweep<.., true>)
+    // and accounted, and if it ran out of sweeps the live sizes in row 0 -- or, after a failed roll-call, nothing changed and
+    // one-sweep launches from here on (re-armed later)
+    int multi_chunk() {
+        const int n = group_multi_sweeps(g.hist.hint[hp], it, e->chunk_iters, e->chunk_explicit);
+        HIP_TRY(hipMemsetAsync(g.mlog, 0, sizeof(int) * (size_t)(n + 2) * GS_MAX, e->stream));
+        HIP_TRY(hipMemsetAsync(e->bar, 0, sizeof(GridBar), e->stream));
+        int rc = timed_launch(e, 0, e->profiling, [&] { // (g.mlog: the status word's row, then a row of frontier sizes per sweep)
+            launch_gsweep<true>(e, g, ep, phase, eps, owed,
+                                {ep.n_ggroups, row(ring.cur), row(3), row(4), g.mlog + GS_MAX, n, e->bar, g.mlog, e->persist_ticks, e->persist_rollcall_extra});
+        });
+        if (rc) return rc;
+        HIP_TRY(hipGetLastError());
+        if ((rc = read_back(e, g.mlog, (size_t)(n + 2) * GS_MAX))) return rc;
+        const int st = e->pinned[0];
+        g.st.persist_launches++;
+        if (st & GSM_FAULT) return fail(e, DPPR_ERR_HIP, "a grid barrier of the multi-sweep group launch timed out");
+        if (st & GSM_ABORTED) {
+            give_up_resident(e, g.st);
+            return DPPR_OK;
+        }
+        const int sweeps = st & GSM_SWEEPS;
+        account_sweeps(g.st, e->pinned + GS_MAX, sweeps, GS_MAX, ITER_SWEEP, it, &active_iters); // (the launch ran no sweep on an empty frontier)
+        if (e->profiling && (rc = credit_launch(e, g.st, 0, false))) return rc;
+        if (sweeps & 1) { // (no rotation: the launch keeps its own counters, rows 3 and 4)
+            swap_snapshots(g, true);
+            owed = !owed;
+        }
+        it += sweeps;
+        more = !(st & GSM_CONVERGED);
+        if (!more) return DPPR_OK;
+        // out of sweeps: the live frontier sizes are in row `sweeps`; the launch left them in cnt[3] -- make them cnt[0]
+        HIP_TRY(hipMemcpyAsync(row(0), row(3), sizeof(int) * GS_MAX, hipMemcpyDeviceToDevice, e->stream));
+        HIP_TRY(hipMemsetAsync(row(1), 0, sizeof(int) * 2 * GS_MAX, e->stream));
+        ring.cur = 0;
+        more = lane_sum(e->pinned + GS_MAX + sweeps * GS_MAX) > 0;
+        return DPPR_OK;
+    }
+    // requires e->pinned to hold the live frontier sizes in row ring.cur; leaves a chunk of one-sweep launches
+    // (GroupLoopPlan::next_chunk) enqueued, read back and accounted, all of g.cnt in e->pinned, and F / more on what they left
+    int sweep_chunk() {
+        const int n = plan.next_chunk(g.hist, hp, it, lane_sum(e->pinned + ring.cur * GS_MAX), e->chunk_iters, e->chunk_explicit);
+        for (int k = 0; k < n; ++k) {
+            int rc = timed_launch(e, k, e->profiling, [&] {
+                launch_gsweep<false>(e, g, ep, phase, eps, owed,
+                                     {sweep_grid, row(ring.cur), row(ring.nxt()), row(ring.zer()), row(5 + k), 1, nullptr, nullptr, 0, 0,
+                                      g.gq + (g.gq_seq % 3) * GQ_PAD, g.gq + ((g.gq_seq + 1) % 3) * GQ_PAD});
+            });
+            if (rc) return rc;
+            swap_snapshots(g, true);
+            ring.rotate();
+            g.gq_seq++;
+            owed = !owed; // (if the frontier emptied on the way, the later launches do nothing and nothing is owed: `more` is false below)
+        }
+        HIP_TRY(hipGetLastError());
+        if (int rc = read_back(e, g.cnt, (size_t)(5 + n) * GS_MAX)) return rc; // (the per-chunk log follows the five counter rows)
+        int rc = account_sweeps(g.st, e->pinned + 5 * GS_MAX, n, GS_MAX, ITER_SWEEP, it, &active_iters, [&](int k, long long f) -> int {
+            plan.saw_frontier(f, it + k);
+            if (!e->profiling) return DPPR_OK;
+            float ms = 0;
+            if (int rc2 = credit_launch(e, g.st, k, true, &ms)) return rc2;
+            static const bool trace = getenv("DPPR_GROUP_TRACE") != nullptr; // (diagnostic: one line per sweep)
+            if (trace) fprintf(stderr, "[gsweep] phase %d sweep %3d  frontier pairs %9lld  %7.1f us\n", phase, it + k, f, ms * 1e3);
+            return DPPR_OK;
+        });
+        if (rc) return rc;
+        F = lane_sum(e->pinned + ring.cur * GS_MAX);
+        more = F > 0;
+        it += n;
+        return DPPR_OK;
+    }
+    // requires a chunk just read back with F pairs left, few enough for the push form (GroupLoopPlan::enter_push); leaves the
+    // tail of the loop run as pushes (group_push_tail) -- or, where that form gave the frontier back or did not take it, the
+    // frontier in sweep form with its sizes read back, and a much lower threshold for the next try
+    int hand_to_push_tail() {
+        plan.saw_frontier(F, it);
+        PushTail t;
+        t.owed = owed;
+        if (int rc = group_push_tail(e, g, ep, phase, eps, F, &t)) return rc;
+        owed = t.owed;
+        if (t.how != PushTail::NOT_ENTERED) {
+            active_iters = it + t.iters;
+            it += t.iters;
+        }
+        if (t.how == PushTail::CONVERGED) more = false;
+        else plan.push_declined(F);
+        if (t.how != PushTail::GAVE_BACK) return DPPR_OK;
+        ring.cur = 0; // back in sweep form: frontier sizes in row 0
+        if (int rc = read_back(e, row(0), GS_MAX)) return rc;
+        more = lane_sum(e->pinned) > 0;
+        return DPPR_OK;
+    }
+};
+
+// One frontier loop of a source group. `tails`: the state was converged before the batch's stream
+// update, so only the batch tails (grouped in batch_tails: each tail one run, dppr_grouping.hpp) can be legal -- no pass over all vertices.
+int group_loop(dppr_engine *e, Group &g, const Epoch &ep, int phase, double eps, bool tails) {
+    GroupLoop l{e, g, ep, phase, eps};
+    HIP_TRY(hipMemsetAsync(g.cnt, 0, sizeof(int) * 3 * GS_MAX, e->stream));
     if (tails) {
         HIP_TRY(hipMemsetAsync(g.act[0], 0, g.act_bytes, e->stream));
         if (ep.L > 0) {
             with_row(g.gw, [&](auto spl, auto gw) {
                 hipLaunchKernelGGL((k_gseed_tails<decltype(spl)::value, decltype(gw)::value>), dim3(grid_for(ep.L, BLOCK / OCT)), dim3(BLOCK), 0,
-                                   e->stream, batch_tails(e, ep), ep.L, g.r, g.x, g.p, g.act[0], phase, eps, g.cnt + cur * GWM);
+                                   e->stream, batch_tails(e, ep), ep.L, g.r, g.x, g.p, g.act[0], phase, eps, l.row(0));
             });
         }
     } else {
         // dense seeding: every legal vertex of every source enters, snapshot taken
         with_row(g.gw, [&](auto spl, auto gw) {
             hipLaunchKernelGGL((k_gseed_dense<decltype(spl)::value, decltype(gw)::value>), dim3(grid_for(ep.grp_n_int, BLOCK / OCT)), dim3(BLOCK), 0,
-                               e->stream, ep.grp_n_int, g.r, g.x, g.p, g.act[0], phase, eps, g.cnt + cur * GWM);
+                               e->stream, ep.grp_n_int, g.r, g.x, g.p, g.act[0], phase, eps, l.row(0));
         });
         g.st.inspected += (int64_t)ep.grp_n_int * g.n;
     }
     HIP_TRY(hipGetLastError());
-    int *log = g.cnt + 5 * GWM;
-    auto any_left = [](const int *row) { return lane_sum(row) > 0; };
-    HIP_TRY(hipMemcpyAsync(e->pinned, g.cnt + cur * GWM, sizeof(int) * GWM, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(loop_wait(e));
-    bool more = any_left(e->pinned);
-    int active_iters = 0;
+    int rc = read_back(e, l.row(0), GS_MAX);
+    if (rc) return rc;
+    l.more = lane_sum(e->pinned) > 0;
     if (e->gsweep_grid_cap <= 0) {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess || cus <= 0) cus = 256;
         e->gsweep_grid_cap = std::min(2 * cus, STAT_SLOTS);
     }
-    const int sweep_grid = std::min(std::max(ep.n_ggroups, 1), e->gsweep_grid_cap);
-    // pagerank is credited every other sweep (dppr_multi.hpp): the seeding credited its snapshot, so the first sweep defers;
-    // `owed` = the live snapshot's share has not been added yet, the next sweep is a crediting one
-    bool owed = false;
-    // the tail of the loop as pushes (dppr_gpush.hpp): below plan.push_thr frontier pairs, one-sweep launches only
-    GroupLoopPlan plan;
-    plan.push_thr = group_push_threshold(e->gpush_enter_pairs, ep.n_ggroups, e->gpush_auto_factor);
-    for (int it = 0; more;) {
-        if (it >= e->max_iters) return fail(e, DPPR_ERR_NOT_CONVERGED, "iteration cap hit");
-        // ---- a window whose sweep groups are all resident at once: a run of sweeps as ONE launch (k_gsweep<.., true>)
+    l.sweep_grid = std::min(std::max(ep.n_ggroups, 1), e->gsweep_grid_cap);
+    l.plan.push_thr = group_push_threshold(e->gpush_enter_pairs, ep.n_ggroups, e->gpush_auto_factor);
+    while (l.more) {
+        if (l.it >= e->max_iters) return fail(e, DPPR_ERR_NOT_CONVERGED, "iteration cap hit");
+        // a window whose sweep groups are all resident at once: a run of sweeps as ONE launch; otherwise one-sweep launches in chunks
         const int mcap = e->group_resident && e->persist_mode && e->persist_ok && e->chunk_iters > 1 ? group_multi_capacity(e, g.spl) : 0;
-        if (mcap > 0 && ep.n_ggroups > 0 && ep.n_ggroups <= mcap) {
-            const int n = group_multi_sweeps(g.hist.hint[hp], it, e->chunk_iters, e->chunk_explicit);
-            HIP_TRY(hipMemsetAsync(g.mlog, 0, sizeof(int) * (size_t)(n + 2) * GWM, e->stream));
-            HIP_TRY(hipMemsetAsync(e->bar, 0, sizeof(GridBar), e->stream));
-            if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[0], e->stream));
-            // (g.mlog: the status word's row, then a row of frontier sizes per sweep)
-            launch_gsweep<true>(e, g, ep, phase, eps, owed,
-                                {ep.n_ggroups, g.cnt + cur * GWM, g.cnt + 3 * GWM, g.cnt + 4 * GWM, g.mlog + GWM, n, e->bar, g.mlog,
-                                 e->persist_ticks, e->persist_rollcall_extra});
-            if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[1], e->stream));
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(e->pinned, g.mlog, sizeof(int) * (size_t)(n + 2) * GWM, hipMemcpyDeviceToHost, e->stream));
-            HIP_TRY(loop_wait(e));
-            const int st = e->pinned[0];
-            g.st.persist_launches++;
-            if (st & GSM_FAULT) return fail(e, DPPR_ERR_HIP, "a grid barrier of the multi-sweep group launch timed out");
-            if (st & GSM_ABORTED) { // not co-resident: nothing was changed; one-sweep launches from here on (re-armed later)
-                g.st.persist_aborts++;
-                e->persist_ok = false;
-                e->persist_retry = PERSIST_RETRY_BATCHES;
-                continue;
-            }
-            const int sweeps = st & GSM_SWEEPS;
-            account_sweeps(g.st, e->pinned + GWM, sweeps, GWM, ITER_SWEEP, it, &active_iters); // (the launch ran no sweep on an empty frontier)
-            if (e->profiling) {
-                float ms = 0;
-                HIP_TRY(hipEventElapsedTime(&ms, e->evpool[0], e->evpool[1]));
-                g.st.push_ms += ms;
-                g.st.push_launches++;
-            }
-            if (sweeps & 1) {
-                std::swap(g.x, g.x2);
-                std::swap(g.act[0], g.act[1]);
-                owed = !owed;
-            }
-            it += sweeps;
-            if (st & GSM_CONVERGED) break;
-            // out of sweeps: the live frontier sizes are in row `sweeps`; the launch left them in cnt[3] -- make them cnt[0]
-            HIP_TRY(hipMemcpyAsync(g.cnt, g.cnt + 3 * GWM, sizeof(int) * GWM, hipMemcpyDeviceToDevice, e->stream));
-            HIP_TRY(hipMemsetAsync(g.cnt + GWM, 0, sizeof(int) * 2 * GWM, e->stream));
-            cur = 0;
-            more = any_left(e->pinned + GWM + sweeps * GWM);
-            continue;
-        }
-        // ---- one-sweep launches, enqueued in chunks (GroupLoopPlan::next_chunk); e->pinned holds the live frontier sizes in row `cur`
-        const int n = plan.next_chunk(g.hist, hp, it, lane_sum(e->pinned + cur * GWM), e->chunk_iters, e->chunk_explicit);
-        for (int k = 0; k < n; ++k) {
-            const int nxt = (cur + 1) % 3, zer = (cur + 2) % 3;
-            if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[2 * k], e->stream));
-            launch_gsweep<false>(e, g, ep, phase, eps, owed,
-                                 {sweep_grid, g.cnt + cur * GWM, g.cnt + nxt * GWM, g.cnt + zer * GWM, log + k * GWM, 1, nullptr, nullptr, 0, 0,
-                                  g.gq + (g.gq_seq % 3) * GQ_PAD, g.gq + ((g.gq_seq + 1) % 3) * GQ_PAD});
-            if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[2 * k + 1], e->stream));
-            std::swap(g.x, g.x2);
-            std::swap(g.act[0], g.act[1]);
-            cur = nxt;
-            g.gq_seq++;
-            owed = !owed; // (if the frontier emptied on the way, the later launches do nothing and nothing is owed: `more` is false below)
-        }
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(e->pinned, g.cnt, sizeof(int) * (size_t)(5 * GWM + n * GWM), hipMemcpyDeviceToHost,
-                               e->stream));
-        HIP_TRY(loop_wait(e));
-        int rc = account_sweeps(g.st, e->pinned + 5 * GWM, n, GWM, ITER_SWEEP, it, &active_iters, [&](int k, long long F) -> int {
-            plan.saw_frontier(F, it + k);
-            if (e->profiling) {
-                float ms = 0;
-                HIP_TRY(hipEventElapsedTime(&ms, e->evpool[2 * k], e->evpool[2 * k + 1]));
-                g.st.push_ms += ms;
-                g.st.push_launches++;
-                g.st.sweep_ms += ms;
-                g.st.sweep_launches++;
-                static const bool trace = getenv("DPPR_GROUP_TRACE") != nullptr; // (diagnostic: one line per sweep)
-                if (trace) fprintf(stderr, "[gsweep] phase %d sweep %3d  frontier pairs %9lld  %7.1f us\n", phase, it + k, F, ms * 1e3);
-            }
-            return DPPR_OK;
-        });
+        if (mcap > 0 && ep.n_ggroups > 0 && ep.n_ggroups <= mcap) rc = l.multi_chunk();
+        else if (!(rc = l.sweep_chunk()) && l.plan.enter_push(l.more, l.F)) rc = l.hand_to_push_tail();
         if (rc) return rc;
-        const long long F = lane_sum(e->pinned + cur * GWM);
-        more = F > 0;
-        it += n;
-        if (plan.enter_push(more, F)) {
-            plan.saw_frontier(F, it);
-            int pushed = 0;
-            bool entered = false, conv = false;
-            rc = group_push_tail(e, g, ep, phase, eps, F, &pushed, &entered, &conv, &owed);
-            if (rc) return rc;
-            if (entered) {
-                active_iters = it + pushed;
-                it += pushed;
-                if (conv) more = false;
-                else { // back in sweep form: frontier sizes in row 0
-                    cur = 0;
-                    HIP_TRY(hipMemcpyAsync(e->pinned, g.cnt, sizeof(int) * GWM, hipMemcpyDeviceToHost, e->stream));
-                    HIP_TRY(loop_wait(e));
-                    more = any_left(e->pinned);
-                    plan.push_declined(F);
-                }
-            } else { // (the frontier did not fit the lists)
-                plan.push_declined(F);
-            }
-        }
     }
-    plan.finish(g.hist, hp, active_iters);
+    l.plan.finish(g.hist, l.hp, l.active_iters);
     return DPPR_OK;
 }
 

@@ -7,11 +7,70 @@
 
 namespace {
 
-int read_count(dppr_engine *e, const int *dptr, int *out) {
-    HIP_TRY(hipMemcpyAsync(e->pinned, dptr, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+template <int N> using IC = std::integral_constant<int, N>; // (a block size, row width, ... handed to a launch as a compile-time constant)
+
+// ---- the steps every loop shares, single source and source group alike
+// n ints from device memory are in e->pinned when this returns (a read-back of a loop: a sign of life, loop_wait)
+int read_back(dppr_engine *e, const void *dptr, size_t n) {
+    HIP_TRY(hipMemcpyAsync(e->pinned, dptr, sizeof(int) * n, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(loop_wait(e));
+    return DPPR_OK;
+}
+int read_count(dppr_engine *e, const int *dptr, int *out) {
+    if (int rc = read_back(e, dptr, 1)) return rc;
     *out = e->pinned[0];
     return DPPR_OK;
+}
+inline long long pinned_u64(const dppr_engine *e, int word) { // (a 64-bit counter that came back at that int of e->pinned)
+    unsigned long long d;
+    memcpy(&d, e->pinned + word, sizeof(d));
+    return (long long)d;
+}
+
+// launch k of a chunk between the events of its pair (`timed`: profiling, or the push / sweep pricing wants its time) ...
+template <class Launch>
+int timed_launch(dppr_engine *e, int k, bool timed, Launch &&launch) {
+    if (timed) HIP_TRY(hipEventRecord(e->evpool[2 * k], e->stream));
+    launch();
+    if (timed) HIP_TRY(hipEventRecord(e->evpool[2 * k + 1], e->stream));
+    return DPPR_OK;
+}
+// ... and what it took, once the chunk was read back, in the profile: every launch of a loop counts as a push launch, ONE sweep
+// also as a sweep launch (the sweep kernel's roofline; resident and multi-sweep launches are none)
+inline int credit_launch(dppr_engine *e, dppr_stats_t &st, int k, bool one_sweep, float *ms_out = nullptr) {
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, e->evpool[2 * k], e->evpool[2 * k + 1]));
+    st.push_ms += ms;
+    st.push_launches++;
+    if (one_sweep) {
+        st.sweep_ms += ms;
+        st.sweep_launches++;
+    }
+    if (ms_out) *ms_out = ms;
+    return DPPR_OK;
+}
+
+// a roll-call failed (the grid was not co-resident): the launch changed nothing; this engine goes on with one launch per
+// iteration (a later slot_update re-arms the resident forms after PERSIST_RETRY_BATCHES; group_update never does)
+inline void give_up_resident(dppr_engine *e, dppr_stats_t &st) {
+    st.persist_aborts++;
+    e->persist_ok = false;
+    e->persist_retry = PERSIST_RETRY_BATCHES;
+}
+
+// The three rotating counters of a loop: a launch takes the live frontier size from `cur`, counts the next frontier into nxt()
+// and zeroes zer() for the launch after it
+struct CounterRing {
+    int cur = 0;
+    int nxt() const { return (cur + 1) % 3; }
+    int zer() const { return (cur + 2) % 3; }
+    void rotate() { cur = nxt(); }
+};
+// a sweep wrote every entry of x2 (`bits`: and the activity bitmap act[1]): they are the next snapshot
+template <class State>
+void swap_snapshots(State &o, bool bits) {
+    std::swap(o.x, o.x2);
+    if (bits) std::swap(o.act[0], o.act[1]);
 }
 
 // ---- accounting of a read-back log: `width` frontier sizes per logged iteration (a source group: one per source)
@@ -48,6 +107,250 @@ inline void account_sweeps(dppr_stats_t &st, const int *rows, int n, int width, 
     account_sweeps(st, rows, n, width, kind, it, active_iters, [](int, long long) -> int { return DPPR_OK; });
 }
 
+int pull_min_frontier(const dppr_engine *e) { return dppr::pull_min_frontier(e->pull_min_frontier, e->Ed); }
+
+// The sweep kernels are instantiated per workgroup size (= max tiles per sweep group x 64: the groups themselves were cut by
+// the builder): f(PB) is called with it as a compile-time constant. ANY: every size dppr_set_tuning takes -- the bitmap form
+// of k_pull_iter alone; a size that is not 256 / 512 / 1024 never runs resident and always takes that form.
+template <bool ANY, class F>
+void with_block(int pb, F &&f) {
+    switch (pb) {
+    case 256: return f(IC<256>{});
+    case 512: return f(IC<512>{});
+    case 1024: return f(IC<1024>{});
+    }
+    if constexpr (ANY) {
+        switch (pb) {
+        case 384: return f(IC<384>{});
+        case 576: return f(IC<576>{});
+        case 640: return f(IC<640>{});
+        case 768: return f(IC<768>{});
+        case 896: return f(IC<896>{});
+        }
+    }
+    f(IC<1024>{});
+}
+
+// k_pull_resident (dppr_resident.hpp) at the sweep's block size: n sweeps from counter `cur` on; plan: PLAN_* of a whole-batch
+// launch (0: a run of sweeps of one loop), upd: the batch's records if the launch applies them itself
+void launch_resident(dppr_engine *e, Slot &s, const Epoch &ep, double eps, int cur, int phase, int n, int plan, const ResUpdate &upd) {
+    with_block<false>(sweep_block(e), [&](auto pb) {
+        hipLaunchKernelGGL(k_pull_resident<decltype(pb)::value>, dim3(ep.n_groups), dim3(decltype(pb)::value), 0, e->stream, ep.grp_n_int,
+                           ep.grp_tile, ep.out_row_ptr, ep.out_col, s.x, e->res_arena, e->res_arena_stride, s.r, s.p, s.cnt, cur, phase, eps,
+                           s.dstats, s.log, n, e->bar, s.cnt + 7, e->persist_ticks, e->persist_rollcall_extra, plan,
+                           ep.res_valid ? ep.res_pk : nullptr, upd);
+    });
+}
+// ... timed where profiling is on; the counters, the status word (s.cnt[7]) and the log of n entries are in e->pinned afterwards
+int run_resident(dppr_engine *e, Slot &s, const Epoch &ep, double eps, int cur, int phase, int n, int plan, const ResUpdate &upd) {
+    if (int rc = timed_launch(e, 0, e->profiling, [&] { launch_resident(e, s, ep, eps, cur, phase, n, plan, upd); })) return rc;
+    HIP_TRY(hipGetLastError());
+    return read_back(e, s.cnt, (size_t)(CNT_HDR + n));
+}
+
+// One frontier loop of a single source (run_frontier_loop, below): what its steps share and hand to each other. Each step says what
+// it requires and what it leaves.
+struct FrontierLoop {
+    dppr_engine *const e;
+    Slot &s;
+    const Epoch &ep;
+    const int phase;
+    const double eps;
+    int buf;           // s.ft[buf]: the frontier's list (where form.list)
+    CounterRing ring;  // s.cnt[ring.cur]: its size
+    FrontierForm form; // which of list and snapshot is live
+    int F, prevF = 0;  // the frontier's size as last read back, and the one read before it
+    long long D = -1;  // in-edges of the frontier (binned windows), -1 = not counted
+    int follow = 4;    // size of the next follow-up chunk of per-iteration sweeps
+    int it, active_iters; // loop position; the position after the last iteration that saw a frontier
+    // fixed when the loop starts (set in the constructor, in this order: each may read the ones before it)
+    int pull_min, pcap0, push_grid;
+    bool sync_sched, binned, use_bits, use_status;
+    const HubTable hubs{ep.hub_v, ep.hub_degp1, ep.n_hubs};
+    unsigned long long *const dsum = reinterpret_cast<unsigned long long *>(s.cnt + 8); // three slots beside the rotating counters
+
+    FrontierLoop(dppr_engine *e_, Slot &s_, const Epoch &ep_, int phase_, double eps_, int buf_, int cur_, const LoopEntry &en)
+        : e(e_), s(s_), ep(ep_), phase(phase_), eps(eps_), buf(buf_), ring{cur_}, form(en), F(en.F), it(en.it), active_iters(en.it) {
+        pull_min = pull_min_frontier(e);
+        pcap0 = persist_capacity(e);
+        sync_sched = e->schedule == DPPR_SCHEDULE_SYNC;
+        // the sparse grid must cover the largest frontier a push chunk can meet
+        push_grid = pull_min == PULL_NEVER ? 2048 : std::min(2048, std::max(64, (pull_min * 4 / WAVE + 3) / 4));
+        binned = ep.bin_valid && ep.bin_n_int <= ep.grp_n_int && (pcap0 <= 0 || ep.n_groups > pcap0 || e->bin_mode == 2);
+        // Sweeps on a window that cannot run resident carry the activity bitmap of their snapshot (k_pull_iter<.., true>)
+        use_bits = e->sweep_bits && !binned && !en.dense && (pcap0 <= 0 || ep.n_groups > pcap0);
+        // The merged loop always filters through the status array: adds of both signs can take a residual across the threshold more
+        // than once per iteration, and with the crossing test every crossing would append -- the next-frontier list (V entries) could
+        // overflow. One entry per vertex and launch keeps it bounded.
+        use_status = e->status_dedup || phase == PHASE_BOTH;
+    }
+
+    // requires the list in s.ft[buf] or the snapshot in s.x (after a sweep); leaves the list, made from the snapshot if need be
+    int need_list() {
+        if (!form.needs_list()) return DPPR_OK;
+        HIP_TRY(hipMemsetAsync(s.cnt + 7, 0, sizeof(int), e->stream));
+        hipLaunchKernelGGL(k_list_from_dense, dim3(grid_for(ep.grp_n_int, BLOCK * INSPECT_ITEMS)), dim3(BLOCK), 0, e->stream,
+                           s.x, ep.grp_n_int, s.cnt + ring.cur, s.ft[buf], s.cnt + 7);
+        HIP_TRY(hipGetLastError());
+        form.list_made();
+        return DPPR_OK;
+    }
+    // requires the list in s.ft[buf]; leaves its snapshot in s.x (bm: and its activity bitmap in s.act[0]; extr: the residuals it took
+    // zeroed). Grid-stride over a frontier whose size is only known on the device (k > 0): sized for the last size the host saw, capped
+    int take_snapshot(bool bm, bool extr) {
+        if (bm) HIP_TRY(hipMemsetAsync(s.act[0], 0, s.act_bytes, e->stream));
+        hipLaunchKernelGGL(k_snapshot_dense, dim3(std::min(grid_for(std::max(F, 1 << 14)), 1024)), dim3(BLOCK), 0, e->stream, s.ft[buf],
+                           s.cnt + ring.cur, s.r, s.p, s.x, bm ? s.act[0] : (uint32_t *)nullptr, phase == PHASE_BOTH ? 1 : 0, extr ? 1 : 0);
+        form.snapshot_taken(extr);
+        return DPPR_OK;
+    }
+    // requires F > 0 as read back; leaves the frontier's external ids appended to the slot's trace (a blocking copy of the list)
+    int trace_frontier() {
+        if (int rc = need_list()) return rc;
+        size_t old = s.trace_ids.size();
+        s.trace_ids.resize(old + (size_t)F);
+        // (not read_back: the ids go to the trace's own memory, not to e->pinned)
+        HIP_TRY(hipMemcpyAsync(s.trace_ids.data() + old, s.ft[buf], sizeof(int) * (size_t)F, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(loop_wait(e));
+        for (size_t i = old; i < s.trace_ids.size(); ++i) s.trace_ids[i] = e->int2ext[(size_t)s.trace_ids[i]];
+        s.trace_off.push_back((int64_t)s.trace_ids.size());
+        return DPPR_OK;
+    }
+    // requires *pull = the decision by vertex count; leaves it replaced by what each form would cost where the window is priced (dppr_loop_plan.hpp).
+    // The frontier's in-edges D are counted by the sweep that left it (k_bin_reduce) or, for a list, here by k_front_degree (one more read-back)
+    int price(bool costly, bool *pull) {
+        if (!costly || !e->cost_model || sync_sched || s.trace || e->pull_min_frontier != 0) return DPPR_OK;
+        if (cost_needs_degrees(F, D)) {
+            if (int rc = need_list()) return rc;
+            HIP_TRY(hipMemsetAsync(dsum + ring.cur, 0, sizeof(unsigned long long), e->stream));
+            hipLaunchKernelGGL(k_front_degree, dim3(grid_for(F)), dim3(BLOCK), 0, e->stream, s.ft[buf], s.cnt + ring.cur, ep.row_ptr, dsum + ring.cur);
+            HIP_TRY(hipGetLastError());
+            if (int rc = read_back(e, dsum + ring.cur, 2)) return rc;
+            D = pinned_u64(e, 0);
+        }
+        if (cost_decides(F, D)) *pull = cost_says_sweep(F, D, s.sweep_us, ep.Ed, s.atomic_ns);
+        return DPPR_OK;
+    }
+    // requires a chunk of n >= 2 sweeps on a window whose groups fit the chip; leaves them run as ONE resident launch (dppr_resident.hpp) and
+    // accounted, the live count in cnt[0], the last sweep's snapshot in s.x -- or, after a failed roll-call, nothing changed and that form given up
+    int resident_run(int n) {
+        if (form.needs_snapshot())
+            if (int rc = take_snapshot(false, false)) return rc;
+        HIP_TRY(hipMemsetAsync(e->bar, 0, sizeof(GridBar), e->stream));
+        if (int rc = run_resident(e, s, ep, eps, ring.cur, phase, n, 0, ResUpdate{})) return rc;
+        const int status = e->pinned[7];
+        s.st.persist_launches++;
+        if (status & PERSIST_FAULT) return fail(e, DPPR_ERR_HIP, "grid barrier of the resident sweep timed out");
+        if (status & PERSIST_ABORTED) {
+            give_up_resident(e, s.st);
+            return DPPR_OK;
+        }
+        account_sweeps(s.st, e->pinned + CNT_HDR, n, 1, ITER_RESIDENT_SWEEP, it, &active_iters);
+        if (e->profiling)
+            if (int rc = credit_launch(e, s.st, 0, false)) return rc;
+        ring.cur = 0;
+        form.resident_returned((status & PERSIST_CONVERGED) != 0);
+        prevF = F;
+        F = e->pinned[0];
+        it += n;
+        return DPPR_OK;
+    }
+    // requires the list in s.ft[buf] (synchronous schedule: and its snapshot); leaves one push iteration enqueued (k_push_iter +
+    // the deferred big rows, k_push_big): the next list in s.ft[buf ^ 1], the snapshot consumed
+    void push_iteration(int *log_slot) {
+        int *big_cnt = s.cnt + 5 + (int)(s.iter_seq & 1), *big_zero = s.cnt + 5 + (int)((s.iter_seq + 1) & 1);
+        s.iter_seq++;
+        const Dedup dd{use_status ? s.status : nullptr, (int)(s.iter_seq & 0x3fffffff)};
+        int *nxt = s.cnt + ring.nxt(), *zer = s.cnt + ring.zer();
+        auto launch = [&](auto dense) { // (k_push_iter<false> is handed no repair flag: only a snapshot can have extracted)
+            hipLaunchKernelGGL(k_push_iter<decltype(dense)::value>, dim3(push_grid), dim3(BLOCK), 0, e->stream, s.ft[buf], s.cnt + ring.cur, s.ft[buf ^ 1],
+                               nxt, zer, s.x, ep.row_ptr, ep.adj, hubs, s.big, big_cnt, big_zero, e->big_row, s.r, s.p, phase, eps, s.dstats, log_slot, dd,
+                               form.extracted ? 1 : 0);
+        };
+        if (form.dense) launch(std::true_type{});
+        else launch(std::false_type{});
+        hipLaunchKernelGGL(k_push_big, dim3(512), dim3(BLOCK), 0, e->stream, s.big, big_cnt, s.ft[buf ^ 1], nxt, ep.adj, hubs, s.r, phase, eps,
+                           s.dstats, dd);
+        form.pushed();
+    }
+    // requires the snapshot in s.x (use_bits: with its bitmap); leaves one gather sweep enqueued (k_pull_iter): the next snapshot
+    // in s.x again, the frontier counted but not listed
+    void gather_sweep(int *log_slot) {
+        auto launch = [&](auto pb, auto bits) {
+            hipLaunchKernelGGL((k_pull_iter<decltype(pb)::value, decltype(bits)::value>), dim3(std::min(std::max(ep.n_groups, 1), 1024)),
+                               dim3(decltype(pb)::value), 0, e->stream, ep.grp_n_int, ep.grp_tile, ep.n_groups, s.cnt + ring.cur, ep.out_row_ptr,
+                               ep.out_col, s.x, s.x2, s.r, s.p, s.cnt + ring.nxt(), s.cnt + ring.zer(), phase, eps, s.dstats + 1, log_slot,
+                               std::min(e->big_row, PULL_BIG_ROW_DEFAULT), s.act[0], s.act[1]);
+        };
+        if (use_bits) with_block<true>(sweep_block(e), [&](auto pb) { launch(pb, std::true_type{}); });
+        else with_block<false>(sweep_block(e), [&](auto pb) { launch(pb, std::false_type{}); });
+        swap_snapshots(s, use_bits);
+        form.swept();
+    }
+    // requires the snapshot in s.x; leaves one binned sweep enqueued, two streaming passes over the epoch's binned edge layout
+    // (dppr_binned.hpp): the next snapshot in s.x again (costly: and the in-edges of the frontier it leaves in dsum[nxt])
+    void binned_sweep(int *log_slot, bool costly) {
+        if (ep.n_chunks > 0)
+            hipLaunchKernelGGL(k_bin_scatter, dim3(ep.n_chunks), dim3(BIN_NT), (size_t)e->bin_ha_tiles * WAVE * sizeof(double), e->stream,
+                               ep.bin_n_int, s.cnt + ring.cur, ep.acut, ep.chunks, ep.hl, ep.tb, ep.tdelta, ep.n_runs, s.x, e->bin_vals);
+        const int rows_cap = e->bin_hb_tiles * WAVE;
+        hipLaunchKernelGGL(k_bin_reduce, dim3(ep.n_b + (ep.grp_n_int - ep.bin_n_int + rows_cap - 1) / rows_cap), dim3(BIN_NT),
+                           (size_t)rows_cap * 20, e->stream, ep.grp_n_int, ep.bin_n_int, ep.n_b, s.cnt + ring.cur, ep.bcut, rows_cap, ep.out_row_ptr,
+                           ep.dl, ep.vb, ep.Ed, e->bin_vals, s.x, s.x2, s.r, s.p, s.cnt + ring.nxt(), s.cnt + ring.zer(), phase, eps, s.dstats + 1,
+                           log_slot, e->directed ? ep.row_ptr : (const int *)nullptr, costly ? dsum + ring.nxt() : (unsigned long long *)nullptr);
+        swap_snapshots(s, false);
+        form.swept();
+    }
+    // requires a chunk of n iterations of one kind, decided; leaves them enqueued, one launch (pair) per iteration, each between
+    // its events where it is timed (profiling; a priced iteration that runs alone)
+    int enqueue_chunk(int n, bool pull, bool costly) {
+        const bool timed = e->profiling || (costly && n == 1); // (the push / sweep decision prices both by what the last ones took)
+        for (int k = 0; k < n; ++k) {
+            if ((pull || sync_sched) && form.needs_snapshot()) // (a sweep repairs by itself, rn -= x[v]: it extracts nothing)
+                if (int rc = take_snapshot(use_bits && pull, e->pre_extract && !pull)) return rc;
+            if (costly) HIP_TRY(hipMemsetAsync(dsum + ring.nxt(), 0, sizeof(unsigned long long), e->stream));
+            int rc = timed_launch(e, k, timed, [&] {
+                if (pull && binned) binned_sweep(s.log + k, costly);
+                else if (pull) gather_sweep(s.log + k);
+                else push_iteration(s.log + k);
+            });
+            if (rc) return rc;
+            buf ^= 1;
+            ring.rotate();
+        }
+        HIP_TRY(hipGetLastError());
+        return DPPR_OK;
+    }
+    // requires those n iterations enqueued; leaves them read back (ONE read-back per chunk: the counters and the F of each iteration) and
+    // accounted -- statistics, profile, trace line, the pricing's running means -- and F / prevF / D / it on the frontier they left
+    int finish_chunk(int n, bool pull, bool costly) {
+        if (int rc = read_back(e, s.cnt, (size_t)(CNT_HDR + n))) return rc;
+        int rc = account_sweeps(s.st, e->pinned + CNT_HDR, n, 1, pull ? ITER_SWEEP : ITER_PUSH, it, &active_iters, [&](int k, long long f) -> int {
+            if (pull && binned) s.st.binned_sweeps++;
+            if (!e->profiling) return DPPR_OK;
+            float ms = 0;
+            if (int rc2 = credit_launch(e, s.st, k, pull, &ms)) return rc2;
+            static const bool trace = getenv("DPPR_LOOP_TRACE") != nullptr; // (diagnostic: one line per iteration of a profiled batch)
+            if (trace)
+                fprintf(stderr, "[loop  ] phase %d iteration %3d  %-6s frontier %9lld  %8.1f us\n", phase, it + k,
+                        pull ? (binned ? "binned" : "sweep") : "push", f, ms * 1e3);
+            return DPPR_OK;
+        });
+        if (rc) return rc;
+        if (costly && n == 1 && e->pinned[CNT_HDR] > 0) { // what a sweep of this window costs / what an atomic of a push does (running means)
+            float ms = 0;
+            HIP_TRY(hipEventElapsedTime(&ms, e->evpool[0], e->evpool[1])); // (the pair of launch 0, read again: this is no profile entry)
+            if (pull) s.sweep_us = mean_sweep_us(s.sweep_us, ms);
+            else s.atomic_ns = mean_atomic_ns(s.atomic_ns, ms, D);
+        }
+        prevF = F;
+        F = e->pinned[ring.cur];
+        D = binned && pull ? pinned_u64(e, 8 + 2 * ring.cur) : -1; // (the sweep counted the in-edges of the frontier it left)
+        it += n;
+        return DPPR_OK;
+    }
+};
+
 // Frontier loop: PPRRevPushGPU::ExecuteOptimized's while(1) (gpu/PPRRevPushGPU.cuh:106-130).
 // On entry s.ft[buf] holds the frontier and s.cnt[cur] its size; cnt[(cur+1)%3] is zero and
 // the dense vectors s.x / s.x2 are all zero (no snapshot taken yet) -- unless `entry` says
@@ -63,276 +366,38 @@ inline void account_sweeps(dppr_stats_t &st, const int *rows, int n, int width, 
 //
 // `entry` (LoopEntry, dppr_loop_plan.hpp) describes a loop that is picked up in the middle (after a
 // launch of batch_ahead that ended before the loop did).
-
-int pull_min_frontier(const dppr_engine *e) { return dppr::pull_min_frontier(e->pull_min_frontier, e->Ed); }
-
-// k_pull_resident (dppr_resident.hpp) at the sweep's block size: n sweeps from counter `cur` on; plan: PLAN_* of a whole-batch
-// launch (0: a run of sweeps of one loop), upd: the batch's records if the launch applies them itself
-void launch_resident(dppr_engine *e, Slot &s, const Epoch &ep, double eps, int cur, int phase, int n, int plan, const ResUpdate &upd) {
-#define DPPR_LAUNCH_PERSIST(PB)                                                                                       \
-    hipLaunchKernelGGL(k_pull_resident<PB>, dim3(ep.n_groups), dim3(PB), 0, e->stream, ep.grp_n_int, ep.grp_tile,       \
-                       ep.out_row_ptr, ep.out_col, s.x, e->res_arena, e->res_arena_stride, s.r, s.p, s.cnt, cur, phase, eps, s.dstats, s.log,  \
-                       n, e->bar, s.cnt + 7, e->persist_ticks, e->persist_rollcall_extra, plan,                       \
-                       ep.res_valid ? ep.res_pk : nullptr, upd)
-    switch (sweep_block(e)) {
-    case 256: DPPR_LAUNCH_PERSIST(256); break;
-    case 512: DPPR_LAUNCH_PERSIST(512); break;
-    default: DPPR_LAUNCH_PERSIST(1024); break;
-    }
-#undef DPPR_LAUNCH_PERSIST
-}
-
 int run_frontier_loop(dppr_engine *e, Slot &s, const Epoch &ep, int phase, double eps, int buf, int cur,
                       LoopEntry entry = LoopEntry()) {
     const int hp = phase == PHASE_BOTH ? 0 : phase; // (loop histories: the merged loop uses slot 0)
-    const int pull_min = pull_min_frontier(e);
-    const bool sync_sched = e->schedule == DPPR_SCHEDULE_SYNC;
-    const HubTable hubs{ep.hub_v, ep.hub_degp1, ep.n_hubs};
-    // the sparse grid must cover the largest frontier a push chunk can meet
-    const int push_grid = pull_min == PULL_NEVER ? 2048 : std::min(2048, std::max(64, (pull_min * 4 / WAVE + 3) / 4));
-    // Sweeps on a window that cannot run resident carry the activity bitmap of their snapshot (k_pull_iter<.., true>)
-    const int pcap0 = persist_capacity(e);
-    const bool binned = ep.bin_valid && ep.bin_n_int <= ep.grp_n_int && (pcap0 <= 0 || ep.n_groups > pcap0 || e->bin_mode == 2);
-    const bool use_bits = e->sweep_bits && !binned && !entry.dense && (pcap0 <= 0 || ep.n_groups > pcap0);
-    // The merged loop always filters through the status array: adds of both signs can take a residual across the threshold more
-    // than once per iteration, and with the crossing test every crossing would append -- the next-frontier list (V entries) could
-    // overflow. One entry per vertex and launch keeps it bounded.
-    const bool use_status = e->status_dedup || phase == PHASE_BOTH;
-    if (use_status && !s.status) { // (first use: -1 everywhere = "never queued")
+    FrontierLoop l(e, s, ep, phase, eps, buf, cur, entry);
+    if (l.use_status && !s.status) { // (first use: -1 everywhere = "never queued")
         HIP_TRY(s.status.alloc((size_t)e->V));
         HIP_TRY(hipMemsetAsync(s.status, 0xff, sizeof(int) * (size_t)e->V, e->stream));
     }
-    bool extracted = false;         // ... and that snapshot zeroed the residuals it took (InspectExtra): the push needs no repair
-    bool dense_valid = entry.dense; // s.x holds the snapshot of the current frontier (p already updated)
-    bool list_valid = !entry.dense; // s.ft[buf] holds the frontier as a list (sweeps only count it)
-    bool any_pull = entry.any_pull;
-    bool x_clean = false;           // a resident launch ended the loop and left s.x / s.x2 all zero
-    auto make_list = [&]() -> int { // dense snapshot -> sparse list (after a sweep)
-        HIP_TRY(hipMemsetAsync(s.cnt + 7, 0, sizeof(int), e->stream));
-        hipLaunchKernelGGL(k_list_from_dense, dim3(grid_for(ep.grp_n_int, BLOCK * INSPECT_ITEMS)), dim3(BLOCK), 0, e->stream,
-                           s.x, ep.grp_n_int, s.cnt + cur, s.ft[buf], s.cnt + 7);
-        HIP_TRY(hipGetLastError());
-        list_valid = true;
-        return DPPR_OK;
-    };
-    int F = entry.F, prevF = 0, active_iters = entry.it;
-    long long D = -1; // in-edges of the current frontier (binned windows), -1 = not counted
-    unsigned long long *dsum = reinterpret_cast<unsigned long long *>(s.cnt + 8); // three slots beside the rotating counters
-    int follow = 4; // size of the next follow-up chunk of per-iteration sweeps
     int rc = DPPR_OK;
-    if (F < 0 && (rc = read_count(e, s.cnt + cur, &F))) return rc;
+    if (l.F < 0 && (rc = read_count(e, s.cnt + cur, &l.F))) return rc;
     if (entry.it == 0) {
-        s.start_dense[hp] = F >= pull_min;
-        s.last_F0[hp] = F;
+        s.start_dense[hp] = l.F >= l.pull_min;
+        s.last_F0[hp] = l.F;
     }
-    for (int it = entry.it; F > 0;) {
-        if (it >= e->max_iters) return fail(e, DPPR_ERR_NOT_CONVERGED, "iteration cap hit");
-        if (s.trace) {
-            if (!list_valid && (rc = make_list())) return rc;
-            size_t old = s.trace_ids.size();
-            s.trace_ids.resize(old + (size_t)F);
-            HIP_TRY(hipMemcpyAsync(s.trace_ids.data() + old, s.ft[buf], sizeof(int) * (size_t)F,
-                                   hipMemcpyDeviceToHost, e->stream));
-            HIP_TRY(loop_wait(e));
-            for (size_t i = old; i < s.trace_ids.size(); ++i) s.trace_ids[i] = e->int2ext[(size_t)s.trace_ids[i]];
-            s.trace_off.push_back((int64_t)s.trace_ids.size());
-        }
-        bool pull = F >= pull_min;
+    while (l.F > 0) {
+        if (l.it >= e->max_iters) return fail(e, DPPR_ERR_NOT_CONVERGED, "iteration cap hit");
+        if (s.trace && (rc = l.trace_frontier())) return rc;
+        bool pull = l.F >= l.pull_min;
         // a window whose iterations cost hundreds of microseconds and more (twitter / friendster size): decisions per iteration
-        const bool costly = window_costly(binned, e->chunk_explicit, s.sweep_us, ep.Ed);
-        if (costly && e->cost_model && !sync_sched && !s.trace && e->pull_min_frontier == 0) {
-            // push or sweep by what each would cost (dppr_loop_plan.hpp); the frontier's in-edges are counted by the sweep that left
-            // it (k_bin_reduce) or, for a list, by k_front_degree
-            if (cost_needs_degrees(F, D)) {
-                if (!list_valid && (rc = make_list())) return rc;
-                HIP_TRY(hipMemsetAsync(dsum + cur, 0, sizeof(unsigned long long), e->stream));
-                hipLaunchKernelGGL(k_front_degree, dim3(grid_for(F)), dim3(BLOCK), 0, e->stream, s.ft[buf], s.cnt + cur, ep.row_ptr, dsum + cur);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipMemcpyAsync(e->pinned, dsum + cur, sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-                HIP_TRY(loop_wait(e));
-                unsigned long long d;
-                memcpy(&d, e->pinned, sizeof(d));
-                D = (long long)d;
-            }
-            if (cost_decides(F, D)) pull = cost_says_sweep(F, D, s.sweep_us, ep.Ed, s.atomic_ns);
-        }
-        int n = single_chunk(s.trace, e->chunk_iters, costly, pull, F, prevF, pull_min, s.hist.hint[hp], it);
+        const bool costly = window_costly(l.binned, e->chunk_explicit, s.sweep_us, ep.Ed);
+        if ((rc = l.price(costly, &pull))) return rc;
+        int n = single_chunk(s.trace, e->chunk_iters, costly, pull, l.F, l.prevF, l.pull_min, s.hist.hint[hp], l.it);
         const int pcap = persist_capacity(e);
         const bool resident = pull && n >= 2 && !s.trace && pcap > 0 && ep.n_groups > 0 && ep.n_groups <= pcap && resident_arena(e, ep);
-        n = single_chunk_for_form(n, resident, pull, s.hist, hp, it, follow, e->chunk_iters, e->chunk_explicit);
-        if (!pull && !list_valid && (rc = make_list())) return rc;
-        if (resident) {
-            // ---- a run of dense iterations as ONE resident launch (dppr_resident.hpp)
-            if (!dense_valid) {
-                hipLaunchKernelGGL(k_snapshot_dense, dim3(std::min(grid_for(std::max(F, 1 << 14)), 1024)), dim3(BLOCK), 0,
-                                   e->stream, s.ft[buf], s.cnt + cur, s.r, s.p, s.x, (uint32_t *)nullptr, phase == PHASE_BOTH ? 1 : 0, 0);
-                dense_valid = true;
-            }
-            HIP_TRY(hipMemsetAsync(e->bar, 0, sizeof(GridBar), e->stream));
-            if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[0], e->stream));
-            launch_resident(e, s, ep, eps, cur, phase, n, 0, ResUpdate{});
-            if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[1], e->stream));
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(e->pinned, s.cnt, sizeof(int) * (size_t)(CNT_HDR + n), hipMemcpyDeviceToHost, e->stream));
-            HIP_TRY(loop_wait(e));
-            const int status = e->pinned[7];
-            s.st.persist_launches++;
-            if (status & PERSIST_FAULT) return fail(e, DPPR_ERR_HIP, "grid barrier of the resident sweep timed out");
-            if (status & PERSIST_ABORTED) {
-                // the roll-call failed (the grid was not co-resident): nothing was changed; this engine
-                // goes on with per-iteration launches
-                s.st.persist_aborts++;
-                e->persist_ok = false;
-                e->persist_retry = PERSIST_RETRY_BATCHES;
-                continue;
-            }
-            account_sweeps(s.st, e->pinned + CNT_HDR, n, 1, ITER_RESIDENT_SWEEP, it, &active_iters);
-            if (e->profiling) {
-                float ms = 0;
-                HIP_TRY(hipEventElapsedTime(&ms, e->evpool[0], e->evpool[1]));
-                s.st.push_ms += ms;
-                s.st.push_launches++;
-            }
-            // (s.x holds the snapshot the last sweep wrote)
-            cur = 0;                              // the launch leaves the live count in cnt[0]
-            list_valid = false;
-            any_pull = true;
-            x_clean = (status & PERSIST_CONVERGED) != 0;
-            prevF = F;
-            F = e->pinned[0];
-            it += n;
-            continue;
-        }
-        for (int k = 0; k < n; ++k) {
-            const int nxt = (cur + 1) % 3, zer = (cur + 2) % 3;
-            int *log_slot = s.log + k;
-            if ((pull || sync_sched) && !dense_valid) {
-                // grid-stride over a frontier whose size is only known on the device (k > 0): sized for
-                // the last size the host saw, capped
-                const bool bm = use_bits && pull;
-                if (bm) HIP_TRY(hipMemsetAsync(s.act[0], 0, s.act_bytes, e->stream));
-                extracted = e->pre_extract && !pull; // (a sweep repairs by itself: rn -= x[v])
-                hipLaunchKernelGGL(k_snapshot_dense, dim3(std::min(grid_for(std::max(F, 1 << 14)), 1024)), dim3(BLOCK), 0,
-                                   e->stream, s.ft[buf], s.cnt + cur, s.r, s.p, s.x, bm ? s.act[0] : (uint32_t *)nullptr, phase == PHASE_BOTH ? 1 : 0,
-                                   extracted ? 1 : 0);
-                dense_valid = true;
-            }
-            if (costly) HIP_TRY(hipMemsetAsync(dsum + nxt, 0, sizeof(unsigned long long), e->stream));
-            const bool timed = e->profiling || (costly && n == 1); // (the push / sweep decision prices both by what the last ones took)
-            if (timed) HIP_TRY(hipEventRecord(e->evpool[2 * k], e->stream));
-            if (pull && binned) {
-                // the sweep as two streaming passes over the epoch's binned edge layout (dppr_binned.hpp)
-                if (ep.n_chunks > 0)
-                    hipLaunchKernelGGL(k_bin_scatter, dim3(ep.n_chunks), dim3(BIN_NT), (size_t)e->bin_ha_tiles * WAVE * sizeof(double), e->stream,
-                                       ep.bin_n_int, s.cnt + cur, ep.acut, ep.chunks, ep.hl, ep.tb, ep.tdelta, ep.n_runs, s.x, e->bin_vals);
-                const int rows_cap = e->bin_hb_tiles * WAVE;
-                hipLaunchKernelGGL(k_bin_reduce, dim3(ep.n_b + (ep.grp_n_int - ep.bin_n_int + rows_cap - 1) / rows_cap), dim3(BIN_NT),
-                                   (size_t)rows_cap * 20, e->stream, ep.grp_n_int, ep.bin_n_int, ep.n_b, s.cnt + cur, ep.bcut, rows_cap,
-                                   ep.out_row_ptr, ep.dl, ep.vb, ep.Ed, e->bin_vals, s.x,
-                                   s.x2, s.r, s.p, s.cnt + nxt, s.cnt + zer, phase, eps, s.dstats + 1, log_slot, e->directed ? ep.row_ptr : (const int *)nullptr,
-                                   costly ? dsum + nxt : (unsigned long long *)nullptr);
-                std::swap(s.x, s.x2);
-                dense_valid = true;
-                extracted = false;
-                list_valid = false;
-                any_pull = true;
-            } else if (pull) {
-                // workgroup size = max tiles per group x 64 (the groups themselves were cut by the builder)
-                const int pb = sweep_block(e);
-#define DPPR_LAUNCH_PULL(PB, BITS)                                                                                    \
-    hipLaunchKernelGGL((k_pull_iter<PB, BITS>), dim3(std::min(std::max(ep.n_groups, 1), 1024)), dim3(PB), 0, e->stream, \
-                       ep.grp_n_int, ep.grp_tile, ep.n_groups, s.cnt + cur, ep.out_row_ptr, ep.out_col, s.x, s.x2, s.r, \
-                       s.p, s.cnt + nxt, s.cnt + zer, phase, eps, s.dstats + 1, log_slot,                               \
-                       std::min(e->big_row, PULL_BIG_ROW_DEFAULT), s.act[0], s.act[1])
-                if (use_bits) {
-                    switch (pb) {
-                    case 256: DPPR_LAUNCH_PULL(256, true); break;
-                    case 384: DPPR_LAUNCH_PULL(384, true); break;
-                    case 512: DPPR_LAUNCH_PULL(512, true); break;
-                    case 576: DPPR_LAUNCH_PULL(576, true); break;
-                    case 640: DPPR_LAUNCH_PULL(640, true); break;
-                    case 768: DPPR_LAUNCH_PULL(768, true); break;
-                    case 896: DPPR_LAUNCH_PULL(896, true); break;
-                    default: DPPR_LAUNCH_PULL(1024, true); break;
-                    }
-                    std::swap(s.act[0], s.act[1]);
-                } else { // (block sizes that are not 256 / 512 / 1024 never run resident: they always take the form above)
-                    switch (pb) {
-                    case 256: DPPR_LAUNCH_PULL(256, false); break;
-                    case 512: DPPR_LAUNCH_PULL(512, false); break;
-                    default: DPPR_LAUNCH_PULL(1024, false); break;
-                    }
-                }
-#undef DPPR_LAUNCH_PULL
-                std::swap(s.x, s.x2); // the sweep wrote every entry of x2: it is the next snapshot
-                dense_valid = true;
-                extracted = false;
-                list_valid = false;
-                any_pull = true;
-            } else {
-                int *big_cnt = s.cnt + 5 + (int)(s.iter_seq & 1), *big_zero = s.cnt + 5 + (int)((s.iter_seq + 1) & 1);
-                s.iter_seq++;
-                const Dedup dd{use_status ? s.status : nullptr, (int)(s.iter_seq & 0x3fffffff)};
-                if (dense_valid)
-                    hipLaunchKernelGGL(k_push_iter<true>, dim3(push_grid), dim3(BLOCK), 0, e->stream, s.ft[buf],
-                                       s.cnt + cur, s.ft[buf ^ 1], s.cnt + nxt, s.cnt + zer, s.x, ep.row_ptr, ep.adj, hubs,
-                                       s.big, big_cnt, big_zero, e->big_row, s.r, s.p, phase, eps, s.dstats, log_slot, dd, extracted ? 1 : 0);
-                else
-                    hipLaunchKernelGGL(k_push_iter<false>, dim3(push_grid), dim3(BLOCK), 0, e->stream, s.ft[buf],
-                                       s.cnt + cur, s.ft[buf ^ 1], s.cnt + nxt, s.cnt + zer, s.x, ep.row_ptr, ep.adj, hubs,
-                                       s.big, big_cnt, big_zero, e->big_row, s.r, s.p, phase, eps, s.dstats, log_slot, dd, 0);
-                hipLaunchKernelGGL(k_push_big, dim3(512), dim3(BLOCK), 0, e->stream, s.big, big_cnt, s.ft[buf ^ 1],
-                                   s.cnt + nxt, ep.adj, hubs, s.r, phase, eps, s.dstats, dd);
-                dense_valid = false; // the push consumed (and zeroed) the snapshot
-                extracted = false;
-                list_valid = true;
-            }
-            if (timed) HIP_TRY(hipEventRecord(e->evpool[2 * k + 1], e->stream));
-            buf ^= 1;
-            cur = nxt;
-        }
-        HIP_TRY(hipGetLastError());
-        // one read-back per chunk: the new frontier size and the F of each iteration just run
-        HIP_TRY(hipMemcpyAsync(e->pinned, s.cnt, sizeof(int) * (size_t)(CNT_HDR + n), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(loop_wait(e));
-        rc = account_sweeps(s.st, e->pinned + CNT_HDR, n, 1, pull ? ITER_SWEEP : ITER_PUSH, it, &active_iters, [&](int k, long long f) -> int {
-            if (pull && binned) s.st.binned_sweeps++;
-            if (e->profiling) {
-                float ms = 0;
-                HIP_TRY(hipEventElapsedTime(&ms, e->evpool[2 * k], e->evpool[2 * k + 1]));
-                s.st.push_ms += ms;
-                s.st.push_launches++;
-                if (pull) {
-                    s.st.sweep_ms += ms;
-                    s.st.sweep_launches++;
-                }
-                static const bool trace = getenv("DPPR_LOOP_TRACE") != nullptr; // (diagnostic: one line per iteration of a profiled batch)
-                if (trace)
-                    fprintf(stderr, "[loop  ] phase %d iteration %3d  %-6s frontier %9lld  %8.1f us\n", phase, it + k,
-                            pull ? (binned ? "binned" : "sweep") : "push", f, ms * 1e3);
-            }
-            return DPPR_OK;
-        });
+        n = single_chunk_for_form(n, resident, pull, s.hist, hp, l.it, l.follow, e->chunk_iters, e->chunk_explicit);
+        if (!pull && (rc = l.need_list())) return rc;
+        if (resident) rc = l.resident_run(n); // (a failed roll-call: the same frontier again, now one launch per iteration)
+        else if (!(rc = l.enqueue_chunk(n, pull, costly))) rc = l.finish_chunk(n, pull, costly);
         if (rc) return rc;
-        if (costly && n == 1 && e->pinned[CNT_HDR] > 0) { // what a sweep of this window costs / what an atomic of a push does (running means)
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, e->evpool[0], e->evpool[1]));
-            if (pull) s.sweep_us = mean_sweep_us(s.sweep_us, ms);
-            else s.atomic_ns = mean_atomic_ns(s.atomic_ns, ms, D);
-        }
-        prevF = F;
-        F = e->pinned[cur];
-        if (binned && pull) { // the sweep counted the in-edges of the frontier it left
-            unsigned long long d;
-            memcpy(&d, e->pinned + 8 + 2 * cur, sizeof(d));
-            D = (long long)d;
-        } else {
-            D = -1;
-        }
-        it += n;
     }
-    s.hist.record(hp, active_iters);
-    if (any_pull && !x_clean) { // leave both dense vectors all-zero for the next loop
+    s.hist.record(hp, l.active_iters);
+    if (l.form.must_zero_x()) { // leave both dense vectors all-zero for the next loop
         // only internal ids below n_int are ever written
         HIP_TRY(hipMemsetAsync(s.x, 0, sizeof(double) * (size_t)ep.grp_n_int, e->stream));
         HIP_TRY(hipMemsetAsync(s.x2, 0, sizeof(double) * (size_t)ep.grp_n_int, e->stream));
@@ -378,13 +443,7 @@ int batch_ahead(dppr_engine *e, Slot &s, const Epoch &ep, double eps, bool merge
                           : ep.grouped   ? ResUpdate{ep.su_rng, ep.sk, ep.sv, ep.b2, ep.ins, ep.deg_after, s.source, nullptr, 0}
                                          : ResUpdate{nullptr, nullptr, nullptr, ep.b2, ep.ins, nullptr, s.source, ep.b1, ep.L}; // raw records
     const int plan = (merged ? PLAN_SEED : (PLAN_SEED | PLAN_BOTH)) | (inline_update ? PLAN_UPDATE : 0);
-    if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[0], e->stream));
-    launch_resident(e, s, ep, eps, 0, merged ? PHASE_BOTH : 0, n, plan, upd);
-    if (e->profiling) HIP_TRY(hipEventRecord(e->evpool[1], e->stream));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(e->pinned, s.cnt, sizeof(int) * (size_t)(CNT_HDR + n), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(loop_wait(e));
-
+    if (int rc = run_resident(e, s, ep, eps, 0, merged ? PHASE_BOTH : 0, n, plan, upd)) return rc;
     out = ahead_outcome(e->pinned[7], e->pinned[4], e->pinned[0], e->pinned + CNT_HDR, n, merged, inline_update, ep.grouped);
     s.st.persist_launches++;
     switch (out.kind) {
@@ -393,18 +452,12 @@ int batch_ahead(dppr_engine *e, Slot &s, const Epoch &ep, double eps, bool merge
         e->raw_backoff = 16;
         return DPPR_OK;
     case AHEAD_CALLED_OFF_ROLLCALL: // nothing was changed, the lists of the stream update stand; per-iteration launches for a while
-        s.st.persist_aborts++;
-        e->persist_ok = false;
-        e->persist_retry = PERSIST_RETRY_BATCHES;
+        give_up_resident(e, s.st);
         return DPPR_OK;
     case AHEAD_RAN: break;
     }
-    if (e->profiling) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, e->evpool[0], e->evpool[1]));
-        s.st.push_ms += ms;
-        s.st.push_launches++;
-    }
+    if (e->profiling)
+        if (int rc = credit_launch(e, s.st, 0, false)) return rc;
     apply_ahead(out, merged, pull_min_frontier(e), s.hist, s.start_dense, s.last_F0, s.st.iterations, s.st.pull_iterations, s.st.sum_F);
     return DPPR_OK;
 }

@@ -1,7 +1,8 @@
 // dppr_loop_plan.hpp -- the POLICY of the frontier loops: how many sweeps to enqueue before the next read-back, what a resident or
 // multi-sweep launch is given, when a group's push tail takes over and at what threshold, push or sweep by estimated cost, and the
 // loop histories all of that is sized from -- and, one layer above the loops, what a whole-batch launch of a single source
-// reported (AheadOutcome) and what a batch therefore runs after it (AfterLaunch). Pure functions of plain integers, without HIP
+// reported (AheadOutcome) and what a batch therefore runs after it (AfterLaunch) -- and which representation of a single-source
+// loop's frontier is live, list or dense snapshot (FrontierForm). Pure functions of plain integers, without HIP
 // includes: run_frontier_loop / batch_ahead / slot_update (dppr_host_loop.hpp) and group_loop / group_push_tail
 // (dppr_host_group.hpp) ask here, launch, read back and account; tests/native/loop_plan_test.cpp drives every function on the CPU
 // against a plain restatement, and replays whole loops.
@@ -261,6 +262,27 @@ struct LoopEntry {
     int F = -1; // -1: read cnt[cur]
     bool dense = false;
     bool any_pull = false;
+};
+
+// Which representation of a single-source loop's frontier is live (run_frontier_loop): the list in s.ft[buf], the dense snapshot
+// in s.x, or both -- never neither. Every launch of the loop is one transition; the loop asks before it enqueues.
+struct FrontierForm {
+    bool list;              // s.ft[buf] holds the frontier as a list (sweeps only count it)
+    bool dense;             // s.x holds the snapshot of the current frontier (p already updated)
+    bool extracted = false; // ... and that snapshot zeroed the residuals it took (InspectExtra): the push needs no repair
+    bool any_pull;          // a sweep ran: s.x / s.x2 are no longer all zero
+    bool x_clean = false;   // a resident launch ended the loop and left s.x / s.x2 all zero
+
+    explicit FrontierForm(const LoopEntry &en) : list(!en.dense), dense(en.dense), any_pull(en.any_pull) {}
+    void list_made() { list = true; }                                // k_list_from_dense: the snapshot as a list
+    void snapshot_taken(bool extr) { dense = true, extracted = extr; } // k_snapshot_dense: the list as a snapshot
+    void pushed() { dense = extracted = false, list = true; }        // a push iteration consumed (and zeroed) the snapshot, wrote a list
+    void swept() { dense = any_pull = true, extracted = list = false; } // a per-iteration sweep wrote the next snapshot, counted the list
+    void resident_returned(bool converged) { list = false, any_pull = true, x_clean = converged; } // (the last sweep's snapshot is in s.x)
+
+    bool needs_list() const { return !list; }         // before a push or a trace copy
+    bool needs_snapshot() const { return !dense; }    // before a sweep or a synchronous push
+    bool must_zero_x() const { return any_pull && !x_clean; } // at the end: leave both dense vectors all zero for the next loop
 };
 
 // What a whole-batch resident launch reported. A launch that was CALLED OFF changed nothing: a sweep group owned more of the raw

@@ -6,7 +6,8 @@
 // One layer above the loops (commit 36757a9, "Move the frontier loops' chunk and launch policy into a tested planner": H2 =
 // dppr_host_loop.hpp, E2 = dppr_engine.hip): what a whole-batch launch reported (ahead_outcome + apply_ahead against the tail of
 // batch_ahead, H2:396-469) and what a batch runs after it (after_launch against dppr_update, E2:905-974), the latter driven by every
-// outcome the former produces.
+// outcome the former produces. And the state the single-source loop keeps between its launches (FrontierForm against the five loose
+// flags of run_frontier_loop, commit dd4feff: H3 = dppr_host_loop.hpp): every sequence of up to six events the loop can enqueue.
 //   loop_plan_test
 #include <algorithm>
 #include <cstdint>
@@ -323,6 +324,75 @@ static std::vector<Did> planned_after_launch(const AfterLaunch &d) {
         did.push_back({DO_LOOP, l.phase, l.inspect, l.inspect ? REntry() : REntry{l.entry.it, l.entry.F, l.entry.dense, l.entry.any_pull}});
     }
     return did;
+}
+
+// ---------------------------------------------------------------------------- restatement: which form of the frontier is live
+// the five loose flags of run_frontier_loop and its assignments to them (commit dd4feff, "Host query layer: one state view and one
+// call skeleton per family": H3 = dppr_host_loop.hpp), one event per place the loop enqueues something that changes them
+struct RForm { bool extracted, dense_valid, list_valid, any_pull, x_clean; };
+static RForm r_form(const REntry &en) { return {false, en.dense, !en.dense, en.any_pull, false}; } // H3:105-109
+enum FormEvent { FE_LIST, FE_SNAP_RESIDENT, FE_RESIDENT_OPEN, FE_RESIDENT_CONVERGED, FE_SNAP, FE_SNAP_EXTRACT, FE_PUSH, FE_SWEEP, FE_COUNT };
+static void r_apply(RForm &f, int ev) {
+    switch (ev) {
+    case FE_LIST: f.list_valid = true; break;            // H3:115 (make_list)
+    case FE_SNAP_RESIDENT: f.dense_valid = true; break;  // H3:169 (the snapshot in front of a resident launch)
+    case FE_RESIDENT_OPEN: case FE_RESIDENT_CONVERGED:   // H3:198-200
+        f.list_valid = false; f.any_pull = true; f.x_clean = ev == FE_RESIDENT_CONVERGED; break;
+    case FE_SNAP: case FE_SNAP_EXTRACT:                  // H3:214, :218 (the snapshot inside a chunk)
+        f.extracted = ev == FE_SNAP_EXTRACT; f.dense_valid = true; break;
+    case FE_PUSH: f.dense_valid = false; f.extracted = false; f.list_valid = true; break;                        // H3:286-288
+    case FE_SWEEP: f.dense_valid = true; f.extracted = false; f.list_valid = false; f.any_pull = true; break;    // H3:235-238, :268-271
+    }
+}
+static void p_apply(FrontierForm &f, int ev) {
+    switch (ev) {
+    case FE_LIST: f.list_made(); break;
+    case FE_SNAP_RESIDENT: case FE_SNAP: f.snapshot_taken(false); break;
+    case FE_SNAP_EXTRACT: f.snapshot_taken(true); break;
+    case FE_RESIDENT_OPEN: f.resident_returned(false); break;
+    case FE_RESIDENT_CONVERGED: f.resident_returned(true); break;
+    case FE_PUSH: f.pushed(); break;
+    case FE_SWEEP: f.swept(); break;
+    }
+}
+// what the loop may enqueue next (its guards: H3:131, :147, :163 make a list only where none is valid; :166, :209 take a snapshot only
+// where none is valid, from the list; a resident launch and a sweep read the snapshot, a push the list; the snapshot in front of a
+// resident launch is followed by that launch, an extracting one by its push -- :214: extracted only where the iteration is no sweep;
+// a converged launch ends the loop)
+static bool may_follow(const RForm &f, int last, int ev) {
+    if (last == FE_RESIDENT_CONVERGED) return false;
+    if (last == FE_SNAP_RESIDENT) return ev == FE_RESIDENT_OPEN || ev == FE_RESIDENT_CONVERGED;
+    if (last == FE_SNAP_EXTRACT) return ev == FE_PUSH;
+    if (last == FE_SNAP) return ev == FE_PUSH || ev == FE_SWEEP;
+    switch (ev) {
+    case FE_LIST: return !f.list_valid;
+    case FE_SNAP_RESIDENT: case FE_SNAP: case FE_SNAP_EXTRACT: return !f.dense_valid && f.list_valid;
+    case FE_RESIDENT_OPEN: case FE_RESIDENT_CONVERGED: case FE_SWEEP: return f.dense_valid;
+    default: return f.list_valid; // FE_PUSH (the eager schedule pushes without a snapshot)
+    }
+}
+static long long form_sequences = 0;
+static void walk_forms(const RForm &rf, const FrontierForm &pf, int last, int depth, bool entry_pull, bool swept) {
+    // the planner's struct against the loose flags, and the combinations the loop relies on
+    CHECK(pf.list == rf.list_valid && pf.dense == rf.dense_valid && pf.extracted == rf.extracted && pf.any_pull == rf.any_pull && pf.x_clean == rf.x_clean,
+          "flags after event %d at depth %d", last, depth);
+    CHECK(pf.needs_list() == !rf.list_valid && pf.needs_snapshot() == !rf.dense_valid && pf.must_zero_x() == (rf.any_pull && !rf.x_clean), "queries");
+    CHECK(pf.list || pf.dense, "the frontier is live as a list, as a snapshot or as both: never as neither");
+    CHECK(!pf.extracted || (pf.dense && last == FE_SNAP_EXTRACT), "an extracting snapshot lives until the push it was taken for, no longer");
+    CHECK(last != FE_PUSH || (!pf.dense && pf.list), "after a push the snapshot is never valid, the list always");
+    CHECK((last != FE_SWEEP && last != FE_RESIDENT_OPEN && last != FE_RESIDENT_CONVERGED) || (pf.dense && !pf.list && pf.any_pull), "a sweep leaves the snapshot alone");
+    CHECK(pf.x_clean == (last == FE_RESIDENT_CONVERGED), "x is known clean only when a resident launch ended the loop");
+    CHECK(pf.any_pull == (entry_pull || swept), "x is dirty once a sweep ran, here or in the launch before the entry");
+    ++form_sequences;
+    if (depth == 6) return;
+    for (int ev = 0; ev < FE_COUNT; ++ev) {
+        if (!may_follow(rf, last, ev)) continue;
+        RForm r2 = rf;
+        FrontierForm p2 = pf;
+        r_apply(r2, ev);
+        p_apply(p2, ev);
+        walk_forms(r2, p2, ev, depth + 1, entry_pull, swept || ev == FE_SWEEP || ev == FE_RESIDENT_OPEN || ev == FE_RESIDENT_CONVERGED);
+    }
 }
 
 // ---------------------------------------------------------------------------- whole loops of a group
@@ -788,6 +858,16 @@ int main() {
             const AfterLaunch d = after_launch(true, true, true, true, o);
             CHECK(o.kind == AHEAD_CALLED_OFF_RECORDS && d.redo_update && !d.count_records && d.filter && !d.filter_clears && d.n_loops == 1 &&
                       d.loop[0].phase == LOOP_PHASE_BOTH && !d.loop[0].inspect && same(d.loop[0].entry, REntry()), "merged loop after a records call-off");
+        }
+    }
+    // ---- which form of a single-source loop's frontier is live: every sequence of up to six events the loop can enqueue, from a loop's
+    // start (the list) and from where a whole-batch launch ran out of sweeps (its snapshot)
+    {
+        const REntry starts[2] = {REntry(), REntry{5, 77, true, true}};
+        for (const REntry &en : starts) {
+            const long long before = form_sequences;
+            walk_forms(r_form(en), FrontierForm(LoopEntry{en.it, en.F, en.dense, en.any_pull}), -1, 0, en.any_pull, false);
+            CHECK(form_sequences - before > 500, "%lld event sequences from entry dense %d", form_sequences - before, (int)en.dense);
         }
     }
     printf("%lld checks, %d failures\n", checked, fails);

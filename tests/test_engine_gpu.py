@@ -1373,6 +1373,88 @@ def test_source_group_tail_as_pushes(nsrc, directed, seeding, mode):
         assert st["pull_iterations"] < st["iterations"]  # some iterations ran as pushes
 
 
+PROFILED_FORMS = {
+    # single source, one launch per iteration
+    "pushes": dict(pull_min_frontier=-1, persistent=0),
+    "gather-sweeps": dict(pull_min_frontier=1, persistent=0),
+    "bitmap-sweeps": dict(pull_min_frontier=1, persistent=0, sweep_bitmap=1, pull_block=256),
+    "binned-sweeps": dict(pull_min_frontier=1, persistent=0, binned=(2, 1, 1, 64, 0, 64, 64)),
+    # single source, resident launches (the default), and with a roll-call that cannot succeed
+    "resident": dict(pull_min_frontier=1),
+    "resident-rollcall-fails": dict(pull_min_frontier=1, persist_timeout_us=-1),
+    # a source group of 10 without a push tail: one launch per sweep, multi-sweep launches
+    "group-one-launch-per-sweep": None,
+    "group-multi-sweep": None,
+}
+
+
+def _profiled_stats(form, profiling):
+    """Statistics of a from-scratch solve and four batches of the toy stream on one launch form."""
+    V, e1, e2 = datagen.rmat_stream(9, 6000, 11)
+    W, c, eps, directed = 600, 20, 1e-9, 1
+    g = orc.Graph(V, e1, e2, directed, W, c)
+    group = form.startswith("group-")
+    e = eng.Engine(V, W, directed, c, schedule=eng.SCHEDULE_SYNC, **(PROFILED_FORMS[form] or {}))
+    e.set_profiling(profiling)
+    e.load_window(*g.window_edges())
+    if group:
+        e.set_group_resident(form == "group-multi-sweep")
+        e.set_group_push(0, 0, 0)
+        h = e.add_source_group([int(x) for x in datagen.top_sources(V, e1, e2, W, directed, 10)])
+        e.group_init_solve(h, eps)
+    else:
+        h = e.add_source(int(datagen.top_sources(V, e1, e2, W, directed, 1)[0]))
+        e.init_solve(h, eps)
+    for _ in range(4):
+        assert not g.stream_updates()
+        g.inc_construct(1)
+        e.set_batch(*g.batch())
+        e.slide(*g.new_stream())
+        if group:
+            e.group_update(h, eps)
+        else:
+            e.update(h, eps)
+    st = e.group_stats(h) if group else e.stats(h)
+    e.close()
+    return st
+
+
+@pytest.mark.parametrize("form", list(PROFILED_FORMS))
+def test_profiling_counters_of_every_launch_form(form):
+    """dppr_set_profiling: push_ms / push_launches count every timed launch of a loop, sweep_ms / sweep_launches those of them
+    that were ONE sweep. A launch per iteration: one timed launch per iteration that saw a frontier, the sweeps among them
+    counted twice. Resident and multi-sweep launches: one timed launch each unless the roll-call failed, and none of them is a
+    sweep launch; after a failed roll-call the loops go on one launch per iteration. Without profiling the four words stay 0."""
+    off = _profiled_stats(form, False)
+    assert (off["push_launches"], off["sweep_launches"], off["push_ms"], off["sweep_ms"]) == (0, 0, 0.0, 0.0)
+    st = _profiled_stats(form, True)
+    print({k: st[k] for k in ("iterations", "pull_iterations", "push_launches", "sweep_launches", "persist_launches", "persist_aborts",
+                              "binned_sweeps", "push_ms", "sweep_ms")})
+    assert st["iterations"] > 0 and st["push_launches"] > 0 and st["push_ms"] > 0
+    for k in ("iterations", "pull_iterations", "persist_launches", "persist_aborts", "binned_sweeps", "sum_F"):
+        assert st[k] == off[k], k   # (profiling changes no launch)
+    per_iteration = form in ("pushes", "gather-sweeps", "bitmap-sweeps", "binned-sweeps", "resident-rollcall-fails",
+                             "group-one-launch-per-sweep")
+    if form == "resident-rollcall-fails":   # the first resident launch gave up untouched, none was tried after it
+        assert st["persist_aborts"] >= 1 and st["persist_launches"] == st["persist_aborts"]
+    elif per_iteration:
+        assert st["persist_launches"] == 0
+    if per_iteration:
+        assert st["push_launches"] == st["iterations"] and st["sweep_launches"] == st["pull_iterations"]
+        assert (st["pull_iterations"] == 0) == (form == "pushes")
+        if st["sweep_launches"]:
+            assert 0 < st["sweep_ms"] <= st["push_ms"]
+        else:
+            assert st["sweep_ms"] == 0
+        assert st["binned_sweeps"] == (st["sweep_launches"] if form == "binned-sweeps" else 0)
+        if form.startswith("group-"):
+            assert st["sweep_launches"] == st["iterations"]
+    else:   # resident / multi-sweep launches
+        assert st["persist_launches"] > st["persist_aborts"]
+        assert st["push_launches"] == st["persist_launches"] - st["persist_aborts"]
+        assert st["sweep_launches"] == 0 and st["sweep_ms"] == 0
+
+
 def test_source_group_sources_outside_the_window_and_duplicates():
     """Sources that have no edge in the window (fresh internal ids: the sweep groups are re-cut) and
     the same vertex twice in one group."""

@@ -6,7 +6,9 @@ the transcribed tail of batch_ahead -- all sixteen combinations of the four stat
 to 128 entries with no zero, a zero in every position in turn (a leading one included), two adjacent zeros and random ones, cnt[4] 0 / 1,
 merged x inline update x grouped; every output field and every mutated history, start_dense, last_F0 and statistics word -- and what a
 batch runs after it (after_launch) against the transcribed body of dppr_update, for every outcome the former produces and without a
-launch. Built with the address and undefined-behaviour sanitizers. CPU only."""
+launch. Which representation of a single-source loop's frontier is live (FrontierForm: list, dense snapshot, extracted, any sweep ran, x left
+clean) against the loop's former loose flags over every sequence of up to six events it can enqueue, from a loop's start and from a resumed
+one, with the combinations the loop relies on asserted. Built with the address and undefined-behaviour sanitizers. CPU only."""
 import os
 import subprocess
 
