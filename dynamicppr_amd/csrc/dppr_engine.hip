@@ -49,6 +49,7 @@
 #include "dppr_export.hpp"
 #include "dppr_dot.hpp"
 #include "dppr_walk.hpp"
+#include "dppr_cluster.hpp"
 
 using namespace dppr;
 
@@ -1429,6 +1430,20 @@ int dppr_group_refine_at(dppr_engine *e, int32_t group, int32_t epoch, const int
     GET_GROUP(e, group);
     GET_EPOCH(e, epoch);
     return refine_call(e, view(g), ep, ids, m, W, seed, out_est, out_corr, out_sumsq);
+}
+
+int dppr_cluster(dppr_engine *e, int32_t slot, int32_t epoch, int32_t k, double min_p, int32_t min_size, dppr_cluster_t *out_best,
+                 int32_t *out_ids, int64_t *out_cut_out, int64_t *out_cut_in, int64_t *out_vol) {
+    GET_SLOT(e, slot);
+    GET_EPOCH(e, epoch);
+    return cluster_call(e, view(s), ep, k, min_p, min_size, out_best, out_ids, out_cut_out, out_cut_in, out_vol);
+}
+
+int dppr_group_cluster(dppr_engine *e, int32_t group, int32_t epoch, int32_t k, double min_p, int32_t min_size, dppr_cluster_t *out_best,
+                       int32_t *out_ids, int64_t *out_cut_out, int64_t *out_cut_in, int64_t *out_vol) {
+    GET_GROUP(e, group);
+    GET_EPOCH(e, epoch);
+    return cluster_call(e, view(g), ep, k, min_p, min_size, out_best, out_ids, out_cut_out, out_cut_in, out_vol);
 }
 
 int dppr_debug_id_map(dppr_engine *e, int32_t *out_ext2int) {

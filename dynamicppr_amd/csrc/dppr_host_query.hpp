@@ -1,9 +1,9 @@
 // dppr_host_query.hpp -- host side of the state queries (dppr_topk / dppr_group_topk / dppr_read_at / dppr_group_read_at, and
 // dppr_group_topk_weighted / dppr_group_score_at, dppr_mark / dppr_changes, dppr_support / dppr_export_sparse /
 // dppr_export_dense_dev and their group forms, dppr_dot_dense_dev / dppr_dot_sparse and theirs, dppr_walks / dppr_refine_at /
-// dppr_group_refine_at). First what the families share -- the opening of a run, room in a buffer, the device-time bracket, the
+// dppr_group_refine_at, dppr_cluster / dppr_group_cluster). First what the families share -- the opening of a run, room in a buffer, the device-time bracket, the
 // copy of a result block to its pinned twin, the check of a caller's device pointer -- then, family by family, the launch sequences
-// of dppr_topk.hpp, dppr_wquery.hpp, dppr_changes.hpp, dppr_export.hpp, dppr_dot.hpp and dppr_walk.hpp (run_*, called with map_mu
+// of dppr_topk.hpp, dppr_wquery.hpp, dppr_changes.hpp, dppr_export.hpp, dppr_dot.hpp, dppr_walk.hpp and dppr_cluster.hpp (run_*, called with map_mu
 // held, on the solver stream) and what an entry point calls (*_call: the checks that need no device, those of the caller's device
 // pointers, map_mu, the run). A state reaches both as a StateView (dppr_host_state.hpp). Nothing here is reached from the update path.
 #pragma once
@@ -753,6 +753,87 @@ int refine_call(dppr_engine *e, const StateView &v, const Epoch &ep, const int32
         return fail(e, DPPR_ERR_INVALID, "refine_at: the state stands on another epoch than the one given: walks over another graph would give a biased estimate");
     std::lock_guard<std::mutex> map_lk(e->map_mu); // (as dppr_read)
     return run_refine(e, ep, v, ids, m, W, seed, out_est, out_corr, out_sumsq);
+}
+
+// ---- the conductance sweep over a top-k order (dppr_cluster.hpp, dppr_cluster_plan.hpp) -------------------------------------------
+// the rank table by the occupied rows, the chunk list by the epoch's edges, the per-position values and the block: in place before
+// the first kernel
+int cluster_workspace(dppr_engine *e, Grow &grow, int n, size_t rows, long long Ed) {
+    QueryWork::Cluster &cl = e->q.cl;
+    if (!cl.pin) { // (the last of the set: one that failed half way is made again)
+        const size_t block = cl_layout(GS_MAX, DPPR_CLUSTER_MAX, true, true, true, true).total_bytes;
+        HIP_TRY(cl.d.regrow(sizeof(ClCtl) / sizeof(int) + (size_t)3 * GS_MAX * DPPR_CLUSTER_MAX));
+        HIP_TRY(cl.blk.regrow(block));
+        HIP_TRY(cl.pin.regrow(block));
+    }
+    int rc = grow(cl.rank, cl_rank_elems(rows, n), with_slack(cl_rank_elems(rows, n)));
+    if (!rc) rc = grow(cl.list, cl_list_cap(n, Ed));
+    return rc;
+}
+
+// The best prefix of every lane's top-k order and, where asked for, the order and its prefix arrays (arguments and the epoch
+// validated by the caller). Results are lane-major: best [n], the arrays [n][k]. The selection writes its ids straight into the
+// block (counts, p and r go to the top-k block, which nobody copies); nothing is read back between the kernels.
+int run_cluster(dppr_engine *e, const Epoch &ep, const StateView &v, int k, double min_p, int min_size, dppr_cluster_t *out_best,
+                int32_t *out_ids, int64_t *out_cut_out, int64_t *out_cut_in, int64_t *out_vol) {
+    if (int rc = query_begin(e, MAP_E2I | MAP_I2E)) return rc;
+    QueryWork::Cluster &cl = e->q.cl;
+    const int n = v.n, stride = cl_stride(n);
+    const TkState st = tk_state(e, v.p, v.r, v.gw, n);
+    Grow grow{e};
+    if (int rc = topk_workspace(e, grow, n, (size_t)st.rows)) return rc;
+    if (int rc = cluster_workspace(e, grow, n, (size_t)st.rows, ep.Ed)) return rc;
+    const TkLayout tkl = tk_layout(n, k, true);
+    const ClLayout lay = cl_layout(n, k, out_ids != nullptr, out_cut_out != nullptr, out_cut_in != nullptr, out_vol != nullptr);
+    unsigned char *tkres = e->q.tk.res.get(), *blk = cl.blk.get();
+    int *cnt = reinterpret_cast<int *>(tkres + tkl.off_cnt), *ids = reinterpret_cast<int *>(blk + lay.off_ids);
+    ClCtl *ctl = reinterpret_cast<ClCtl *>(cl.d.get());
+    int *d = cl.d + sizeof(ClCtl) / sizeof(int);
+    ClGraph g;
+    g.out_row_ptr = ep.out_row_ptr.get();
+    g.out_col = ep.out_col.get();
+    g.in_row_ptr = ep.row_ptr.get();
+    g.in_adj = ep.adj.get();
+    g.n_int = st.n_int;
+    g.lo_parked = st.lo_parked;
+    g.rows = st.rows;
+    const unsigned list_cap = (unsigned)std::min<size_t>(cl_list_cap(n, ep.Ed), 0xffffffffu);
+    const int nk = n * k;
+    if (int rc = DeviceTime{e}.open()) return rc;
+    if (st.rows > 0) HIP_TRY(hipMemsetAsync(cl.rank, 0xff, sizeof(unsigned short) * (size_t)st.rows * (size_t)stride, e->stream));
+    HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(ClCtl), e->stream));
+    if (int rc = select_enqueue(e, st, e->d_int2ext, k, min_p, cnt, ids, reinterpret_cast<double *>(tkres + tkl.off_p),
+                                reinterpret_cast<double *>(tkres + tkl.off_r)))
+        return rc;
+    const int *x2i = e->d_ext2int.get();
+    hipLaunchKernelGGL(k_cl_rank, dim3((nk + CL_BLOCK - 1) / CL_BLOCK), dim3(CL_BLOCK), 0, e->stream, g, x2i, cnt, ids, n, k, stride,
+                       cl.rank.get());
+    hipLaunchKernelGGL(k_cl_rows, dim3((nk + CL_WAVES - 1) / CL_WAVES), dim3(CL_BLOCK), 0, e->stream, g, x2i, cnt, ids, n, k, stride,
+                       cl.rank.get(), d, ctl, cl.list.get(), list_cap);
+    hipLaunchKernelGGL(k_cl_big, dim3(grid_for((int64_t)list_cap, CL_WAVES, 1024)), dim3(CL_BLOCK), 0, e->stream, g, x2i, ids, n, k, stride,
+                       cl.rank.get(), d, ctl, cl.list.get(), list_cap);
+    hipLaunchKernelGGL(k_cl_scan, dim3(n), dim3(CL_SCAN_BLOCK), 0, e->stream, cnt, d, n, k, (long long)ep.Ed, min_size,
+                       reinterpret_cast<dppr_cluster_t *>(blk + lay.off_best), reinterpret_cast<long long *>(blk + lay.off_cut_out),
+                       reinterpret_cast<long long *>(blk + lay.off_cut_in), reinterpret_cast<long long *>(blk + lay.off_vol));
+    HIP_TRY(hipGetLastError());
+    if (int rc = fetch_block(e, cl.blk, cl.pin, lay.copy_bytes)) return rc;
+    const size_t nks = (size_t)n * (size_t)k;
+    memcpy(out_best, cl.pin + lay.off_best, sizeof(dppr_cluster_t) * (size_t)n);
+    if (out_ids) memcpy(out_ids, cl.pin + lay.off_ids, sizeof(int32_t) * nks);
+    if (out_cut_out) memcpy(out_cut_out, cl.pin + lay.off_cut_out, sizeof(int64_t) * nks);
+    if (out_cut_in) memcpy(out_cut_in, cl.pin + lay.off_cut_in, sizeof(int64_t) * nks);
+    if (out_vol) memcpy(out_vol, cl.pin + lay.off_vol, sizeof(int64_t) * nks);
+    return DPPR_OK;
+}
+
+int cluster_call(dppr_engine *e, const StateView &v, const Epoch &ep, int32_t k, double min_p, int32_t min_size, dppr_cluster_t *out_best,
+                 int32_t *out_ids, int64_t *out_cut_out, int64_t *out_cut_in, int64_t *out_vol) {
+    if (!cluster_args_ok(k, min_p, min_size, out_best))
+        return fail(e, DPPR_ERR_INVALID, "cluster: k in [1, DPPR_CLUSTER_MAX], min_p >= 0, min_size in [1, k], non-null out_best");
+    if (!refine_epoch_ok(v.st.last_epoch, ep.id))
+        return fail(e, DPPR_ERR_INVALID, "cluster: the state stands on another epoch than the one given: a cut of another graph says nothing about it");
+    std::lock_guard<std::mutex> map_lk(e->map_mu); // (as dppr_read: one state of the id space for the whole query)
+    return run_cluster(e, ep, v, k, min_p, min_size, out_best, out_ids, out_cut_out, out_cut_in, out_vol);
 }
 
 } // namespace

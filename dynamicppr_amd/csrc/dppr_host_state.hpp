@@ -215,6 +215,12 @@ struct QueryWork {
         DevBuf<double> res;       // a refine call: folded [m][2 n], then est | corr | sumsq [m][n] each
         std::vector<int64_t> off; // a refine call: the offsets q * W of its m queries (kept for its capacity)
     } wk;
+    struct Cluster { // the conductance sweep over a top-k order (dppr_cluster.hpp, dppr_cluster_plan.hpp)
+        DevBuf<unsigned short> rank;     // [occupied rows][cl_stride(n)] position of a vertex in every lane's order (0xffff: absent)
+        DevBuf<int> d;                   // the control words (ClCtl), then d_out | d_in | deg, each [n][k]
+        DevBuf<unsigned long long> list; // chunk items of the rows walked in pieces (cl_list_cap)
+        DevBuf<unsigned char> blk; PinBuf<unsigned char> pin; // the records, ids, cut_out, cut_in, vol: device / pinned host
+    } cl;
 };
 
 } // namespace

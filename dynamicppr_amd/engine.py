@@ -68,6 +68,7 @@ EXPORTS = [
     "dppr_group_export_dense_dev",
     "dppr_dot_dense_dev", "dppr_group_dot_dense_dev", "dppr_dot_sparse", "dppr_group_dot_sparse",
     "dppr_walks", "dppr_refine_at", "dppr_group_refine_at", "dppr_debug_id_map", "dppr_debug_walk_form",
+    "dppr_cluster", "dppr_group_cluster",
 ]
 
 DEST_HOST, DEST_DEVICE = 0, 1
@@ -78,6 +79,16 @@ DOT_MAX_F = 4096
 H_FEATURE_MAJOR, H_VERTEX_MAJOR = 0, 1
 WALK_MAX_M, WALK_MAX_W, WALK_MAX_TOTAL = 4096, 1 << 20, 1 << 26
 WALK_REFILL, WALK_PER_THREAD = 0, 1
+CLUSTER_MAX = 8192
+
+
+class Cluster(C.Structure):
+    """dppr_cluster_t: the best prefix of one source's order."""
+    _fields_ = [("count", C.c_int32), ("best_size", C.c_int32), ("best_cut", C.c_int64), ("best_vol", C.c_int64),
+                ("best_phi", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 def lib():
@@ -191,6 +202,9 @@ def lib():
     L.dppr_refine_at.argtypes = [vp, C.c_int32, C.c_int32, ip, C.c_int32, C.c_int32, C.c_uint64, vp, vp, vp]
     L.dppr_group_refine_at.argtypes = [vp, C.c_int32, C.c_int32, ip, C.c_int32, C.c_int32, C.c_uint64, vp, vp, vp]
     L.dppr_debug_id_map.argtypes = [vp, ip]
+    # (best as a plain address: one record, or n of a group; ids / cut_out / cut_in / vol may be NULL)
+    L.dppr_cluster.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, vp, vp, vp, vp, vp]
+    L.dppr_group_cluster.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, vp, vp, vp, vp, vp]
     L.dppr_debug_walk_form.argtypes = [vp, C.c_int]
     for name in EXPORTS:
         if name not in ("dppr_strerror", "dppr_last_error", "dppr_destroy", "dppr_build_id", "dppr_heartbeat"):
@@ -768,6 +782,27 @@ class Engine:
         outs = [np.empty((len(a), n), dtype=np.float64) if want else None for want in (True, corr, sumsq)]
         self._ck(fn(self._h, int(handle), int(epoch), pa, len(a), int(W), int(seed), *[None if o is None else o.ctypes.data for o in outs]), what)
         return tuple(None if o is None else (o[:, 0] if flat else o) for o in outs)
+
+    def cluster(self, slot, k, min_p=0.0, min_size=1, epoch=-1, profile=False):
+        """The lowest-conductance prefix of the slot's top-k order (dppr_cluster): a dict of count, best_size, best_cut, best_vol,
+        best_phi. profile=True: (that dict, ids, cut_out, cut_in, vol), the four arrays [k] (ids -1 and counts 0 past `count`)."""
+        best, arrays = self._cluster(self._L.dppr_cluster, slot, 1, k, min_p, min_size, epoch, profile, "cluster")
+        return (best[0], *[a[0] for a in arrays]) if profile else best[0]
+
+    def group_cluster(self, group, k, min_p=0.0, min_size=1, epoch=-1, profile=False):
+        """... for every source of a group at once: a list of dicts in group order; profile=True: (that list, ids, cut_out, cut_in,
+        vol), the four arrays [n][k]."""
+        best, arrays = self._cluster(self._L.dppr_group_cluster, group, self._group_n.get(group, 1), k, min_p, min_size, epoch, profile,
+                                     "group_cluster")
+        return (best, *arrays) if profile else best
+
+    def _cluster(self, fn, which, n, k, min_p, min_size, epoch, profile, what):
+        kk = max(int(k), 1)
+        best = (Cluster * n)()
+        arrays = [np.empty((n, kk), dtype=dt) for dt in (np.int32, np.int64, np.int64, np.int64)] if profile else []
+        self._ck(fn(self._h, int(which), int(epoch), int(k), float(min_p), int(min_size), C.addressof(best),
+                    *([a.ctypes.data for a in arrays] if profile else [None] * 4)), what)
+        return [b.as_dict() for b in best], arrays
 
     def id_map(self):
         """Test hook (dppr_debug_id_map): the internal id of every external id, -1 without one."""

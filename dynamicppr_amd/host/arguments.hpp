@@ -139,6 +139,9 @@ inline void PrintUsage() {
               << "--refine <file> --walks <W> [--walk-seed <S>]: <file> holds one vertex id per line (ids in [0, V), at most 4096, W in [1, 2^20],\n"
               << "            ids x W <= 2^26); after every batch print, per id and per source (index from 0, in source order), the pagerank\n"
               << "            refined by W random walks, its correction and its standard error: refined <vertex> <source index> <est> <corr> <stderr>\n"
+              << "--cluster <K> [--cluster-min <P>] [--cluster-min-size <M>]: after every batch print, per source in source order, the prefix of\n"
+              << "            lowest conductance of the source's K vertices of largest pagerank > P (1 <= K <= 8192, P >= 0, 1 <= M <= K vertices\n"
+              << "            at least): cluster <source> size <vertices> cut <edges leaving it> vol <its out-degrees> phi <conductance>\n"
               << "--validate: residual bound + power-iteration check after every solve\n"
               << "--split: drive each batch through IncrementalBatchUpdate/ExecuteMainLoop(0)/(1)\n"
               << "--sync: synchronous (deterministic) push schedule\n"
@@ -185,6 +188,9 @@ inline void ArgumentsChecker() {
     if (!gRefineFile.empty() && !gRefineBad &&
         (gWalks < 1 || gWalks > DPPR_WALK_MAX_W || gRefineIds.size() > (size_t)DPPR_WALK_MAX_M || (long long)gRefineIds.size() * gWalks > (1ll << 26)))
         ok = false;
+    if (gClusterGiven && (gClusterK < 1 || gClusterK > DPPR_CLUSTER_MAX || !(gClusterMin >= 0.0) || gClusterMinSize < 1 || gClusterMinSize > gClusterK))
+        ok = false;
+    if (gClusterOptsGiven && !gClusterGiven) ok = false;
     if (gTopKWeightsGiven && (gTopK == 0 || gTopKWeights.empty())) ok = false; // (the count is checked against the sources in main)
     if (!ok) {
         std::cout << "invalid arguments" << std::endl;
@@ -234,6 +240,11 @@ inline void ArgumentsParser(int argc, char **argv) {
     gWalksGiven = find(argc, argv, "--walks") != nullptr;
     gWalks = as_int(argc, argv, "--walks", 0);
     if (const char *v = find(argc, argv, "--walk-seed")) gWalkSeed = std::strtoull(v, nullptr, 0);
+    gClusterGiven = find(argc, argv, "--cluster") != nullptr;
+    gClusterK = as_int(argc, argv, "--cluster", 0);
+    gClusterOptsGiven = find(argc, argv, "--cluster-min") != nullptr || find(argc, argv, "--cluster-min-size") != nullptr;
+    gClusterMin = as_double(argc, argv, "--cluster-min", 0.0);
+    gClusterMinSize = as_int(argc, argv, "--cluster-min-size", 1);
     gValidate = has(argc, argv, "--validate");
     gSplitInterface = has(argc, argv, "--split");
     gSchedule = has(argc, argv, "--sync") ? 1 : 0;

@@ -60,6 +60,11 @@ inline std::vector<int32_t> gRefineIds;
 inline int gWalks = 0;                // --walks W : walks per refined vertex (with --refine)
 inline bool gWalksGiven = false;
 inline unsigned long long gWalkSeed = 0; // --walk-seed S
+inline int gClusterK = 0;             // --cluster K : after every batch print cluster <source> size <n> cut <c> vol <v> phi <phi>, the best prefix of the top-K order (0: off)
+inline bool gClusterGiven = false;
+inline double gClusterMin = 0.0;      // --cluster-min P : the order holds the vertices with pagerank > P
+inline int gClusterMinSize = 1;       // --cluster-min-size M : the smallest prefix that may be the cluster
+inline bool gClusterOptsGiven = false; //   --cluster-min or --cluster-min-size was given
 inline bool gValidate = false;        // --validate : the reference's -DVALIDATE checks at run time
 inline bool gShareDevice = false;     // --share-device (or DPPR_DEVICE_ALIAS=1): the -g N device threads share the devices that exist (d % count)
 inline bool gPushOnly = false;        // --push-only : no pull sweeps (the ablation of the -o variants times their push mechanisms)

@@ -255,6 +255,7 @@ public:
             }
             if (gChangesK > 0) PrintChanges(stream_batch_count);
             if (!gRefineIds.empty()) PrintRefined(-1);
+            if (gClusterK > 0) PrintClusters(-1);
         }
         batches_done = stream_batch_count - 1;
         if (!quiet_) Report(stream_batch_count);
@@ -348,6 +349,7 @@ public:
             }
             if (gChangesK > 0) PrintChanges(stream_batch_count);
             if (!gRefineIds.empty()) PrintRefined(epoch); // (the epoch the states stand on: the helper may have built the next one)
+            if (gClusterK > 0) PrintClusters(epoch);
         }
         batches_done = stream_batch_count - 1;
         if (!quiet_) Report(stream_batch_count);
@@ -583,6 +585,32 @@ public:
                     std::snprintf(line, sizeof(line), "refined %d %zu %.17g %.17g %.17g\n", (int)gRefineIds[q], first + j, est[at], corr[at], se);
                     out += line;
                 }
+        }
+        progress++;
+        static std::mutex print_mu;
+        std::lock_guard<std::mutex> lk(print_mu);
+        std::cout << out << std::flush;
+    }
+
+    // --cluster: after a batch, the prefix of lowest conductance of every source's top-K order over `epoch` (dppr_cluster /
+    // dppr_group_cluster: the records alone, no array comes back). Outside the timed region, printed as one block like --changes.
+    void PrintClusters(int32_t epoch) {
+        const size_t n_src = source_vertex_ids.size();
+        std::vector<dppr_cluster_t> best;
+        std::string out;
+        char line[200];
+        for (size_t first = 0; first < n_src; first += use_groups ? kGroupMax : 1) {
+            const size_t n = use_groups ? std::min(kGroupMax, n_src - first) : 1;
+            best.assign(n, dppr_cluster_t{});
+            if (use_groups)
+                DPPR_CHECK(engine, dppr_group_cluster(engine, groups[first / kGroupMax], epoch, gClusterK, gClusterMin, gClusterMinSize, best.data(), nullptr, nullptr, nullptr, nullptr));
+            else
+                DPPR_CHECK(engine, dppr_cluster(engine, slots[first], epoch, gClusterK, gClusterMin, gClusterMinSize, best.data(), nullptr, nullptr, nullptr, nullptr));
+            for (size_t j = 0; j < n; ++j) {
+                std::snprintf(line, sizeof(line), "cluster %d size %d cut %lld vol %lld phi %.17g\n", (int)source_vertex_ids[first + j], (int)best[j].best_size,
+                              (long long)best[j].best_cut, (long long)best[j].best_vol, best[j].best_phi);
+                out += line;
+            }
         }
         progress++;
         static std::mutex print_mu;

@@ -678,6 +678,63 @@ int dppr_group_refine_at(dppr_engine *e, int32_t group, int32_t epoch, const int
 int dppr_debug_id_map(dppr_engine *e, int32_t *out_ext2int /* [V], -1 without an internal id */);
 int dppr_debug_walk_form(dppr_engine *e, int form);
 
+/* ---- local clusters of the tracked sources: a conductance sweep over the top-k order (backward-compatible additions, ABI 6) ----
+ * Every other query reads the state; this one asks the graph about it. The vertices are ordered by p, the order is walked, and the
+ * cut is made where the conductance of the prefix is lowest (Andersen, Chung, Lang: "Local graph partitioning using PageRank
+ * vectors", FOCS 2006) -- on the device, next to the state, instead of dppr_group_topk + dppr_read_out_graph + a sweep on the host.
+ * The loop invariant normalises by outdeg + 1, and on a window that stores both directions (d(v) + 1) pi_v(s) = (d(s) + 1) pi_s(v):
+ * p_i[v] is proportional to the forward PPR of s_i at v divided by d(v) + 1, the degree-normalised vector the ACL sweep orders by.
+ * On a directed window the order is by contribution to s_i and the cut is the out-boundary of the prefix.
+ *
+ * For source i (lane order; a slot is n = 1), every output is defined exactly:
+ *   ORDER   v_0 .. v_{L-1}: exactly what dppr_topk / dppr_group_topk return for (k, min_p) -- p > min_p, p descending, external
+ *           id ascending, live and parked zone -- with L = count = min(k, #qualifying). out_ids[i][j] = v_j; entries past L are -1.
+ *   GRAPH   the out-CSR of `epoch` with multiplicity: a duplicate edge counts as often as it is stored, a self loop never crosses
+ *           a cut. Ed is what dppr_graph_edges returns for the epoch. A vertex without a row in that epoch (parked, or never
+ *           named) has degree 0.
+ *   PREFIX  with S_j = {v_0 .. v_j}:
+ *             vol[j]     = sum over u in S_j of outdeg(u)
+ *             cut_out[j] = #{stored edges u -> w : u in S_j, w not in S_j}
+ *             cut_in[j]  = #{stored edges u -> w : u not in S_j, w in S_j}
+ *           Entries past L are 0. (directed = 0: both directions are stored and cut_in == cut_out.)
+ *   BEST    den[j] = min(vol[j], Ed - vol[j]). Prefix j is ELIGIBLE if j + 1 >= min_size and den[j] > 0.
+ *           phi[j] = (double)cut_out[j] / (double)den[j]: one IEEE division of two exactly converted integers.
+ *           The best prefix is the eligible j of smallest phi, the smallest j among equal values:
+ *           best_size = j + 1, best_cut = cut_out[j], best_vol = vol[j], best_phi = phi[j].
+ *           No eligible prefix: best_size = 0, best_cut = best_vol = 0, best_phi = +infinity.
+ * A prefix's values do not depend on what follows it: the arrays of a smaller k are the head of those of a larger one.
+ * Group outputs are source-major: out_best [n], the four arrays [n][k]; each of the four may be NULL (only what is asked for is
+ * copied back).
+ *
+ * The epoch must be resident (-1: the newest). If the epoch the state stands on is known (anything but a state set by dppr_write)
+ * it must be the one given: a cut of another graph says nothing about this state, and the call is refused. Convergence is NOT
+ * required: like dppr_topk the call works on any state.
+ *
+ * Rejected with DPPR_ERR_INVALID before any device work, nothing written: k outside [1, DPPR_CLUSTER_MAX], min_p negative or NaN,
+ * min_size outside [1, k], a NULL out_best, a bad slot / group, an epoch that is not resident or not the state's.
+ * Threading and stream as dppr_topk: the id-map lock of dppr_read (safe beside dppr_slide_concurrent), the solver stream, never
+ * part of the update path or of a timed region. Work space beyond dppr_topk's: a rank table of 2 bytes per source (rounded up to
+ * a power of two) and row that holds a vertex, 8 bytes per 512 edges of the epoch and source for the rows that are walked in
+ * pieces, and the result block; all of it is the engine's, obtained before the first kernel, grown on demand and released with
+ * the engine: after DPPR_ERR_NOMEM the states and the engine are as before. With dppr_set_profiling on, dppr_debug_query_ms also
+ * reports the device time of the last of these calls, first to last kernel. */
+#define DPPR_CLUSTER_MAX DPPR_TOPK_MAX      /* 8192: the sweep walks the order dppr_topk defines */
+typedef struct {
+    int32_t count;      /* L: vertices of the order, min(k, #qualifying)                         */
+    int32_t best_size;  /* j*+1, 0 if no prefix is eligible                                      */
+    int64_t best_cut;   /* cut_out of that prefix                                                */
+    int64_t best_vol;   /* vol of that prefix                                                    */
+    double  best_phi;   /* its conductance; +infinity if best_size == 0                          */
+} dppr_cluster_t;
+int dppr_cluster(dppr_engine *e, int32_t slot, int32_t epoch, int32_t k, double min_p, int32_t min_size,
+                 dppr_cluster_t *out_best,
+                 int32_t *out_ids /* [k] or NULL */, int64_t *out_cut_out /* [k] or NULL */,
+                 int64_t *out_cut_in /* [k] or NULL */, int64_t *out_vol /* [k] or NULL */);
+int dppr_group_cluster(dppr_engine *e, int32_t group, int32_t epoch, int32_t k, double min_p, int32_t min_size,
+                       dppr_cluster_t *out_best /* [n] */,
+                       int32_t *out_ids /* [n][k] or NULL */, int64_t *out_cut_out /* [n][k] or NULL */,
+                       int64_t *out_cut_in /* [n][k] or NULL */, int64_t *out_vol /* [n][k] or NULL */);
+
 /* Windows whose sweep groups are all resident at once run a frontier loop of a source group as
  * multi-sweep launches (grid barrier between sweeps, row tables kept in LDS; dppr_multi.hpp). on by
  * default; 0 = one launch per sweep everywhere. The roll-call / time-out rules are those of
