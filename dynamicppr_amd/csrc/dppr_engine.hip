@@ -50,6 +50,7 @@
 #include "dppr_dot.hpp"
 #include "dppr_walk.hpp"
 #include "dppr_cluster.hpp"
+#include "dppr_subgraph.hpp"
 
 using namespace dppr;
 
@@ -1444,6 +1445,26 @@ int dppr_group_cluster(dppr_engine *e, int32_t group, int32_t epoch, int32_t k, 
     GET_GROUP(e, group);
     GET_EPOCH(e, epoch);
     return cluster_call(e, view(g), ep, k, min_p, min_size, out_best, out_ids, out_cut_out, out_cut_in, out_vol);
+}
+
+int dppr_subgraph(dppr_engine *e, int32_t slot, int32_t epoch, int32_t k, double min_p, int64_t cap, int dest, int32_t *out_count,
+                  int64_t *out_offsets, int32_t *out_ids, double *out_p, int64_t *out_row_ptr, int32_t *out_col) {
+    GET_SLOT(e, slot);
+    GET_EPOCH(e, epoch);
+    return subgraph_call(e, view(s), ep, k, min_p, cap, dest, out_count, out_offsets, out_ids, out_p, out_row_ptr, out_col);
+}
+
+int dppr_group_subgraph(dppr_engine *e, int32_t group, int32_t epoch, int32_t k, double min_p, int64_t cap, int dest, int32_t *out_counts,
+                        int64_t *out_offsets, int32_t *out_ids, double *out_p, int64_t *out_row_ptr, int32_t *out_col) {
+    GET_GROUP(e, group);
+    GET_EPOCH(e, epoch);
+    return subgraph_call(e, view(g), ep, k, min_p, cap, dest, out_counts, out_offsets, out_ids, out_p, out_row_ptr, out_col);
+}
+
+int dppr_debug_subgraph_wave_max(dppr_engine *e, int wave_max) {
+    if (!e || !sg_wave_max_ok(wave_max)) return fail(e, DPPR_ERR_INVALID, "debug_subgraph_wave_max: 0 (every row by the histogram kernel) .. 256");
+    e->sg_wave_max = wave_max;
+    return DPPR_OK;
 }
 
 int dppr_debug_id_map(dppr_engine *e, int32_t *out_ext2int) {

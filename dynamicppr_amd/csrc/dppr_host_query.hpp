@@ -1,9 +1,9 @@
 // dppr_host_query.hpp -- host side of the state queries (dppr_topk / dppr_group_topk / dppr_read_at / dppr_group_read_at, and
 // dppr_group_topk_weighted / dppr_group_score_at, dppr_mark / dppr_changes, dppr_support / dppr_export_sparse /
 // dppr_export_dense_dev and their group forms, dppr_dot_dense_dev / dppr_dot_sparse and theirs, dppr_walks / dppr_refine_at /
-// dppr_group_refine_at, dppr_cluster / dppr_group_cluster). First what the families share -- the opening of a run, room in a buffer, the device-time bracket, the
+// dppr_group_refine_at, dppr_cluster / dppr_group_cluster, dppr_subgraph / dppr_group_subgraph). First what the families share -- the opening of a run, room in a buffer, the device-time bracket, the
 // copy of a result block to its pinned twin, the check of a caller's device pointer -- then, family by family, the launch sequences
-// of dppr_topk.hpp, dppr_wquery.hpp, dppr_changes.hpp, dppr_export.hpp, dppr_dot.hpp, dppr_walk.hpp and dppr_cluster.hpp (run_*, called with map_mu
+// of dppr_topk.hpp, dppr_wquery.hpp, dppr_changes.hpp, dppr_export.hpp, dppr_dot.hpp, dppr_walk.hpp, dppr_cluster.hpp and dppr_subgraph.hpp (run_*, called with map_mu
 // held, on the solver stream) and what an entry point calls (*_call: the checks that need no device, those of the caller's device
 // pointers, map_mu, the run). A state reaches both as a StateView (dppr_host_state.hpp). Nothing here is reached from the update path.
 #pragma once
@@ -834,6 +834,119 @@ int cluster_call(dppr_engine *e, const StateView &v, const Epoch &ep, int32_t k,
         return fail(e, DPPR_ERR_INVALID, "cluster: the state stands on another epoch than the one given: a cut of another graph says nothing about it");
     std::lock_guard<std::mutex> map_lk(e->map_mu); // (as dppr_read: one state of the id space for the whole query)
     return run_cluster(e, ep, v, k, min_p, min_size, out_best, out_ids, out_cut_out, out_cut_in, out_vol);
+}
+
+// ---- the subgraph a top-k order induces (dppr_subgraph.hpp, dppr_subgraph_plan.hpp) ------------------------------------------------
+// the rank table and the chunk list of the conductance sweep, the per-position work and the block with its pinned twin: in place
+// before the first kernel
+int subgraph_workspace(dppr_engine *e, Grow &grow, int n, size_t rows, long long Ed, size_t block_bytes) {
+    QueryWork::Subgraph &sg = e->q.sg;
+    int rc = grow(e->q.cl.rank, cl_rank_elems(rows, n), with_slack(cl_rank_elems(rows, n)));
+    if (!rc) rc = grow(e->q.cl.list, cl_list_cap(n, Ed));
+    if (!rc) rc = grow(sg.work, sg_work_elems(GS_MAX, DPPR_SUBGRAPH_MAX));
+    if (!rc) rc = grow(sg.blk, block_bytes);
+    if (!rc) rc = grow(sg.pin, block_bytes);
+    return rc;
+}
+
+// every section a device destination names: aligned device memory of the engine's device, inside one allocation
+bool sg_dest_ok(const dppr_engine *e, int n, int k, int64_t capc, const int32_t *ids, const double *p, const int64_t *row_ptr, const int32_t *col) {
+    return (!ids || dev_range_ok(e, ids, sg_ids_bytes(n, k), sizeof(int32_t))) && (!p || dev_range_ok(e, p, sg_p_bytes(n, k), sizeof(double))) &&
+           (!row_ptr || dev_range_ok(e, row_ptr, sg_row_ptr_bytes(n, k), sizeof(int64_t))) &&
+           (capc <= 0 || dev_range_ok(e, col, sg_col_bytes(capc), sizeof(int32_t)));
+}
+
+// The order of every lane and the CSR of the stored edges among its vertices (arguments, the epoch and a device destination
+// validated by the caller). The selection writes ids and p where they are wanted; count, chunks and scan follow without a read
+// back; the head comes to the host once, the offsets and counts are written, and the fill runs if the entries fit cap.
+int run_subgraph(dppr_engine *e, const Epoch &ep, const StateView &v, int k, double min_p, int64_t cap, int dest, int32_t *out_counts,
+                 int64_t *out_offsets, int32_t *out_ids, double *out_p, int64_t *out_row_ptr, int32_t *out_col) {
+    if (int rc = query_begin(e, MAP_E2I | MAP_I2E)) return rc;
+    QueryWork::Subgraph &sg = e->q.sg;
+    const int n = v.n, stride = cl_stride(n);
+    const bool host = dest == DPPR_DEST_HOST;
+    const int64_t capc = sg_cap_clamped(cap, ep.Ed, n);
+    const TkState st = tk_state(e, v.p, v.r, v.gw, n);
+    const SgLayout lay = sg_layout(n, k, host ? capc : 0, out_ids != nullptr, out_p != nullptr, out_row_ptr != nullptr, out_col != nullptr);
+    Grow grow{e};
+    if (int rc = topk_workspace(e, grow, n, (size_t)st.rows)) return rc;
+    if (int rc = subgraph_workspace(e, grow, n, (size_t)st.rows, ep.Ed, lay.total_bytes)) return rc;
+    const TkLayout tkl = tk_layout(n, k, true);
+    unsigned char *tkres = e->q.tk.res.get(), *blk = sg.blk.get();
+    int *cnt = reinterpret_cast<int *>(tkres + tkl.off_cnt);
+    SgHead *head = reinterpret_cast<SgHead *>(blk + lay.off_head);
+    int *d_ids = !host && out_ids ? out_ids : reinterpret_cast<int *>(blk + lay.off_ids);
+    double *d_p = !host && out_p ? out_p : reinterpret_cast<double *>(blk + lay.off_p);
+    long long *d_row_ptr = !host && out_row_ptr ? reinterpret_cast<long long *>(out_row_ptr) : reinterpret_cast<long long *>(blk + lay.off_row_ptr);
+    int *d_col = host ? reinterpret_cast<int *>(blk + lay.off_col) : out_col;
+    SgCtl *ctl = reinterpret_cast<SgCtl *>(sg.work.get());
+    const int nk = n * k;
+    int *m = sg.work + sizeof(SgCtl) / sizeof(int), *long_list = m + nk;
+    ClGraph g;
+    g.out_row_ptr = ep.out_row_ptr.get();
+    g.out_col = ep.out_col.get();
+    g.in_row_ptr = ep.row_ptr.get();
+    g.in_adj = ep.adj.get();
+    g.n_int = st.n_int;
+    g.lo_parked = st.lo_parked;
+    g.rows = st.rows;
+    const unsigned list_cap = (unsigned)std::min<size_t>(cl_list_cap(n, ep.Ed), 0xffffffffu);
+    if (int rc = DeviceTime{e}.open()) return rc;
+    if (st.rows > 0) HIP_TRY(hipMemsetAsync(e->q.cl.rank, 0xff, sizeof(unsigned short) * (size_t)st.rows * (size_t)stride, e->stream));
+    HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(SgCtl), e->stream));
+    if (int rc = select_enqueue(e, st, e->d_int2ext, k, min_p, cnt, d_ids, d_p, reinterpret_cast<double *>(tkres + tkl.off_r))) return rc;
+    const int *x2i = e->d_ext2int.get();
+    const unsigned short *rank = e->q.cl.rank.get();
+    hipLaunchKernelGGL(k_cl_rank, dim3((nk + CL_BLOCK - 1) / CL_BLOCK), dim3(CL_BLOCK), 0, e->stream, g, x2i, cnt, d_ids, n, k, stride,
+                       e->q.cl.rank.get());
+    hipLaunchKernelGGL(k_sg_count, dim3((nk + CL_WAVES - 1) / CL_WAVES), dim3(CL_BLOCK), 0, e->stream, g, x2i, cnt, d_ids, n, k, stride, rank, m,
+                       ctl, e->q.cl.list.get(), list_cap);
+    hipLaunchKernelGGL(k_sg_big, dim3(grid_for((int64_t)list_cap, CL_WAVES, 1024)), dim3(CL_BLOCK), 0, e->stream, g, x2i, d_ids, k, stride, rank, m,
+                       ctl, e->q.cl.list.get(), list_cap);
+    hipLaunchKernelGGL(k_sg_scan, dim3(n), dim3(CL_SCAN_BLOCK), 0, e->stream, cnt, m, n, k, head, d_row_ptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(sg.pin, blk + lay.off_head, SG_HEAD_BYTES, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const SgHead *h = reinterpret_cast<const SgHead *>(sg.pin.get());
+    for (int i = 0; i <= n; ++i) out_offsets[i] = h->offsets[i];
+    for (int i = 0; i < n; ++i) out_counts[i] = h->count[i];
+    const int64_t total = h->offsets[n];
+    const bool fill = capc > 0 && total > 0 && total <= capc;
+    if (fill) {
+        hipLaunchKernelGGL(k_sg_fill, dim3((nk + CL_WAVES - 1) / CL_WAVES), dim3(CL_BLOCK), 0, e->stream, g, x2i, cnt, d_ids, n, k, stride, rank,
+                           d_row_ptr, e->sg_wave_max, d_col, ctl, long_list);
+        hipLaunchKernelGGL(k_sg_long, dim3(SG_LONG_GRID), dim3(SG_LONG_BLOCK), 0, e->stream, g, x2i, d_ids, k, stride, rank, d_row_ptr, d_col, ctl,
+                           long_list, (unsigned)nk);
+        HIP_TRY(hipGetLastError());
+    }
+    if (int rc = DeviceTime{e}.close()) return rc;
+    // a host destination: one copy from the first to the last section asked for (col by the entries it holds, not by cap)
+    size_t hi = lay.copy_hi;
+    if (host && out_col && capc > 0) hi = fill ? lay.off_col + sg_col_bytes(total) : std::min(hi, lay.off_col);
+    const bool copy = host && hi > lay.copy_lo;
+    if (copy) HIP_TRY(hipMemcpyAsync(sg.pin + lay.copy_lo, blk + lay.copy_lo, hi - lay.copy_lo, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream)); // (a device destination is complete here: any stream of the caller may read it)
+    if (int rc = DeviceTime{e}.read()) return rc;
+    if (host) {
+        if (out_ids) memcpy(out_ids, sg.pin + lay.off_ids, sg_ids_bytes(n, k));
+        if (out_p) memcpy(out_p, sg.pin + lay.off_p, sg_p_bytes(n, k));
+        if (out_row_ptr) memcpy(out_row_ptr, sg.pin + lay.off_row_ptr, sg_row_ptr_bytes(n, k));
+        if (fill) memcpy(out_col, sg.pin + lay.off_col, sg_col_bytes(total));
+    }
+    return DPPR_OK;
+}
+
+int subgraph_call(dppr_engine *e, const StateView &v, const Epoch &ep, int32_t k, double min_p, int64_t cap, int dest, int32_t *out_counts,
+                  int64_t *out_offsets, int32_t *out_ids, double *out_p, int64_t *out_row_ptr, int32_t *out_col) {
+    if (!subgraph_args_ok(k, min_p, cap, dest, out_offsets, out_counts, out_col))
+        return fail(e, DPPR_ERR_INVALID, "subgraph: k in [1, DPPR_SUBGRAPH_MAX], min_p >= 0, cap >= 0, dest 0 or 1, non-null offsets / counts, non-null col when cap > 0");
+    if (!refine_epoch_ok(v.st.last_epoch, ep.id))
+        return fail(e, DPPR_ERR_INVALID, "subgraph: the state stands on another epoch than the one given: the edges of another graph are not those its order was computed on");
+    HIP_TRY(hipSetDevice(e->device));
+    if (dest == DPPR_DEST_DEVICE && !sg_dest_ok(e, v.n, k, sg_cap_clamped(cap, ep.Ed, v.n), out_ids, out_p, out_row_ptr, out_col))
+        return fail(e, DPPR_ERR_INVALID, "subgraph: ids / p / row_ptr / col must be aligned device memory of the engine's device, n x k (row_ptr: n x (k + 1), col: cap) entries inside one allocation");
+    std::lock_guard<std::mutex> map_lk(e->map_mu); // (as dppr_read: one state of the id space for the whole query)
+    return run_subgraph(e, ep, v, k, min_p, cap, dest, out_counts, out_offsets, out_ids, out_p, out_row_ptr, out_col);
 }
 
 } // namespace

@@ -221,6 +221,10 @@ struct QueryWork {
         DevBuf<unsigned long long> list; // chunk items of the rows walked in pieces (cl_list_cap)
         DevBuf<unsigned char> blk; PinBuf<unsigned char> pin; // the records, ids, cut_out, cut_in, vol: device / pinned host
     } cl;
+    struct Subgraph { // the subgraph a top-k order induces (dppr_subgraph.hpp, dppr_subgraph_plan.hpp); the rank table and the chunk list are cl's
+        DevBuf<int> work;                                     // the control words (SgCtl), the matches of every position [n][k], the rows queued for k_sg_long [n][k]
+        DevBuf<unsigned char> blk; PinBuf<unsigned char> pin; // the head, ids, p, row_ptr and a host destination's col: device / pinned host
+    } sg;
 };
 
 } // namespace
@@ -393,6 +397,7 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     unsigned i2e_gen_on_device = 0;    // IdSpace::map_gen that copy was taken at
     QueryWork q;                    // their workspace
     int walk_form = 0;              // 0: lane refill, 1: one walk per thread (dppr_debug_walk_form)
+    int sg_wave_max = SG_WAVE_MAX;  // matched entries of a row up to which the wave that owns it places them (dppr_debug_subgraph_wave_max)
     float query_ms = -1.0f;         // dppr_set_profiling: device time of the last top-k, changes, export or dot call, first to last kernel (dppr_debug_query_ms)
     std::vector<int32_t> h_tmp1, h_tmp2;
     std::vector<int32_t> h_tiles; // host copy of the tile edge prefix / group table

@@ -69,6 +69,7 @@ EXPORTS = [
     "dppr_dot_dense_dev", "dppr_group_dot_dense_dev", "dppr_dot_sparse", "dppr_group_dot_sparse",
     "dppr_walks", "dppr_refine_at", "dppr_group_refine_at", "dppr_debug_id_map", "dppr_debug_walk_form",
     "dppr_cluster", "dppr_group_cluster",
+    "dppr_subgraph", "dppr_group_subgraph", "dppr_debug_subgraph_wave_max",
 ]
 
 DEST_HOST, DEST_DEVICE = 0, 1
@@ -80,6 +81,7 @@ H_FEATURE_MAJOR, H_VERTEX_MAJOR = 0, 1
 WALK_MAX_M, WALK_MAX_W, WALK_MAX_TOTAL = 4096, 1 << 20, 1 << 26
 WALK_REFILL, WALK_PER_THREAD = 0, 1
 CLUSTER_MAX = 8192
+SUBGRAPH_MAX = 8192
 
 
 class Cluster(C.Structure):
@@ -205,6 +207,10 @@ def lib():
     # (best as a plain address: one record, or n of a group; ids / cut_out / cut_in / vol may be NULL)
     L.dppr_cluster.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, vp, vp, vp, vp, vp]
     L.dppr_group_cluster.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, vp, vp, vp, vp, vp]
+    # (counts / offsets are host arrays; ids / p / row_ptr / col as plain addresses, host or device by `dest`, NULL allowed)
+    L.dppr_subgraph.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.dppr_group_subgraph.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.dppr_debug_subgraph_wave_max.argtypes = [vp, C.c_int]
     L.dppr_debug_walk_form.argtypes = [vp, C.c_int]
     for name in EXPORTS:
         if name not in ("dppr_strerror", "dppr_last_error", "dppr_destroy", "dppr_build_id", "dppr_heartbeat"):
@@ -803,6 +809,53 @@ class Engine:
         self._ck(fn(self._h, int(which), int(epoch), int(k), float(min_p), int(min_size), C.addressof(best),
                     *([a.ctypes.data for a in arrays] if profile else [None] * 4)), what)
         return [b.as_dict() for b in best], arrays
+
+    def subgraph(self, slot, k, min_p=0.0, epoch=-1):
+        """The slot's top-k order and every stored edge among its vertices (dppr_subgraph): (count, ids [k], p [k], row_ptr [k + 1],
+        col). Row j holds the positions, ascending, of the heads of v_j's out-edges that lie in the order; ids -1 / p 0 past count."""
+        cnt, _, ids, p, row_ptr, col = self._subgraph(self._L.dppr_subgraph, slot, 1, k, min_p, epoch, "subgraph")
+        return int(cnt[0]), ids[0], p[0], row_ptr[0], col
+
+    def group_subgraph(self, group, k, min_p=0.0, epoch=-1):
+        """... for every source of a group as one CSR over the sources: (counts [n], offsets [n + 1], ids [n][k], p [n][k],
+        row_ptr [n][k + 1], col). row_ptr holds absolute indices into col; source i's entries are [offsets[i], offsets[i + 1])."""
+        return self._subgraph(self._L.dppr_group_subgraph, group, self._group_n.get(group, 1), k, min_p, epoch, "group_subgraph")
+
+    def _subgraph(self, fn, which, n, k, min_p, epoch, what):
+        kk = max(int(k), 1)
+        cnt, off = np.zeros(n, dtype=np.int32), np.zeros(n + 1, dtype=np.int64)
+        ids, p = np.empty((n, kk), dtype=np.int32), np.empty((n, kk), dtype=np.float64)
+        row_ptr = np.empty((n, kk + 1), dtype=np.int64)
+        head = (self._h, int(which), int(epoch), int(k), float(min_p))
+        self._ck(fn(*head, 0, DEST_HOST, cnt.ctypes.data, off.ctypes.data, ids.ctypes.data, p.ctypes.data, row_ptr.ctypes.data, None), what)  # the size call
+        total = int(off[n])
+        col = np.empty(total, dtype=np.int32)
+        if total:   # the fill (the state does not change between the two calls of one thread)
+            self._ck(fn(*head, total, DEST_HOST, cnt.ctypes.data, off.ctypes.data, None, None, None, col.ctypes.data), what)
+            if int(off[n]) != total:
+                raise DpprError(f"{what}: the state changed between the size call and the fill")
+        return cnt, off, ids, p, row_ptr, col
+
+    def group_subgraph_dev(self, group, k, min_p, cap, ids_ptr, p_ptr, row_ptr_ptr, col_ptr, epoch=-1):
+        """dppr_group_subgraph into device memory at the given raw addresses (ids / p [n][k], row_ptr [n][k + 1], col cap entries;
+        each of the first three may be None): the host (counts [n], offsets [n + 1]). Nothing is written to col if offsets[n] > cap."""
+        return self._subgraph_dev(self._L.dppr_group_subgraph, group, self._group_n.get(group, 1), k, min_p, cap, ids_ptr, p_ptr,
+                                  row_ptr_ptr, col_ptr, epoch, "group_subgraph_dev")
+
+    def subgraph_dev(self, slot, k, min_p, cap, ids_ptr, p_ptr, row_ptr_ptr, col_ptr, epoch=-1):
+        """dppr_subgraph into device memory at the given raw addresses: the host (counts [1], offsets [2])."""
+        return self._subgraph_dev(self._L.dppr_subgraph, slot, 1, k, min_p, cap, ids_ptr, p_ptr, row_ptr_ptr, col_ptr, epoch, "subgraph_dev")
+
+    def _subgraph_dev(self, fn, which, n, k, min_p, cap, ids_ptr, p_ptr, row_ptr_ptr, col_ptr, epoch, what):
+        cnt, off = np.zeros(n, dtype=np.int32), np.zeros(n + 1, dtype=np.int64)
+        self._ck(fn(self._h, int(which), int(epoch), int(k), float(min_p), int(cap), DEST_DEVICE, cnt.ctypes.data, off.ctypes.data,
+                    ids_ptr or None, p_ptr or None, row_ptr_ptr or None, col_ptr or None), what)
+        return cnt, off
+
+    def set_subgraph_wave_max(self, wave_max):
+        """Test and measurement hook (dppr_debug_subgraph_wave_max): rows of the subgraph calls with at most this many entries in
+        the order are placed by one wave, the others by a workgroup; 0 .. 256, default 256. The results do not depend on it."""
+        self._ck(self._L.dppr_debug_subgraph_wave_max(self._h, int(wave_max)), "set_subgraph_wave_max")
 
     def id_map(self):
         """Test hook (dppr_debug_id_map): the internal id of every external id, -1 without one."""

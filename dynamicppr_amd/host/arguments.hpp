@@ -142,6 +142,10 @@ inline void PrintUsage() {
               << "--cluster <K> [--cluster-min <P>] [--cluster-min-size <M>]: after every batch print, per source in source order, the prefix of\n"
               << "            lowest conductance of the source's K vertices of largest pagerank > P (1 <= K <= 8192, P >= 0, 1 <= M <= K vertices\n"
               << "            at least): cluster <source> size <vertices> cut <edges leaving it> vol <its out-degrees> phi <conductance>\n"
+              << "--subgraph <K> [--subgraph-out <file>]: after every batch print, per source in source order, the size of the subgraph its K\n"
+              << "            vertices of largest pagerank induce (1 <= K <= 8192): subgraph <source> vertices <L> edges <stored edges among them>;\n"
+              << "            with --subgraph-out also write it to <file> (the last batch's; with -g N one file per device, <file>.<device>):\n"
+              << "            v <source> <position> <vertex> <pagerank> per vertex, e <source> <tail position> <head position> per edge\n"
               << "--validate: residual bound + power-iteration check after every solve\n"
               << "--split: drive each batch through IncrementalBatchUpdate/ExecuteMainLoop(0)/(1)\n"
               << "--sync: synchronous (deterministic) push schedule\n"
@@ -191,6 +195,7 @@ inline void ArgumentsChecker() {
     if (gClusterGiven && (gClusterK < 1 || gClusterK > DPPR_CLUSTER_MAX || !(gClusterMin >= 0.0) || gClusterMinSize < 1 || gClusterMinSize > gClusterK))
         ok = false;
     if (gClusterOptsGiven && !gClusterGiven) ok = false;
+    if ((gSubgraphGiven && (gSubgraphK < 1 || gSubgraphK > DPPR_SUBGRAPH_MAX)) || (!gSubgraphOut.empty() && !gSubgraphGiven)) ok = false;
     if (gTopKWeightsGiven && (gTopK == 0 || gTopKWeights.empty())) ok = false; // (the count is checked against the sources in main)
     if (!ok) {
         std::cout << "invalid arguments" << std::endl;
@@ -245,6 +250,9 @@ inline void ArgumentsParser(int argc, char **argv) {
     gClusterOptsGiven = find(argc, argv, "--cluster-min") != nullptr || find(argc, argv, "--cluster-min-size") != nullptr;
     gClusterMin = as_double(argc, argv, "--cluster-min", 0.0);
     gClusterMinSize = as_int(argc, argv, "--cluster-min-size", 1);
+    gSubgraphGiven = find(argc, argv, "--subgraph") != nullptr;
+    gSubgraphK = as_int(argc, argv, "--subgraph", 0);
+    if (const char *f = find(argc, argv, "--subgraph-out")) gSubgraphOut = f;
     gValidate = has(argc, argv, "--validate");
     gSplitInterface = has(argc, argv, "--split");
     gSchedule = has(argc, argv, "--sync") ? 1 : 0;

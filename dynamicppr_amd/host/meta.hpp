@@ -65,6 +65,9 @@ inline bool gClusterGiven = false;
 inline double gClusterMin = 0.0;      // --cluster-min P : the order holds the vertices with pagerank > P
 inline int gClusterMinSize = 1;       // --cluster-min-size M : the smallest prefix that may be the cluster
 inline bool gClusterOptsGiven = false; //   --cluster-min or --cluster-min-size was given
+inline int gSubgraphK = 0;            // --subgraph K : after every batch print subgraph <source> vertices <L> edges <m>, the top-K order and the stored edges among it (0: off)
+inline bool gSubgraphGiven = false;
+inline std::string gSubgraphOut;      // --subgraph-out FILE : ... and write the CSR of the last batch, text lines `v source position id pagerank` and `e source tail head`
 inline bool gValidate = false;        // --validate : the reference's -DVALIDATE checks at run time
 inline bool gShareDevice = false;     // --share-device (or DPPR_DEVICE_ALIAS=1): the -g N device threads share the devices that exist (d % count)
 inline bool gPushOnly = false;        // --push-only : no pull sweeps (the ablation of the -o variants times their push mechanisms)

@@ -78,6 +78,8 @@ int main(int argc, char *argv[]) {
             }
         }
         drivers[(size_t)d].reset(new PPRRevPushGPU(graphs[(size_t)d].get(), present ? d % present : d, mine, /*quiet=*/d != 0 && ngpu > 1));
+        drivers[(size_t)d]->driver_index = d;
+        drivers[(size_t)d]->n_drivers = ngpu;
     }
     // DPPR_WATCHDOG_S=<seconds>: a thread that ends the process -- after printing dppr_debug_dump of every engine -- when no
     // driver has made progress (a from-scratch solve, a slide, a batch) for that long. The engine waits on device-side

@@ -256,6 +256,7 @@ public:
             if (gChangesK > 0) PrintChanges(stream_batch_count);
             if (!gRefineIds.empty()) PrintRefined(-1);
             if (gClusterK > 0) PrintClusters(-1);
+            if (gSubgraphK > 0) PrintSubgraphs(-1);
         }
         batches_done = stream_batch_count - 1;
         if (!quiet_) Report(stream_batch_count);
@@ -350,6 +351,7 @@ public:
             if (gChangesK > 0) PrintChanges(stream_batch_count);
             if (!gRefineIds.empty()) PrintRefined(epoch); // (the epoch the states stand on: the helper may have built the next one)
             if (gClusterK > 0) PrintClusters(epoch);
+            if (gSubgraphK > 0) PrintSubgraphs(epoch);
         }
         batches_done = stream_batch_count - 1;
         if (!quiet_) Report(stream_batch_count);
@@ -618,6 +620,62 @@ public:
         std::cout << out << std::flush;
     }
 
+    // --subgraph: after a batch, every source's top-K order and the stored edges of `epoch` among its vertices (dppr_subgraph /
+    // dppr_group_subgraph: the size query, then the fill). Outside the timed region, printed as one block like --changes; the file
+    // of --subgraph-out is written anew after every batch, so it holds the last one's.
+    void PrintSubgraphs(int32_t epoch) {
+        const size_t n_src = source_vertex_ids.size(), k = (size_t)gSubgraphK;
+        std::string out, file;
+        char line[200];
+        std::vector<int32_t> cnt, ids, col;
+        std::vector<int64_t> off, row_ptr;
+        std::vector<double> p;
+        for (size_t first = 0; first < n_src; first += use_groups ? kGroupMax : 1) {
+            const size_t n = use_groups ? std::min(kGroupMax, n_src - first) : 1;
+            cnt.assign(n, 0), off.assign(n + 1, 0), ids.assign(n * k, -1), p.assign(n * k, 0.0), row_ptr.assign(n * (k + 1), 0);
+            auto call = [&](int64_t cap) {
+                if (use_groups)
+                    DPPR_CHECK(engine, dppr_group_subgraph(engine, groups[first / kGroupMax], epoch, gSubgraphK, 0.0, cap, DPPR_DEST_HOST, cnt.data(), off.data(), ids.data(),
+                                                           p.data(), row_ptr.data(), cap ? col.data() : nullptr));
+                else
+                    DPPR_CHECK(engine, dppr_subgraph(engine, slots[first], epoch, gSubgraphK, 0.0, cap, DPPR_DEST_HOST, cnt.data(), off.data(), ids.data(), p.data(),
+                                                     row_ptr.data(), cap ? col.data() : nullptr));
+            };
+            call(0);
+            col.assign((size_t)off[n], 0);
+            if (off[n] > 0) call(off[n]);
+            for (size_t j = 0; j < n; ++j) {
+                const int src = (int)source_vertex_ids[first + j];
+                std::snprintf(line, sizeof(line), "subgraph %d vertices %d edges %lld\n", src, (int)cnt[j], (long long)(off[j + 1] - off[j]));
+                out += line;
+                if (gSubgraphOut.empty()) continue;
+                for (int32_t t = 0; t < cnt[j]; ++t) {
+                    std::snprintf(line, sizeof(line), "v %d %d %d %.17g\n", src, (int)t, (int)ids[j * k + (size_t)t], p[j * k + (size_t)t]);
+                    file += line;
+                }
+                for (int32_t t = 0; t < cnt[j]; ++t)
+                    for (int64_t x = row_ptr[j * (k + 1) + (size_t)t]; x < row_ptr[j * (k + 1) + (size_t)t + 1]; ++x) {
+                        std::snprintf(line, sizeof(line), "e %d %d %d\n", src, (int)t, (int)col[(size_t)x]);
+                        file += line;
+                    }
+            }
+        }
+        if (!gSubgraphOut.empty()) {
+            const std::string path = gSubgraphOut + (n_drivers > 1 ? "." + std::to_string(driver_index) : "");
+            std::FILE *f = std::fopen(path.c_str(), "w");
+            if (!f) {
+                std::cout << "cannot write " << path << std::endl;
+                std::exit(-1);
+            }
+            std::fwrite(file.data(), 1, file.size(), f);
+            std::fclose(f);
+        }
+        progress++;
+        static std::mutex print_mu;
+        std::lock_guard<std::mutex> lk(print_mu);
+        std::cout << out << std::flush;
+    }
+
     // --topk-weights: the k vertices of largest sum_i w_i * p_i over this device's sources, which are one group (checked in main)
     std::vector<TopEntry> TopKWeighted(int k, const std::vector<double> &w) {
         std::vector<int32_t> ids((size_t)k, -1);
@@ -638,6 +696,7 @@ public:
     SlidingGraphVec *graph;
     dppr_engine *engine = nullptr;
     int device_id;
+    int driver_index = 0, n_drivers = 1; // which of the -g N drivers this is (the suffix of a per-driver file)
     std::vector<IndexType> source_vertex_ids;
     std::vector<int32_t> slots;  // one per source (single-source mode)
     static constexpr size_t kGroupMax = 16; // sources per group (dppr_add_source_group)

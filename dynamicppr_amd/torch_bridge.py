@@ -1,5 +1,5 @@
 """The engine's state as torch tensors on the engine's device: the device-side exports of include/dppr.h
-(dppr_group_export_sparse / dppr_group_export_dense_dev) written straight into memory that torch allocated.
+(dppr_group_export_sparse / dppr_group_export_dense_dev, dppr_group_subgraph) written straight into memory that torch allocated.
 
 The engine binding itself (``engine.py``) stays torch-free: nothing there imports torch, and importing this module puts no
 torch into it.
@@ -135,3 +135,28 @@ def group_dot(engine, gid, H, which="p", layout="feature_major"):
     torch.cuda.synchronize(dev)
     engine.group_dot_dense_dev(gid, H.data_ptr(), F, _WHICH[which], _DTYPES[H.dtype], _H_LAYOUTS[layout], out_ptr=out.data_ptr())
     return out
+
+
+def group_subgraph(engine, gid, k, min_p=0.0, epoch=-1):
+    """The top-k order of every source of group `gid` and the stored edges among its vertices (dppr_group_subgraph) as tensors on the
+    engine's device, filled in place: (counts [n] int32, ids [n, k] int32, p [n, k] float64, row_ptr [n, k + 1] int64, col int32).
+    Row j of source i is col[row_ptr[i, j]:row_ptr[i, j + 1]]: positions in source i's order, ascending; ids are -1 and p is 0 past
+    counts[i]. Two calls: the size query, then the fill with exactly that many entries."""
+    if not 1 <= int(k) <= _eng.SUBGRAPH_MAX:
+        raise _eng.DpprError(f"group_subgraph: 1 <= k <= {_eng.SUBGRAPH_MAX}, not {k}")
+    n = len(engine.group_sources(gid))
+    dev = _device(engine)
+    k = int(k)
+    ids = torch.empty((n, k), dtype=torch.int32, device=dev)
+    p = torch.empty((n, k), dtype=torch.float64, device=dev)
+    row_ptr = torch.empty((n, k + 1), dtype=torch.int64, device=dev)
+    torch.cuda.synchronize(dev)   # (the allocations are torch's; nothing of torch's is in flight on them when the engine writes)
+    cnt, off = engine.group_subgraph_dev(gid, k, min_p, 0, ids.data_ptr(), p.data_ptr(), row_ptr.data_ptr(), None, epoch)
+    total = int(off[n])
+    col = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+    if total:
+        torch.cuda.synchronize(dev)
+        cnt, off = engine.group_subgraph_dev(gid, k, min_p, total, None, None, None, col.data_ptr(), epoch)
+        if int(off[n]) != total:
+            raise _eng.DpprError("group_subgraph: the state changed between the size call and the fill")
+    return torch.from_numpy(cnt).to(dev), ids, p, row_ptr, col[:total]

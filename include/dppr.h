@@ -735,6 +735,65 @@ int dppr_group_cluster(dppr_engine *e, int32_t group, int32_t epoch, int32_t k, 
                        int32_t *out_ids /* [n][k] or NULL */, int64_t *out_cut_out /* [n][k] or NULL */,
                        int64_t *out_cut_in /* [n][k] or NULL */, int64_t *out_vol /* [n][k] or NULL */);
 
+/* ---- the subgraph around a source: its top-k order and every stored edge among it (backward-compatible additions, ABI 6) ----
+ * What a PPR index is most often kept for downstream: the k vertices of largest p and the edges among them as a CSR in LOCAL
+ * numbering (vertex = its position in the order) -- the input of a PPR-neighbourhood sampler or of a plot -- built on the device,
+ * next to the state, instead of dppr_group_topk + dppr_read_out_graph + a filter on the host and a copy back.
+ *
+ * For source i (lane order; a slot is n = 1), every output is defined exactly:
+ *   ORDER   v_0 .. v_{L-1}: exactly what dppr_topk / dppr_group_topk return for (k, min_p) -- p > min_p, p descending, external
+ *           id ascending, live and parked zone -- with L = min(k, #qualifying). out_counts[i] = L; out_ids[i][j] = v_j and -1
+ *           past L; out_p[i][j] is the stored double and 0.0 past L.
+ *   GRAPH   the out-CSR of `epoch` with multiplicity: a duplicate edge appears as often as it is stored. A self loop of a vertex
+ *           of the order IS an edge of the subgraph (tail position = head position); dppr_cluster differs here, because a self
+ *           loop never crosses a cut. A vertex without a row in that epoch (parked, or never named) has an empty row and is
+ *           nobody's head.
+ *   ROWS    with rho_i(w) the position of w in the order, row j of source i holds rho_i(w) for every stored out-edge v_j -> w
+ *           whose head lies in the order, in ascending position; equal positions are adjacent. The order in which the device
+ *           stores a row's entries is no part of this: the rule does not depend on it.
+ *   LAYOUT  one CSR over all sources. out_offsets [n + 1]: source i's entries occupy [offsets[i], offsets[i + 1]) of out_col;
+ *           offsets[0] = 0. out_row_ptr [n][k + 1] holds ABSOLUTE indices into out_col: row j of source i is
+ *           [row_ptr[i][j], row_ptr[i][j + 1]), row_ptr[i][0] = offsets[i], and row_ptr[i][j] = offsets[i + 1] for j >= L.
+ *           out_col [cap] holds local positions in [0, L).
+ * Prefix property: with k' < k and both orders longer than k', row j < k' of the smaller call is row j of the larger one
+ * restricted to positions < k'.
+ * Capacity: out_offsets and out_counts are always HOST memory and are always written with the TRUE counts. If offsets[n] > cap
+ * nothing is written to out_col and the call still returns DPPR_OK -- the caller compares offsets[n] with cap; out_ids, out_p and
+ * out_row_ptr are written either way. cap = 0 with a NULL out_col is the size query; the pattern is two calls, the second with
+ * cap = offsets[n] of the first.
+ * dest (DPPR_DEST_HOST / DPPR_DEST_DEVICE): where out_ids, out_p, out_row_ptr and out_col live; each of the first three may be
+ * NULL. A device destination is checked as the exports check theirs, before any device work: device memory of the ENGINE'S
+ * device, the bytes needed (n * k ids / p, n * (k + 1) row_ptr, cap entries of col, cap taken as at most n * Ed) wholly inside
+ * one allocation, aligned to the element size; and the call returns after the solver stream has finished writing, so any stream
+ * of the caller may read afterwards.
+ * Determinism: the result is a function of the state and the epoch alone; no output position comes from the return value of an
+ * atomic (integer sums are used to count).
+ *
+ * Epoch rule as dppr_cluster: the epoch must be resident (-1: the newest) and, if the epoch the state stands on is known
+ * (anything but a state set by dppr_write), it must be the one given. Convergence is NOT required.
+ * Rejected with DPPR_ERR_INVALID before any device work, nothing written: k outside [1, DPPR_SUBGRAPH_MAX], min_p negative or
+ * NaN, cap < 0, cap > 0 with a NULL out_col, a NULL out_offsets or out_counts, dest outside its values, a bad slot / group, an
+ * epoch that is not resident or not the state's, a bad device pointer.
+ * Threading and stream as dppr_cluster: the id-map lock of dppr_read (safe beside dppr_slide_concurrent), the solver stream, never
+ * part of the update path or of a timed region. Work space beyond dppr_cluster's rank table and chunk list: 1 MiB of per-position
+ * counters and the block (ids, p, row_ptr; a host destination's col by cap, device and pinned host); all of it is the engine's,
+ * obtained before the first kernel, grown on demand and released with the engine: after DPPR_ERR_NOMEM the states and the engine
+ * are as before. With dppr_set_profiling on, dppr_debug_query_ms also reports the device time of the last of these calls, first
+ * to last kernel (the one read of the counts by the host lies between them).
+ * dppr_debug_subgraph_wave_max: a test and measurement hook. A row with at most this many entries in the order (default and largest
+ * value 256; and at most 2048 stored entries) is placed by the wave that owns it, any other by a workgroup with a histogram; 0
+ * sends every row there. The results do not depend on it. */
+#define DPPR_SUBGRAPH_MAX DPPR_TOPK_MAX     /* 8192: the subgraph is induced by the order dppr_topk defines */
+int dppr_subgraph(dppr_engine *e, int32_t slot, int32_t epoch, int32_t k, double min_p, int64_t cap, int dest,
+                  int32_t *out_count /* HOST */, int64_t *out_offsets /* [2], HOST */,
+                  int32_t *out_ids /* [k] or NULL */, double *out_p /* [k] or NULL */,
+                  int64_t *out_row_ptr /* [k + 1] or NULL */, int32_t *out_col /* [cap]; NULL with cap = 0 */);
+int dppr_group_subgraph(dppr_engine *e, int32_t group, int32_t epoch, int32_t k, double min_p, int64_t cap, int dest,
+                        int32_t *out_counts /* [n], HOST */, int64_t *out_offsets /* [n + 1], HOST */,
+                        int32_t *out_ids /* [n][k] or NULL */, double *out_p /* [n][k] or NULL */,
+                        int64_t *out_row_ptr /* [n][k + 1] or NULL */, int32_t *out_col /* [cap]; NULL with cap = 0 */);
+int dppr_debug_subgraph_wave_max(dppr_engine *e, int wave_max);
+
 /* Windows whose sweep groups are all resident at once run a frontier loop of a source group as
  * multi-sweep launches (grid barrier between sweeps, row tables kept in LDS; dppr_multi.hpp). on by
  * default; 0 = one launch per sweep everywhere. The roll-call / time-out rules are those of
