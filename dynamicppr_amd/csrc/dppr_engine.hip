@@ -1076,9 +1076,33 @@ int dppr_trace_get(dppr_engine *e, int32_t slot, int64_t *n_iters, int64_t *n_id
     if ((e)->broken) return fail((e), DPPR_ERR_INVALID, "engine unusable after a failed renumbering");           \
     Group &g = (e)->groups[(size_t)(gid)]
 
-int dppr_add_source_group(dppr_engine *e, const int32_t *sources, int32_t n, int32_t *out_group) {
-    if (!e || e->broken || !sources || n < 1 || n > GS_MAX) return fail(e, DPPR_ERR_INVALID, "add_source_group: 1..16 sources");
-    if (!ids_in_range(e, sources, n)) return fail(e, DPPR_ERR_INVALID, "add_source_group: vertex out of range"); // before anything is touched
+static_assert(TG_LANES == GS_MAX, "dppr_targets_plan.hpp plans for the group size of dppr_multi.hpp");
+static_assert(TG_SET_MAX == DPPR_TARGET_SET_MAX, "dppr_targets_plan.hpp restates DPPR_TARGET_SET_MAX of include/dppr.h");
+
+// The seed table of `ts` in the current numbering (every seed has an id), packed and copied into `buf` (tg_bytes(total) bytes,
+// allocated by the caller before anything changed); the host copy goes to `tab`.
+static int tg_upload(dppr_engine *e, const TargetSets &ts, DevBuf<unsigned char> &buf, TgTable &tab) {
+    tab = tg_table(ts, [&](int32_t ext) { return e->ext2int[(size_t)ext]; });
+    std::vector<unsigned char> blob(tg_bytes(tab.total()));
+    tg_pack(tab, blob.data());
+    HIP_TRY(hipMemcpyAsync(buf, blob.data(), blob.size(), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return DPPR_OK;
+}
+
+// Init of a group (gpu/PPRCommon.cuh:12-22 per lane): r = e_s for plain sources; with a set lane p = r = 0 in one streaming pass and
+// the weights scattered by a second, tiny launch (dppr_targets.hpp)
+static void launch_group_init(dppr_engine *e, Group &g) {
+    if (g.tsets.n > 0) {
+        hipLaunchKernelGGL(k_tg_init, dim3(grid_for((int64_t)e->V * g.gw)), dim3(BLOCK), 0, e->stream, g.p.get(), g.r.get(), e->V, g.gw);
+        hipLaunchKernelGGL(k_tg_scatter, dim3(grid_for(g.ttab.total())), dim3(BLOCK), 0, e->stream, g.r.get(), e->V, g.gw, tg_dev(g), 0, g.n);
+    } else {
+        hipLaunchKernelGGL(k_ginit, dim3(grid_for((int64_t)e->V * g.gw)), dim3(BLOCK), 0, e->stream, g.p, g.r, e->V, g.gw, g.src);
+    }
+}
+
+// dppr_add_source_group (ts == nullptr) and dppr_add_target_group with at least one set lane (sources[s] = -1 there); arguments checked
+static int add_group(dppr_engine *e, const int32_t *sources, int32_t n, const TargetSets *ts, int32_t *out_group) {
     HIP_TRY(hipSetDevice(e->device));
     Group g;
     g.n = n;
@@ -1105,11 +1129,21 @@ int dppr_add_source_group(dppr_engine *e, const int32_t *sources, int32_t n, int
     HIP_TRY_MSG("add_source_group: ", hipMemsetAsync(g.act[1], 0, g.act_bytes, e->stream));
     HIP_TRY_MSG("add_source_group: ", hipMemsetAsync(g.cnt, 0, sizeof(int) * (5 * GS_MAX + MAX_CHUNK * GS_MAX), e->stream));
     HIP_TRY_MSG("add_source_group: ", hipMemsetAsync(g.dstats, 0, 2 * sizeof(IterStats), e->stream));
-    // the memory is there: now the ids (a source outside the window receives one; a parked one is revived)
-    for (int s = 0; s < n; ++s) (void)to_int(e, sources[s]);
-    for (int s = 0; s < n; ++s) g.src.s[s] = e->ext2int[(size_t)sources[s]]; // (after ALL revivals: one may move another)
+    if (ts) HIP_TRY_MSG("add_target_group: ", g.tg.alloc(tg_bytes(ts->total())));
+    // the memory is there: now the ids (a source or seed outside the window receives one; a parked one is revived)
+    if (ts) {
+        for (int s = 0; s < n; ++s)
+            for (const TgSeed &sd : ts->lane[s]) (void)to_int(e, sd.id);
+    } else {
+        for (int s = 0; s < n; ++s) (void)to_int(e, sources[s]);
+    }
+    for (int s = 0; s < n; ++s) g.src.s[s] = sources[s] >= 0 ? e->ext2int[(size_t)sources[s]] : -1; // (after ALL revivals: one may move another)
     if (int rc = flush_moves(e)) return rc;
-    hipLaunchKernelGGL(k_ginit, dim3(grid_for((int64_t)e->V * g.gw)), dim3(BLOCK), 0, e->stream, g.p, g.r, e->V, g.gw, g.src);
+    if (ts) {
+        g.tsets = *ts;
+        if (int rc = tg_upload(e, g.tsets, g.tg, g.ttab)) return rc;
+    }
+    launch_group_init(e, g);
     HIP_TRY_MSG("add_source_group: ", hipGetLastError());
     HIP_TRY_MSG("add_source_group: ", hipStreamSynchronize(e->stream));
     if (g.spl == 2) e->wide_groups = true;
@@ -1118,6 +1152,23 @@ int dppr_add_source_group(dppr_engine *e, const int32_t *sources, int32_t n, int
     if (int rc = recut_stale_groups(e)) return rc;
     if (out_group) *out_group = (int)e->groups.size() - 1;
     return DPPR_OK;
+}
+
+int dppr_add_source_group(dppr_engine *e, const int32_t *sources, int32_t n, int32_t *out_group) {
+    if (!e || e->broken || !sources || n < 1 || n > GS_MAX) return fail(e, DPPR_ERR_INVALID, "add_source_group: 1..16 sources");
+    if (!ids_in_range(e, sources, n)) return fail(e, DPPR_ERR_INVALID, "add_source_group: vertex out of range"); // before anything is touched
+    return add_group(e, sources, n, nullptr, out_group);
+}
+
+int dppr_add_target_group(dppr_engine *e, const int64_t *offsets, const int32_t *ids, const double *weights, int32_t n, int32_t *out_group) {
+    if (!e || e->broken) return fail(e, DPPR_ERR_INVALID, "add_target_group: no usable engine");
+    if (const TgCheck c = tg_check(offsets, ids, weights, n, e->V)) // before anything is touched
+        return fail(e, DPPR_ERR_INVALID, (std::string("add_target_group: ") + tg_check_text(c)).c_str());
+    const TargetSets ts = tg_build(offsets, ids, weights, n);
+    int32_t sources[GS_MAX];
+    tg_sources(ts, sources);
+    // a group of single seeds of weight 1.0 IS a source group: the same state, the same kernels
+    return add_group(e, sources, n, tg_has_set(ts) ? &ts : nullptr, out_group);
 }
 
 int dppr_group_init_solve(dppr_engine *e, int32_t group, double eps, float *out_ms) {
@@ -1131,13 +1182,13 @@ int dppr_group_init_solve_at(dppr_engine *e, int32_t group, int32_t epoch, doubl
     HIP_TRY(hipSetDevice(e->device));
     int rc = bracket_open(e);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_ginit, dim3(grid_for((int64_t)e->V * g.gw)), dim3(BLOCK), 0, e->stream, g.p, g.r, e->V, g.gw, g.src);
+    launch_group_init(e, g);
     HIP_TRY(hipGetLastError());
     g.converged = false;
     g.park_eps = 0.0;
     rc = group_loop(e, g, ep, 0, eps, false);
     if (rc) return rc;
-    return solve_finished(e, g, eps, ep.id, false, out_ms); // r = e_s >= 0 and phase 0 left every r <= eps: nothing is below -eps
+    return solve_finished(e, g, eps, ep.id, false, out_ms); // r = e_s (or h) >= 0 and phase 0 left every r <= eps: nothing is below -eps
 }
 
 int dppr_group_update(dppr_engine *e, int32_t group, int32_t epoch, double eps, float *out_ms) {
@@ -1193,13 +1244,20 @@ int dppr_group_sources(dppr_engine *e, int32_t group, int32_t *out_sources, int3
 // The three changes share one sequence: every check, every new buffer, then the ids (the first step that touches anything),
 // the re-cut of a fresh id or of the first wide group (the builder's work: outside the event bracket), then the device
 // work on the solver stream -- relayout, owners swapped, column init, the column's loop.
-static int group_churn(dppr_engine *e, int32_t group, ChurnOp op, int32_t index, int32_t new_source, int32_t *out_index, float *out_ms) {
-    static const char *const what[3] = {"group_replace_source", "group_add_source", "group_remove_source"};
+// `fresh`: the seed set the (re)initialised lane receives (dppr_group_replace_target; checked by the caller), nullptr: the source
+// new_source. A group that neither has nor receives a set lane takes the steps it always took.
+static int group_churn(dppr_engine *e, int32_t group, ChurnOp op, int32_t index, int32_t new_source, int32_t *out_index, float *out_ms,
+                       const std::vector<TgSeed> *fresh = nullptr) {
+    const char *const what[3] = {fresh ? "group_replace_target" : "group_replace_source", "group_add_source", "group_remove_source"};
+    if (fresh && tg_is_source(*fresh)) { // one seed of weight 1.0: a source lane
+        new_source = (*fresh)[0].id;
+        fresh = nullptr;
+    }
     auto refuse = [&](const char *why) { return fail(e, DPPR_ERR_INVALID, (std::string(what[op]) + ": " + why).c_str()); };
     GET_GROUP(e, group);
     const ChurnPlan pl = churn_plan(op, g.n, g.gw, index, e->group_full_rows, e->wide_groups);
     if (!pl.ok) return refuse(op == CHURN_ADD ? "the group holds 16 sources" : op == CHURN_REMOVE && g.n <= 1 ? "the last source of a group cannot be removed" : "bad source index");
-    if (op != CHURN_REMOVE && (new_source < 0 || new_source >= e->V)) return refuse("vertex out of range");
+    if (op != CHURN_REMOVE && !fresh && (new_source < 0 || new_source >= e->V)) return refuse("vertex out of range");
     if (!g.converged || g.last_epoch < 0) return refuse("the group is not converged (solve or update it first)");
     Epoch *epp = find_epoch(e, g.last_epoch);
     if (!epp) return refuse("the epoch the group was last solved on is not resident any more");
@@ -1217,15 +1275,39 @@ static int group_churn(dppr_engine *e, int32_t group, ChurnOp op, int32_t index,
         HIP_TRY(x_new.alloc((size_t)x_stride(pl.gw) * V));
         HIP_TRY(x2_new.alloc((size_t)x_stride(pl.gw) * V));
     }
+    // the seed sets afterwards (a group without a set lane keeps none) and the table that goes with them
+    TargetSets nts;
+    DevBuf<unsigned char> tg_new;
+    if (g.tsets.n > 0 || fresh) {
+        TargetSets base = g.tsets;
+        if (base.n == 0) { // the first set lane of a source group: its sources as lanes of one seed
+            base.n = g.n;
+            for (int s = 0; s < g.n; ++s) base.lane[s] = tg_source_lane(g.src_ext[s]);
+        }
+        nts = tg_relane(base, pl.map, pl.n, pl.lane, pl.lane < 0 ? std::vector<TgSeed>() : fresh ? *fresh : tg_source_lane(new_source));
+        if (!tg_has_set(nts)) nts = TargetSets(); // (the last set lane became a source or left: a source group again)
+        else HIP_TRY(tg_new.alloc(tg_bytes(nts.total())));
+    }
     int src_int = -1;
     if (op != CHURN_REMOVE) { // the id (a vertex outside the window receives one, a parked one is revived), rows moved in the old layout
-        (void)to_int(e, new_source);
+        if (fresh) {
+            for (const TgSeed &sd : *fresh) (void)to_int(e, sd.id);
+            new_source = -1; // (what dppr_group_sources reports for the lane)
+        } else {
+            (void)to_int(e, new_source);
+        }
         if (int rc = flush_moves(e)) return rc;
-        src_int = e->ext2int[(size_t)new_source];
+        src_int = fresh ? -1 : e->ext2int[(size_t)new_source];
         if (pl.recut) e->wide_groups = true;
         if (int rc = recut_stale_groups(e)) return rc; // (a fresh id lies beyond every resident epoch's tables; the first wide group halves the sweep groups)
     }
     g.mark.reset(); // (the lanes change meaning: a mark does not survive a change of the sources)
+    TgTable ttab_new;
+    if (nts.n > 0) // (after the revivals: the ids are final; the old table is read by nothing between two loops)
+        if (int rc = tg_upload(e, nts, tg_new, ttab_new)) return rc;
+    g.tg.swap(tg_new);
+    g.ttab = std::move(ttab_new);
+    g.tsets = std::move(nts);
     if (int rc = bracket_open(e)) return rc;
     if (pl.relayout) {
         ColMap cm;
@@ -1259,7 +1341,13 @@ static int group_churn(dppr_engine *e, int32_t group, ChurnOp op, int32_t index,
     if (pl.lane >= 0) {
         // (a padding lane that is taken into use is initialised like any other, not trusted to be zero; the new column is
         // zero in the parked zone too, which satisfies any park_eps)
-        hipLaunchKernelGGL(k_gcol_init, dim3(grid_for(e->V)), dim3(BLOCK), 0, e->stream, g.p.get(), g.r.get(), e->V, g.gw, pl.lane, src_int);
+        if (g.tsets.n > 0) {
+            hipLaunchKernelGGL(k_tg_col_init, dim3(grid_for(e->V)), dim3(BLOCK), 0, e->stream, g.p.get(), g.r.get(), e->V, g.gw, pl.lane);
+            hipLaunchKernelGGL(k_tg_scatter, dim3(grid_for(g.ttab.off[pl.lane + 1] - g.ttab.off[pl.lane])), dim3(BLOCK), 0, e->stream, g.r.get(),
+                               e->V, g.gw, tg_dev(g), pl.lane, pl.lane + 1);
+        } else {
+            hipLaunchKernelGGL(k_gcol_init, dim3(grid_for(e->V)), dim3(BLOCK), 0, e->stream, g.p.get(), g.r.get(), e->V, g.gw, pl.lane, src_int);
+        }
         HIP_TRY(hipGetLastError());
         g.converged = false;
         if (int rc = group_solve_column(e, g, ep)) return rc;
@@ -1274,6 +1362,28 @@ static int group_churn(dppr_engine *e, int32_t group, ChurnOp op, int32_t index,
 
 int dppr_group_replace_source(dppr_engine *e, int32_t group, int32_t index, int32_t new_source, float *out_ms) {
     return group_churn(e, group, CHURN_REPLACE, index, new_source, nullptr, out_ms);
+}
+
+int dppr_group_replace_target(dppr_engine *e, int32_t group, int32_t index, const int32_t *ids, const double *weights, int32_t m, float *out_ms) {
+    if (!e) return DPPR_ERR_INVALID;
+    if (const TgCheck c = tg_check_lane(ids, weights, m, e->V)) // before anything is touched
+        return fail(e, DPPR_ERR_INVALID, (std::string("group_replace_target: ") + tg_check_text(c)).c_str());
+    const std::vector<TgSeed> fresh = tg_lane(ids, weights, m);
+    return group_churn(e, group, CHURN_REPLACE, index, -1, nullptr, out_ms, &fresh);
+}
+
+int dppr_group_targets(dppr_engine *e, int32_t group, int64_t *out_offsets, int32_t *out_ids, double *out_weights, int64_t cap) {
+    GET_GROUP(e, group);
+    if (!out_offsets || cap < 0 || (cap > 0 && (!out_ids || !out_weights))) return fail(e, DPPR_ERR_INVALID, "group_targets: out_offsets, cap >= 0, arrays for cap > 0");
+    if (g.tsets.n > 0) {
+        tg_list(g.tsets, out_offsets, out_ids, out_weights, cap);
+    } else { // a source group: lanes of one seed of weight 1.0
+        TargetSets ts;
+        ts.n = g.n;
+        for (int s = 0; s < g.n; ++s) ts.lane[s] = tg_source_lane(g.src_ext[s]);
+        tg_list(ts, out_offsets, out_ids, out_weights, cap);
+    }
+    return DPPR_OK;
 }
 
 int dppr_group_add_source(dppr_engine *e, int32_t group, int32_t new_source, int32_t *out_index, float *out_ms) {

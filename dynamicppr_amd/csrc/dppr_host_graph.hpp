@@ -205,8 +205,11 @@ int compact_ids(dppr_engine *e, bool *did) {
         for (int v : e->st_b2) live[(size_t)v] = 1;
     }
     for (const auto &s : e->slots) live[(size_t)s.source] = 1;
-    for (const auto &g : e->groups)
-        for (int k = 0; k < g.n; ++k) live[(size_t)g.src.s[k]] = 1;
+    for (const auto &g : e->groups) {
+        for (int k = 0; k < g.n; ++k)
+            if (g.src.s[k] >= 0) live[(size_t)g.src.s[k]] = 1;
+        for (int v : g.ttab.ids) live[(size_t)v] = 1; // every seed of a set lane stays live, like a source: the stream update looks h[u] up by id
+    }
     int n_live = 0;
     for (int v = 0; v < n_old; ++v) n_live += live[(size_t)v];
     mark("live flags");
@@ -282,13 +285,21 @@ int compact_ids(dppr_engine *e, bool *did) {
         s.phase0_done = false;
         s.park_eps = std::max(s.park_eps, s.conv_eps);
     }
+    std::vector<std::vector<unsigned char>> tg_blobs; // (alive until the stream has been waited for)
     for (auto &g : e->groups) {
         RN_TRY(permute(g.p, g.gw));
         RN_TRY(permute(g.r, g.gw));
         // (snapshot rows mean something only where an activity bit is set, and between loops none is)
         RN_TRY(hipMemsetAsync(g.act[0], 0, g.act_bytes, e->bs));
         RN_TRY(hipMemsetAsync(g.act[1], 0, g.act_bytes, e->bs));
-        for (int k = 0; k < g.n; ++k) g.src.s[k] = perm[(size_t)g.src.s[k]];
+        for (int k = 0; k < g.n; ++k)
+            if (g.src.s[k] >= 0) g.src.s[k] = perm[(size_t)g.src.s[k]];
+        if (g.tsets.n > 0) { // the seed table in the new numbering, its lanes sorted again (same size: written in place)
+            tg_remap(g.ttab, perm.data());
+            tg_blobs.emplace_back(tg_bytes(g.ttab.total()));
+            tg_pack(g.ttab, tg_blobs.back().data());
+            RN_TRY(hipMemcpyAsync(g.tg, tg_blobs.back().data(), tg_blobs.back().size(), hipMemcpyHostToDevice, e->bs));
+        }
         g.park_eps = std::max(g.park_eps, g.conv_eps);
     }
     RN_TRY(hipStreamSynchronize(e->bs));

@@ -361,9 +361,13 @@ int group_stream_update(dppr_engine *e, Group &g, const Epoch &ep) {
     // blockIdx.y = source lane; state element (v, lane) at base[v * gw + lane]
     hipLaunchKernelGGL(k_su_terms, dim3(grid_for(L), g.n), dim3(BLOCK), 0, e->stream, batch_tails(e, ep), batch_order(e, ep), ep.b2,
                        ep.ins, L, g.p, g.gw, e->su_term, e->su_ins);
-    hipLaunchKernelGGL(k_su_apply, dim3(grid_for(L), g.n), dim3(BLOCK), 0, e->stream, batch_tails(e, ep), batch_order(e, ep), e->su_term,
-                       e->su_ins, ep.deg_after, L, g.r, g.gw, srcs, 0.0, (int *)nullptr, (int *)nullptr, (int *)nullptr,
-                       (int *)nullptr);
+    if (g.tsets.n > 0) // a group with a set lane: the source term of a tail is ALPHA * h[u] from the seed table (dppr_targets.hpp)
+        hipLaunchKernelGGL(k_su_apply_seeded, dim3(grid_for(L), g.n), dim3(BLOCK), 0, e->stream, batch_tails(e, ep), batch_order(e, ep),
+                           e->su_term, e->su_ins, ep.deg_after, L, g.r, g.gw, tg_dev(g));
+    else
+        hipLaunchKernelGGL(k_su_apply, dim3(grid_for(L), g.n), dim3(BLOCK), 0, e->stream, batch_tails(e, ep), batch_order(e, ep), e->su_term,
+                           e->su_ins, ep.deg_after, L, g.r, g.gw, srcs, 0.0, (int *)nullptr, (int *)nullptr, (int *)nullptr,
+                           (int *)nullptr);
     HIP_TRY(hipGetLastError());
     g.st.records += (int64_t)L * g.n;
     return DPPR_OK;

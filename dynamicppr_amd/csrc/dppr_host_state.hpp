@@ -147,7 +147,10 @@ struct Group : SolveState {
     int spl = 1;               // doubles per lane of an octet: 1 (rows of <= 8 doubles) or 2
     int gw = OCT;              // doubles per vertex = row_width(n): 2, 4, .. 16 (dppr_multi.hpp)
     int src_ext[GS_MAX] = {0}; // ids the caller gave
-    SrcN src{};                // internal ids, -1 = unused lane
+    SrcN src{};                // internal ids, -1 = unused lane (and a lane whose target is a vertex set: src_ext -1 too)
+    TargetSets tsets;          // the lanes' seed sets by external id (dppr_targets_plan.hpp); n == 0: every lane is a plain source
+    TgTable ttab;              // ... as the device holds them: internal ids ascending within a lane (host copy, remapped by a renumbering)
+    DevBuf<unsigned char> tg;  // ... the seed table on the device (dppr_targets.hpp; empty without a set lane)
     DevBuf<double> p, r, x, x2; // [V][gw]
     DevBuf<double> mark;       // dppr_group_mark: p as it was then, [V][gw] by EXTERNAL id (empty: no mark; dropped when the sources change)
     DevBuf<uint32_t> act[2]; // activity bitmaps that go with x / x2
@@ -171,6 +174,12 @@ struct StateView {
     const SolveState &st;
     bool group; // (the words of a rejection name a slot or a group)
 };
+// the three sections of a group's seed table (dppr_targets_plan.hpp lays the block out)
+inline TgDev tg_dev(const Group &g) {
+    const int64_t total = g.ttab.total();
+    return {reinterpret_cast<const double *>(g.tg.get() + tg_w_at()), reinterpret_cast<const int *>(g.tg.get() + tg_off_at(total)),
+            reinterpret_cast<const int *>(g.tg.get() + tg_ids_at(total))};
+}
 inline StateView view(Slot &s) { return {s.p, s.r, 1, 1, s.mark, s, false}; }
 inline StateView view(Group &g) { return {g.p, g.r, g.gw, g.n, g.mark, g, true}; }
 

@@ -23,6 +23,7 @@
 //   dppr_update.hpp   IncrementalBatchUpdate (lock-free, batch-index order)
 //   dppr_builder.hpp  sliding-window graph builder (full sort / incremental merge), id translation
 //   dppr_churn.hpp    a source group changes its sources: column init, row re-interleaving
+//   dppr_targets.hpp  weighted vertex sets as a group's targets: seed table lookup, seeded Init (included by dppr_update.hpp)
 //   dppr_multi.hpp    multi-source batched sweeps (included separately by the engine)
 #pragma once
 

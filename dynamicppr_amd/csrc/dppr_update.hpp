@@ -3,6 +3,7 @@
 
 #include "dppr_common.hpp"
 #include "dppr_grouping.hpp"
+#include "dppr_targets.hpp"
 
 namespace dppr {
 
@@ -23,7 +24,7 @@ namespace dppr {
 //  k_su_terms: per record (parallel): t = (1-ALPHA)*p[v] - p[u]   (first two terms of
 //              the reference's add expression, evaluated left to right)
 //  k_su_apply: per group leader (sequential over the group):
-//              add = t - ALPHA*r[u] + ALPHA*[u==s]
+//              add = t - ALPHA*r[u] + ALPHA*[u==s]        (a group with a set lane, k_su_apply_seeded: + ALPHA*h[u])
 //              insert: d++; r[u] += add/(d+1)/ALPHA    delete: d--; r[u] -= add/(d+1)/ALPHA
 //              where d starts at the PRE-batch out-degree = post-batch degree reverted
 //              by the group's own records (CopyOutDegree + RevertOutDegree).
@@ -383,6 +384,99 @@ __global__ __launch_bounds__(BLOCK) void k_su_apply(const uint32_t *__restrict__
             if (lane_id() == 0) gb = atomicAdd(cnt_neg, __popcll(m));
             gb = __shfl(gb, 0, WAVE);
             if (neg) ft_neg[gb + mbcnt(m)] = u;
+        }
+    }
+}
+
+// k_su_apply for a group that has a set lane (dppr_targets.hpp): blockIdx.y = lane of the group's seed table, and the source term of a
+// tail run is ALPHA * h[u]. h[u] is looked up ONCE per run, before its recurrence -- in the wave path by every lane alike (the tail is
+// wave-uniform). The recurrence, its order and its divisions are k_su_apply's, statement for statement: a lane of one seed of weight
+// 1.0 receives the bits k_su_apply gives a source. Groups seed densely (k_gseed), so there are no frontier lists to append to. A kernel
+// of its own so that k_su_apply's code stays what it was for groups without a set lane.
+__global__ __launch_bounds__(BLOCK) void k_su_apply_seeded(const uint32_t *__restrict__ skeys, const uint32_t *__restrict__ svals,
+                                                           const double *__restrict__ term_base, const uint8_t *__restrict__ sins,
+                                                           const int *__restrict__ deg_after, int L, double *__restrict__ r_base,
+                                                           int stride, TgDev tg) {
+    __shared__ int s_long[WAVES_PER_BLOCK][WAVE][2]; // (first record, end) of the long groups a wave's lanes lead
+    double *r = r_base + blockIdx.y;
+    const double *term = term_base + (size_t)blockIdx.y * (size_t)L;
+    const int tg_lane = (int)blockIdx.y;
+    const int nthreads = gridDim.x * BLOCK;
+    const int lane = lane_id(), w = wave_id();
+    for (int j0 = blockIdx.x * BLOCK; j0 < L; j0 += nthreads) {
+        const int j = j0 + threadIdx.x;
+        bool is_long = false;
+        int end = 0;
+        if (j < L) {
+            const int u = (int)skeys[j];
+            const bool leader = (j == 0) || ((int)skeys[j - 1] != u);
+            if (leader) {
+                int lo = j, hi = L; // end of the group (as in k_su_apply)
+                while (hi - lo > 1) {
+                    const int mid = lo + ((hi - lo) >> 1);
+                    if ((int)skeys[mid] == u) lo = mid; else hi = mid;
+                }
+                end = hi;
+                is_long = end - j > SU_LONG;
+                if (!is_long) {
+                    int delta = 0; // post-batch degree minus pre-batch degree
+                    for (int k = j; k < end; ++k) delta += sins[k] ? 1 : -1;
+                    int d = deg_after[svals[j]] - delta; // RevertOutDegree (gpu/StreamUpdate.cuh:18-33)
+                    double ru = r[(size_t)u * stride];
+                    const double src_term = ALPHA * tg_h(tg, tg_lane, u);
+                    for (int k = j; k < end; ++k) {
+                        const double add = term[k] - ALPHA * ru + src_term;
+                        if (sins[k]) {
+                            d++;
+                            ru += add / (double)(d + 1) / ALPHA;
+                        } else {
+                            d--;
+                            ru -= add / (double)(d + 1) / ALPHA;
+                        }
+                    }
+                    r[(size_t)u * stride] = ru;
+                }
+            }
+        }
+        // ---- the wave's long groups, one after the other, all lanes together
+        const uint64_t ml = __ballot(is_long);
+        if (ml) { // wave-uniform
+            if (is_long) {
+                s_long[w][mbcnt(ml)][0] = j;
+                s_long[w][mbcnt(ml)][1] = end;
+            }
+            __builtin_amdgcn_wave_barrier();
+            const int n_long = __popcll(ml);
+            for (int g = 0; g < n_long; ++g) {
+                const int gj = s_long[w][g][0], gend = s_long[w][g][1];
+                const int gu = (int)skeys[gj];
+                int part = 0;
+                for (int k = gj + lane; k < gend; k += WAVE) part += sins[k] ? 1 : -1;
+                const int delta = __builtin_amdgcn_readlane(wave_inclusive_scan(part), WAVE - 1);
+                int d = deg_after[svals[gj]] - delta;
+                double ru = r[(size_t)gu * stride];
+                const double src_term = ALPHA * tg_h(tg, tg_lane, gu);
+                for (int base = gj; base < gend; base += WAVE) {
+                    const int k = base + lane;
+                    const double tk = k < gend ? term[k] : 0.0;
+                    const int ik = k < gend ? (int)sins[k] : 0;
+                    const int n = min(WAVE, gend - base);
+                    for (int i = 0; i < n; ++i) { // wave-uniform: every lane evaluates the same recurrence
+                        const double t = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(tk), i), __builtin_amdgcn_readlane(__double2loint(tk), i));
+                        const int is_ins = __builtin_amdgcn_readlane(ik, i);
+                        const double add = t - ALPHA * ru + src_term;
+                        if (is_ins) {
+                            d++;
+                            ru += add / (double)(d + 1) / ALPHA;
+                        } else {
+                            d--;
+                            ru -= add / (double)(d + 1) / ALPHA;
+                        }
+                    }
+                }
+                if (lane == 0) r[(size_t)gu * stride] = ru;
+            }
+            __builtin_amdgcn_wave_barrier();
         }
     }
 }

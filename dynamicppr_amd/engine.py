@@ -70,6 +70,7 @@ EXPORTS = [
     "dppr_walks", "dppr_refine_at", "dppr_group_refine_at", "dppr_debug_id_map", "dppr_debug_walk_form",
     "dppr_cluster", "dppr_group_cluster",
     "dppr_subgraph", "dppr_group_subgraph", "dppr_debug_subgraph_wave_max",
+    "dppr_add_target_group", "dppr_group_replace_target", "dppr_group_targets",
 ]
 
 DEST_HOST, DEST_DEVICE = 0, 1
@@ -82,6 +83,7 @@ WALK_MAX_M, WALK_MAX_W, WALK_MAX_TOTAL = 4096, 1 << 20, 1 << 26
 WALK_REFILL, WALK_PER_THREAD = 0, 1
 CLUSTER_MAX = 8192
 SUBGRAPH_MAX = 8192
+TARGET_SET_MAX = 65536
 
 
 class Cluster(C.Structure):
@@ -212,6 +214,9 @@ def lib():
     L.dppr_group_subgraph.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_int, vp, vp, vp, vp, vp, vp]
     L.dppr_debug_subgraph_wave_max.argtypes = [vp, C.c_int]
     L.dppr_debug_walk_form.argtypes = [vp, C.c_int]
+    L.dppr_add_target_group.argtypes = [vp, i64p, ip, dp, C.c_int32, ip]
+    L.dppr_group_replace_target.argtypes = [vp, C.c_int32, C.c_int32, ip, dp, C.c_int32, fp]
+    L.dppr_group_targets.argtypes = [vp, C.c_int32, i64p, ip, dp, C.c_int64]
     for name in EXPORTS:
         if name not in ("dppr_strerror", "dppr_last_error", "dppr_destroy", "dppr_build_id", "dppr_heartbeat"):
             getattr(L, name).restype = C.c_int
@@ -522,6 +527,61 @@ class Engine:
         """Drops source `index`; the sources behind it move down by one."""
         self._ck(self._L.dppr_group_remove_source(self._h, int(group), int(index)), "group_remove_source")
         self.group_sources(group)   # (keeps _group_n in step: group_topk / group_read_at size their outputs from it)
+
+    # ---- weighted vertex sets as the targets of a group (include/dppr.h) ----
+    @staticmethod
+    def _seed_set(s):
+        """(ids, weights) of one lane: a vertex, a sequence of vertices (weight 1.0 each) or a pair (ids, weights)."""
+        if np.isscalar(s):
+            return np.array([s], dtype=np.int32), np.ones(1)
+        if isinstance(s, tuple) and len(s) == 2 and not np.isscalar(s[0]):
+            ids, w = np.ascontiguousarray(s[0], dtype=np.int32).ravel(), np.ascontiguousarray(s[1], dtype=np.float64).ravel()
+            if len(ids) != len(w):
+                raise ValueError("a seed set needs one weight per id")
+            return ids, w
+        ids = np.ascontiguousarray(s, dtype=np.int32).ravel()
+        return ids, np.ones(len(ids))
+
+    def add_target_group(self, sets):
+        """A group whose lane i tracks the PPR towards the weighted vertex set sets[i] (see _seed_set); a lane of one seed of
+        weight 1.0 is a source lane. Returns the group id."""
+        lanes = [self._seed_set(s) for s in sets]
+        off = np.zeros(len(lanes) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(i) for i, _ in lanes])
+        ids = np.ascontiguousarray(np.concatenate([i for i, _ in lanes]) if lanes else np.zeros(0), dtype=np.int32)
+        w = np.ascontiguousarray(np.concatenate([x for _, x in lanes]) if lanes else np.zeros(0), dtype=np.float64)
+        gid = C.c_int32(-1)
+        self._ck(self._L.dppr_add_target_group(self._h, off.ctypes.data_as(C.POINTER(C.c_int64)), ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               w.ctypes.data_as(C.POINTER(C.c_double)), len(lanes), C.byref(gid)), "add_target_group")
+        self._group_n[gid.value] = len(lanes)
+        return gid.value
+
+    def group_replace_target(self, group, index, ids, weights=None):
+        """Lane `index` of a converged group becomes the weighted set (ids, weights; weight 1.0 each without weights), solved from
+        scratch at the group's tolerance: ms of the device work."""
+        ids, w = self._seed_set(ids if weights is None else (ids, weights))
+        ms = C.c_float(0)
+        self._ck(self._L.dppr_group_replace_target(self._h, int(group), int(index), ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                   w.ctypes.data_as(C.POINTER(C.c_double)), len(ids), C.byref(ms)), "group_replace_target")
+        return ms.value
+
+    def group_targets(self, group, cap=None):
+        """The seed sets of the group in lane order, external ids ascending: a list of (ids, weights). With cap: the raw call,
+        (offsets[17], ids[cap], weights[cap]) -- the arrays untouched when offsets[16] > cap."""
+        off = np.zeros(17, dtype=np.int64)
+        i64p, ip, dp = C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        if cap is None:
+            self._ck(self._L.dppr_group_targets(self._h, int(group), off.ctypes.data_as(i64p), None, None, 0), "group_targets")
+            total = int(off[16])
+        else:
+            total = int(cap)
+        ids, w = np.full(max(total, 1), -7, dtype=np.int32), np.full(max(total, 1), -7.0)
+        self._ck(self._L.dppr_group_targets(self._h, int(group), off.ctypes.data_as(i64p), ids.ctypes.data_as(ip), w.ctypes.data_as(dp), total),
+                 "group_targets")
+        if cap is not None:
+            return off, ids[:total], w[:total]
+        n = len(self.group_sources(group))
+        return [(ids[off[i]:off[i + 1]].copy(), w[off[i]:off[i + 1]].copy()) for i in range(n)]
 
     # ---- queries of a state (top-k and point reads on the device) ----
     def topk(self, slot, k, min_p=0.0):

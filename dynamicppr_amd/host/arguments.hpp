@@ -94,6 +94,21 @@ inline bool load_seeds(const char *path, std::vector<int64_t> &off, std::vector<
     }
     return off.size() > 1;
 }
+// --target-sets: the format of --seeds, one lane per line. false: what load_seeds rejects, or a blank line (a lane has a seed).
+// The weights' sign, the ids' range and an id twice in a lane are the engine's to reject (dppr_add_target_group).
+inline bool load_target_sets(const char *path, std::vector<std::vector<std::pair<int32_t, double>>> &lanes) {
+    std::vector<int64_t> off;
+    std::vector<int32_t> ids;
+    std::vector<double> w;
+    lanes.clear();
+    if (!load_seeds(path, off, ids, w)) return false;
+    for (size_t i = 0; i + 1 < off.size(); ++i) {
+        if (off[i + 1] == off[i]) return false;
+        lanes.emplace_back();
+        for (int64_t k = off[i]; k < off[i + 1]; ++k) lanes.back().emplace_back(ids[(size_t)k], w[(size_t)k]);
+    }
+    return !lanes.empty();
+}
 // --refine: one external vertex id per line (blank lines are skipped). false: unreadable, no id, or a token that is not an id >= 0.
 inline bool load_ids(const char *path, std::vector<int32_t> &ids) {
     std::ifstream in(path);
@@ -121,6 +136,11 @@ inline void PrintUsage() {
               << "-s: gSourceVertexId\n-t: gThreadNum (ignored on the GPU)\n-o: gVariant\n-e: error tolerance\n"
               << "-g: number of GPUs (sources are dealt round-robin)\n"
               << "--sources <file>: one source vertex id per line (overrides -s)\n"
+              << "--target-sets <file>: instead of --sources / -s: one weighted vertex set per line, tokens `id` or `id:weight` (a bare id\n"
+              << "            weighs 1.0; weights finite and > 0, no id twice in a line). Every line is one lane that tracks the pagerank\n"
+              << "            towards its set; lanes are dealt into groups of up to 16 like sources (not with --split / --no-groups /\n"
+              << "            --topk-weights). A lane is named by its first id in the outputs; --validate checks the residual bound and the\n"
+              << "            invariant with the lane's seed vector\n"
               << "--dump <path>: write pagerank/residual of every source after the last batch\n"
               << "--topk <K>: after the last batch print the K vertices of largest pagerank of every source (1 <= K <= 8192),\n"
               << "            one line each, in source order: topk <source> <rank from 1> <vertex> <pagerank>\n"
@@ -197,6 +217,7 @@ inline void ArgumentsChecker() {
     if (gClusterOptsGiven && !gClusterGiven) ok = false;
     if ((gSubgraphGiven && (gSubgraphK < 1 || gSubgraphK > DPPR_SUBGRAPH_MAX)) || (!gSubgraphOut.empty() && !gSubgraphGiven)) ok = false;
     if (gTopKWeightsGiven && (gTopK == 0 || gTopKWeights.empty())) ok = false; // (the count is checked against the sources in main)
+    if (!gTargetSetsFile.empty() && (gTargetSetsBad || gTargetSets.empty() || !gSourcesFile.empty() || gSplitInterface || gNoGroups || gTopKWeightsGiven)) ok = false;
     if (!ok) {
         std::cout << "invalid arguments" << std::endl;
         PrintUsage();
@@ -222,6 +243,10 @@ inline void ArgumentsParser(int argc, char **argv) {
     gTolerance = as_double(argc, argv, "-e", 1e-9);
     gNumGpus = as_int(argc, argv, "-g", 1);
     if (const char *f = find(argc, argv, "--sources")) gSourcesFile = f;
+    if (const char *f = find(argc, argv, "--target-sets")) {
+        gTargetSetsFile = f;
+        gTargetSetsBad = !load_target_sets(f, gTargetSets);
+    }
     if (const char *f = find(argc, argv, "--dump")) gDumpPath = f;
     gTopK = as_int(argc, argv, "--topk", 0);
     if (const char *w = find(argc, argv, "--topk-weights")) {

@@ -39,6 +39,9 @@ inline ValueType gTolerance = 1e-9;
 // ---- additions of this build ------------------------------------------------------------
 inline int gNumGpus = 1;              // -g : devices; sources are dealt round-robin over them
 inline std::string gSourcesFile;      // --sources : file with one source vertex id per line
+inline std::string gTargetSetsFile;   // --target-sets : file with one weighted vertex set per line (a lane each; instead of --sources)
+inline std::vector<std::vector<std::pair<int32_t, double>>> gTargetSets; // ... its lanes: (vertex, weight)
+inline bool gTargetSetsBad = false;   // ... unreadable, or a token that is no `id` / `id:weight`
 inline std::string gDumpPath;         // --dump : write p/r of every source after the last batch
 inline int gTopK = 0;                 // --topk K : print the K vertices of largest p of every source after the last batch (0: off)
 inline std::vector<double> gTopKWeights; // --topk-weights w1,w2,.. : also rank the weighted combination of the sources (one weight per source, all in one group)

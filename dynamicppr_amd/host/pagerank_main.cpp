@@ -19,6 +19,10 @@
 
 static std::vector<IndexType> LoadSources() {
     std::vector<IndexType> s;
+    if (!gTargetSets.empty()) { // --target-sets: a lane is named by its first id
+        for (const auto &lane : gTargetSets) s.push_back((IndexType)lane[0].first);
+        return s;
+    }
     if (gSourcesFile.empty()) {
         s.push_back(gSourceVertexId);
         return s;
@@ -59,7 +63,11 @@ int main(int argc, char *argv[]) {
     std::vector<std::unique_ptr<PPRGPU>> drivers((size_t)ngpu);
     for (int d = 0; d < ngpu; ++d) {
         std::vector<IndexType> mine;
-        for (size_t i = (size_t)d; i < sources.size(); i += (size_t)ngpu) mine.push_back(sources[i]);
+        std::vector<size_t> mine_lanes; // (--target-sets: which lines of the file this device tracks)
+        for (size_t i = (size_t)d; i < sources.size(); i += (size_t)ngpu) {
+            mine.push_back(sources[i]);
+            if (!gTargetSets.empty()) mine_lanes.push_back(i);
+        }
         for (IndexType s : mine) {
             if (s < 0) {
                 std::cout << "negative source id" << std::endl;
@@ -78,6 +86,7 @@ int main(int argc, char *argv[]) {
             }
         }
         drivers[(size_t)d].reset(new PPRRevPushGPU(graphs[(size_t)d].get(), present ? d % present : d, mine, /*quiet=*/d != 0 && ngpu > 1));
+        drivers[(size_t)d]->target_lanes = mine_lanes;
         drivers[(size_t)d]->driver_index = d;
         drivers[(size_t)d]->n_drivers = ngpu;
     }

@@ -95,18 +95,32 @@ public:
         }
         // several sources on one device are solved together, up to 16 per group (multi-source batched
         // sweeps); --split keeps the reference's one-source-at-a-time driver flow
-        use_groups = source_vertex_ids.size() > 1 && !gSplitInterface && !gNoGroups;
+        use_groups = (source_vertex_ids.size() > 1 && !gSplitInterface && !gNoGroups) || !target_lanes.empty(); // (set lanes exist in groups only)
         // two or three sources on a large window: one after the other on the single-source path (binned sweeps) beats a group, whose
         // sweep costs about the same for 2 as for 8 sources (friendster stand-in, 3 sources: 422 ms per batch as a group, 3 x 100 in series)
         // (--topk-weights asks for the group)
-        if (use_groups && source_vertex_ids.size() <= 3 && graph->sliding_window_size >= 4000000 && !gTopKWeightsGiven) use_groups = false;
+        if (use_groups && source_vertex_ids.size() <= 3 && graph->sliding_window_size >= 4000000 && !gTopKWeightsGiven && target_lanes.empty()) use_groups = false;
         if (gProfile) DPPR_CHECK(engine, dppr_set_profiling(engine, 1));
         if (!quiet_) std::cout << "start..." << std::endl;
         if (use_groups) {
             for (size_t i = 0; i < source_vertex_ids.size(); i += kGroupMax) {
                 const int32_t n = (int32_t)std::min<size_t>(kGroupMax, source_vertex_ids.size() - i);
                 int32_t gid = -1;
-                DPPR_CHECK(engine, dppr_add_source_group(engine, source_vertex_ids.data() + i, n, &gid));
+                if (target_lanes.empty()) {
+                    DPPR_CHECK(engine, dppr_add_source_group(engine, source_vertex_ids.data() + i, n, &gid));
+                } else { // --target-sets: lanes i .. i + n of this device as one group of weighted vertex sets
+                    std::vector<int64_t> off(1, 0);
+                    std::vector<int32_t> ids;
+                    std::vector<double> w;
+                    for (int32_t j = 0; j < n; ++j) {
+                        for (const auto &sd : gTargetSets[target_lanes[i + (size_t)j]]) {
+                            ids.push_back(sd.first);
+                            w.push_back(sd.second);
+                        }
+                        off.push_back((int64_t)ids.size());
+                    }
+                    DPPR_CHECK(engine, dppr_add_target_group(engine, off.data(), ids.data(), w.data(), n, &gid));
+                }
                 groups.push_back(gid);
             }
             ppr_time.assign(groups.size(), 0.0f);
@@ -393,6 +407,33 @@ public:
         }
         std::vector<IndexType> row, col;
         graph->ConstructGraph(row, col);
+        if (!target_lanes.empty()) {
+            // a lane of --target-sets: the residual bound above, then the invariant with the lane's seed vector h,
+            //   p[u] + ALPHA r[u] == ALPHA h[u] + (1 - ALPHA) / (outdeg(u) + 1) * sum over v in out(u) of p[v],
+            // to rounding (1e-13 for sum(h) <= 1, as the tests hold it; p scales with sum(h)). |p - exact| < eps follows from
+            // the two (include/dppr.h).
+            std::vector<double> h((size_t)V, 0.0);
+            double total = 0.0;
+            for (const auto &sd : gTargetSets[target_lanes[i]]) {
+                h[(size_t)sd.first] = sd.second;
+                total += sd.second;
+            }
+            const double bound = 1e-13 * std::max(1.0, total);
+            double worst = 0.0;
+            for (IndexType u = 0; u < V; ++u) {
+                double acc = 0.0;
+                for (IndexType j = row[u]; j < row[u + 1]; ++j) acc += p[col[j]];
+                const double rhs = ALPHA * h[u] + (1.0 - ALPHA) / (double)(row[u + 1] - row[u] + 1) * acc;
+                const double err = std::fabs(p[u] + ALPHA * r[u] - rhs);
+                worst = std::max(worst, err);
+                if (!(err < bound)) {
+                    std::cout << "VALIDATE FAILED: invariant " << err << "," << bound << " at vertex " << u << std::endl;
+                    std::exit(-1);
+                }
+            }
+            if (!quiet_) std::cout << "validate ok (set lane of " << gTargetSets[target_lanes[i]].size() << " seeds: residual bound + invariant with h, max error=" << worst << ")" << std::endl;
+            return;
+        }
         std::vector<double> a((size_t)V), b((size_t)V);
         for (IndexType u = 0; u < V; ++u) a[u] = (u == s) ? 1 : 0;
         size_t iters = 0;
@@ -698,6 +739,7 @@ public:
     int device_id;
     int driver_index = 0, n_drivers = 1; // which of the -g N drivers this is (the suffix of a per-driver file)
     std::vector<IndexType> source_vertex_ids;
+    std::vector<size_t> target_lanes; // --target-sets: the lines of gTargetSets this device tracks, in the order of source_vertex_ids (empty: sources)
     std::vector<int32_t> slots;  // one per source (single-source mode)
     static constexpr size_t kGroupMax = 16; // sources per group (dppr_add_source_group)
     std::vector<int32_t> groups; // one per 16 sources (group mode: several sources per device)

@@ -364,6 +364,58 @@ int dppr_group_add_source(dppr_engine *e, int32_t group, int32_t new_source, int
  * (dppr_group_mark): the lanes behind the dropped one change meaning. */
 int dppr_group_remove_source(dppr_engine *e, int32_t group, int32_t index);
 
+/* ---- weighted vertex sets as the targets of a group (backward-compatible additions, ABI 6) ----
+ * A lane of a group need not stand for one vertex: it may track the PPR towards a WEIGHTED SET of vertices (a community,
+ * a labelled class -- one lane per class, the argmax over the lanes is label propagation on a live stream --, a block
+ * list, a topic) with up to DPPR_TARGET_SET_MAX seeds, solved and kept current by the same sweeps as a source lane. The
+ * reference has no counterpart (one source vertex per process, gpu/PPRGPU.cuh:24).
+ *
+ * THE LANE. With the seed vector h (h[v] = the weight of seed v, 0.0 elsewhere) the lane keeps the engine's invariant
+ * with the indicator of the source replaced by h:
+ *     p[u] + ALPHA * r[u] == ALPHA * h[u] + (1 - ALPHA) / (outdeg(u) + 1) * sum over v in out(u) of p[v]
+ * Init is p = 0, r = h (gpu/PPRCommon.cuh:12-22 with h for e_s) and the stream update's source term is ALPHA * h[u]
+ * (gpu/StreamUpdate.cuh:50-72 with h[u] for [u == s]). PPR IS LINEAR IN THE TARGET: the lane converges to
+ * sum_v h[v] * p_v, p_v being the column a source lane of v would hold, and a converged lane (max|r| <= eps) satisfies
+ * |p - exact| < eps FOR ANY h -- with e = p - exact and M the row-substochastic operator of the invariant,
+ * e = M e - ALPHA r, hence |e|_inf <= |r|_inf --, so the weights need not sum to 1 and the tolerance means what it
+ * means for a source. Weights must be finite and > 0: Init leaves r = h >= 0 and dppr_group_init_solve_at runs the
+ * loop of the positive residuals only. Every query of a group (top-k, weighted top-k, changes, export, dot, refine,
+ * cluster, subgraph, point reads) reads p / r rows and works on a set lane unchanged.
+ * Every seed vertex receives an internal id when the set is given (a seed outside the window too; a parked one is
+ * revived) and counts as in use when the ids are renumbered, like a source: it is never parked while its lane has it.
+ *
+ * A lane of ONE seed of weight exactly 1.0 is a source lane. A group made only of such lanes IS a group of
+ * dppr_add_source_group: the same state, the same kernels, the same results bit for bit.
+ *
+ * dppr_add_target_group: n lanes, lane i with the seeds ids[offsets[i] .. offsets[i + 1]) and their weights; offsets is
+ * [n + 1], HOST memory like the arrays. Otherwise as dppr_add_source_group (an EXCLUSIVE call).
+ * dppr_group_replace_target: the contract of dppr_group_replace_source (the group converged, its epoch resident, an
+ * EXCLUSIVE call; no eps argument) with a seed set for the vertex: lane `index` is re-initialised to p = 0, r = h and
+ * solved on that epoch at the group's tolerance. The other lanes are not changed by value, bit for bit. Drops the
+ * group's mark. The seeds the lane had before no longer count as in use.
+ * dppr_group_targets: the seed sets in lane order, external ids ascending within a lane: lane i occupies
+ * [out_offsets[i], out_offsets[i + 1]) of out_ids and out_weights. out_offsets is [17], HOST memory, and is ALWAYS written
+ * with the true offsets (entries beyond the group's lanes repeat the total). Capacity as for the sparse exports: if
+ * out_offsets[16] > cap nothing is written to out_ids / out_weights and the call still returns DPPR_OK; cap = 0 with
+ * NULL arrays is the size query. A source lane is listed as its vertex with weight 1.0.
+ * dppr_group_sources reports -1 for a lane that is not a single seed of weight 1.0. dppr_group_replace_source may
+ * replace a set lane (it becomes a source lane); dppr_group_add_source and dppr_group_remove_source carry the other
+ * lanes' sets along, a removal moving the sets behind the dropped lane down by one with their lanes.
+ *
+ * Rejected with DPPR_ERR_INVALID before any device work or id assignment, nothing touched: n outside [1, 16]; a NULL
+ * offsets, ids or weights; offsets that do not start at 0 or decrease; a lane with no seed or more than
+ * DPPR_TARGET_SET_MAX; an id outside [0, V); an id twice within a lane (the same id in different lanes is fine); a
+ * weight that is not finite or not > 0; and what dppr_group_replace_source rejects. dppr_group_targets: a NULL
+ * out_offsets, cap < 0, cap > 0 with a NULL array. Every buffer a call needs -- the seed table of 12 bytes per seed
+ * included -- is obtained before anything changes: after DPPR_ERR_NOMEM the engine is as it was before the call. */
+#define DPPR_TARGET_SET_MAX 65536
+int dppr_add_target_group(dppr_engine *e, const int64_t *offsets /* [n + 1], HOST */, const int32_t *ids, const double *weights,
+                          int32_t n /* 1..16 */, int32_t *out_group);
+int dppr_group_replace_target(dppr_engine *e, int32_t group, int32_t index, const int32_t *ids, const double *weights,
+                              int32_t m /* 1..DPPR_TARGET_SET_MAX */, float *out_ms);
+int dppr_group_targets(dppr_engine *e, int32_t group, int64_t *out_offsets /* [17], HOST */, int32_t *out_ids, double *out_weights,
+                       int64_t cap);
+
 /* ---- queries of a state: top-k and point reads (added in ABI 6, backward compatible) ----
  * The answer a dense dppr_read / dppr_group_read would give, without moving V doubles per source to the
  * host: a radix select runs on the device over the rows that hold a vertex (the live and the parked
