@@ -51,6 +51,7 @@
 #include "dppr_walk.hpp"
 #include "dppr_cluster.hpp"
 #include "dppr_subgraph.hpp"
+#include "dppr_rank.hpp"
 
 using namespace dppr;
 
@@ -1574,6 +1575,36 @@ int dppr_group_subgraph(dppr_engine *e, int32_t group, int32_t epoch, int32_t k,
 int dppr_debug_subgraph_wave_max(dppr_engine *e, int wave_max) {
     if (!e || !sg_wave_max_ok(wave_max)) return fail(e, DPPR_ERR_INVALID, "debug_subgraph_wave_max: 0 (every row by the histogram kernel) .. 256");
     e->sg_wave_max = wave_max;
+    return DPPR_OK;
+}
+
+int dppr_topk_ranked(dppr_engine *e, int32_t slot, int32_t epoch, const dppr_rank_spec_t *spec, int32_t k, double min_score, int32_t *out_ids,
+                     double *out_score, int32_t *out_count) {
+    GET_SLOT(e, slot);
+    return topk_ranked_call(e, s, epoch, spec, k, min_score, out_ids, out_score, out_count);
+}
+
+int dppr_group_topk_ranked(dppr_engine *e, int32_t group, int32_t epoch, const dppr_rank_spec_t *spec, int32_t k, double min_score,
+                           int32_t *out_ids, double *out_score, int32_t *out_counts) {
+    GET_GROUP(e, group);
+    return topk_ranked_call(e, g, epoch, spec, k, min_score, out_ids, out_score, out_counts);
+}
+
+int dppr_rank_score_at(dppr_engine *e, int32_t slot, int32_t epoch, const dppr_rank_spec_t *spec, const int32_t *ids, int32_t m,
+                       double *out_score) {
+    GET_SLOT(e, slot);
+    return rank_score_at_call(e, s, epoch, spec, ids, m, out_score);
+}
+
+int dppr_group_rank_score_at(dppr_engine *e, int32_t group, int32_t epoch, const dppr_rank_spec_t *spec, const int32_t *ids, int32_t m,
+                             double *out_score) {
+    GET_GROUP(e, group);
+    return rank_score_at_call(e, g, epoch, spec, ids, m, out_score);
+}
+
+int dppr_debug_rank_piece(dppr_engine *e, int edges) {
+    if (!e || !rank_piece_ok(edges)) return fail(e, DPPR_ERR_INVALID, "debug_rank_piece: 1 .. 512 entries of a row per wave");
+    e->rk_piece = edges;
     return DPPR_OK;
 }
 

@@ -1,9 +1,9 @@
 // dppr_host_query.hpp -- host side of the state queries (dppr_topk / dppr_group_topk / dppr_read_at / dppr_group_read_at, and
 // dppr_group_topk_weighted / dppr_group_score_at, dppr_mark / dppr_changes, dppr_support / dppr_export_sparse /
 // dppr_export_dense_dev and their group forms, dppr_dot_dense_dev / dppr_dot_sparse and theirs, dppr_walks / dppr_refine_at /
-// dppr_group_refine_at, dppr_cluster / dppr_group_cluster, dppr_subgraph / dppr_group_subgraph). First what the families share -- the opening of a run, room in a buffer, the device-time bracket, the
+// dppr_group_refine_at, dppr_cluster / dppr_group_cluster, dppr_subgraph / dppr_group_subgraph, dppr_topk_ranked / dppr_rank_score_at and theirs). First what the families share -- the opening of a run, room in a buffer, the device-time bracket, the
 // copy of a result block to its pinned twin, the check of a caller's device pointer -- then, family by family, the launch sequences
-// of dppr_topk.hpp, dppr_wquery.hpp, dppr_changes.hpp, dppr_export.hpp, dppr_dot.hpp, dppr_walk.hpp, dppr_cluster.hpp and dppr_subgraph.hpp (run_*, called with map_mu
+// of dppr_topk.hpp, dppr_wquery.hpp, dppr_changes.hpp, dppr_export.hpp, dppr_dot.hpp, dppr_walk.hpp, dppr_cluster.hpp, dppr_subgraph.hpp and dppr_rank.hpp (run_*, called with map_mu
 // held, on the solver stream) and what an entry point calls (*_call: the checks that need no device, those of the caller's device
 // pointers, map_mu, the run). A state reaches both as a StateView (dppr_host_state.hpp). Nothing here is reached from the update path.
 #pragma once
@@ -947,6 +947,199 @@ int subgraph_call(dppr_engine *e, const StateView &v, const Epoch &ep, int32_t k
         return fail(e, DPPR_ERR_INVALID, "subgraph: ids / p / row_ptr / col must be aligned device memory of the engine's device, n x k (row_ptr: n x (k + 1), col: cap) entries inside one allocation");
     std::lock_guard<std::mutex> map_lk(e->map_mu); // (as dppr_read: one state of the id space for the whole query)
     return run_subgraph(e, ep, v, k, min_p, cap, dest, out_counts, out_offsets, out_ids, out_p, out_row_ptr, out_col);
+}
+
+// ---- ranked candidates (dppr_rank.hpp, dppr_rank_plan.hpp) ----------------------------------------------------------------------
+// the seeds of a state's lanes as the kernels read them: a slot's source, a group's sources and the seed table of its set lanes
+RkLanes rank_lanes(const Slot &s) {
+    RkLanes l{};
+    for (int i = 0; i < GS_MAX; ++i) l.src.s[i] = -1;
+    l.src.s[0] = s.source;
+    l.seeds = rk_seeds(l.src.s, nullptr, 1);
+    return l;
+}
+RkLanes rank_lanes(const Group &g) {
+    RkLanes l{};
+    l.src = g.src;
+    const bool table = (bool)g.tg;
+    if (table) l.tg = tg_dev(g);
+    l.seeds = rk_seeds(g.src.s, table ? g.ttab.off : nullptr, g.n);
+    return l;
+}
+
+// the epoch's CSRs (ep NULL: the spec reads none) and the live zone
+RkGraph rank_graph(const dppr_engine *e, const Epoch *ep) {
+    RkGraph g{};
+    if (ep) {
+        g.out_row_ptr = ep->out_row_ptr.get();
+        g.out_col = ep->out_col.get();
+        g.in_row_ptr = ep->row_ptr.get();
+        g.in_adj = ep->adj.get();
+    }
+    g.n_int = e->n_int;
+    g.V = e->V;
+    return g;
+}
+
+RkRule rank_rule(const RkSpec &sp) { return {sp.mask_dev, sp.mask == DPPR_MASK_DENY ? 1 : 0, sp.factor_dev}; }
+
+// One of the instantiations of a kernel template <KIND, T> by a spec's factor and the dtype of g: f(integral_constant<int, KIND>(), T())
+template <class F> int by_factor(const RkSpec &sp, F &&f) {
+    switch (sp.factor) {
+    case DPPR_FACTOR_DEV:
+        return sp.factor_dtype == DPPR_F32 ? f(std::integral_constant<int, DPPR_FACTOR_DEV>(), float())
+                                           : f(std::integral_constant<int, DPPR_FACTOR_DEV>(), double());
+    case DPPR_FACTOR_DEG: return f(std::integral_constant<int, DPPR_FACTOR_DEG>(), double());
+    case DPPR_FACTOR_INV_DEG: return f(std::integral_constant<int, DPPR_FACTOR_INV_DEG>(), double());
+    default: return f(std::integral_constant<int, DPPR_FACTOR_NONE>(), double());
+    }
+}
+
+// the exclusion words by the live rows, the seeds' row lengths and the piece list by its bound: in place before the first kernel
+int rank_mark_workspace(dppr_engine *e, Grow &grow, const RkLanes &l, const RkSpec &sp, const Epoch *ep) {
+    if (!sp.exclude) return DPPR_OK;
+    QueryWork::Rank &rk = e->q.rk;
+    const size_t live = rk_excl_elems((size_t)e->n_int);
+    int rc = grow(rk.excl, live, std::min<size_t>((size_t)e->V, with_slack(live)));
+    if (rc || !(sp.exclude & RK_EXCLUDE_ROWS)) return rc;
+    const size_t len = rk_len_elems((size_t)l.seeds.total());
+    rc = grow(rk.len, len);
+    if (!rc) rc = grow(rk.len_pin, len);
+    if (!rc) rc = grow(rk.list, std::max<size_t>(rk_piece_cap(l.seeds, ep->Ed, sp.exclude, e->rk_piece), 1));
+    return rc;
+}
+
+// The marking stage, enqueued (its workspace is in place): the words zeroed, the seeds' row lengths read back -- the one wait of
+// the stage -- and cut into pieces on the host, one wave of k_rk_mark per piece. Returns the words, or NULL: nothing is excluded.
+int rank_mark_enqueue(dppr_engine *e, const RkLanes &l, const RkSpec &sp, const RkGraph &g, const unsigned **out_excl) {
+    *out_excl = nullptr;
+    if (!sp.exclude) return DPPR_OK;
+    QueryWork::Rank &rk = e->q.rk;
+    const int total = l.seeds.total();
+    HIP_TRY(hipMemsetAsync(rk.excl, 0, sizeof(unsigned) * rk_excl_elems((size_t)e->n_int), e->stream));
+    size_t n_items = 0;
+    if ((sp.exclude & RK_EXCLUDE_ROWS) && total > 0) {
+        hipLaunchKernelGGL(k_rk_rowlen, dim3(grid_for(total, RK_BLOCK)), dim3(RK_BLOCK), 0, e->stream, l, g, rk.len.get());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(rk.len_pin, rk.len, sizeof(int) * 2 * (size_t)total, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        rk_pieces(rk.len_pin.get(), total, sp.exclude, e->rk_piece, rk.items);
+        n_items = std::min(rk.items.size(), rk.list.capacity()); // (rk_piece_cap bounds what a call can have)
+        if (n_items > 0)
+            HIP_TRY(hipMemcpyAsync(rk.list, rk.items.data(), sizeof(unsigned long long) * n_items, hipMemcpyHostToDevice, e->stream));
+    }
+    const int64_t blocks = std::max<int64_t>(((int64_t)n_items + RK_WAVES - 1) / RK_WAVES, ((int64_t)total + RK_BLOCK - 1) / RK_BLOCK);
+    hipLaunchKernelGGL(k_rk_mark, dim3(grid_for(blocks, 1)), dim3(RK_BLOCK), 0, e->stream, l, g, sp.exclude, e->rk_piece, rk.list.get(),
+                       (unsigned)n_items, rk.excl.get());
+    HIP_TRY(hipGetLastError());
+    *out_excl = rk.excl.get();
+    return DPPR_OK;
+}
+
+// Top k of every lane by the spec's score (arguments, the spec's device pointers and the epoch validated by the caller; ep NULL:
+// the spec reads no CSR). Results are lane-major: [n][k]. Every buffer is in place before the first kernel; the scratch state is
+// 8 n + 4 bytes per occupied row.
+int run_topk_ranked(dppr_engine *e, const StateView &v, const RkLanes &l, const Epoch *ep, const RkSpec &sp, int k, double min_score,
+                    int32_t *out_ids, double *out_score, int32_t *out_counts) {
+    if (int rc = query_begin(e, MAP_I2E)) return rc;
+    QueryWork::Rank &rk = e->q.rk;
+    const TkState st = tk_state(e, v.p, v.p, v.gw, v.n);
+    Grow grow{e};
+    if (int rc = topk_workspace(e, grow, v.n, (size_t)st.rows)) return rc;
+    const size_t sc = rk_score_elems((size_t)st.rows, v.n), ex = rk_ext_elems((size_t)st.rows);
+    if (int rc = grow(rk.score, sc, with_slack(sc))) return rc;
+    if (int rc = grow(rk.ext, ex, with_slack(ex))) return rc;
+    if (int rc = rank_mark_workspace(e, grow, l, sp, ep)) return rc;
+    const RkGraph g = rank_graph(e, ep);
+    const RkRule rule = rank_rule(sp);
+    if (int rc = DeviceTime{e}.open()) return rc;
+    const unsigned *excl = nullptr;
+    if (int rc = rank_mark_enqueue(e, l, sp, g, &excl)) return rc;
+    const int n_tiles = std::max((st.rows + RK_ROWS - 1) / RK_ROWS, 1);
+    by_factor(sp, [&](auto kind, auto elem) -> int {
+        using T = decltype(elem);
+        hipLaunchKernelGGL((k_rk_scores<decltype(kind)::value, T>), dim3(std::min(n_tiles, 2048)), dim3(RK_BLOCK), 0, e->stream, st,
+                           e->d_int2ext.get(), excl, rule, g, rk.score.get(), rk.ext.get());
+        return DPPR_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    return run_select(e, scratch_state(rk.score, rk.score, v.n, st.rows), rk.ext, k, min_score, out_ids, out_score, nullptr, out_counts);
+}
+
+// the scores at m external ids (validated by the caller like the rest, m > 0), [m][n]
+int run_rank_score_at(dppr_engine *e, const StateView &v, const RkLanes &l, const Epoch *ep, const RkSpec &sp, const int32_t *ids, int m,
+                      double *out_score) {
+    if (int rc = query_begin(e, MAP_E2I)) return rc;
+    const size_t mn = (size_t)m * (size_t)v.n;
+    const RaLayout lay = ra_layout(m, v.n, 1);
+    Grow grow{e};
+    if (int rc = grow(e->q.ra.buf, lay.total_bytes)) return rc;
+    if (int rc = rank_mark_workspace(e, grow, l, sp, ep)) return rc;
+    int *d_ids = reinterpret_cast<int *>(e->q.ra.buf + lay.off_ids);
+    double *d_out = reinterpret_cast<double *>(e->q.ra.buf + lay.off_a);
+    const RkGraph g = rank_graph(e, ep);
+    const RkRule rule = rank_rule(sp);
+    HIP_TRY(hipMemcpyAsync(d_ids, ids, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, e->stream));
+    if (int rc = DeviceTime{e}.open()) return rc;
+    const unsigned *excl = nullptr;
+    if (int rc = rank_mark_enqueue(e, l, sp, g, &excl)) return rc;
+    by_factor(sp, [&](auto kind, auto elem) -> int {
+        using T = decltype(elem);
+        hipLaunchKernelGGL((k_rk_score_at<decltype(kind)::value, T>), dim3(grid_for((int64_t)mn, RK_BLOCK)), dim3(RK_BLOCK), 0, e->stream,
+                           v.p, v.gw, v.n, e->d_ext2int.get(), d_ids, m, excl, rule, g, d_out);
+        return DPPR_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    if (int rc = DeviceTime{e}.close()) return rc;
+    HIP_TRY(hipMemcpyAsync(out_score, d_out, sizeof(double) * mn, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return DeviceTime{e}.read();
+}
+
+// What both forms check after their own arguments: the epoch, where the spec needs one (*out_ep stays NULL otherwise), and the
+// spec's device pointers. NULL: fine; otherwise the words of the rejection.
+const char *rank_spec_refused(dppr_engine *e, const StateView &v, int32_t epoch, const dppr_rank_spec_t *spec, const Epoch **out_ep) {
+    *out_ep = nullptr;
+    if (rank_needs_epoch(spec)) {
+        const Epoch *ep = find_epoch(e, epoch);
+        if (!ep) return "ranked: epoch not resident (evicted or never built)";
+        if (!refine_epoch_ok(v.st.last_epoch, ep->id))
+            return "ranked: the state stands on another epoch than the one given: the degrees and neighbours of another graph are not those its order was computed on";
+        *out_ep = ep;
+    }
+    if (rank_needs_factor_dev(spec) &&
+        !dev_range_ok(e, spec->factor_dev, rank_factor_bytes(spec->factor_dtype, e->V), rank_factor_elem_bytes(spec->factor_dtype)))
+        return "ranked: factor_dev must be aligned device memory of the engine's device, V elements inside one allocation";
+    if (rank_needs_mask_dev(spec) && !dev_range_ok(e, spec->mask_dev, rank_mask_bytes(e->V), 1))
+        return "ranked: mask_dev must be device memory of the engine's device, V bytes inside one allocation";
+    return nullptr;
+}
+
+// (Owner: a Slot or a Group. Its seeds are read under map_mu: a renumbering beside the call renames them)
+template <class Owner>
+int topk_ranked_call(dppr_engine *e, Owner &o, int32_t epoch, const dppr_rank_spec_t *spec, int32_t k, double min_score, int32_t *out_ids,
+                     double *out_score, int32_t *out_counts) {
+    const StateView v = view(o);
+    if (!rank_topk_args_ok(spec, k, min_score, out_ids, out_score, out_counts))
+        return fail(e, DPPR_ERR_INVALID, "topk_ranked: factor 0..3, factor_dtype 0 or 1, mask 0..2, exclude bits 1 | 2 | 4, k in [1, DPPR_TOPK_MAX], min_score >= 0, non-null ids / score / counts");
+    HIP_TRY(hipSetDevice(e->device));
+    const Epoch *ep = nullptr;
+    if (const char *why = rank_spec_refused(e, v, epoch, spec, &ep)) return fail(e, DPPR_ERR_INVALID, why);
+    std::lock_guard<std::mutex> map_lk(e->map_mu); // (as dppr_read: one state of the id space for the whole query)
+    return run_topk_ranked(e, v, rank_lanes(o), ep, rank_spec(spec), k, min_score, out_ids, out_score, out_counts);
+}
+
+template <class Owner>
+int rank_score_at_call(dppr_engine *e, Owner &o, int32_t epoch, const dppr_rank_spec_t *spec, const int32_t *ids, int32_t m, double *out_score) {
+    const StateView v = view(o);
+    if (!rank_score_at_args_ok(spec, ids, m, e->V, out_score))
+        return fail(e, DPPR_ERR_INVALID, "rank_score_at: factor 0..3, factor_dtype 0 or 1, mask 0..2, exclude bits 1 | 2 | 4, ids in [0, V), non-null score");
+    HIP_TRY(hipSetDevice(e->device));
+    const Epoch *ep = nullptr;
+    if (const char *why = rank_spec_refused(e, v, epoch, spec, &ep)) return fail(e, DPPR_ERR_INVALID, why);
+    if (m == 0) return DPPR_OK;
+    std::lock_guard<std::mutex> map_lk(e->map_mu);
+    return run_rank_score_at(e, v, rank_lanes(o), ep, rank_spec(spec), ids, m, out_score);
 }
 
 } // namespace

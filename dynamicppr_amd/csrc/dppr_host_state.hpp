@@ -234,6 +234,14 @@ struct QueryWork {
         DevBuf<int> work;                                     // the control words (SgCtl), the matches of every position [n][k], the rows queued for k_sg_long [n][k]
         DevBuf<unsigned char> blk; PinBuf<unsigned char> pin; // the head, ids, p, row_ptr and a host destination's col: device / pinned host
     } sg;
+    struct Rank { // ranked candidates (dppr_rank.hpp, dppr_rank_plan.hpp)
+        DevBuf<double> score;  // scratch state: [occupied rows][n] scores
+        DevBuf<int> ext;       // ... and the external id of every row of it
+        DevBuf<unsigned> excl; // [live rows] bit i: excluded for lane i (zeroed per call)
+        DevBuf<int> len; PinBuf<int> len_pin;     // [seeds][2] out-row and in-row length of every seed: device / pinned host
+        DevBuf<unsigned long long> list;          // the piece list of the call (rk_piece_cap)
+        std::vector<unsigned long long> items;    // ... as the host builds it (kept for its capacity)
+    } rk;
 };
 
 } // namespace
@@ -407,6 +415,7 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     QueryWork q;                    // their workspace
     int walk_form = 0;              // 0: lane refill, 1: one walk per thread (dppr_debug_walk_form)
     int sg_wave_max = SG_WAVE_MAX;  // matched entries of a row up to which the wave that owns it places them (dppr_debug_subgraph_wave_max)
+    int rk_piece = RK_PIECE;        // entries of a seed's row one wave of k_rk_mark walks (dppr_debug_rank_piece)
     float query_ms = -1.0f;         // dppr_set_profiling: device time of the last top-k, changes, export or dot call, first to last kernel (dppr_debug_query_ms)
     std::vector<int32_t> h_tmp1, h_tmp2;
     std::vector<int32_t> h_tiles; // host copy of the tile edge prefix / group table

@@ -71,6 +71,7 @@ EXPORTS = [
     "dppr_cluster", "dppr_group_cluster",
     "dppr_subgraph", "dppr_group_subgraph", "dppr_debug_subgraph_wave_max",
     "dppr_add_target_group", "dppr_group_replace_target", "dppr_group_targets",
+    "dppr_topk_ranked", "dppr_group_topk_ranked", "dppr_rank_score_at", "dppr_group_rank_score_at", "dppr_debug_rank_piece",
 ]
 
 DEST_HOST, DEST_DEVICE = 0, 1
@@ -84,6 +85,16 @@ WALK_REFILL, WALK_PER_THREAD = 0, 1
 CLUSTER_MAX = 8192
 SUBGRAPH_MAX = 8192
 TARGET_SET_MAX = 65536
+FACTOR_NONE, FACTOR_DEV, FACTOR_DEG, FACTOR_INV_DEG = 0, 1, 2, 3
+MASK_NONE, MASK_ALLOW, MASK_DENY = 0, 1, 2
+EXCLUDE_SEEDS, EXCLUDE_IN_NEIGHBOURS, EXCLUDE_OUT_NEIGHBOURS = 1, 2, 4
+RANK_PIECE = 512
+
+
+class RankSpec(C.Structure):
+    """dppr_rank_spec_t: the factor, the mask and the exclusions of a ranked query."""
+    _fields_ = [("factor", C.c_int32), ("factor_dtype", C.c_int32), ("factor_dev", C.c_void_p), ("mask", C.c_int32),
+                ("mask_dev", C.c_void_p), ("exclude", C.c_uint32)]
 
 
 class Cluster(C.Structure):
@@ -217,6 +228,11 @@ def lib():
     L.dppr_add_target_group.argtypes = [vp, i64p, ip, dp, C.c_int32, ip]
     L.dppr_group_replace_target.argtypes = [vp, C.c_int32, C.c_int32, ip, dp, C.c_int32, fp]
     L.dppr_group_targets.argtypes = [vp, C.c_int32, i64p, ip, dp, C.c_int64]
+    L.dppr_topk_ranked.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_double, ip, dp, ip]
+    L.dppr_group_topk_ranked.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_double, ip, dp, ip]
+    L.dppr_rank_score_at.argtypes = [vp, C.c_int32, C.c_int32, vp, ip, C.c_int32, dp]
+    L.dppr_group_rank_score_at.argtypes = [vp, C.c_int32, C.c_int32, vp, ip, C.c_int32, dp]
+    L.dppr_debug_rank_piece.argtypes = [vp, C.c_int]
     for name in EXPORTS:
         if name not in ("dppr_strerror", "dppr_last_error", "dppr_destroy", "dppr_build_id", "dppr_heartbeat"):
             getattr(L, name).restype = C.c_int
@@ -661,6 +677,53 @@ class Engine:
         self._ck(self._L.dppr_group_score_at(self._h, int(group), w.ctypes.data_as(dp), w.shape[0], pa, len(a),
                                              out.ctypes.data_as(dp)), "group_score_at")
         return out
+
+    # ---- ranked candidates: factor, mask and neighbour exclusion before the selection ----
+    @staticmethod
+    def rank_spec(factor=FACTOR_NONE, factor_dev=0, factor_dtype=F64, mask=MASK_NONE, mask_dev=0, exclude=0):
+        """A dppr_rank_spec_t. factor_dev / mask_dev are integer device addresses ([V] by external id) that the caller keeps alive."""
+        return RankSpec(int(factor), int(factor_dtype), int(factor_dev) or None, int(mask), int(mask_dev) or None, int(exclude))
+
+    def _topk_ranked(self, fn, which, n, spec, k, min_score, epoch, what):
+        kk = max(int(k), 1)
+        ids = np.empty((n, kk), dtype=np.int32)
+        sc = np.empty((n, kk), dtype=np.float64)
+        cnt = np.empty(n, dtype=np.int32)
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        self._ck(fn(self._h, int(which), int(epoch), C.byref(spec) if spec is not None else None, int(k), float(min_score),
+                    ids.ctypes.data_as(ip), sc.ctypes.data_as(dp), cnt.ctypes.data_as(ip)), what)
+        return [(ids[i, :c].copy(), sc[i, :c].copy()) for i, c in enumerate(cnt)]
+
+    def topk_ranked(self, slot, k, min_score=0.0, spec=None, epoch=-1):
+        """The k vertices of largest score (include/dppr.h: p times or over the spec's factor, +0.0 where masked out or excluded)
+        with score > min_score, by score descending then id ascending: (ids, scores), trimmed to the count. spec: rank_spec()."""
+        return self._topk_ranked(self._L.dppr_topk_ranked, slot, 1, spec, k, min_score, epoch, "topk_ranked")[0]
+
+    def group_topk_ranked(self, group, k, min_score=0.0, spec=None, epoch=-1):
+        """topk_ranked for every lane of a group at once: a list of (ids, scores), one per lane in group order."""
+        return self._topk_ranked(self._L.dppr_group_topk_ranked, group, self._group_n.get(group, 1), spec, k, min_score, epoch,
+                                 "group_topk_ranked")
+
+    def _rank_score_at(self, fn, which, n, spec, ids, epoch, what):
+        a, pa = _i32(ids)
+        out = np.empty((len(a), n), dtype=np.float64)
+        self._ck(fn(self._h, int(which), int(epoch), C.byref(spec) if spec is not None else None, pa, len(a),
+                    out.ctypes.data_as(C.POINTER(C.c_double))), what)
+        return out
+
+    def rank_score_at(self, slot, ids, spec=None, epoch=-1):
+        """The score of topk_ranked at the given external ids: an array of len(ids)."""
+        return self._rank_score_at(self._L.dppr_rank_score_at, slot, 1, spec, ids, epoch, "rank_score_at")[:, 0]
+
+    def group_rank_score_at(self, group, ids, spec=None, epoch=-1):
+        """The scores of every lane of a group at the given external ids: a [len(ids)][n] array (vertex-major, as the state)."""
+        return self._rank_score_at(self._L.dppr_group_rank_score_at, group, self._group_n.get(group, 1), spec, ids, epoch,
+                                   "group_rank_score_at")
+
+    def debug_rank_piece(self, edges):
+        """Test hook (dppr_debug_rank_piece): the rows of the seeds are marked in pieces of at most `edges` entries, one wave each;
+        1 .. 512, default 512. The results do not depend on it."""
+        self._ck(self._L.dppr_debug_rank_piece(self._h, int(edges)), "debug_rank_piece")
 
     # ---- what a batch moved: marks and the top k of |p - mark| ----
     def mark(self, slot):

@@ -64,6 +64,28 @@ inline std::vector<double> parse_weights(const char *v) {
         p = end + 1;
     }
 }
+// --rank-factor: none | deg | inv-deg as DPPR_FACTOR_*; anything else -1 (rejected by ArgumentsChecker)
+inline int parse_rank_factor(const char *v) {
+    if (std::strcmp(v, "none") == 0) return DPPR_FACTOR_NONE;
+    if (std::strcmp(v, "deg") == 0) return DPPR_FACTOR_DEG;
+    if (std::strcmp(v, "inv-deg") == 0) return DPPR_FACTOR_INV_DEG;
+    return -1;
+}
+// --rank-exclude: a comma-separated list of seeds | in | out as the OR of DPPR_EXCLUDE_*; an empty or unknown token gives -1
+inline int parse_rank_exclude(const char *v) {
+    int flags = 0;
+    const std::string s(v);
+    for (size_t at = 0;;) {
+        const size_t end = s.find(',', at);
+        const std::string tok = s.substr(at, end == std::string::npos ? std::string::npos : end - at);
+        if (tok == "seeds") flags |= (int)DPPR_EXCLUDE_SEEDS;
+        else if (tok == "in") flags |= (int)DPPR_EXCLUDE_IN_NEIGHBOURS;
+        else if (tok == "out") flags |= (int)DPPR_EXCLUDE_OUT_NEIGHBOURS;
+        else return -1;
+        if (end == std::string::npos) return flags;
+        at = end + 1;
+    }
+}
 // --seeds: every line of `path` is one seed set `id[:weight] id[:weight] ...` (weight 1 where none is given; a blank line is an
 // empty set). false: unreadable, no line at all, or a token that is not a non-negative id with an optional finite weight.
 inline bool load_seeds(const char *path, std::vector<int64_t> &off, std::vector<int32_t> &ids, std::vector<double> &w) {
@@ -147,6 +169,10 @@ inline void PrintUsage() {
               << "--topk-weights <w1,w2,...>: with --topk and all sources in one group (one GPU, 2 to 16 sources, no --no-groups / --split),\n"
               << "            one finite weight per source: after the topk lines, the K vertices of largest sum_i w_i * pagerank_i,\n"
               << "            one line each: topkw <rank from 1> <vertex> <score>\n"
+              << "--rank-factor <none|deg|inv-deg> [--rank-exclude <seeds,in,out>]: with --topk, after the topk lines the K best of every source\n"
+              << "            by pagerank * (outdeg + 1) (deg: the forward-PPR order on an undirected window), / (outdeg + 1) (inv-deg) or as it\n"
+              << "            is (none), without the source itself (seeds), the vertices with an edge to it (in) or from it (out), one line each:\n"
+              << "            ranked <source> <rank from 1> <vertex> <score>   (either flag alone is enough; not with --split)\n"
               << "--changes <K> [--changes-min <D>]: after every batch print, per source in source order, what the batch moved (1 <= K <= 8192, D >= 0):\n"
               << "            moved <batch> <source> <vertices with |delta pagerank| > D>, then the K largest of them by |delta|, one line each:\n"
               << "            changes <batch> <source> <rank from 1> <vertex> <delta> <pagerank>\n"
@@ -217,6 +243,7 @@ inline void ArgumentsChecker() {
     if (gClusterOptsGiven && !gClusterGiven) ok = false;
     if ((gSubgraphGiven && (gSubgraphK < 1 || gSubgraphK > DPPR_SUBGRAPH_MAX)) || (!gSubgraphOut.empty() && !gSubgraphGiven)) ok = false;
     if (gTopKWeightsGiven && (gTopK == 0 || gTopKWeights.empty())) ok = false; // (the count is checked against the sources in main)
+    if (gRankGiven && (gTopK == 0 || gRankFactor < 0 || gRankExclude < 0 || gSplitInterface)) ok = false;
     if (!gTargetSetsFile.empty() && (gTargetSetsBad || gTargetSets.empty() || !gSourcesFile.empty() || gSplitInterface || gNoGroups || gTopKWeightsGiven)) ok = false;
     if (!ok) {
         std::cout << "invalid arguments" << std::endl;
@@ -252,6 +279,14 @@ inline void ArgumentsParser(int argc, char **argv) {
     if (const char *w = find(argc, argv, "--topk-weights")) {
         gTopKWeightsGiven = true;
         gTopKWeights = parse_weights(w);
+    }
+    if (const char *f = find(argc, argv, "--rank-factor")) {
+        gRankGiven = true;
+        gRankFactor = parse_rank_factor(f);
+    }
+    if (const char *x = find(argc, argv, "--rank-exclude")) {
+        gRankGiven = true;
+        gRankExclude = parse_rank_exclude(x);
     }
     gChangesK = as_int(argc, argv, "--changes", 0);
     gChangesMinGiven = find(argc, argv, "--changes-min") != nullptr;

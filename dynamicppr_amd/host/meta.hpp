@@ -46,6 +46,9 @@ inline std::string gDumpPath;         // --dump : write p/r of every source afte
 inline int gTopK = 0;                 // --topk K : print the K vertices of largest p of every source after the last batch (0: off)
 inline std::vector<double> gTopKWeights; // --topk-weights w1,w2,.. : also rank the weighted combination of the sources (one weight per source, all in one group)
 inline bool gTopKWeightsGiven = false;
+inline bool gRankGiven = false;       // --rank-factor / --rank-exclude : with --topk, also print the K best by the ranked query (ranked <source> ...)
+inline int gRankFactor = 0;           // --rank-factor none|deg|inv-deg : DPPR_FACTOR_NONE / _DEG / _INV_DEG (-1: not one of them)
+inline int gRankExclude = 0;          // --rank-exclude seeds,in,out : OR of DPPR_EXCLUDE_* (-1: a token that is none of the three)
 inline int gChangesK = 0;             // --changes K : after every batch print, per source, how many vertices moved and the K largest |delta p| (0: off)
 inline double gChangesMin = 0.0;      // --changes-min D : only vertices with |delta p| > D count and are printed
 inline bool gSparseGiven = false;     // --sparse-min P : after the last batch print, per source, how many vertices have pagerank > P (support <source> <count>)

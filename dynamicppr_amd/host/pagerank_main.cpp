@@ -177,6 +177,16 @@ int main(int argc, char *argv[]) {
                 std::cout << line << "\n";
             }
         }
+        if (gRankGiven) { // dealt like the topk lines
+            for (int d = 0; d < ngpu; ++d) top[(size_t)d] = drivers[(size_t)d]->TopKRanked(gTopK, gRankFactor, (unsigned)gRankExclude);
+            for (size_t j = 0; j < sources.size(); ++j) {
+                const auto &list = top[j % (size_t)ngpu][j / (size_t)ngpu];
+                for (size_t t = 0; t < list.size(); ++t) {
+                    std::snprintf(line, sizeof(line), "ranked %d %zu %d %.17g", (int)sources[j], t + 1, (int)list[t].vertex, list[t].p);
+                    std::cout << line << "\n";
+                }
+            }
+        }
         std::cout << std::flush;
     }
     if (gSparseGiven) { // (not a line of the reference) as --topk: source j is device j % ngpu's source j / ngpu

@@ -504,6 +504,31 @@ public:
         return out;
     }
 
+    // --rank-factor / --rank-exclude: the same lists by the ranked query on the newest epoch (dppr_topk_ranked /
+    // dppr_group_topk_ranked; TopEntry::p holds the score). No mask: the program owns no device memory.
+    std::vector<std::vector<TopEntry>> TopKRanked(int k, int factor, unsigned exclude) {
+        const size_t n_src = source_vertex_ids.size();
+        std::vector<std::vector<TopEntry>> out(n_src);
+        std::vector<int32_t> ids, cnt;
+        std::vector<double> score;
+        dppr_rank_spec_t spec{};
+        spec.factor = factor;
+        spec.exclude = exclude;
+        for (size_t first = 0; first < n_src; first += use_groups ? kGroupMax : 1) {
+            const size_t n = use_groups ? std::min(kGroupMax, n_src - first) : 1;
+            ids.assign(n * (size_t)k, -1);
+            score.assign(n * (size_t)k, 0.0);
+            cnt.assign(n, 0);
+            if (use_groups)
+                DPPR_CHECK(engine, dppr_group_topk_ranked(engine, groups[first / kGroupMax], -1, &spec, k, 0.0, ids.data(), score.data(), cnt.data()));
+            else
+                DPPR_CHECK(engine, dppr_topk_ranked(engine, slots[first], -1, &spec, k, 0.0, ids.data(), score.data(), cnt.data()));
+            for (size_t j = 0; j < n; ++j)
+                for (int32_t t = 0; t < cnt[j]; ++t) out[first + j].push_back({ids[j * (size_t)k + t], score[j * (size_t)k + t]});
+        }
+        return out;
+    }
+
     // --sparse-min: every vertex with p > min_p of every source of this device, in this device's source order and by id, through
     // the device-side compaction (dppr_export_sparse / dppr_group_export_sparse: the size call, then the fill)
     struct SparseVec {

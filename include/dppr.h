@@ -846,6 +846,94 @@ int dppr_group_subgraph(dppr_engine *e, int32_t group, int32_t epoch, int32_t k,
                         int64_t *out_row_ptr /* [n][k + 1] or NULL */, int32_t *out_col /* [cap]; NULL with cap = 0 */);
 int dppr_debug_subgraph_wave_max(dppr_engine *e, int wave_max);
 
+/* ---- ranked candidates: factor, mask and neighbour exclusion before the selection (backward-compatible additions, ABI 6) ----
+ * dppr_topk / dppr_group_topk return the k best of ALL vertices by raw p. What a consumer ranks is rarely that: the head of every
+ * source's order is the source itself and the vertices with a stored edge to it, the candidates are one type of vertex or what is
+ * outside a block list, and the order wanted is often p times a per-vertex factor. These calls apply all three on the device,
+ * between the state and the selection, instead of a large k or a dense read finished on the host.
+ *
+ * THE SCORE of lane i (lane order; a slot is n = 1) at vertex v is defined exactly. With p = p_i[v] exactly what dppr_read /
+ * dppr_group_read returns (0.0 for a vertex without an internal id), and outdeg(v) the out-degree of v in `epoch` with
+ * multiplicity as stored (0 for a parked vertex or one without a row):
+ *     DPPR_FACTOR_NONE      score = p
+ *     DPPR_FACTOR_DEV       score = p * g[v]                  g = factor_dev[v] by EXTERNAL id; an f32 g is converted to double exactly
+ *     DPPR_FACTOR_DEG       score = p * (double)(outdeg(v) + 1)
+ *     DPPR_FACTOR_INV_DEG   score = p / (double)(outdeg(v) + 1)
+ * Each is ONE rounding to double (round to nearest even), nothing fused: numpy's `*` and `/` over the dense read reproduce every
+ * score bit for bit. On a window that stores both directions (d(v) + 1) p_i[v] = (d(s_i) + 1) pi_{s_i}(v), so DPPR_FACTOR_DEG
+ * ranks by the FORWARD PPR of the source, the vector this reverse-push engine does not hold.
+ *   MASKED OUT   DPPR_MASK_ALLOW: only vertices with mask_dev[v] != 0 take part; DPPR_MASK_DENY: vertices with mask_dev[v] != 0
+ *                do not. mask_dev is [V] by external id, one byte per vertex. A vertex that is masked out scores exactly +0.0.
+ *   EXCLUDED     per lane, by the OR of DPPR_EXCLUDE_*: SEEDS -- the lane's source, or every seed of its set
+ *                (dppr_add_target_group); IN_NEIGHBOURS -- v with a stored edge v -> seed in `epoch`, for any seed of the lane;
+ *                OUT_NEIGHBOURS -- v with a stored edge seed -> v. A vertex excluded for the lane scores +0.0 IN THAT LANE: the
+ *                same vertex may be excluded for lane 2 and rank first for lane 3. On an undirected window the two neighbour
+ *                flags mean the same set. Self loops and duplicate edges need no special case (a self loop makes the seed its
+ *                own neighbour).
+ *   NO ID        a vertex without an internal id has no row and no edge: it scores +0.0 if it is masked out, otherwise its score
+ *                follows the formula from p = 0.0 (DPPR_FACTOR_DEV: 0.0 * g[v], which is -0.0 for a negative and NaN for an
+ *                infinite or NaN g[v]).
+ *
+ * dppr_topk_ranked / dppr_group_topk_ranked: THE ORDER is as in dppr_group_topk. The qualifying vertices of lane i are the external
+ * ids with score > min_score (min_score >= 0: a score of +-0, a negative or a NaN score never qualifies, +inf orders first), ordered
+ * by score descending, then external id ascending; the first min(k, #qualifying) are returned with their count and their scores,
+ * entries past the count hold id -1 and 0.0. Group outputs are lane-major: ids [n][k], scores [n][k], counts [n]. The live and the
+ * parked zone are scanned.
+ * ANCHOR: with spec == NULL, or a spec of DPPR_FACTOR_NONE / DPPR_MASK_NONE / exclude 0, ids and scores equal the ids and p of
+ * dppr_topk / dppr_group_topk(k, min_p = min_score) bit for bit.
+ *
+ * dppr_rank_score_at / dppr_group_rank_score_at: the same score at m caller-given external ids, vertex-major [m][n] like the state.
+ * m == 0 is a valid no-op.
+ *
+ * EPOCH. A spec that needs neither degrees nor neighbours (no DPPR_FACTOR_DEG / _INV_DEG, no neighbour flag) does not look at
+ * `epoch`. Otherwise the epoch rule of dppr_cluster: the epoch must be resident (-1: the newest) and, if the epoch the state stands
+ * on is known (anything but a state set by dppr_write), it must be the one given. Convergence is NOT required.
+ *
+ * Rejected with DPPR_ERR_INVALID before any device work, nothing written: an unknown factor, factor_dtype (read only for
+ * DPPR_FACTOR_DEV) or mask value, unknown exclude bits; a factor_dev (DPPR_FACTOR_DEV) or mask_dev (a mask) that is not device
+ * memory of the ENGINE'S device, whose V elements do not lie inside one allocation, or that is not aligned to its element size; k
+ * outside [1, DPPR_TOPK_MAX]; min_score negative or NaN; a NULL out_ids, out_score or count pointer; a bad slot / group; for the
+ * score_at forms a NULL out_score, a NULL ids with m > 0, m < 0 or an id outside [0, V); an epoch that is not resident or not the
+ * state's, where the spec needs one. factor_dev and mask_dev are only read, on the solver stream, before the call returns.
+ * Threading and stream as dppr_topk: the id-map lock of dppr_read (safe beside dppr_slide_concurrent), the solver stream, any state
+ * (converged or not), never part of the update path or of a timed region. Work space beyond dppr_topk's: a scratch state of
+ * 8 n + 4 bytes per row that holds a vertex, 4 bytes per live row for the exclusion words, and for the neighbour flags 8 bytes per
+ * seed and 8 bytes per piece of 512 entries of the seeds' rows (bounded by the epoch's edges per lane and direction); all of it is
+ * the engine's, obtained before the first kernel, grown on demand and released with the engine: after DPPR_ERR_NOMEM the states and
+ * the engine are as before. With dppr_set_profiling on, dppr_debug_query_ms also reports the device time of the last of these
+ * calls, first to last kernel (with a neighbour flag the one read of the seeds' row lengths by the host lies between them).
+ * OUT OF SCOPE: weight vectors as in dppr_group_topk_weighted. A set lane IS the combined target; "the neighbours of a combination"
+ * of lanes has no single meaning.
+ * dppr_debug_rank_piece: a test hook, as dppr_debug_subgraph_wave_max. The rows of the seeds are walked in pieces of at most `edges`
+ * entries, one wave each (default and largest value 512, smallest 1). The results do not depend on it. */
+#define DPPR_FACTOR_NONE      0   /* score = p                                                        */
+#define DPPR_FACTOR_DEV       1   /* score = p * g[v], g = factor_dev[v] by EXTERNAL id, [V], f64/f32 */
+#define DPPR_FACTOR_DEG       2   /* score = p * (double)(outdeg(v) + 1)   (forward PPR order on a    */
+                                  /*                                        window of both directions)*/
+#define DPPR_FACTOR_INV_DEG   3   /* score = p / (double)(outdeg(v) + 1)                              */
+#define DPPR_MASK_NONE  0
+#define DPPR_MASK_ALLOW 1         /* only vertices with mask_dev[v] != 0 take part */
+#define DPPR_MASK_DENY  2         /* vertices with mask_dev[v] != 0 do not         */
+#define DPPR_EXCLUDE_SEEDS          1u  /* the lane's source / every seed of its set                  */
+#define DPPR_EXCLUDE_IN_NEIGHBOURS  2u  /* v with a stored edge v -> seed, for any seed of the lane   */
+#define DPPR_EXCLUDE_OUT_NEIGHBOURS 4u  /* v with a stored edge seed -> v                             */
+typedef struct {
+    int32_t factor, factor_dtype;      /* DPPR_FACTOR_*, DPPR_F64 | DPPR_F32 (read only for _DEV) */
+    const void *factor_dev;            /* [V] by external id, device memory of the engine's device */
+    int32_t mask;                      /* DPPR_MASK_* */
+    const uint8_t *mask_dev;           /* [V] by external id, one byte per vertex, device memory  */
+    uint32_t exclude;                  /* OR of DPPR_EXCLUDE_* */
+} dppr_rank_spec_t;
+int dppr_topk_ranked(dppr_engine *e, int32_t slot, int32_t epoch, const dppr_rank_spec_t *spec, int32_t k, double min_score,
+                     int32_t *out_ids, double *out_score, int32_t *out_count);
+int dppr_group_topk_ranked(dppr_engine *e, int32_t group, int32_t epoch, const dppr_rank_spec_t *spec, int32_t k, double min_score,
+                           int32_t *out_ids /* [n][k] */, double *out_score /* [n][k] */, int32_t *out_counts /* [n] */);
+int dppr_rank_score_at(dppr_engine *e, int32_t slot, int32_t epoch, const dppr_rank_spec_t *spec, const int32_t *ids, int32_t m,
+                       double *out_score /* [m] */);
+int dppr_group_rank_score_at(dppr_engine *e, int32_t group, int32_t epoch, const dppr_rank_spec_t *spec, const int32_t *ids, int32_t m,
+                             double *out_score /* [m][n] */);
+int dppr_debug_rank_piece(dppr_engine *e, int edges);
+
 /* Windows whose sweep groups are all resident at once run a frontier loop of a source group as
  * multi-sweep launches (grid barrier between sweeps, row tables kept in LDS; dppr_multi.hpp). on by
  * default; 0 = one launch per sweep everywhere. The roll-call / time-out rules are those of
