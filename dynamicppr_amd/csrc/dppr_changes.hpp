@@ -16,10 +16,12 @@
 // current p at the result ids. In the same pass k_ch_delta counts the qualifying entries of every lane (LDS, then one global
 // atomic per lane and workgroup) and, for a re-mark, stores p into the mark row it has just read.
 //
-// k_ch_delta: one tile of CH_ROWS rows per step. The p row and the mark row are read with 16-byte loads where a row is an even
-// number of doubles (every group), 8-byte loads on a single-source slot (gw = 1), into LDS rows padded by one double (the bank
-// argument of dppr_wquery.hpp); |d| and d leave with consecutive threads at consecutive addresses. Every store is an ordinary
-// vector store; the counters are LDS / global vector atomics.
+// k_ch_delta: one tile of dppr_topk.hpp per step (its rows, block and padded LDS rows; the bank argument is there). It keeps a load
+// loop of its own, not tk_stage_tile: the p row and the mark row of a vertex are read in ONE iteration, so that both loads are in
+// flight together and a re-mark stores the p it holds in registers -- with p staged first and the mark gathered in a second loop
+// the query measured 3 % slower (profiles/query_layer_refactor_times.md). 16-byte loads where a row is an even number of doubles
+// (every group), 8-byte loads on a single-source slot (gw = 1); |d| and d leave with consecutive threads at consecutive addresses.
+// Every store is an ordinary vector store; the counters are LDS / global vector atomics.
 #pragma once
 
 #include "dppr_changes_plan.hpp"
@@ -27,9 +29,7 @@
 
 namespace dppr {
 
-constexpr int CH_BLOCK = 256;
-constexpr int CH_ROWS = 128;                 // rows per tile: 2 x 128 x 17 doubles of LDS (34 KiB)
-constexpr int CH_LDS_ROW = CH_LANES + 1;     // widest padded row
+constexpr int CH_BLOCK = 256;                // k_ch_mark, k_ch_gather
 
 // mark[ext * gw + lane] = p of the row that holds ext, 0.0 for a vertex without an id: one pass over the external ids
 __global__ __launch_bounds__(CH_BLOCK) void k_ch_mark(const double *__restrict__ p, int gw, const int *__restrict__ ext2int, int V,
@@ -44,27 +44,27 @@ __global__ __launch_bounds__(CH_BLOCK) void k_ch_mark(const double *__restrict__
 
 // st: the state (rows of gw doubles, n lanes in use). i2e: external id of every occupied row. mark: [V][gw].
 // abs_c, d_c: [st.rows][n], ext_c: [st.rows], moved: [n] (zeroed by the caller).
-__global__ __launch_bounds__(CH_BLOCK) void k_ch_delta(TkState st, const int *__restrict__ i2e, double *__restrict__ mark, int V,
-                                                       double min_delta, int remark, double *__restrict__ abs_c,
-                                                       double *__restrict__ d_c, int *__restrict__ ext_c, int *__restrict__ moved) {
-    __shared__ double s_p[CH_ROWS * CH_LDS_ROW];
-    __shared__ double s_m[CH_ROWS * CH_LDS_ROW];
-    __shared__ int s_ext[CH_ROWS];
+__global__ __launch_bounds__(TK_TILE_BLOCK) void k_ch_delta(TkState st, const int *__restrict__ i2e, double *__restrict__ mark, int V,
+                                                            double min_delta, int remark, double *__restrict__ abs_c,
+                                                            double *__restrict__ d_c, int *__restrict__ ext_c, int *__restrict__ moved) {
+    __shared__ double s_p[TK_TILE_ROWS * TK_TILE_LDS_ROW];
+    __shared__ double s_m[TK_TILE_ROWS * TK_TILE_LDS_ROW];
+    __shared__ int s_ext[TK_TILE_ROWS];
     __shared__ int s_cnt[CH_LANES];
     if (threadIdx.x < CH_LANES) s_cnt[threadIdx.x] = 0;
     const int ls = st.gw + 1, half = st.gw / 2;
-    const int n_tiles = (st.rows + CH_ROWS - 1) / CH_ROWS;
+    const int n_tiles = (st.rows + TK_TILE_ROWS - 1) / TK_TILE_ROWS;
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int c0 = tile * CH_ROWS, cnt = min(CH_ROWS, st.rows - c0);
+        const int c0 = tile * TK_TILE_ROWS, cnt = min(TK_TILE_ROWS, st.rows - c0);
         __syncthreads(); // (the subtractions of the previous tile are over; the counters are cleared)
-        for (int rl = threadIdx.x; rl < cnt; rl += CH_BLOCK) {
+        for (int rl = threadIdx.x; rl < cnt; rl += TK_TILE_BLOCK) {
             const int ext = i2e[tk_row(st, c0 + rl)];
             s_ext[rl] = ext;
             ext_c[c0 + rl] = ext;
         }
         __syncthreads();
         if (st.gw & 1) { // a single-source slot: rows of one double
-            for (int j = threadIdx.x; j < cnt * st.gw; j += CH_BLOCK) {
+            for (int j = threadIdx.x; j < cnt * st.gw; j += TK_TILE_BLOCK) {
                 const int rl = j / st.gw, l = j % st.gw, ext = s_ext[rl];
                 const double v = st.p[(size_t)tk_row(st, c0 + rl) * st.gw + l];
                 double m = 0.0;
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(CH_BLOCK) void k_ch_delta(TkState st, const int *__
                 s_m[rl * ls + l] = m;
             }
         } else {
-            for (int j = threadIdx.x; j < cnt * half; j += CH_BLOCK) {
+            for (int j = threadIdx.x; j < cnt * half; j += TK_TILE_BLOCK) {
                 const int rl = j / half, h = j % half, ext = s_ext[rl];
                 const double2 v = *reinterpret_cast<const double2 *>(st.p + (size_t)tk_row(st, c0 + rl) * st.gw + 2 * h);
                 double2 m = make_double2(0.0, 0.0);
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(CH_BLOCK) void k_ch_delta(TkState st, const int *__
             }
         }
         __syncthreads();
-        for (int o = threadIdx.x; o < cnt * st.n; o += CH_BLOCK) {
+        for (int o = threadIdx.x; o < cnt * st.n; o += TK_TILE_BLOCK) {
             const int rl = o / st.n, lane = o % st.n;
             const double d = __dsub_rn(s_p[rl * ls + lane], s_m[rl * ls + lane]);
             const double a = fabs(d);

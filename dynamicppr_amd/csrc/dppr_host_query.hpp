@@ -1,11 +1,12 @@
-// dppr_host_query.hpp -- host side of the state queries (dppr_topk / dppr_group_topk / dppr_read_at / dppr_group_read_at, and
-// dppr_group_topk_weighted / dppr_group_score_at, dppr_mark / dppr_changes, dppr_support / dppr_export_sparse /
-// dppr_export_dense_dev and their group forms, dppr_dot_dense_dev / dppr_dot_sparse and theirs, dppr_walks / dppr_refine_at /
-// dppr_group_refine_at, dppr_cluster / dppr_group_cluster, dppr_subgraph / dppr_group_subgraph, dppr_topk_ranked / dppr_rank_score_at and theirs). First what the families share -- the opening of a run, room in a buffer, the device-time bracket, the
-// copy of a result block to its pinned twin, the check of a caller's device pointer -- then, family by family, the launch sequences
-// of dppr_topk.hpp, dppr_wquery.hpp, dppr_changes.hpp, dppr_export.hpp, dppr_dot.hpp, dppr_walk.hpp, dppr_cluster.hpp, dppr_subgraph.hpp and dppr_rank.hpp (run_*, called with map_mu
-// held, on the solver stream) and what an entry point calls (*_call: the checks that need no device, those of the caller's device
-// pointers, map_mu, the run). A state reaches both as a StateView (dppr_host_state.hpp). Nothing here is reached from the update path.
+// dppr_host_query.hpp -- host side of the state queries: every dppr_* entry point that reads a state without changing it, from
+// dppr_topk to dppr_group_rank_score_at. Nothing here is reached from the update path. A state reaches a query as a StateView
+// (dppr_host_state.hpp); a family has a run_* (the launch sequence of its kernel header, called with map_mu held, on the solver
+// stream) and a *_call (the checks that need no device, those of the caller's device pointers, map_mu, the run). Shared, each
+// written once: query_begin (the device, the id maps), Grow / with_slack (room in a buffer before anything is written), DeviceTime
+// (the bracket around a call's kernels), run_end and fetch_block (the end of a run), dev_range_ok (a caller's device pointer),
+// topk_workspace / select_enqueue / run_select (the selection over a state or a scratch state), scratch_workspace (the one scratch
+// state of the weighted, changes and ranked queries), point_read (read_at, score_at, rank_score_at), cl_graph / order_workspace /
+// order_enqueue (the top-k order and its rank table: the opening of cluster and subgraph).
 #pragma once
 
 namespace {
@@ -73,13 +74,16 @@ struct DeviceTime {
     }
 };
 
-// The end of a run whose results come back in a block: the bracket closes, one copy takes `bytes` of the block to its pinned
-// twin, the wait
+// The end of every run, after the bracket has closed and the copies back are enqueued: the wait, then the bracket's reading
+int run_end(dppr_engine *e) {
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return DeviceTime{e}.read();
+}
+// ... of a run whose results come back in a block: the bracket closes, one copy takes `bytes` of the block to its pinned twin
 int fetch_block(dppr_engine *e, const DevBuf<unsigned char> &blk, PinBuf<unsigned char> &pin, size_t bytes) {
     if (int rc = DeviceTime{e}.close()) return rc;
     HIP_TRY(hipMemcpyAsync(pin, blk, bytes, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return DeviceTime{e}.read();
+    return run_end(e);
 }
 
 // One of the four instantiations of a kernel template <T, bool> by a call's dtype and layout flag: f(T(), std::bool_constant<flag>())
@@ -185,7 +189,20 @@ TkState tk_state(const dppr_engine *e, const double *p, const double *r, int gw,
     return st;
 }
 
-// a scratch state: q lanes, rows q doubles wide, compacted (no parked zone)
+// Room for the scratch state of a call and the selection over it: topk_workspace, `planes` (1 or 2) of [rows][lanes] doubles and
+// the external id of every row, a quarter ahead
+int scratch_workspace(dppr_engine *e, Grow &grow, size_t rows, int lanes, int planes) {
+    QueryWork::Scratch &sc = e->q.sc;
+    const size_t plane = scratch_plane_elems(rows, lanes), ext = scratch_ext_elems(rows);
+    int rc = topk_workspace(e, grow, lanes, rows);
+    if (!rc) rc = grow(sc.a, plane, with_slack(plane));
+    if (!rc && planes == 2) rc = grow(sc.b, plane, with_slack(plane));
+    if (!rc) rc = grow(sc.ext, ext, with_slack(ext));
+    return rc;
+}
+// the grid of a kernel that fills it: one workgroup per tile of dppr_topk.hpp, 2048 at the most
+int tile_grid(int rows) { return std::min(std::max((rows + TK_TILE_ROWS - 1) / TK_TILE_ROWS, 1), 2048); }
+// ... as the selection reads it: q lanes, rows q doubles wide, compacted (no parked zone)
 TkState scratch_state(const double *p, const double *r, int q, int rows) {
     TkState sc;
     sc.p = p;
@@ -215,24 +232,36 @@ int topk_call(dppr_engine *e, const StateView &v, int32_t k, double min_p, int32
     return run_topk(e, v, k, min_p, out_ids, out_p, out_r, out_counts);
 }
 
-// p / r at m external ids (validated by the caller), [m][n]
-int run_read_at(dppr_engine *e, const StateView &v, const int32_t *ids, int m, double *out_p, double *out_r) {
-    if (int rc = query_begin(e, MAP_E2I)) return rc;
-    const size_t mn = (size_t)m * (size_t)v.n;
-    const RaLayout lay = ra_layout(m, v.n, 2);
-    Grow grow{e};
+// The point reads: m external ids (validated by the caller, m > 0) up, `outs` (1 or 2) outputs of [m][cols] doubles written by
+// what launch(d_ids, d_a, d_b) enqueues inside the bracket, those the caller wants (out_a / out_b not NULL) back. The caller's
+// own buffers are in place before the call.
+template <class Launch>
+int point_read(dppr_engine *e, Grow &grow, const int32_t *ids, int m, int cols, int outs, double *out_a, double *out_b, Launch &&launch) {
+    const size_t bytes = sizeof(double) * (size_t)m * (size_t)cols;
+    const RaLayout lay = ra_layout(m, cols, outs);
     if (int rc = grow(e->q.ra.buf, lay.total_bytes)) return rc;
     unsigned char *buf = e->q.ra.buf.get();
     int *d_ids = reinterpret_cast<int *>(buf + lay.off_ids);
-    double *d_p = reinterpret_cast<double *>(buf + lay.off_a), *d_r = reinterpret_cast<double *>(buf + lay.off_b);
+    double *d_a = reinterpret_cast<double *>(buf + lay.off_a), *d_b = outs == 2 ? reinterpret_cast<double *>(buf + lay.off_b) : nullptr;
     HIP_TRY(hipMemcpyAsync(d_ids, ids, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, e->stream));
-    hipLaunchKernelGGL(k_read_at, dim3(grid_for((int64_t)mn)), dim3(BLOCK), 0, e->stream, v.p, v.r, v.gw, v.n, e->d_ext2int, d_ids, m,
-                       d_p, d_r);
+    if (int rc = DeviceTime{e}.open()) return rc;
+    if (int rc = launch(d_ids, d_a, d_b)) return rc;
     HIP_TRY(hipGetLastError());
-    if (out_p) HIP_TRY(hipMemcpyAsync(out_p, d_p, sizeof(double) * mn, hipMemcpyDeviceToHost, e->stream));
-    if (out_r) HIP_TRY(hipMemcpyAsync(out_r, d_r, sizeof(double) * mn, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return DPPR_OK;
+    if (int rc = DeviceTime{e}.close()) return rc;
+    if (out_a) HIP_TRY(hipMemcpyAsync(out_a, d_a, bytes, hipMemcpyDeviceToHost, e->stream));
+    if (out_b) HIP_TRY(hipMemcpyAsync(out_b, d_b, bytes, hipMemcpyDeviceToHost, e->stream));
+    return run_end(e);
+}
+
+// p / r at m external ids, [m][n]
+int run_read_at(dppr_engine *e, const StateView &v, const int32_t *ids, int m, double *out_p, double *out_r) {
+    if (int rc = query_begin(e, MAP_E2I)) return rc;
+    Grow grow{e};
+    return point_read(e, grow, ids, m, v.n, 2, out_p, out_r, [&](const int *d_ids, double *d_p, double *d_r) {
+        hipLaunchKernelGGL(k_read_at, dim3(grid_for((int64_t)m * v.n)), dim3(BLOCK), 0, e->stream, v.p, v.r, v.gw, v.n, e->d_ext2int, d_ids, m, d_p,
+                           d_r);
+        return DPPR_OK;
+    });
 }
 
 int read_at_call(dppr_engine *e, const StateView &v, const int32_t *ids, int32_t m, double *out_p, double *out_r) {
@@ -255,39 +284,27 @@ int wq_upload(dppr_engine *e, const double *weights, int q, int n) {
 int run_topk_weighted(dppr_engine *e, const StateView &v, const double *weights, int q, int k, double min_score, int32_t *out_ids,
                       double *out_score, int32_t *out_counts) {
     if (int rc = query_begin(e, MAP_I2E)) return rc;
-    QueryWork::Weighted &wq = e->q.wq;
+    QueryWork::Scratch &sc = e->q.sc;
     const TkState st = tk_state(e, v.p, v.p, v.gw, v.n);
     Grow grow{e};
-    if (int rc = topk_workspace(e, grow, q, (size_t)st.rows)) return rc;
-    const size_t rows = std::max<size_t>((size_t)st.rows, 1);
-    if (int rc = grow(wq.score, rows * (size_t)q, with_slack(rows * (size_t)q))) return rc;
-    if (int rc = grow(wq.ext, rows, with_slack(rows))) return rc;
+    if (int rc = scratch_workspace(e, grow, (size_t)st.rows, q, 1)) return rc;
     if (int rc = wq_upload(e, weights, q, v.n)) return rc;
     if (int rc = DeviceTime{e}.open()) return rc;
-    const int n_tiles = std::max((st.rows + WQ_ROWS - 1) / WQ_ROWS, 1);
-    hipLaunchKernelGGL(k_wq_scores, dim3(std::min(n_tiles, 2048)), dim3(WQ_BLOCK), 0, e->stream, st, e->d_int2ext, wq.w, q, wq.score,
-                       wq.ext);
+    hipLaunchKernelGGL(k_wq_scores, dim3(tile_grid(st.rows)), dim3(TK_TILE_BLOCK), 0, e->stream, st, e->d_int2ext, e->q.wq.w, q, sc.a, sc.ext);
     HIP_TRY(hipGetLastError());
-    return run_select(e, scratch_state(wq.score, wq.score, q, st.rows), wq.ext, k, min_score, out_ids, out_score, nullptr, out_counts);
+    return run_select(e, scratch_state(sc.a, sc.a, q, st.rows), sc.ext, k, min_score, out_ids, out_score, nullptr, out_counts);
 }
 
 // scores of q weighted combinations at m external ids (ids and weights validated by the caller, m > 0), [m][q]
 int run_score_at(dppr_engine *e, const StateView &v, const double *weights, int q, const int32_t *ids, int m, double *out_score) {
     if (int rc = query_begin(e, MAP_E2I)) return rc;
-    const size_t mq = (size_t)m * (size_t)q;
-    const RaLayout lay = ra_layout(m, q, 1);
-    Grow grow{e};
-    if (int rc = grow(e->q.ra.buf, lay.total_bytes)) return rc;
     if (int rc = wq_upload(e, weights, q, v.n)) return rc;
-    int *d_ids = reinterpret_cast<int *>(e->q.ra.buf + lay.off_ids);
-    double *d_out = reinterpret_cast<double *>(e->q.ra.buf + lay.off_a);
-    HIP_TRY(hipMemcpyAsync(d_ids, ids, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, e->stream));
-    hipLaunchKernelGGL(k_score_at, dim3(grid_for((int64_t)mq, WQ_BLOCK)), dim3(WQ_BLOCK), 0, e->stream, v.p, v.gw, v.n, e->d_ext2int, d_ids,
-                       m, e->q.wq.w, q, d_out);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out_score, d_out, sizeof(double) * mq, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return DPPR_OK;
+    Grow grow{e};
+    return point_read(e, grow, ids, m, q, 1, out_score, nullptr, [&](const int *d_ids, double *d_out, double *) {
+        hipLaunchKernelGGL(k_score_at, dim3(grid_for((int64_t)m * q, WQ_BLOCK)), dim3(WQ_BLOCK), 0, e->stream, v.p, v.gw, v.n, e->d_ext2int, d_ids,
+                           m, e->q.wq.w, q, d_out);
+        return DPPR_OK;
+    });
 }
 
 int topk_weighted_call(dppr_engine *e, const StateView &v, const double *weights, int32_t q, int32_t k, double min_score,
@@ -336,14 +353,11 @@ int run_changes(dppr_engine *e, const StateView &v, int k, double min_delta, int
                 double *out_p, int32_t *out_counts, int32_t *out_moved) {
     if (int rc = query_begin(e, MAP_E2I | MAP_I2E)) return rc;
     QueryWork::Changes &ch = e->q.ch;
+    QueryWork::Scratch &sc = e->q.sc;
     const int n = v.n;
     const TkState st = tk_state(e, v.p, v.p, v.gw, n);
     Grow grow{e};
-    if (int rc = topk_workspace(e, grow, n, (size_t)st.rows)) return rc;
-    const size_t rows = std::max<size_t>((size_t)st.rows, 1);
-    if (int rc = grow(ch.abs, rows * (size_t)n, with_slack(rows * (size_t)n))) return rc;
-    if (int rc = grow(ch.d, rows * (size_t)n, with_slack(rows * (size_t)n))) return rc;
-    if (int rc = grow(ch.ext, rows, with_slack(rows))) return rc;
+    if (int rc = scratch_workspace(e, grow, (size_t)st.rows, n, 2)) return rc;
     if (!ch.pin) { // (the last of the pair: one that failed half way is made again)
         HIP_TRY(ch.res.regrow(ch_layout(GS_MAX, DPPR_TOPK_MAX).total_bytes));
         HIP_TRY(ch.pin.regrow(ch_layout(GS_MAX, DPPR_TOPK_MAX).copy_bytes));
@@ -356,12 +370,11 @@ int run_changes(dppr_engine *e, const StateView &v, int k, double min_delta, int
     double *res_abs = reinterpret_cast<double *>(res + lay.off_abs);
     if (int rc = DeviceTime{e}.open()) return rc;
     HIP_TRY(hipMemsetAsync(res_moved, 0, sizeof(int) * GS_MAX, e->stream));
-    const int n_tiles = std::max((st.rows + CH_ROWS - 1) / CH_ROWS, 1);
-    hipLaunchKernelGGL(k_ch_delta, dim3(std::min(n_tiles, 2048)), dim3(CH_BLOCK), 0, e->stream, st, e->d_int2ext.get(), v.mark.get(), e->V,
-                       min_delta, remark, ch.abs.get(), ch.d.get(), ch.ext.get(), res_moved);
+    hipLaunchKernelGGL(k_ch_delta, dim3(tile_grid(st.rows)), dim3(TK_TILE_BLOCK), 0, e->stream, st, e->d_int2ext.get(), v.mark.get(), e->V,
+                       min_delta, remark, sc.a.get(), sc.b.get(), sc.ext.get(), res_moved);
     HIP_TRY(hipGetLastError());
     // (the scratch: p = |d|, r = d)
-    if (int rc = select_enqueue(e, scratch_state(ch.abs, ch.d, n, st.rows), ch.ext, k, min_delta, res_cnt, res_id, res_abs, res_d)) return rc;
+    if (int rc = select_enqueue(e, scratch_state(sc.a, sc.b, n, st.rows), sc.ext, k, min_delta, res_cnt, res_id, res_abs, res_d)) return rc;
     hipLaunchKernelGGL(k_ch_gather, dim3(grid_for((int64_t)n * k, CH_BLOCK)), dim3(CH_BLOCK), 0, e->stream, v.p, v.gw, n, k,
                        e->d_ext2int.get(), res_id, res_p);
     HIP_TRY(hipGetLastError());
@@ -462,8 +475,7 @@ int run_export_dense(dppr_engine *e, const StateView &v, int which, int dtype, i
     });
     HIP_TRY(hipGetLastError());
     if (int rc = DeviceTime{e}.close()) return rc;
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return DeviceTime{e}.read();
+    return run_end(e);
 }
 
 int export_sparse_call(dppr_engine *e, const StateView &v, double min_p, int64_t cap, int dest, int64_t *out_offsets, int32_t *out_ids,
@@ -694,8 +706,7 @@ int run_walks(dppr_engine *e, const Epoch &ep, const int32_t *starts, int m, int
     if (int rc = walk_enqueue(e, ep, m, W, seed, d_ends)) return rc;
     if (int rc = DeviceTime{e}.close()) return rc;
     if (host) HIP_TRY(hipMemcpyAsync(out_ends, d_ends, walk_ends_bytes(m, W), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream)); // (a device destination is complete here: any stream of the caller may read it)
-    return DeviceTime{e}.read();
+    return run_end(e); // (a device destination is complete here: any stream of the caller may read it)
 }
 
 // est / corr / sumsq at m ids, [m][n]: the walks, the fold of r at their endpoints over the pieces of the dot products, the finish
@@ -728,8 +739,7 @@ int run_refine(dppr_engine *e, const Epoch &ep, const StateView &v, const int32_
     HIP_TRY(hipMemcpyAsync(out_est, d_res, sizeof(double) * mn, hipMemcpyDeviceToHost, e->stream));
     if (out_corr) HIP_TRY(hipMemcpyAsync(out_corr, d_res + mn, sizeof(double) * mn, hipMemcpyDeviceToHost, e->stream));
     if (out_sumsq) HIP_TRY(hipMemcpyAsync(out_sumsq, d_res + 2 * mn, sizeof(double) * mn, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return DeviceTime{e}.read();
+    return run_end(e);
 }
 
 int walks_call(dppr_engine *e, const Epoch &ep, const int32_t *starts, int32_t m, int32_t W, uint64_t seed, int dest, int32_t *out_ends) {
@@ -756,9 +766,41 @@ int refine_call(dppr_engine *e, const StateView &v, const Epoch &ep, const int32
 }
 
 // ---- the conductance sweep over a top-k order (dppr_cluster.hpp, dppr_cluster_plan.hpp) -------------------------------------------
-// the rank table by the occupied rows, the chunk list by the epoch's edges, the per-position values and the block: in place before
-// the first kernel
-int cluster_workspace(dppr_engine *e, Grow &grow, int n, size_t rows, long long Ed) {
+// The ORDER STAGE, the opening cluster and subgraph share: the top-k order of every lane and the rank table that says where a
+// vertex stands in it. cl_graph: the epoch's two CSRs and the zones of the state, as the kernels of both families read them.
+ClGraph cl_graph(const Epoch &ep, const TkState &st) {
+    return {ep.out_row_ptr.get(), ep.out_col.get(), ep.row_ptr.get(), ep.adj.get(), st.n_int, st.lo_parked, st.rows};
+}
+
+// ... its workspace: the selection's, the rank table by the occupied rows, the chunk list of the later kernels by the epoch's edges
+int order_workspace(dppr_engine *e, Grow &grow, int n, size_t rows, long long Ed) {
+    int rc = topk_workspace(e, grow, n, rows);
+    if (!rc) rc = grow(e->q.cl.rank, cl_rank_elems(rows, n), with_slack(cl_rank_elems(rows, n)));
+    if (!rc) rc = grow(e->q.cl.list, cl_list_cap(n, Ed));
+    return rc;
+}
+unsigned order_list_cap(int n, long long Ed) { return (unsigned)std::min<size_t>(cl_list_cap(n, Ed), 0xffffffffu); }
+
+// ... and its kernels, enqueued: the rank table cleared, the selection with its ids and p where the caller says (p NULL: to the
+// top-k block, which nobody copies, like the counts -- *out_cnt -- and r), k_cl_rank
+int order_enqueue(dppr_engine *e, const ClGraph &g, const TkState &st, int k, double min_p, int *ids, double *p, const int **out_cnt) {
+    const TkLayout tkl = tk_layout(st.n, k, true);
+    unsigned char *tkres = e->q.tk.res.get();
+    int *cnt = reinterpret_cast<int *>(tkres + tkl.off_cnt);
+    const int stride = cl_stride(st.n), nk = st.n * k;
+    if (st.rows > 0) HIP_TRY(hipMemsetAsync(e->q.cl.rank, 0xff, sizeof(unsigned short) * (size_t)st.rows * (size_t)stride, e->stream));
+    if (int rc = select_enqueue(e, st, e->d_int2ext, k, min_p, cnt, ids, p ? p : reinterpret_cast<double *>(tkres + tkl.off_p),
+                                reinterpret_cast<double *>(tkres + tkl.off_r)))
+        return rc;
+    hipLaunchKernelGGL(k_cl_rank, dim3((nk + CL_BLOCK - 1) / CL_BLOCK), dim3(CL_BLOCK), 0, e->stream, g, e->d_ext2int.get(), cnt, ids, st.n, k, stride,
+                       e->q.cl.rank.get());
+    HIP_TRY(hipGetLastError());
+    *out_cnt = cnt;
+    return DPPR_OK;
+}
+
+// the per-position values and the block of the sweep: in place before the first kernel
+int cluster_workspace(dppr_engine *e) {
     QueryWork::Cluster &cl = e->q.cl;
     if (!cl.pin) { // (the last of the set: one that failed half way is made again)
         const size_t block = cl_layout(GS_MAX, DPPR_CLUSTER_MAX, true, true, true, true).total_bytes;
@@ -766,14 +808,12 @@ int cluster_workspace(dppr_engine *e, Grow &grow, int n, size_t rows, long long 
         HIP_TRY(cl.blk.regrow(block));
         HIP_TRY(cl.pin.regrow(block));
     }
-    int rc = grow(cl.rank, cl_rank_elems(rows, n), with_slack(cl_rank_elems(rows, n)));
-    if (!rc) rc = grow(cl.list, cl_list_cap(n, Ed));
-    return rc;
+    return DPPR_OK;
 }
 
 // The best prefix of every lane's top-k order and, where asked for, the order and its prefix arrays (arguments and the epoch
 // validated by the caller). Results are lane-major: best [n], the arrays [n][k]. The selection writes its ids straight into the
-// block (counts, p and r go to the top-k block, which nobody copies); nothing is read back between the kernels.
+// block; nothing is read back between the kernels.
 int run_cluster(dppr_engine *e, const Epoch &ep, const StateView &v, int k, double min_p, int min_size, dppr_cluster_t *out_best,
                 int32_t *out_ids, int64_t *out_cut_out, int64_t *out_cut_in, int64_t *out_vol) {
     if (int rc = query_begin(e, MAP_E2I | MAP_I2E)) return rc;
@@ -781,33 +821,20 @@ int run_cluster(dppr_engine *e, const Epoch &ep, const StateView &v, int k, doub
     const int n = v.n, stride = cl_stride(n);
     const TkState st = tk_state(e, v.p, v.r, v.gw, n);
     Grow grow{e};
-    if (int rc = topk_workspace(e, grow, n, (size_t)st.rows)) return rc;
-    if (int rc = cluster_workspace(e, grow, n, (size_t)st.rows, ep.Ed)) return rc;
-    const TkLayout tkl = tk_layout(n, k, true);
+    if (int rc = order_workspace(e, grow, n, (size_t)st.rows, ep.Ed)) return rc;
+    if (int rc = cluster_workspace(e)) return rc;
     const ClLayout lay = cl_layout(n, k, out_ids != nullptr, out_cut_out != nullptr, out_cut_in != nullptr, out_vol != nullptr);
-    unsigned char *tkres = e->q.tk.res.get(), *blk = cl.blk.get();
-    int *cnt = reinterpret_cast<int *>(tkres + tkl.off_cnt), *ids = reinterpret_cast<int *>(blk + lay.off_ids);
+    unsigned char *blk = cl.blk.get();
+    int *ids = reinterpret_cast<int *>(blk + lay.off_ids);
     ClCtl *ctl = reinterpret_cast<ClCtl *>(cl.d.get());
     int *d = cl.d + sizeof(ClCtl) / sizeof(int);
-    ClGraph g;
-    g.out_row_ptr = ep.out_row_ptr.get();
-    g.out_col = ep.out_col.get();
-    g.in_row_ptr = ep.row_ptr.get();
-    g.in_adj = ep.adj.get();
-    g.n_int = st.n_int;
-    g.lo_parked = st.lo_parked;
-    g.rows = st.rows;
-    const unsigned list_cap = (unsigned)std::min<size_t>(cl_list_cap(n, ep.Ed), 0xffffffffu);
+    const ClGraph g = cl_graph(ep, st);
+    const unsigned list_cap = order_list_cap(n, ep.Ed);
     const int nk = n * k;
+    const int *cnt = nullptr, *x2i = e->d_ext2int.get();
     if (int rc = DeviceTime{e}.open()) return rc;
-    if (st.rows > 0) HIP_TRY(hipMemsetAsync(cl.rank, 0xff, sizeof(unsigned short) * (size_t)st.rows * (size_t)stride, e->stream));
     HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(ClCtl), e->stream));
-    if (int rc = select_enqueue(e, st, e->d_int2ext, k, min_p, cnt, ids, reinterpret_cast<double *>(tkres + tkl.off_p),
-                                reinterpret_cast<double *>(tkres + tkl.off_r)))
-        return rc;
-    const int *x2i = e->d_ext2int.get();
-    hipLaunchKernelGGL(k_cl_rank, dim3((nk + CL_BLOCK - 1) / CL_BLOCK), dim3(CL_BLOCK), 0, e->stream, g, x2i, cnt, ids, n, k, stride,
-                       cl.rank.get());
+    if (int rc = order_enqueue(e, g, st, k, min_p, ids, nullptr, &cnt)) return rc;
     hipLaunchKernelGGL(k_cl_rows, dim3((nk + CL_WAVES - 1) / CL_WAVES), dim3(CL_BLOCK), 0, e->stream, g, x2i, cnt, ids, n, k, stride,
                        cl.rank.get(), d, ctl, cl.list.get(), list_cap);
     hipLaunchKernelGGL(k_cl_big, dim3(grid_for((int64_t)list_cap, CL_WAVES, 1024)), dim3(CL_BLOCK), 0, e->stream, g, x2i, ids, n, k, stride,
@@ -837,13 +864,10 @@ int cluster_call(dppr_engine *e, const StateView &v, const Epoch &ep, int32_t k,
 }
 
 // ---- the subgraph a top-k order induces (dppr_subgraph.hpp, dppr_subgraph_plan.hpp) ------------------------------------------------
-// the rank table and the chunk list of the conductance sweep, the per-position work and the block with its pinned twin: in place
-// before the first kernel
-int subgraph_workspace(dppr_engine *e, Grow &grow, int n, size_t rows, long long Ed, size_t block_bytes) {
+// the per-position work and the block with its pinned twin: in place before the first kernel
+int subgraph_workspace(dppr_engine *e, Grow &grow, size_t block_bytes) {
     QueryWork::Subgraph &sg = e->q.sg;
-    int rc = grow(e->q.cl.rank, cl_rank_elems(rows, n), with_slack(cl_rank_elems(rows, n)));
-    if (!rc) rc = grow(e->q.cl.list, cl_list_cap(n, Ed));
-    if (!rc) rc = grow(sg.work, sg_work_elems(GS_MAX, DPPR_SUBGRAPH_MAX));
+    int rc = grow(sg.work, sg_work_elems(GS_MAX, DPPR_SUBGRAPH_MAX));
     if (!rc) rc = grow(sg.blk, block_bytes);
     if (!rc) rc = grow(sg.pin, block_bytes);
     return rc;
@@ -869,11 +893,9 @@ int run_subgraph(dppr_engine *e, const Epoch &ep, const StateView &v, int k, dou
     const TkState st = tk_state(e, v.p, v.r, v.gw, n);
     const SgLayout lay = sg_layout(n, k, host ? capc : 0, out_ids != nullptr, out_p != nullptr, out_row_ptr != nullptr, out_col != nullptr);
     Grow grow{e};
-    if (int rc = topk_workspace(e, grow, n, (size_t)st.rows)) return rc;
-    if (int rc = subgraph_workspace(e, grow, n, (size_t)st.rows, ep.Ed, lay.total_bytes)) return rc;
-    const TkLayout tkl = tk_layout(n, k, true);
-    unsigned char *tkres = e->q.tk.res.get(), *blk = sg.blk.get();
-    int *cnt = reinterpret_cast<int *>(tkres + tkl.off_cnt);
+    if (int rc = order_workspace(e, grow, n, (size_t)st.rows, ep.Ed)) return rc;
+    if (int rc = subgraph_workspace(e, grow, lay.total_bytes)) return rc;
+    unsigned char *blk = sg.blk.get();
     SgHead *head = reinterpret_cast<SgHead *>(blk + lay.off_head);
     int *d_ids = !host && out_ids ? out_ids : reinterpret_cast<int *>(blk + lay.off_ids);
     double *d_p = !host && out_p ? out_p : reinterpret_cast<double *>(blk + lay.off_p);
@@ -882,23 +904,13 @@ int run_subgraph(dppr_engine *e, const Epoch &ep, const StateView &v, int k, dou
     SgCtl *ctl = reinterpret_cast<SgCtl *>(sg.work.get());
     const int nk = n * k;
     int *m = sg.work + sizeof(SgCtl) / sizeof(int), *long_list = m + nk;
-    ClGraph g;
-    g.out_row_ptr = ep.out_row_ptr.get();
-    g.out_col = ep.out_col.get();
-    g.in_row_ptr = ep.row_ptr.get();
-    g.in_adj = ep.adj.get();
-    g.n_int = st.n_int;
-    g.lo_parked = st.lo_parked;
-    g.rows = st.rows;
-    const unsigned list_cap = (unsigned)std::min<size_t>(cl_list_cap(n, ep.Ed), 0xffffffffu);
-    if (int rc = DeviceTime{e}.open()) return rc;
-    if (st.rows > 0) HIP_TRY(hipMemsetAsync(e->q.cl.rank, 0xff, sizeof(unsigned short) * (size_t)st.rows * (size_t)stride, e->stream));
-    HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(SgCtl), e->stream));
-    if (int rc = select_enqueue(e, st, e->d_int2ext, k, min_p, cnt, d_ids, d_p, reinterpret_cast<double *>(tkres + tkl.off_r))) return rc;
-    const int *x2i = e->d_ext2int.get();
+    const ClGraph g = cl_graph(ep, st);
+    const unsigned list_cap = order_list_cap(n, ep.Ed);
+    const int *cnt = nullptr, *x2i = e->d_ext2int.get();
     const unsigned short *rank = e->q.cl.rank.get();
-    hipLaunchKernelGGL(k_cl_rank, dim3((nk + CL_BLOCK - 1) / CL_BLOCK), dim3(CL_BLOCK), 0, e->stream, g, x2i, cnt, d_ids, n, k, stride,
-                       e->q.cl.rank.get());
+    if (int rc = DeviceTime{e}.open()) return rc;
+    HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(SgCtl), e->stream));
+    if (int rc = order_enqueue(e, g, st, k, min_p, d_ids, d_p, &cnt)) return rc;
     hipLaunchKernelGGL(k_sg_count, dim3((nk + CL_WAVES - 1) / CL_WAVES), dim3(CL_BLOCK), 0, e->stream, g, x2i, cnt, d_ids, n, k, stride, rank, m,
                        ctl, e->q.cl.list.get(), list_cap);
     hipLaunchKernelGGL(k_sg_big, dim3(grid_for((int64_t)list_cap, CL_WAVES, 1024)), dim3(CL_BLOCK), 0, e->stream, g, x2i, d_ids, k, stride, rank, m,
@@ -925,8 +937,7 @@ int run_subgraph(dppr_engine *e, const Epoch &ep, const StateView &v, int k, dou
     if (host && out_col && capc > 0) hi = fill ? lay.off_col + sg_col_bytes(total) : std::min(hi, lay.off_col);
     const bool copy = host && hi > lay.copy_lo;
     if (copy) HIP_TRY(hipMemcpyAsync(sg.pin + lay.copy_lo, blk + lay.copy_lo, hi - lay.copy_lo, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream)); // (a device destination is complete here: any stream of the caller may read it)
-    if (int rc = DeviceTime{e}.read()) return rc;
+    if (int rc = run_end(e)) return rc; // (a device destination is complete here: any stream of the caller may read it)
     if (host) {
         if (out_ids) memcpy(out_ids, sg.pin + lay.off_ids, sg_ids_bytes(n, k));
         if (out_p) memcpy(out_p, sg.pin + lay.off_p, sg_p_bytes(n, k));
@@ -1042,58 +1053,44 @@ int rank_mark_enqueue(dppr_engine *e, const RkLanes &l, const RkSpec &sp, const 
 int run_topk_ranked(dppr_engine *e, const StateView &v, const RkLanes &l, const Epoch *ep, const RkSpec &sp, int k, double min_score,
                     int32_t *out_ids, double *out_score, int32_t *out_counts) {
     if (int rc = query_begin(e, MAP_I2E)) return rc;
-    QueryWork::Rank &rk = e->q.rk;
+    QueryWork::Scratch &sc = e->q.sc;
     const TkState st = tk_state(e, v.p, v.p, v.gw, v.n);
     Grow grow{e};
-    if (int rc = topk_workspace(e, grow, v.n, (size_t)st.rows)) return rc;
-    const size_t sc = rk_score_elems((size_t)st.rows, v.n), ex = rk_ext_elems((size_t)st.rows);
-    if (int rc = grow(rk.score, sc, with_slack(sc))) return rc;
-    if (int rc = grow(rk.ext, ex, with_slack(ex))) return rc;
+    if (int rc = scratch_workspace(e, grow, (size_t)st.rows, v.n, 1)) return rc;
     if (int rc = rank_mark_workspace(e, grow, l, sp, ep)) return rc;
     const RkGraph g = rank_graph(e, ep);
     const RkRule rule = rank_rule(sp);
     if (int rc = DeviceTime{e}.open()) return rc;
     const unsigned *excl = nullptr;
     if (int rc = rank_mark_enqueue(e, l, sp, g, &excl)) return rc;
-    const int n_tiles = std::max((st.rows + RK_ROWS - 1) / RK_ROWS, 1);
     by_factor(sp, [&](auto kind, auto elem) -> int {
         using T = decltype(elem);
-        hipLaunchKernelGGL((k_rk_scores<decltype(kind)::value, T>), dim3(std::min(n_tiles, 2048)), dim3(RK_BLOCK), 0, e->stream, st,
-                           e->d_int2ext.get(), excl, rule, g, rk.score.get(), rk.ext.get());
+        hipLaunchKernelGGL((k_rk_scores<decltype(kind)::value, T>), dim3(tile_grid(st.rows)), dim3(TK_TILE_BLOCK), 0, e->stream, st,
+                           e->d_int2ext.get(), excl, rule, g, sc.a.get(), sc.ext.get());
         return DPPR_OK;
     });
     HIP_TRY(hipGetLastError());
-    return run_select(e, scratch_state(rk.score, rk.score, v.n, st.rows), rk.ext, k, min_score, out_ids, out_score, nullptr, out_counts);
+    return run_select(e, scratch_state(sc.a, sc.a, v.n, st.rows), sc.ext, k, min_score, out_ids, out_score, nullptr, out_counts);
 }
 
 // the scores at m external ids (validated by the caller like the rest, m > 0), [m][n]
 int run_rank_score_at(dppr_engine *e, const StateView &v, const RkLanes &l, const Epoch *ep, const RkSpec &sp, const int32_t *ids, int m,
                       double *out_score) {
     if (int rc = query_begin(e, MAP_E2I)) return rc;
-    const size_t mn = (size_t)m * (size_t)v.n;
-    const RaLayout lay = ra_layout(m, v.n, 1);
     Grow grow{e};
-    if (int rc = grow(e->q.ra.buf, lay.total_bytes)) return rc;
     if (int rc = rank_mark_workspace(e, grow, l, sp, ep)) return rc;
-    int *d_ids = reinterpret_cast<int *>(e->q.ra.buf + lay.off_ids);
-    double *d_out = reinterpret_cast<double *>(e->q.ra.buf + lay.off_a);
     const RkGraph g = rank_graph(e, ep);
     const RkRule rule = rank_rule(sp);
-    HIP_TRY(hipMemcpyAsync(d_ids, ids, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, e->stream));
-    if (int rc = DeviceTime{e}.open()) return rc;
-    const unsigned *excl = nullptr;
-    if (int rc = rank_mark_enqueue(e, l, sp, g, &excl)) return rc;
-    by_factor(sp, [&](auto kind, auto elem) -> int {
-        using T = decltype(elem);
-        hipLaunchKernelGGL((k_rk_score_at<decltype(kind)::value, T>), dim3(grid_for((int64_t)mn, RK_BLOCK)), dim3(RK_BLOCK), 0, e->stream,
-                           v.p, v.gw, v.n, e->d_ext2int.get(), d_ids, m, excl, rule, g, d_out);
-        return DPPR_OK;
+    return point_read(e, grow, ids, m, v.n, 1, out_score, nullptr, [&](const int *d_ids, double *d_out, double *) {
+        const unsigned *excl = nullptr;
+        if (int rc = rank_mark_enqueue(e, l, sp, g, &excl)) return rc;
+        return by_factor(sp, [&](auto kind, auto elem) -> int {
+            using T = decltype(elem);
+            hipLaunchKernelGGL((k_rk_score_at<decltype(kind)::value, T>), dim3(grid_for((int64_t)m * v.n, RK_BLOCK)), dim3(RK_BLOCK), 0, e->stream,
+                               v.p, v.gw, v.n, e->d_ext2int.get(), d_ids, m, excl, rule, g, d_out);
+            return DPPR_OK;
+        });
     });
-    HIP_TRY(hipGetLastError());
-    if (int rc = DeviceTime{e}.close()) return rc;
-    HIP_TRY(hipMemcpyAsync(out_score, d_out, sizeof(double) * mn, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return DeviceTime{e}.read();
 }
 
 // What both forms check after their own arguments: the epoch, where the spec needs one (*out_ep stays NULL otherwise), and the

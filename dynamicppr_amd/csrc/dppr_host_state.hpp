@@ -195,14 +195,14 @@ struct QueryWork {
     struct ReadAt {
         DevBuf<unsigned char> buf; // point reads: ids, then p and r outputs (dppr_group_score_at: ids, then the scores)
     } ra;
-    struct Weighted { // a group as a weighted set of targets (dppr_wquery.hpp)
-        DevBuf<double> w;     // [16][16] weights of the call
-        DevBuf<double> score; // scratch state: [occupied rows][q] scores
-        DevBuf<int> ext;      // ... and the external id of every row of it
+    struct Scratch { // the compacted scratch state of the weighted, changes and ranked queries (one call at a time: map_mu, the solver stream)
+        DevBuf<double> a, b; // [occupied rows][lanes] each: the scores of a weighted or ranked call (a alone), |p - mark| and p - mark of changes
+        DevBuf<int> ext;     // the external id of every row of it
+    } sc;
+    struct Weighted { // a group as a weighted set of targets (dppr_wquery.hpp); its scores: sc
+        DevBuf<double> w; // [16][16] weights of the call
     } wq;
-    struct Changes { // what a batch moved (dppr_changes.hpp)
-        DevBuf<double> abs, d; // scratch states: [occupied rows][n] |p - mark| and p - mark
-        DevBuf<int> ext;       // ... and the external id of every row of them
+    struct Changes { // what a batch moved (dppr_changes.hpp); |p - mark| and p - mark: sc
         DevBuf<unsigned char> res; PinBuf<unsigned char> pin; // counts, moved, ids, deltas, p (dppr_changes_plan.hpp): device / pinned host
     } ch;
     struct Export { // dppr_export.hpp, dppr_export_plan.hpp; the block grows with a host destination's cap
@@ -234,9 +234,7 @@ struct QueryWork {
         DevBuf<int> work;                                     // the control words (SgCtl), the matches of every position [n][k], the rows queued for k_sg_long [n][k]
         DevBuf<unsigned char> blk; PinBuf<unsigned char> pin; // the head, ids, p, row_ptr and a host destination's col: device / pinned host
     } sg;
-    struct Rank { // ranked candidates (dppr_rank.hpp, dppr_rank_plan.hpp)
-        DevBuf<double> score;  // scratch state: [occupied rows][n] scores
-        DevBuf<int> ext;       // ... and the external id of every row of it
+    struct Rank { // ranked candidates (dppr_rank.hpp, dppr_rank_plan.hpp); its scores: sc
         DevBuf<unsigned> excl; // [live rows] bit i: excluded for lane i (zeroed per call)
         DevBuf<int> len; PinBuf<int> len_pin;     // [seeds][2] out-row and in-row length of every seed: device / pinned host
         DevBuf<unsigned long long> list;          // the piece list of the call (rk_piece_cap)

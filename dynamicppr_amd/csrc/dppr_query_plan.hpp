@@ -62,6 +62,11 @@ constexpr TkLayout tk_layout(int n, int k, bool with_r) {
     return l;
 }
 
+// The compacted scratch state of the weighted, changes and ranked queries: one or two planes of [occupied rows][lanes] doubles
+// and the external id of every row (a state without an occupied row still has room for one)
+constexpr size_t scratch_plane_elems(size_t rows, int lanes) { return (rows > 0 ? rows : 1) * (size_t)lanes; }
+constexpr size_t scratch_ext_elems(size_t rows) { return rows > 0 ? rows : 1; }
+
 struct RaLayout {
     size_t off_ids = 0, off_a = 0, off_b = 0; // off_b: the second output of a call that has two
     size_t total_bytes = 0;

@@ -14,10 +14,10 @@
 //                 atomic OR per entry; the seeds' own bits by one thread per seed. excl is one word per LIVE row, zeroed per call
 //                 (parked rows have no edges and are never seeds). Nothing else is written, and an OR does not depend on the order
 //                 in which the pieces arrive.
-//   k_rk_scores   the tile of k_wq_scores: RK_ROWS rows per step read with 16-byte loads, consecutive threads at consecutive
-//                 addresses, into LDS rows padded by one double; per row the external id, the exclusion word (all ones where the
-//                 mask takes the vertex out) and the factor -- a DEV factor gathered by external id, a degree from out_row_ptr
-//                 by internal id -- then n scores per row into the COMPACTED scratch state score[c * n + lane] with ext_c[c].
+//   k_rk_scores   one tile of dppr_topk.hpp (tk_stage_tile) per step; per row, beside the external id, the exclusion word (all
+//                 ones where the mask takes the vertex out) and the factor -- a DEV factor gathered by external id, a degree
+//                 from out_row_ptr by internal id -- then n scores per row into the COMPACTED scratch state
+//                 score[c * n + lane] with ext_c[c].
 //                 Templated on the factor kind and the dtype of g: the NONE path carries no gather.
 //   selection     dppr_topk.hpp over the scratch as a state of n lanes without a parked zone, as it is.
 //   k_rk_score_at one thread per (id, lane); the row, and with it the exclusion word and the degree, through ext2int.
@@ -32,8 +32,8 @@
 
 namespace dppr {
 
-static_assert(RK_BLOCK == 4 * WAVE && Q_LANES == GS_MAX && Q_LANES == TG_LANES, "dppr_rank_plan.hpp restates the wave and the lanes");
-constexpr int RK_LDS_ROW = GS_MAX + 1; // widest padded row
+static_assert(RK_BLOCK == 4 * WAVE && Q_LANES == GS_MAX && Q_LANES == TG_LANES && TK_TILE_LDS_ROW == GS_MAX + 1,
+              "dppr_rank_plan.hpp restates the wave and the lanes, dppr_topk.hpp the lanes");
 
 // the seeds of a call's lanes: a source lane's from src, a set lane's from the group's seed table
 struct RkLanes {
@@ -133,39 +133,24 @@ __global__ __launch_bounds__(RK_BLOCK) void k_rk_mark(RkLanes l, RkGraph g, unsi
 // st: the state (rows of gw doubles; gw even for a group, 1 for a slot). excl: [n_int] or NULL (nothing is excluded).
 // score: [st.rows][st.n], ext_c: [st.rows].
 template <int KIND, class T>
-__global__ __launch_bounds__(RK_BLOCK) void k_rk_scores(TkState st, const int *__restrict__ i2e, const unsigned *__restrict__ excl,
-                                                        RkRule rule, RkGraph g, double *__restrict__ score, int *__restrict__ ext_c) {
-    __shared__ double s_p[RK_ROWS * RK_LDS_ROW];
-    __shared__ double s_f[RK_ROWS];
-    __shared__ unsigned s_x[RK_ROWS];
-    const int n = st.n, ls = st.gw + 1, half = st.gw / 2;
-    const int n_tiles = (st.rows + RK_ROWS - 1) / RK_ROWS;
+__global__ __launch_bounds__(TK_TILE_BLOCK) void k_rk_scores(TkState st, const int *__restrict__ i2e, const unsigned *__restrict__ excl,
+                                                             RkRule rule, RkGraph g, double *__restrict__ score, int *__restrict__ ext_c) {
+    __shared__ double s_p[TK_TILE_ROWS * TK_TILE_LDS_ROW];
+    __shared__ double s_f[TK_TILE_ROWS];
+    __shared__ unsigned s_x[TK_TILE_ROWS];
+    const int n = st.n, ls = st.gw + 1;
+    const int n_tiles = (st.rows + TK_TILE_ROWS - 1) / TK_TILE_ROWS;
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int c0 = tile * RK_ROWS, cnt = min(RK_ROWS, st.rows - c0);
+        const int c0 = tile * TK_TILE_ROWS, cnt = min(TK_TILE_ROWS, st.rows - c0);
         __syncthreads(); // (the scores of the previous tile are out)
-        if (st.gw & 1) { // (a slot: rows of one double)
-            for (int j = threadIdx.x; j < cnt * st.gw; j += RK_BLOCK) {
-                const int rl = j / st.gw, h = j % st.gw;
-                s_p[rl * ls + h] = st.p[(size_t)tk_row(st, c0 + rl) * st.gw + h];
-            }
-        } else {
-            for (int j = threadIdx.x; j < cnt * half; j += RK_BLOCK) {
-                const int rl = j / half, h = j % half;
-                const double2 v = *reinterpret_cast<const double2 *>(st.p + (size_t)tk_row(st, c0 + rl) * st.gw + 2 * h);
-                s_p[rl * ls + 2 * h] = v.x;
-                s_p[rl * ls + 2 * h + 1] = v.y;
-            }
-        }
-        for (int rl = threadIdx.x; rl < cnt; rl += RK_BLOCK) {
-            const int row = tk_row(st, c0 + rl), ext = i2e[row];
-            ext_c[c0 + rl] = ext;
+        tk_stage_tile(st, i2e, c0, cnt, s_p, ext_c, [&](int rl, int row, int ext) {
             unsigned x = (excl && row < st.n_int) ? excl[row] : 0u;
             if (rk_masked_out(rule, ext)) x = 0xffffffffu;
             s_x[rl] = x;
             s_f[rl] = rk_factor<KIND, T>(rule, g, ext, row);
-        }
+        });
         __syncthreads();
-        for (int o = threadIdx.x; o < cnt * n; o += RK_BLOCK) {
+        for (int o = threadIdx.x; o < cnt * n; o += TK_TILE_BLOCK) {
             const int rl = o / n, lane = o % n;
             score[(size_t)c0 * n + o] = rk_score<KIND>(s_p[rl * ls + lane], s_f[rl], (s_x[rl] >> lane) & 1u);
         }

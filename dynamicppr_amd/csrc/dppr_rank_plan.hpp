@@ -2,7 +2,7 @@
 // dppr_group_rank_score_at) decide before any device is involved: the check of a spec and of a call's arguments, whether a spec
 // needs the epoch's CSRs at all, the seeds of a call's lanes as one flat list, the PIECE LIST of the marking stage -- the rows of
 // the seeds cut into pieces of at most `piece` entries, one wave of k_rk_mark each -- with the bound on its length, and the sizes
-// of the scratch. Pure host code without HIP includes (dppr_host_query.hpp checks a call and plans its marking stage with it;
+// of the stage's buffers. Pure host code without HIP includes (dppr_host_query.hpp checks a call and plans its marking stage with it;
 // tests/native/rank_plan_test.cpp drives it on the CPU under the sanitizers).
 //
 // A piece is an item of the conductance sweep's chunk list (dppr_cluster_plan.hpp: cl_item): position | direction | chunk number.
@@ -17,9 +17,8 @@
 namespace dppr {
 
 constexpr int RK_PIECE = 512;   // entries of a row one wave of k_rk_mark walks (dppr_debug_rank_piece lowers it)
-constexpr int RK_BLOCK = 256;   // every kernel of dppr_rank.hpp: four waves
+constexpr int RK_BLOCK = 256;   // the kernels of dppr_rank.hpp but k_rk_scores (the tile of dppr_topk.hpp): four waves
 constexpr int RK_WAVES = RK_BLOCK / 64;
-constexpr int RK_ROWS = 128;    // rows per tile of k_rk_scores: the tile of k_wq_scores
 constexpr uint32_t RK_EXCLUDE_ALL = DPPR_EXCLUDE_SEEDS | DPPR_EXCLUDE_IN_NEIGHBOURS | DPPR_EXCLUDE_OUT_NEIGHBOURS;
 constexpr uint32_t RK_EXCLUDE_ROWS = DPPR_EXCLUDE_IN_NEIGHBOURS | DPPR_EXCLUDE_OUT_NEIGHBOURS; // the flags that walk a row
 
@@ -114,10 +113,8 @@ inline size_t rk_piece_cap(const RkSeeds &s, long long Ed, uint32_t exclude, int
     return dirs * ((size_t)s.total() + (size_t)s.n * (size_t)(Ed / piece + 1));
 }
 
-// the scratch: the compacted scores [occupied rows][n] with the external id of every row, the exclusion word of every live row,
-// the two row lengths of every seed
-constexpr size_t rk_score_elems(size_t rows, int n) { return (rows > 0 ? rows : 1) * (size_t)n; }
-constexpr size_t rk_ext_elems(size_t rows) { return rows > 0 ? rows : 1; }
+// the marking stage's buffers: the exclusion word of every live row, the two row lengths of every seed (the scratch state is sized
+// by dppr_query_plan.hpp)
 constexpr size_t rk_excl_elems(size_t n_int) { return n_int > 0 ? n_int : 1; }
 constexpr size_t rk_len_elems(size_t total_seeds) { return 2 * (total_seeds > 0 ? total_seeds : 1); }
 

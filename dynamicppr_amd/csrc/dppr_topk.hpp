@@ -59,6 +59,44 @@ struct TkState {             // the state being queried
 __device__ __forceinline__ int tk_row(const TkState &st, int q) { return q < st.n_int ? q : st.lo_parked + (q - st.n_int); }
 __device__ __forceinline__ unsigned long long tk_key(double v) { return (unsigned long long)__double_as_longlong(v); }
 
+// ---- the tile of the kernels that fill a scratch state (k_wq_scores, k_ch_delta, k_rk_scores) ------------------------------
+// Such a kernel streams the occupied rows once, TK_TILE_ROWS rows per step and workgroup of TK_TILE_BLOCK threads, and writes a
+// COMPACTED state (row c = 0 .. rows - 1, no parked zone) with the external id of every row beside it, over which the selection
+// below then runs as it is. A tile of p is staged in LDS rows padded by one double: the threads of a wave that then work on one
+// output each read rows 17 (9, 5, ..) doubles apart, which the 64 banks serve without conflict, and the threads of one row read
+// the same address (a broadcast).
+constexpr int TK_TILE_ROWS = 128;                   // rows per tile: 128 x 17 doubles of LDS (17 KiB) per staged plane
+constexpr int TK_TILE_BLOCK = 256;
+constexpr int TK_TILE_LDS_ROW = 16 + 1;             // widest padded row (16 lanes: GS_MAX of dppr_multi.hpp)
+
+// Rows [c0, c0 + cnt) of st.p into s_p (row rl at s_p + rl * (gw + 1)) and their external ids into ext_c: 16-byte loads where a
+// row is an even number of doubles (every group), 8-byte loads on a single-source slot (gw = 1), consecutive threads at
+// consecutive addresses (rows are contiguous inside a zone). per_row(rl, row, ext) runs once per row, by the thread that wrote
+// its id. The caller synchronises before it reads s_p.
+template <class PerRow>
+__device__ __forceinline__ void tk_stage_tile(const TkState &st, const int *__restrict__ i2e, int c0, int cnt, double *s_p,
+                                              int *__restrict__ ext_c, PerRow &&per_row) {
+    const int ls = st.gw + 1, half = st.gw / 2;
+    if (st.gw & 1) {
+        for (int j = threadIdx.x; j < cnt * st.gw; j += TK_TILE_BLOCK) {
+            const int rl = j / st.gw, h = j % st.gw;
+            s_p[rl * ls + h] = st.p[(size_t)tk_row(st, c0 + rl) * st.gw + h];
+        }
+    } else {
+        for (int j = threadIdx.x; j < cnt * half; j += TK_TILE_BLOCK) {
+            const int rl = j / half, h = j % half;
+            const double2 v = *reinterpret_cast<const double2 *>(st.p + (size_t)tk_row(st, c0 + rl) * st.gw + 2 * h);
+            s_p[rl * ls + 2 * h] = v.x;
+            s_p[rl * ls + 2 * h + 1] = v.y;
+        }
+    }
+    for (int rl = threadIdx.x; rl < cnt; rl += TK_TILE_BLOCK) {
+        const int row = tk_row(st, c0 + rl), ext = i2e[row];
+        ext_c[c0 + rl] = ext;
+        per_row(rl, row, ext);
+    }
+}
+
 // digit of U = hi:lo (96 bits) whose lowest bit is bit s
 __device__ __forceinline__ int tk_digit(unsigned long long hi, unsigned lo, int s) {
     const unsigned long long w = s >= 32 ? hi >> (s - 32) : (hi << (32 - s)) | ((unsigned long long)lo >> s);

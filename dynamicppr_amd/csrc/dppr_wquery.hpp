@@ -13,20 +13,16 @@
 // compaction). The selection of dppr_topk.hpp then runs over the scratch as a state of q lanes, rows q doubles wide, without
 // a parked zone: its kernels are used as they are. DESIGN.md section 9c has the byte counts of this shape and of the fused one.
 //
-// k_wq_scores: one tile of WQ_ROWS rows per step. The tile is read with 16-byte loads, consecutive threads at consecutive
-// addresses (rows are contiguous inside a zone; a row is an even number of doubles), into LDS rows padded by one double:
-// in the fold, the threads of a wave read rows 17 (9, 5, ..) doubles apart, which the 64 banks serve without conflict, and threads
-// of one row read the same address (a broadcast). Scores leave with consecutive threads at consecutive addresses.
+// k_wq_scores: one tile of dppr_topk.hpp (tk_stage_tile) per step, then one thread per (row, query): the fold over the staged row.
+// Scores leave with consecutive threads at consecutive addresses.
 #pragma once
 
 #include "dppr_topk.hpp"
 
 namespace dppr {
 
-constexpr int WQ_BLOCK = 256;
-constexpr int WQ_ROWS = 128;                      // rows per tile: 128 x 17 doubles of LDS (17 KiB) beside the 2 KiB of weights
+constexpr int WQ_BLOCK = 256;                     // k_score_at
 constexpr int WQ_LANES = 16;                      // sources of a group, weight vectors of a call (GS_MAX)
-constexpr int WQ_LDS_ROW = WQ_LANES + 1;          // widest padded row
 
 // the fold of the header over n consecutive weights and n consecutive doubles of a row
 __device__ __forceinline__ double wq_fold(const double *w, const double *p, int n) {
@@ -35,26 +31,20 @@ __device__ __forceinline__ double wq_fold(const double *w, const double *p, int 
     return acc;
 }
 
-// st: the group's state (rows of gw doubles, gw even). w: [q][n] on the device. score: [st.rows][q], ext_c: [st.rows].
-__global__ __launch_bounds__(WQ_BLOCK) void k_wq_scores(TkState st, const int *__restrict__ i2e, const double *__restrict__ w, int q,
-                                                        double *__restrict__ score, int *__restrict__ ext_c) {
+// st: the group's state. w: [q][n] on the device. score: [st.rows][q], ext_c: [st.rows].
+__global__ __launch_bounds__(TK_TILE_BLOCK) void k_wq_scores(TkState st, const int *__restrict__ i2e, const double *__restrict__ w,
+                                                             int q, double *__restrict__ score, int *__restrict__ ext_c) {
     __shared__ double s_w[WQ_LANES * WQ_LANES];
-    __shared__ double s_p[WQ_ROWS * WQ_LDS_ROW];
-    for (int i = threadIdx.x; i < q * st.n; i += WQ_BLOCK) s_w[i] = w[i];
-    const int ls = st.gw + 1, half = st.gw / 2;
-    const int n_tiles = (st.rows + WQ_ROWS - 1) / WQ_ROWS;
+    __shared__ double s_p[TK_TILE_ROWS * TK_TILE_LDS_ROW];
+    for (int i = threadIdx.x; i < q * st.n; i += TK_TILE_BLOCK) s_w[i] = w[i];
+    const int ls = st.gw + 1;
+    const int n_tiles = (st.rows + TK_TILE_ROWS - 1) / TK_TILE_ROWS;
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int c0 = tile * WQ_ROWS, cnt = min(WQ_ROWS, st.rows - c0);
+        const int c0 = tile * TK_TILE_ROWS, cnt = min(TK_TILE_ROWS, st.rows - c0);
         __syncthreads(); // (the folds of the previous tile are over; the weights are in place)
-        for (int j = threadIdx.x; j < cnt * half; j += WQ_BLOCK) {
-            const int rl = j / half, h = j % half;
-            const double2 v = *reinterpret_cast<const double2 *>(st.p + (size_t)tk_row(st, c0 + rl) * st.gw + 2 * h);
-            s_p[rl * ls + 2 * h] = v.x;
-            s_p[rl * ls + 2 * h + 1] = v.y;
-        }
-        for (int rl = threadIdx.x; rl < cnt; rl += WQ_BLOCK) ext_c[c0 + rl] = i2e[tk_row(st, c0 + rl)];
+        tk_stage_tile(st, i2e, c0, cnt, s_p, ext_c, [](int, int, int) {});
         __syncthreads();
-        for (int o = threadIdx.x; o < cnt * q; o += WQ_BLOCK) {
+        for (int o = threadIdx.x; o < cnt * q; o += TK_TILE_BLOCK) {
             const int rl = o / q, j = o % q;
             score[(size_t)c0 * q + o] = wq_fold(s_w + j * st.n, s_p + rl * ls, st.n);
         }

@@ -481,15 +481,16 @@ int dppr_group_read_at(dppr_engine *e, int32_t group, const int32_t *ids, int32_
  * stream, work on any state (converged or not), scan the live and the parked zone, and are never part of the
  * update path. The top-k query keeps a device scratch of 8 q + 4 bytes per row that holds a vertex (not per V),
  * obtained -- like every other buffer of the call -- before anything is written: after DPPR_ERR_NOMEM the states
- * and the engine are as before. */
+ * and the engine are as before. The scratch is ONE, shared with dppr_changes and dppr_topk_ranked and their group
+ * forms: an engine holds the largest any call of the three families has needed, not one per family. */
 int dppr_group_topk_weighted(dppr_engine *e, int32_t group, const double *weights /* [q][n] */, int32_t q /* 1..16 */,
                              int32_t k, double min_score, int32_t *out_ids /* [q][k] */, double *out_score /* [q][k] */,
                              int32_t *out_counts /* [q] */);
 int dppr_group_score_at(dppr_engine *e, int32_t group, const double *weights /* [q][n] */, int32_t q,
                         const int32_t *ids, int32_t m, double *out_score /* [m][q] */);
 /* Measurement aid: with dppr_set_profiling on, *out_ms is the device time of the last dppr_topk / dppr_group_topk /
- * dppr_group_topk_weighted call on this engine, from the first to the last kernel (the copy back not included);
- * -1 before the first such call. */
+ * dppr_group_topk_weighted / dppr_read_at / dppr_group_read_at / dppr_group_score_at call on this engine, from the first
+ * to the last kernel (the copy back not included); -1 before the first such call. */
 int dppr_debug_query_ms(dppr_engine *e, float *out_ms);
 
 /* ---- what a batch moved: marks and per-source top-k of |delta p| (backward-compatible additions, ABI 6) ----
@@ -528,7 +529,7 @@ int dppr_debug_query_ms(dppr_engine *e, float *out_ms);
  * Rejected with DPPR_ERR_INVALID before any device work, nothing written: a slot or group without a mark, k
  * outside [1, DPPR_TOPK_MAX], min_delta negative or NaN, a NULL out_ids, out_delta or out_counts, a bad slot /
  * group. Every buffer a call needs -- the mark itself (dppr_mark), the scratch of 16 n + 4 bytes per row that
- * holds a vertex and the result block (dppr_changes) -- is obtained before anything is written: after
+ * holds a vertex (the one of dppr_group_topk_weighted) and the result block (dppr_changes) -- is obtained before anything is written: after
  * DPPR_ERR_NOMEM the state and any earlier mark are as before.
  * Threading and stream as dppr_topk: mark and query hold the id-map lock as dppr_read does (safe beside
  * dppr_slide_concurrent), run on the solver stream, work on any state (converged or not, or set by dppr_write),
@@ -897,7 +898,7 @@ int dppr_debug_subgraph_wave_max(dppr_engine *e, int wave_max);
  * state's, where the spec needs one. factor_dev and mask_dev are only read, on the solver stream, before the call returns.
  * Threading and stream as dppr_topk: the id-map lock of dppr_read (safe beside dppr_slide_concurrent), the solver stream, any state
  * (converged or not), never part of the update path or of a timed region. Work space beyond dppr_topk's: a scratch state of
- * 8 n + 4 bytes per row that holds a vertex, 4 bytes per live row for the exclusion words, and for the neighbour flags 8 bytes per
+ * 8 n + 4 bytes per row that holds a vertex (the one of dppr_group_topk_weighted), 4 bytes per live row for the exclusion words, and for the neighbour flags 8 bytes per
  * seed and 8 bytes per piece of 512 entries of the seeds' rows (bounded by the epoch's edges per lane and direction); all of it is
  * the engine's, obtained before the first kernel, grown on demand and released with the engine: after DPPR_ERR_NOMEM the states and
  * the engine are as before. With dppr_set_profiling on, dppr_debug_query_ms also reports the device time of the last of these

@@ -143,6 +143,10 @@ int main() {
             w[0] = -0.0;
             CHECK(weights_ok(w.data(), q, n), "q %d n %d: negative and zero weights are finite", q, n);
         }
+    // the scratch state of the weighted, changes and ranked queries
+    ++cases;
+    CHECK(scratch_plane_elems(0, 3) == 3 && scratch_plane_elems(1000, 10) == 10000 && scratch_ext_elems(0) == 1 && scratch_ext_elems(77) == 77,
+          "scratch state");
     std::printf("query_plan_test: %ld cases, %d failures\n", cases, failures);
     return failures ? 1 : 0;
 }

@@ -211,7 +211,6 @@ static void pieces() {
 }
 
 static void scratch() {
-    CHECK(rk_score_elems(0, 3) == 3 && rk_score_elems(1000, 10) == 10000 && rk_ext_elems(0) == 1 && rk_ext_elems(77) == 77, "scratch state");
     CHECK(rk_excl_elems(0) == 1 && rk_excl_elems(4096) == 4096 && rk_len_elems(0) == 2 && rk_len_elems(343) == 686, "marking");
     CHECK(rk_chunks(0, 512) == 0 && rk_chunks(1, 512) == 1 && rk_chunks(512, 512) == 1 && rk_chunks(513, 512) == 2, "chunks");
 }
