@@ -3,7 +3,8 @@ from a BUILDER thread while the SOLVER thread runs dppr_update / dppr_group_upda
 epochs; the builder has its own HIP stream and scratch inside the engine. Bars: the device CSR of every epoch built that way is the
 oracle's bit for bit, p / r after every batch are the synchronous oracle's to rounding -- on a stream whose vertices come and go
 (fresh ids in most batches, parked vertices that come back: their state rows move while the solver runs), with the id-space
-renumbering taking its exclusive slides in between (dppr_renumbering_due)."""
+renumbering taking its exclusive slides in between (dppr_renumbering_due).
+The state queries beside the builder (top-k to ranked): tests/test_queries_beside_slide_gpu.py."""
 import threading
 
 import numpy as np
