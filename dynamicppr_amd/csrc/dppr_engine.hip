@@ -52,6 +52,7 @@
 #include "dppr_cluster.hpp"
 #include "dppr_subgraph.hpp"
 #include "dppr_rank.hpp"
+#include "dppr_assign.hpp"
 
 using namespace dppr;
 
@@ -1600,6 +1601,18 @@ int dppr_group_rank_score_at(dppr_engine *e, int32_t group, int32_t epoch, const
                              double *out_score) {
     GET_GROUP(e, group);
     return rank_score_at_call(e, g, epoch, spec, ids, m, out_score);
+}
+
+int dppr_assign(dppr_engine *e, const int32_t *groups, int32_t n_groups, const double *scale, double min_score, int dest, int32_t *out_label,
+                double *out_best, double *out_margin, int64_t *out_counts, const int32_t *prev_label, int64_t cap, int64_t *out_n_flips,
+                int32_t *flip_id, int32_t *flip_old, int32_t *flip_new) {
+    return assign_call(e, groups, n_groups, scale, min_score, dest, out_label, out_best, out_margin, out_counts, prev_label, cap, out_n_flips,
+                       flip_id, flip_old, flip_new);
+}
+
+int dppr_assign_at(dppr_engine *e, const int32_t *groups, int32_t n_groups, const double *scale, double min_score, const int32_t *ids, int32_t m,
+                   int32_t *out_label, double *out_best, int32_t *out_second_label, double *out_margin) {
+    return assign_at_call(e, groups, n_groups, scale, min_score, ids, m, out_label, out_best, out_second_label, out_margin);
 }
 
 int dppr_debug_rank_piece(dppr_engine *e, int edges) {

@@ -1139,4 +1139,195 @@ int rank_score_at_call(dppr_engine *e, Owner &o, int32_t epoch, const dppr_rank_
     return run_rank_score_at(e, v, rank_lanes(o), ep, rank_spec(spec), ids, m, out_score);
 }
 
+// ---- every vertex to its best lane, across groups (dppr_assign.hpp, dppr_assign_plan.hpp) --------------------------------------
+static_assert(AS_TEAM_MAX * 2 == GS_MAX, "the widest row of a group is one step of the widest team");
+
+// The groups of a call, looked up under the checks GET_GROUP makes, as the kernels' descriptors and the team that reads them.
+// NULL: fine; otherwise the words of the rejection.
+const char *assign_desc(dppr_engine *e, const int32_t *groups, int n_groups, AsDesc &d, int &team) {
+    int n[AS_GROUPS_MAX], max_gw = 0;
+    for (int i = 0; i < n_groups; ++i) {
+        if (groups[i] < 0 || groups[i] >= (int)e->groups.size()) return "assign: bad group";
+        n[i] = e->groups[(size_t)groups[i]].n;
+    }
+    const AsTable tb = as_table(n, n_groups);
+    if (!tb.ok) return "assign: more than DPPR_ASSIGN_CLASSES_MAX classes";
+    memset(&d, 0, sizeof(d));
+    for (int i = 0; i < n_groups; ++i) {
+        const Group &g = e->groups[(size_t)groups[i]];
+        d.g[i] = AsGroup{g.p.get(), g.gw, g.n, tb.base[i]};
+        max_gw = std::max(max_gw, g.gw);
+    }
+    d.n_groups = n_groups;
+    d.C = tb.C;
+    team = as_team(max_gw);
+    return nullptr;
+}
+
+// One of the four instantiations of a kernel template <TEAM>: f(std::integral_constant<int, TEAM>())
+template <class F> int by_team(int team, F &&f) {
+    switch (team) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 4: return f(std::integral_constant<int, 4>());
+    default: return f(std::integral_constant<int, 8>());
+    }
+}
+
+struct AsCall { // (arguments, the groups and a device destination validated by the caller)
+    AsDesc d;
+    int team;
+    const double *scale;
+    double min_score;
+    int dest;
+    int32_t *out_label;
+    double *out_best, *out_margin;
+    int64_t *out_counts;
+    const int32_t *prev;
+    int64_t cap;
+    int64_t *out_n_flips;
+    int32_t *flip_id, *flip_old, *flip_new;
+};
+
+// Labels, best, margin, counts and flips of every external id. Every buffer is in place before anything is written; the flip
+// positions are decided on the device and so is whether the fill runs: nothing is read back between the kernels; one copy brings
+// the head -- and a host destination's arrays -- back. A host destination's prev_label goes into the label section and is updated there.
+int run_assign(dppr_engine *e, const AsCall &c) {
+    if (int rc = query_begin(e, MAP_E2I)) return rc;
+    QueryWork::Assign &as = e->q.as;
+    const int V = e->V;
+    const bool host = c.dest == DPPR_DEST_HOST;
+    const int64_t capc = c.prev ? as_cap_clamped(c.cap, V) : 0;
+    const AsLayout lay = as_layout(V, capc, c.out_best != nullptr, c.out_margin != nullptr, host);
+    const AsWork wk = as_workspace(V);
+    Grow grow{e};
+    int rc = grow(as.scale, wk.scale_elems);
+    if (!rc) rc = grow(as.cnt, wk.cnt_elems);
+    if (!rc) rc = grow(as.base, wk.base_elems);
+    if (!rc) rc = grow(as.ws, wk.ws_elems);
+    if (!rc) rc = grow(as.blk, lay.total_bytes);
+    if (!rc) rc = grow(as.pin, lay.total_bytes);
+    if (rc) return rc;
+    unsigned char *blk = as.blk.get();
+    AsHead *head = reinterpret_cast<AsHead *>(blk);
+    int *d_label = host ? reinterpret_cast<int *>(blk + lay.off_label) : c.out_label;
+    double *d_best = !c.out_best ? nullptr : host ? reinterpret_cast<double *>(blk + lay.off_best) : c.out_best;
+    double *d_margin = !c.out_margin ? nullptr : host ? reinterpret_cast<double *>(blk + lay.off_margin) : c.out_margin;
+    int *d_fid = host ? reinterpret_cast<int *>(blk + lay.off_fid) : c.flip_id;
+    int *d_fold = host ? reinterpret_cast<int *>(blk + lay.off_fold) : c.flip_old;
+    int *d_fnew = host ? reinterpret_cast<int *>(blk + lay.off_fnew) : c.flip_new;
+    const int *d_prev = !c.prev ? nullptr : host ? d_label : c.prev;
+    const double *d_scale = c.scale ? as.scale.get() : nullptr;
+    if (c.scale) HIP_TRY(hipMemcpyAsync(as.scale, c.scale, sizeof(double) * (size_t)c.d.C, hipMemcpyHostToDevice, e->stream));
+    if (host && c.prev) HIP_TRY(hipMemcpyAsync(d_label, c.prev, sizeof(int32_t) * (size_t)V, hipMemcpyHostToDevice, e->stream));
+    const int tiles = (int)as_tiles(V), grid = std::min(tiles, 2048);
+    if (int rc2 = DeviceTime{e}.open()) return rc2;
+    HIP_TRY(hipMemsetAsync(head, 0, AS_HEAD_BYTES, e->stream));
+    by_team(c.team, [&](auto team) -> int {
+        hipLaunchKernelGGL((k_as_label<decltype(team)::value>), dim3(grid), dim3(AS_TILE), 0, e->stream, c.d, d_scale, c.min_score,
+                           e->d_ext2int.get(), V, d_prev, d_label, d_best, d_margin, as.cnt.get(), as.ws.get(), wk.ws_plane,
+                           reinterpret_cast<unsigned long long *>(head->counts));
+        return DPPR_OK;
+    });
+    if (d_prev) {
+        hipLaunchKernelGGL(k_as_scan, dim3(1), dim3(AS_TILE), 0, e->stream, as.cnt.get(), tiles, (long long)capc, as.base.get(), head);
+        if (capc > 0)
+            hipLaunchKernelGGL(k_as_fill, dim3(grid), dim3(AS_TILE), 0, e->stream, as.cnt.get(), as.base.get(), as.ws.get(), wk.ws_plane,
+                               tiles, head, d_fid, d_fold, d_fnew);
+    }
+    HIP_TRY(hipGetLastError());
+    if (int rc2 = fetch_block(e, as.blk, as.pin, lay.total_bytes)) return rc2; // (a device destination is complete here: any stream of the caller may read it)
+    const AsHead *h = reinterpret_cast<const AsHead *>(as.pin.get());
+    for (int i = 0; i <= c.d.C; ++i) c.out_counts[i] = h->counts[i];
+    if (c.out_n_flips) *c.out_n_flips = h->n_flips;
+    if (host) {
+        memcpy(c.out_label, as.pin + lay.off_label, sizeof(int32_t) * (size_t)V);
+        if (c.out_best) memcpy(c.out_best, as.pin + lay.off_best, sizeof(double) * (size_t)V);
+        if (c.out_margin) memcpy(c.out_margin, as.pin + lay.off_margin, sizeof(double) * (size_t)V);
+        if (capc > 0 && h->go && h->n_flips > 0) {
+            const size_t bytes = sizeof(int32_t) * (size_t)h->n_flips;
+            memcpy(c.flip_id, as.pin + lay.off_fid, bytes);
+            memcpy(c.flip_old, as.pin + lay.off_fold, bytes);
+            memcpy(c.flip_new, as.pin + lay.off_fnew, bytes);
+        }
+    }
+    return DPPR_OK;
+}
+
+// the same values at m external ids (validated by the caller like the rest, m > 0)
+int run_assign_at(dppr_engine *e, const AsDesc &d, int team, const double *scale, double min_score, const int32_t *ids, int m,
+                  int32_t *out_label, double *out_best, int32_t *out_second_label, double *out_margin) {
+    if (int rc = query_begin(e, MAP_E2I)) return rc;
+    QueryWork::Assign &as = e->q.as;
+    Grow grow{e};
+    if (int rc = grow(as.scale, as_workspace(e->V).scale_elems)) return rc;
+    if (int rc = grow(e->q.ra.buf, ra_layout(m, AS_AT_COLS, 2).total_bytes)) return rc;
+    if (scale) HIP_TRY(hipMemcpyAsync(as.scale, scale, sizeof(double) * (size_t)d.C, hipMemcpyHostToDevice, e->stream));
+    const double *d_scale = scale ? as.scale.get() : nullptr;
+    std::vector<double> val((size_t)m * AS_AT_COLS), lab((size_t)m * AS_AT_COLS);
+    const int rc = point_read(e, grow, ids, m, AS_AT_COLS, 2, val.data(), lab.data(), [&](const int *d_ids, double *d_val, double *d_lab) {
+        return by_team(team, [&](auto tm) -> int {
+            constexpr int T = decltype(tm)::value;
+            hipLaunchKernelGGL((k_as_at<T>), dim3(grid_for((int64_t)m * T, AS_TILE)), dim3(AS_TILE), 0, e->stream, d, d_scale, min_score,
+                               e->d_ext2int.get(), d_ids, m, d_val, reinterpret_cast<int *>(d_lab));
+            return DPPR_OK;
+        });
+    });
+    if (rc) return rc;
+    const int32_t *li = reinterpret_cast<const int32_t *>(lab.data());
+    for (int i = 0; i < m; ++i) {
+        out_label[i] = li[4 * (size_t)i];
+        if (out_second_label) out_second_label[i] = li[4 * (size_t)i + 1];
+        if (out_best) out_best[i] = val[2 * (size_t)i];
+        if (out_margin) out_margin[i] = val[2 * (size_t)i + 1];
+    }
+    return DPPR_OK;
+}
+
+int assign_call(dppr_engine *e, const int32_t *groups, int32_t n_groups, const double *scale, double min_score, int dest, int32_t *out_label,
+                double *out_best, double *out_margin, int64_t *out_counts, const int32_t *prev_label, int64_t cap, int64_t *out_n_flips,
+                int32_t *flip_id, int32_t *flip_old, int32_t *flip_new) {
+    if (!e) return fail(e, DPPR_ERR_INVALID, "assign: no engine");
+    if (e->broken) return fail(e, DPPR_ERR_INVALID, "engine unusable after a failed renumbering");
+    if (const AsCheck ck = as_check(groups, n_groups, min_score, dest, out_label, out_counts, cap, flip_id, flip_old, flip_new))
+        return fail(e, DPPR_ERR_INVALID, (std::string("assign: ") + as_check_text(ck)).c_str());
+    AsCall c{};
+    if (const char *why = assign_desc(e, groups, n_groups, c.d, c.team)) return fail(e, DPPR_ERR_INVALID, why);
+    if (!as_scale_ok(scale, c.d.C)) return fail(e, DPPR_ERR_INVALID, (std::string("assign: ") + as_check_text(AS_BAD_SCALE)).c_str());
+    HIP_TRY(hipSetDevice(e->device));
+    if (dest == DPPR_DEST_DEVICE) {
+        const size_t V = (size_t)e->V, capc = (size_t)as_cap_clamped(cap, e->V);
+        bool ok = dev_range_ok(e, out_label, sizeof(int32_t) * V, sizeof(int32_t)) &&
+                  (!out_best || dev_range_ok(e, out_best, sizeof(double) * V, sizeof(double))) &&
+                  (!out_margin || dev_range_ok(e, out_margin, sizeof(double) * V, sizeof(double))) &&
+                  (!prev_label || dev_range_ok(e, prev_label, sizeof(int32_t) * V, sizeof(int32_t)));
+        if (ok && capc > 0)
+            ok = dev_range_ok(e, flip_id, sizeof(int32_t) * capc, sizeof(int32_t)) && dev_range_ok(e, flip_old, sizeof(int32_t) * capc, sizeof(int32_t)) &&
+                 dev_range_ok(e, flip_new, sizeof(int32_t) * capc, sizeof(int32_t));
+        if (!ok)
+            return fail(e, DPPR_ERR_INVALID, "assign: label / best / margin / prev_label / flip lists must be aligned device memory of the engine's device, V (the lists: cap) entries inside one allocation");
+    }
+    c.scale = scale, c.min_score = min_score, c.dest = dest;
+    c.out_label = out_label, c.out_best = out_best, c.out_margin = out_margin, c.out_counts = out_counts;
+    c.prev = prev_label, c.cap = cap, c.out_n_flips = out_n_flips;
+    c.flip_id = flip_id, c.flip_old = flip_old, c.flip_new = flip_new;
+    std::lock_guard<std::mutex> map_lk(e->map_mu); // (as dppr_read: one state of the id space for the whole query)
+    return run_assign(e, c);
+}
+
+int assign_at_call(dppr_engine *e, const int32_t *groups, int32_t n_groups, const double *scale, double min_score, const int32_t *ids, int32_t m,
+                   int32_t *out_label, double *out_best, int32_t *out_second_label, double *out_margin) {
+    if (!e) return fail(e, DPPR_ERR_INVALID, "assign_at: no engine");
+    if (e->broken) return fail(e, DPPR_ERR_INVALID, "engine unusable after a failed renumbering");
+    if (const AsCheck ck = as_at_check(groups, n_groups, min_score, ids, m, e->V, out_label))
+        return fail(e, DPPR_ERR_INVALID, (std::string("assign_at: ") + as_check_text(ck)).c_str());
+    AsDesc d;
+    int team = 1;
+    if (const char *why = assign_desc(e, groups, n_groups, d, team)) return fail(e, DPPR_ERR_INVALID, why);
+    if (!as_scale_ok(scale, d.C)) return fail(e, DPPR_ERR_INVALID, (std::string("assign_at: ") + as_check_text(AS_BAD_SCALE)).c_str());
+    if (m == 0) return DPPR_OK;
+    std::lock_guard<std::mutex> map_lk(e->map_mu);
+    return run_assign_at(e, d, team, scale, min_score, ids, m, out_label, out_best, out_second_label, out_margin);
+}
+
 } // namespace

@@ -240,6 +240,13 @@ struct QueryWork {
         DevBuf<unsigned long long> list;          // the piece list of the call (rk_piece_cap)
         std::vector<unsigned long long> items;    // ... as the host builds it (kept for its capacity)
     } rk;
+    struct Assign { // every vertex to its best lane across groups (dppr_assign.hpp, dppr_assign_plan.hpp); the block grows with a host destination
+        DevBuf<double> scale; // [256] the scales of the call
+        DevBuf<int> cnt;      // [tiles] flips per tile
+        DevBuf<int> base;     // [tiles] first output position of a tile's flips
+        DevBuf<int> ws;       // [3][tiles x 256] id | old | new of every tile's flips, compacted inside the tile
+        DevBuf<unsigned char> blk; PinBuf<unsigned char> pin; // head (n_flips, go, counts), then label / best / margin / flips of a host destination: device / pinned host
+    } as;
 };
 
 } // namespace

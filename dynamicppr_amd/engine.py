@@ -72,6 +72,7 @@ EXPORTS = [
     "dppr_subgraph", "dppr_group_subgraph", "dppr_debug_subgraph_wave_max",
     "dppr_add_target_group", "dppr_group_replace_target", "dppr_group_targets",
     "dppr_topk_ranked", "dppr_group_topk_ranked", "dppr_rank_score_at", "dppr_group_rank_score_at", "dppr_debug_rank_piece",
+    "dppr_assign", "dppr_assign_at",
 ]
 
 DEST_HOST, DEST_DEVICE = 0, 1
@@ -89,6 +90,7 @@ FACTOR_NONE, FACTOR_DEV, FACTOR_DEG, FACTOR_INV_DEG = 0, 1, 2, 3
 MASK_NONE, MASK_ALLOW, MASK_DENY = 0, 1, 2
 EXCLUDE_SEEDS, EXCLUDE_IN_NEIGHBOURS, EXCLUDE_OUT_NEIGHBOURS = 1, 2, 4
 RANK_PIECE = 512
+ASSIGN_GROUPS_MAX, ASSIGN_CLASSES_MAX = 16, 256
 
 
 class RankSpec(C.Structure):
@@ -233,6 +235,8 @@ def lib():
     L.dppr_rank_score_at.argtypes = [vp, C.c_int32, C.c_int32, vp, ip, C.c_int32, dp]
     L.dppr_group_rank_score_at.argtypes = [vp, C.c_int32, C.c_int32, vp, ip, C.c_int32, dp]
     L.dppr_debug_rank_piece.argtypes = [vp, C.c_int]
+    L.dppr_assign.argtypes = [vp, ip, C.c_int32, dp, C.c_double, C.c_int, vp, vp, vp, i64p, vp, C.c_int64, i64p, vp, vp, vp]
+    L.dppr_assign_at.argtypes = [vp, ip, C.c_int32, dp, C.c_double, ip, C.c_int32, ip, dp, ip, dp]
     for name in EXPORTS:
         if name not in ("dppr_strerror", "dppr_last_error", "dppr_destroy", "dppr_build_id", "dppr_heartbeat"):
             getattr(L, name).restype = C.c_int
@@ -724,6 +728,81 @@ class Engine:
         """Test hook (dppr_debug_rank_piece): the rows of the seeds are marked in pieces of at most `edges` entries, one wave each;
         1 .. 512, default 512. The results do not depend on it."""
         self._ck(self._L.dppr_debug_rank_piece(self._h, int(edges)), "debug_rank_piece")
+
+    # ---- every vertex to its best lane, across groups ----
+    def _assign_classes(self, groups, scale, what):
+        """The groups of a call as an int32 array, and its scales as a contiguous [C] array (or None), checked against the class count."""
+        g = np.ascontiguousarray(groups, dtype=np.int32).ravel()
+        n_classes = sum(self._group_n.get(int(x), 0) for x in g)
+        sc = None
+        if scale is not None:
+            sc = np.ascontiguousarray(scale, dtype=np.float64).ravel()
+            if len(sc) != n_classes:
+                raise DpprError(f"{what}: scale must hold one entry per class ({n_classes}), got {len(sc)}")
+        return g, n_classes, sc
+
+    def assign(self, groups, scale=None, min_score=0.0, prev=None, cap=None, best=True, margin=True, inplace=False, lists=None):
+        """dppr_assign with a host destination. The classes are the lanes of `groups` (group handles of this engine, in call
+        order); every external id gets the smallest class of largest score = scale[c] * p_c above min_score, or -1. Returns a dict:
+        label [V] int32, best / margin [V] (None where not asked for), counts [C + 1] int64 (the last: unassigned), n_flips and
+        flips = (id, old, new) against `prev` ([V] int32), ascending by id; flips is None without prev or when n_flips > cap
+        (cap defaults to V: everything fits). inplace: the labels are written into `prev` itself (a contiguous int32 array).
+        lists: three preallocated int32 arrays of at least cap entries to take the flips."""
+        g, n_classes, sc = self._assign_classes(groups, scale, "assign")
+        V = self.V
+        if prev is not None:
+            if inplace and not (isinstance(prev, np.ndarray) and prev.dtype == np.int32 and prev.flags.c_contiguous):
+                raise DpprError("assign: an in-place prev must be a contiguous int32 array")
+            prev = np.ascontiguousarray(prev, dtype=np.int32)
+            if prev.shape != (V,):
+                raise DpprError(f"assign: prev must hold V = {V} labels, got shape {prev.shape}")
+        label = prev if (inplace and prev is not None) else np.empty(V, dtype=np.int32)
+        b = np.empty(V, dtype=np.float64) if best else None
+        mg = np.empty(V, dtype=np.float64) if margin else None
+        counts = np.zeros(n_classes + 1, dtype=np.int64)
+        cap = 0 if prev is None else V if cap is None else int(cap)
+        if lists is None and cap > 0:
+            lists = tuple(np.full(min(cap, V), -1, dtype=np.int32) for _ in range(3))
+        fl = lists if cap > 0 else (None, None, None)
+        nf = C.c_int64(0)
+        dp, i64p = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+        self._ck(self._L.dppr_assign(self._h, g.ctypes.data_as(C.POINTER(C.c_int32)), len(g), sc.ctypes.data_as(dp) if sc is not None else None,
+                                     float(min_score), DEST_HOST, label.ctypes.data, b.ctypes.data if best else None,
+                                     mg.ctypes.data if margin else None, counts.ctypes.data_as(i64p),
+                                     prev.ctypes.data if prev is not None else None, cap, C.byref(nf),
+                                     *(a.ctypes.data if a is not None else None for a in fl)), "assign")
+        n = int(nf.value)
+        flips = tuple(a[:n].copy() for a in fl) if prev is not None and cap > 0 and n <= cap else None
+        if prev is not None and cap == 0 and n == 0:
+            flips = tuple(np.empty(0, dtype=np.int32) for _ in range(3))
+        return {"label": label, "best": b, "margin": mg, "counts": counts, "n_flips": n, "flips": flips}
+
+    def assign_dev(self, groups, label_ptr, scale=None, min_score=0.0, best_ptr=None, margin_ptr=None, prev_ptr=None, cap=0,
+                   flip_ptrs=(None, None, None)):
+        """dppr_assign into device memory at the given raw addresses ([V] each; prev_ptr may equal label_ptr; the three flip
+        lists hold cap entries): (counts [C + 1], n_flips) on the host. Nothing is written to the lists if n_flips > cap."""
+        g, n_classes, sc = self._assign_classes(groups, scale, "assign_dev")
+        counts = np.zeros(n_classes + 1, dtype=np.int64)
+        nf = C.c_int64(0)
+        dp, i64p = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+        self._ck(self._L.dppr_assign(self._h, g.ctypes.data_as(C.POINTER(C.c_int32)), len(g), sc.ctypes.data_as(dp) if sc is not None else None,
+                                     float(min_score), DEST_DEVICE, label_ptr or None, best_ptr or None, margin_ptr or None,
+                                     counts.ctypes.data_as(i64p), prev_ptr or None, int(cap), C.byref(nf),
+                                     *(a or None for a in flip_ptrs)), "assign_dev")
+        return counts, int(nf.value)
+
+    def assign_at(self, groups, ids, scale=None, min_score=0.0):
+        """dppr_assign_at: (label, best, second_label, margin) at the given external ids, arrays of len(ids)."""
+        g, _, sc = self._assign_classes(groups, scale, "assign_at")
+        a, pa = _i32(ids)
+        m = len(a)
+        label, second = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.int32)
+        b, mg = np.empty(m, dtype=np.float64), np.empty(m, dtype=np.float64)
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        self._ck(self._L.dppr_assign_at(self._h, g.ctypes.data_as(ip), len(g), sc.ctypes.data_as(dp) if sc is not None else None,
+                                        float(min_score), pa, m, label.ctypes.data_as(ip), b.ctypes.data_as(dp), second.ctypes.data_as(ip),
+                                        mg.ctypes.data_as(dp)), "assign_at")
+        return label, b, second, mg
 
     # ---- what a batch moved: marks and the top k of |p - mark| ----
     def mark(self, slot):

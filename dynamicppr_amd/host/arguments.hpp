@@ -192,6 +192,12 @@ inline void PrintUsage() {
               << "            vertices of largest pagerank induce (1 <= K <= 8192): subgraph <source> vertices <L> edges <stored edges among them>;\n"
               << "            with --subgraph-out also write it to <file> (the last batch's; with -g N one file per device, <file>.<device>):\n"
               << "            v <source> <position> <vertex> <pagerank> per vertex, e <source> <tail position> <head position> per edge\n"
+              << "--assign [--assign-min <S>] [--assign-out <file>]: one class per source (or per line of --target-sets), in source order;\n"
+              << "            after every batch print the label propagation over them -- every vertex goes to the class of its largest\n"
+              << "            pagerank > S (S >= 0, default 0; ties to the first class; none: unassigned) --, flips counted against the batch before\n"
+              << "            (the first against all unassigned): assign <batch> classes=<C> unassigned=<n> flips=<n> counts=c0,c1,...\n"
+              << "            with --assign-out also write the last labels to <file>, raw int32 [V], -1 = unassigned. Needs the sources in groups\n"
+              << "            on ONE device (2 to 256 sources or --target-sets; not with -g N > 1, --no-groups, --split)\n"
               << "--validate: residual bound + power-iteration check after every solve\n"
               << "--split: drive each batch through IncrementalBatchUpdate/ExecuteMainLoop(0)/(1)\n"
               << "--sync: synchronous (deterministic) push schedule\n"
@@ -245,6 +251,8 @@ inline void ArgumentsChecker() {
     if (gTopKWeightsGiven && (gTopK == 0 || gTopKWeights.empty())) ok = false; // (the count is checked against the sources in main)
     if (gRankGiven && (gTopK == 0 || gRankFactor < 0 || gRankExclude < 0 || gSplitInterface)) ok = false;
     if (!gTargetSetsFile.empty() && (gTargetSetsBad || gTargetSets.empty() || !gSourcesFile.empty() || gSplitInterface || gNoGroups || gTopKWeightsGiven)) ok = false;
+    if ((gAssignMinGiven || !gAssignOut.empty()) && !gAssign) ok = false;
+    if (gAssign && (!(gAssignMin >= 0.0) || gSplitInterface || gNoGroups)) ok = false; // (one device, groups in use: checked against the sources in main)
     if (!ok) {
         std::cout << "invalid arguments" << std::endl;
         PrintUsage();
@@ -313,6 +321,10 @@ inline void ArgumentsParser(int argc, char **argv) {
     gSubgraphGiven = find(argc, argv, "--subgraph") != nullptr;
     gSubgraphK = as_int(argc, argv, "--subgraph", 0);
     if (const char *f = find(argc, argv, "--subgraph-out")) gSubgraphOut = f;
+    gAssign = has(argc, argv, "--assign");
+    gAssignMinGiven = find(argc, argv, "--assign-min") != nullptr;
+    gAssignMin = as_double(argc, argv, "--assign-min", 0.0);
+    if (const char *f = find(argc, argv, "--assign-out")) gAssignOut = f;
     gValidate = has(argc, argv, "--validate");
     gSplitInterface = has(argc, argv, "--split");
     gSchedule = has(argc, argv, "--sync") ? 1 : 0;

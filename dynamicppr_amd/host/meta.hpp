@@ -74,6 +74,10 @@ inline bool gClusterOptsGiven = false; //   --cluster-min or --cluster-min-size 
 inline int gSubgraphK = 0;            // --subgraph K : after every batch print subgraph <source> vertices <L> edges <m>, the top-K order and the stored edges among it (0: off)
 inline bool gSubgraphGiven = false;
 inline std::string gSubgraphOut;      // --subgraph-out FILE : ... and write the CSR of the last batch, text lines `v source position id pagerank` and `e source tail head`
+inline bool gAssign = false;          // --assign : after every batch print assign <batch> classes=<C> unassigned=<n> flips=<n> counts=c0,c1,.. (dppr_assign over this device's groups)
+inline double gAssignMin = 0.0;       // --assign-min S : a class labels a vertex only with a score > S
+inline bool gAssignMinGiven = false;
+inline std::string gAssignOut;        // --assign-out FILE : ... and write the last labels, raw int32 [V]
 inline bool gValidate = false;        // --validate : the reference's -DVALIDATE checks at run time
 inline bool gShareDevice = false;     // --share-device (or DPPR_DEVICE_ALIAS=1): the -g N device threads share the devices that exist (d % count)
 inline bool gPushOnly = false;        // --push-only : no pull sweeps (the ablation of the -o variants times their push mechanisms)

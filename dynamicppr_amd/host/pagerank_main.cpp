@@ -54,6 +54,13 @@ int main(int argc, char *argv[]) {
         return -1;
     }
 
+    // --assign labels every vertex over the lanes of ONE engine's groups: one device, and the lanes in groups (of up to 16, at most 256)
+    if (gAssign && (ngpu != 1 || (gTargetSets.empty() && sources.size() < 2) || sources.size() > (size_t)DPPR_ASSIGN_CLASSES_MAX)) {
+        std::cout << "invalid arguments" << std::endl;
+        PrintUsage();
+        return -1;
+    }
+
     // Every device thread streams the same file through its own SlidingGraphVec (a position in
     // a shared read-only mapping of the page cache) and owns one engine.
     // --share-device / DPPR_DEVICE_ALIAS=1: the N device threads (each with its own engine, stream and graph replica) run on the
@@ -216,6 +223,10 @@ int main(int argc, char *argv[]) {
                 std::cout << line << "\n";
             }
         std::cout << std::flush;
+    }
+    if (!gAssignOut.empty() && !drivers[0]->WriteAssign(gAssignOut)) {
+        std::cout << "cannot write " << gAssignOut << std::endl;
+        return -1;
     }
     if (!gDumpPath.empty())
         for (int d = 0; d < ngpu; ++d) drivers[(size_t)d]->Dump(gDumpPath + (ngpu > 1 ? "." + std::to_string(d) : ""));

@@ -99,7 +99,7 @@ public:
         // two or three sources on a large window: one after the other on the single-source path (binned sweeps) beats a group, whose
         // sweep costs about the same for 2 as for 8 sources (friendster stand-in, 3 sources: 422 ms per batch as a group, 3 x 100 in series)
         // (--topk-weights asks for the group)
-        if (use_groups && source_vertex_ids.size() <= 3 && graph->sliding_window_size >= 4000000 && !gTopKWeightsGiven && target_lanes.empty()) use_groups = false;
+        if (use_groups && source_vertex_ids.size() <= 3 && graph->sliding_window_size >= 4000000 && !gTopKWeightsGiven && !gAssign && target_lanes.empty()) use_groups = false;
         if (gProfile) DPPR_CHECK(engine, dppr_set_profiling(engine, 1));
         if (!quiet_) std::cout << "start..." << std::endl;
         if (use_groups) {
@@ -268,6 +268,7 @@ public:
                 DPPR_CHECK(engine, ahead_rc);
             }
             if (gChangesK > 0) PrintChanges(stream_batch_count);
+            if (gAssign) PrintAssign(stream_batch_count);
             if (!gRefineIds.empty()) PrintRefined(-1);
             if (gClusterK > 0) PrintClusters(-1);
             if (gSubgraphK > 0) PrintSubgraphs(-1);
@@ -363,6 +364,7 @@ public:
                 build_beside_ms += nxt.ms;
             }
             if (gChangesK > 0) PrintChanges(stream_batch_count);
+            if (gAssign) PrintAssign(stream_batch_count);
             if (!gRefineIds.empty()) PrintRefined(epoch); // (the epoch the states stand on: the helper may have built the next one)
             if (gClusterK > 0) PrintClusters(epoch);
             if (gSubgraphK > 0) PrintSubgraphs(epoch);
@@ -627,6 +629,31 @@ public:
         std::cout << out << std::flush;
     }
 
+    // --assign: after a batch, every vertex to the lane that holds it best over ALL groups of this device (dppr_assign, host
+    // destination, no scale), the flips counted against the labels of the batch before, which the host keeps and passes back in
+    // place (the first batch: against all -1). Outside the timed region, one line per batch.
+    void PrintAssign(size_t batch) {
+        const size_t V = (size_t)graph->vertex_count, n_classes = source_vertex_ids.size();
+        if (assign_label.size() != V) assign_label.assign(V, -1);
+        std::vector<int64_t> counts(n_classes + 1, 0);
+        int64_t flips = 0;
+        DPPR_CHECK(engine, dppr_assign(engine, groups.data(), (int32_t)groups.size(), nullptr, gAssignMin, DPPR_DEST_HOST, assign_label.data(), nullptr,
+                                       nullptr, counts.data(), assign_label.data(), 0, &flips, nullptr, nullptr, nullptr));
+        std::string out = "assign " + std::to_string(batch) + " classes=" + std::to_string(n_classes) + " unassigned=" + std::to_string(counts[n_classes]) +
+                          " flips=" + std::to_string(flips) + " counts=";
+        for (size_t c = 0; c < n_classes; ++c) out += (c ? "," : "") + std::to_string(counts[c]);
+        progress++;
+        std::cout << out << std::endl;
+    }
+    // --assign-out: the labels of the last batch, raw int32 [V] (all -1 if no batch ran)
+    bool WriteAssign(const std::string &path) {
+        if (assign_label.size() != (size_t)graph->vertex_count) assign_label.assign((size_t)graph->vertex_count, -1);
+        std::FILE *f = std::fopen(path.c_str(), "wb");
+        if (!f) return false;
+        const bool ok = std::fwrite(assign_label.data(), sizeof(int32_t), assign_label.size(), f) == assign_label.size();
+        return std::fclose(f) == 0 && ok;
+    }
+
     // --refine: after a batch, the pagerank of every listed vertex towards every source of this device refined by gWalks forward
     // walks over `epoch` (dppr_refine_at / dppr_group_refine_at: one set of walks serves all sources of a group), with the
     // standard error a caller derives from sumsq. Outside the timed region, printed as one block like --changes.
@@ -767,6 +794,7 @@ public:
     std::vector<size_t> target_lanes; // --target-sets: the lines of gTargetSets this device tracks, in the order of source_vertex_ids (empty: sources)
     std::vector<int32_t> slots;  // one per source (single-source mode)
     static constexpr size_t kGroupMax = 16; // sources per group (dppr_add_source_group)
+    std::vector<int32_t> assign_label; // --assign: the labels of the batch before, by external id
     std::vector<int32_t> groups; // one per 16 sources (group mode: several sources per device)
     bool use_groups = false;
     std::vector<float> ppr_time; // ms per source (single mode) or per group, timed region only

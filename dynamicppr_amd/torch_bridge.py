@@ -1,5 +1,6 @@
 """The engine's state as torch tensors on the engine's device: the device-side exports of include/dppr.h
-(dppr_group_export_sparse / dppr_group_export_dense_dev, dppr_group_subgraph) written straight into memory that torch allocated.
+(dppr_group_export_sparse / dppr_group_export_dense_dev, dppr_group_subgraph, dppr_assign) written straight into memory that torch
+allocated.
 
 The engine binding itself (``engine.py``) stays torch-free: nothing there imports torch, and importing this module puts no
 torch into it.
@@ -221,3 +222,34 @@ def group_topk_ranked(engine, gid, k, min_score=0.0, factor=None, allow=None, de
     spec = _eng.Engine.rank_spec(kind, g_ptr, g_dtype, mode, m_ptr, flags)
     torch.cuda.synchronize(_device(engine))   # (the tensors are torch's; nothing of torch's is in flight on them when the engine reads)
     return engine.group_topk_ranked(gid, k, min_score, spec, epoch)
+
+
+def assign(engine, groups, scale=None, min_score=0.0, prev=None, want=("best", "margin")):
+    """dppr_assign over torch tensors on the engine's device: every external id gets the smallest class of largest score =
+    scale[c] * p_c above min_score, or -1; the classes are the lanes of `groups` (handles of this engine) in call order. Returns a
+    dict: label [V] int32, best / margin [V] float64 (those named in `want`, else None), counts [C + 1] int64 on the host (the last:
+    unassigned), n_flips, and flips = (id, old, new) int32 tensors against `prev`, ascending by id (None without prev).
+    prev: an int32 tensor of V labels on the engine's device, contiguous; it is UPDATED IN PLACE and returned as label. scale: a
+    host sequence of C finite values >= 0, or None. Anything else raises ValueError before the engine is called."""
+    dev = _device(engine)
+    unknown = set(want) - {"best", "margin"}
+    if unknown:
+        raise ValueError(f"assign: want holds any of 'best', 'margin', not {sorted(unknown)}")
+    V = engine.V
+    if prev is not None:
+        if not isinstance(prev, torch.Tensor) or prev.layout != torch.strided or prev.dtype != torch.int32:
+            raise ValueError("assign: prev is a dense int32 tensor")
+        if prev.device != dev:
+            raise ValueError(f"assign: prev must be on the engine's device {dev}, not {prev.device}")
+        if prev.dim() != 1 or prev.numel() != V or not prev.is_contiguous():
+            raise ValueError(f"assign: prev holds V = {V} labels, contiguous, not {tuple(prev.shape)}")
+    label = prev if prev is not None else torch.empty(V, dtype=torch.int32, device=dev)
+    best = torch.empty(V, dtype=torch.float64, device=dev) if "best" in want else None
+    margin = torch.empty(V, dtype=torch.float64, device=dev) if "margin" in want else None
+    lists = tuple(torch.empty(V, dtype=torch.int32, device=dev) for _ in range(3)) if prev is not None else (None, None, None)
+    torch.cuda.synchronize(dev)   # (the tensors are torch's; nothing of torch's is in flight on them when the engine reads and writes)
+    counts, n_flips = engine.assign_dev(groups, label.data_ptr(), scale, min_score, best.data_ptr() if best is not None else None,
+                                        margin.data_ptr() if margin is not None else None, label.data_ptr() if prev is not None else None,
+                                        V if prev is not None else 0, tuple(t.data_ptr() if t is not None else None for t in lists))
+    flips = tuple(t[:n_flips] for t in lists) if prev is not None else None
+    return {"label": label, "best": best, "margin": margin, "counts": counts, "n_flips": n_flips, "flips": flips}

@@ -935,6 +935,63 @@ int dppr_group_rank_score_at(dppr_engine *e, int32_t group, int32_t epoch, const
                              double *out_score /* [m][n] */);
 int dppr_debug_rank_piece(dppr_engine *e, int edges);
 
+/* ---- every vertex to its best lane, across groups (backward-compatible additions, ABI 6) ----
+ * The queries above answer per lane. With one lane per class -- sources or target sets -- the question per VERTEX is which lane
+ * holds it best: label propagation on a live stream. dppr_assign reduces over the lane axis in one pass over the states, across
+ * groups, and reports what a batch changed against a previous labelling (what dppr_changes is for p).
+ *
+ * CLASSES are the lanes of the n_groups groups of ONE engine named in `groups`, concatenated in call order: n_groups in
+ * [1, DPPR_ASSIGN_GROUPS_MAX], C = sum of the groups' lane counts <= DPPR_ASSIGN_CLASSES_MAX. A group may be named twice; its
+ * lanes are then two sets of classes. Source lanes and set lanes are alike.
+ * For every external id v in [0, V):
+ *     score_c[v] = scale[c] * p_c[v]     ONE multiplication (nothing fused); p_c[v] is exactly what dppr_group_read returns, 0.0
+ *                                        for a vertex without an internal id. scale: HOST memory, [C], every entry finite and
+ *                                        >= 0. scale == NULL: the scores are the stored p bit for bit, no multiplication.
+ *     label[v]   the SMALLEST class whose score is the maximum of the scores that are > min_score (min_score >= 0, not NaN); -1
+ *                if no score is. A negative score, +-0.0 and a class scaled by 0 never win.
+ *     best[v]    score_label[v].
+ *     second[v]  starts at +0.0 and is replaced only by a strictly greater score of a class other than label[v], classes taken in
+ *                ascending order (so the class that set it is the smallest of those that hold it).
+ *     margin[v]  best[v] - second[v], ONE subtraction.
+ *     Where label[v] = -1: best[v] = margin[v] = +0.0 (no class is left out of second, which dppr_assign_at still reports).
+ *     out_counts HOST memory, int64 [C + 1]: counts[c] = vertices labelled c, counts[C] = vertices labelled -1.
+ *     FLIPS      with prev_label given ([V] int32, where `dest` says): the ids with prev_label[v] != label[v], in ascending id
+ *                order, as three int32 arrays flip_id / flip_old / flip_new. *out_n_flips (HOST, may be NULL) is always the TRUE
+ *                number of flips (0 without prev_label). The lists are written only if n_flips <= cap; otherwise NOTHING is
+ *                written to them and the call is still DPPR_OK: the capacity rule of dppr_export_sparse. cap = 0 with NULL lists
+ *                counts only. prev_label may BE out_label: an update in place (every element is read by the thread that then
+ *                writes it). Arrays that overlap in any other way are not supported.
+ * No output position comes from an atomic: the result is a function of the states alone, whatever the grid or the scheduling.
+ * dest (DPPR_DEST_HOST / DPPR_DEST_DEVICE) governs every [V] array (out_label, out_best, out_margin -- the latter two may be NULL --,
+ * prev_label) and the flip lists; counts and n_flips are always host memory. For DPPR_DEST_DEVICE the call returns after the solver
+ * stream has finished: any stream of the caller may read the arrays.
+ *
+ * dppr_assign_at: the same values at m caller-given external ids (duplicates allowed), host memory, plus out_second_label: the
+ * class that set second, or -1. out_best / out_second_label / out_margin may be NULL. m == 0 is a valid no-op.
+ *
+ * Rejected with DPPR_ERR_INVALID before any device work, nothing written: a bad handle or group; n_groups out of range or a NULL
+ * groups; more than DPPR_ASSIGN_CLASSES_MAX classes; a scale that is not finite or is negative; min_score negative or NaN; a dest
+ * that is neither; a NULL out_label or out_counts; cap < 0; cap > 0 with a NULL list; for DPPR_DEST_DEVICE an array that is not
+ * device memory of the ENGINE'S device, is not aligned to its element size, or whose V (the lists: min(cap, V)) entries do not lie
+ * inside one allocation; for dppr_assign_at m < 0, a NULL ids with m > 0, an id outside [0, V), a NULL out_label.
+ * Threading and stream as dppr_topk: the id-map lock of dppr_read for the whole call (safe beside dppr_slide_concurrent), the
+ * solver stream, the live and the parked zone, any state (converged or not); needs no resident epoch; never part of the update
+ * path or of a timed region. Work space: 12 bytes per external id rounded up to tiles of 256, 8 bytes per tile, 2 KiB of scales
+ * and a block of 2072 bytes -- for a host destination plus the arrays asked for --, with its pinned twin; all of it is the
+ * engine's, obtained before anything is written, grown on demand and released with the engine: after DPPR_ERR_NOMEM the states
+ * and the engine are as before. With dppr_set_profiling on, dppr_debug_query_ms reports the device time of the last of these
+ * calls, first to last kernel.
+ * OUT OF SCOPE: single-source slots (a group of one source serves); classes spread over several engines. */
+#define DPPR_ASSIGN_GROUPS_MAX  16
+#define DPPR_ASSIGN_CLASSES_MAX 256
+int dppr_assign(dppr_engine *e, const int32_t *groups, int32_t n_groups, const double *scale /* [C], NULL ok */, double min_score, int dest,
+                int32_t *out_label /* [V] */, double *out_best /* [V], NULL ok */, double *out_margin /* [V], NULL ok */,
+                int64_t *out_counts /* host [C + 1] */, const int32_t *prev_label /* [V], NULL ok */, int64_t cap,
+                int64_t *out_n_flips /* host */, int32_t *flip_id, int32_t *flip_old, int32_t *flip_new);
+int dppr_assign_at(dppr_engine *e, const int32_t *groups, int32_t n_groups, const double *scale, double min_score, const int32_t *ids,
+                   int32_t m, int32_t *out_label /* [m] */, double *out_best /* [m] */, int32_t *out_second_label /* [m] */,
+                   double *out_margin /* [m] */);
+
 /* Windows whose sweep groups are all resident at once run a frontier loop of a source group as
  * multi-sweep launches (grid barrier between sweeps, row tables kept in LDS; dppr_multi.hpp). on by
  * default; 0 = one launch per sweep everywhere. The roll-call / time-out rules are those of
