@@ -53,6 +53,7 @@
 #include "dppr_subgraph.hpp"
 #include "dppr_rank.hpp"
 #include "dppr_assign.hpp"
+#include "dppr_position.hpp"
 
 using namespace dppr;
 
@@ -1618,6 +1619,25 @@ int dppr_assign_at(dppr_engine *e, const int32_t *groups, int32_t n_groups, cons
 int dppr_debug_rank_piece(dppr_engine *e, int edges) {
     if (!e || !rank_piece_ok(edges)) return fail(e, DPPR_ERR_INVALID, "debug_rank_piece: 1 .. 512 entries of a row per wave");
     e->rk_piece = edges;
+    return DPPR_OK;
+}
+
+int dppr_position_at(dppr_engine *e, int32_t slot, int32_t epoch, const dppr_rank_spec_t *spec, double min_score, const int32_t *ids, int32_t m,
+                     int32_t *out_pos, int32_t *out_count) {
+    GET_SLOT(e, slot);
+    return position_call(e, s, epoch, spec, min_score, ids, m, out_pos, out_count);
+}
+
+int dppr_group_position_at(dppr_engine *e, int32_t group, int32_t epoch, const dppr_rank_spec_t *spec, double min_score, const int32_t *ids,
+                           int32_t m, int32_t *out_pos, int32_t *out_counts) {
+    GET_GROUP(e, group);
+    return position_call(e, g, epoch, spec, min_score, ids, m, out_pos, out_counts);
+}
+
+int dppr_debug_position_tile(dppr_engine *e, int queries) {
+    if (!e || !position_tile_ok(queries))
+        return fail(e, DPPR_ERR_INVALID, "debug_position_tile: 1 .. 4096 queries of a lane's order per workgroup and pass, 0: the plan's choice");
+    e->pos_tile = queries;
     return DPPR_OK;
 }
 

@@ -1139,6 +1139,93 @@ int rank_score_at_call(dppr_engine *e, Owner &o, int32_t epoch, const dppr_rank_
     return run_rank_score_at(e, v, rank_lanes(o), ep, rank_spec(spec), ids, m, out_score);
 }
 
+// ---- positions of given vertices in a lane's order (dppr_position.hpp, dppr_position_plan.hpp) -----------------------------------
+// the ids and the query scores (the buffer of the point reads), keys and places, slots, the block and its pinned twin: in place
+// before the first kernel
+int position_workspace(dppr_engine *e, Grow &grow, int n, int m) {
+    QueryWork::Position &ps = e->q.pos;
+    if (!ps.lds_set) { // (a lane's 4096 queries take 64 bytes more than the 64 KiB a kernel has without asking)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_pos_count), hipFuncAttributeMaxDynamicSharedMemorySize, (int)POS_LDS_MAX));
+        ps.lds_set = true;
+    }
+    const PosWork w = pos_work(n, m);
+    const size_t blk = pos_layout(n, m).total_bytes;
+    int rc = grow(e->q.ra.buf, ra_layout(m, n, 1).total_bytes);
+    if (!rc) rc = grow(ps.keys, std::max<size_t>(w.key_bytes, 1));
+    if (!rc) rc = grow(ps.slots, w.slot_elems);
+    if (!rc) rc = grow(ps.blk, blk);
+    if (!rc) rc = grow(ps.pin, blk);
+    return rc;
+}
+
+// Positions of m external ids in every lane's order by the spec's score, and every lane's count of qualifying vertices (arguments,
+// the spec's device pointers and the epoch validated by the caller; m == 0: the counts alone). Every buffer is in place before the
+// first kernel, every stage is enqueued before the one copy back: the marking and the scratch state of run_topk_ranked, the scores
+// at the ids of run_rank_score_at, the order of the queries, the count pass, the sums.
+int run_position(dppr_engine *e, const StateView &v, const RkLanes &l, const Epoch *ep, const RkSpec &sp, double min_score, const int32_t *ids,
+                 int m, int32_t *out_pos, int32_t *out_counts) {
+    if (int rc = query_begin(e, MAP_E2I | MAP_I2E)) return rc;
+    QueryWork::Scratch &sc = e->q.sc;
+    QueryWork::Position &ps = e->q.pos;
+    const int n = v.n;
+    const TkState st = tk_state(e, v.p, v.p, v.gw, n);
+    Grow grow{e};
+    if (int rc = scratch_workspace(e, grow, (size_t)st.rows, n, 1)) return rc;
+    if (int rc = rank_mark_workspace(e, grow, l, sp, ep)) return rc;
+    if (int rc = position_workspace(e, grow, n, m)) return rc;
+    const RkGraph g = rank_graph(e, ep);
+    const RkRule rule = rank_rule(sp);
+    const PosShape shape = pos_shape(n, m, e->pos_tile);
+    const PosWork w = pos_work(n, m);
+    const PosLayout lay = pos_layout(n, m);
+    const RaLayout ra = ra_layout(m, n, 1);
+    int *d_ids = reinterpret_cast<int *>(e->q.ra.buf + ra.off_ids);
+    double *d_qs = reinterpret_cast<double *>(e->q.ra.buf + ra.off_a);
+    unsigned long long *d_key = reinterpret_cast<unsigned long long *>(ps.keys + w.off_key);
+    int *d_place = reinterpret_cast<int *>(ps.keys + w.off_place);
+    int *res_cnt = reinterpret_cast<int *>(ps.blk + lay.off_cnt), *res_pos = reinterpret_cast<int *>(ps.blk + lay.off_pos);
+    if (m > 0) HIP_TRY(hipMemcpyAsync(d_ids, ids, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, e->stream));
+    if (int rc = DeviceTime{e}.open()) return rc;
+    const unsigned *excl = nullptr;
+    if (int rc = rank_mark_enqueue(e, l, sp, g, &excl)) return rc;
+    HIP_TRY(hipMemsetAsync(ps.slots, 0, sizeof(unsigned) * w.slot_elems, e->stream));
+    by_factor(sp, [&](auto kind, auto elem) -> int {
+        using T = decltype(elem);
+        hipLaunchKernelGGL((k_rk_scores<decltype(kind)::value, T>), dim3(tile_grid(st.rows)), dim3(TK_TILE_BLOCK), 0, e->stream, st,
+                           e->d_int2ext.get(), excl, rule, g, sc.a.get(), sc.ext.get());
+        if (m > 0)
+            hipLaunchKernelGGL((k_rk_score_at<decltype(kind)::value, T>), dim3(grid_for((int64_t)m * n, RK_BLOCK)), dim3(RK_BLOCK), 0, e->stream,
+                               v.p, v.gw, n, e->d_ext2int.get(), d_ids, m, excl, rule, g, d_qs);
+        return DPPR_OK;
+    });
+    if (m > 0)
+        hipLaunchKernelGGL(k_pos_order, dim3((m + POS_ORDER_BLOCK - 1) / POS_ORDER_BLOCK, n), dim3(POS_ORDER_BLOCK), 0, e->stream, d_qs, d_ids, m, n,
+                           min_score, d_key, d_place);
+    hipLaunchKernelGGL(k_pos_count, dim3(pos_grid_x(st.rows, shape), shape.lane_blocks, shape.passes), dim3(POS_BLOCK),
+                       pos_lds_bytes(shape.lanes, shape.tile), e->stream, sc.a.get(), sc.ext.get(), st.rows, n, min_score, d_key, d_place, d_ids, m,
+                       shape.tile, shape.lanes, ps.slots.get());
+    hipLaunchKernelGGL(k_pos_finish, dim3(n), dim3(POS_BLOCK), 0, e->stream, ps.slots.get(), d_key, d_place, m, n, shape.tile, res_cnt, res_pos);
+    HIP_TRY(hipGetLastError());
+    if (int rc = fetch_block(e, ps.blk, ps.pin, lay.total_bytes)) return rc;
+    if (out_counts) memcpy(out_counts, ps.pin + lay.off_cnt, sizeof(int32_t) * (size_t)n);
+    if (m > 0) memcpy(out_pos, ps.pin + lay.off_pos, sizeof(int32_t) * (size_t)m * (size_t)n);
+    return DPPR_OK;
+}
+
+template <class Owner>
+int position_call(dppr_engine *e, Owner &o, int32_t epoch, const dppr_rank_spec_t *spec, double min_score, const int32_t *ids, int32_t m,
+                  int32_t *out_pos, int32_t *out_counts) {
+    const StateView v = view(o);
+    if (!position_args_ok(spec, min_score, ids, m, e->V, out_pos))
+        return fail(e, DPPR_ERR_INVALID, "position_at: factor 0..3, factor_dtype 0 or 1, mask 0..2, exclude bits 1 | 2 | 4, min_score >= 0, m in [0, DPPR_POSITION_MAX], ids in [0, V), non-null ids / pos when m > 0");
+    HIP_TRY(hipSetDevice(e->device));
+    const Epoch *ep = nullptr;
+    if (const char *why = rank_spec_refused(e, v, epoch, spec, &ep)) return fail(e, DPPR_ERR_INVALID, why);
+    if (m == 0 && !out_counts) return DPPR_OK;
+    std::lock_guard<std::mutex> map_lk(e->map_mu); // (as dppr_read: one state of the id space for the whole query)
+    return run_position(e, v, rank_lanes(o), ep, rank_spec(spec), min_score, ids, m, out_pos, out_counts);
+}
+
 // ---- every vertex to its best lane, across groups (dppr_assign.hpp, dppr_assign_plan.hpp) --------------------------------------
 static_assert(AS_TEAM_MAX * 2 == GS_MAX, "the widest row of a group is one step of the widest team");
 

@@ -240,6 +240,12 @@ struct QueryWork {
         DevBuf<unsigned long long> list;          // the piece list of the call (rk_piece_cap)
         std::vector<unsigned long long> items;    // ... as the host builds it (kept for its capacity)
     } rk;
+    struct Position { // positions of given vertices in a lane's order (dppr_position.hpp, dppr_position_plan.hpp); its scores: sc, its ids and query scores: ra
+        DevBuf<unsigned char> keys; // [n][m] keys of the queries by position in the lane's order, then [n][m] their places in `ids`
+        DevBuf<unsigned> slots;     // [n][m + 1] entries per first preceded position, the lane's count last (zeroed per call)
+        DevBuf<unsigned char> blk; PinBuf<unsigned char> pin; // counts, positions: device / pinned host
+        bool lds_set = false;       // the count pass was given its dynamic LDS limit
+    } pos;
     struct Assign { // every vertex to its best lane across groups (dppr_assign.hpp, dppr_assign_plan.hpp); the block grows with a host destination
         DevBuf<double> scale; // [256] the scales of the call
         DevBuf<int> cnt;      // [tiles] flips per tile
@@ -421,6 +427,7 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     int walk_form = 0;              // 0: lane refill, 1: one walk per thread (dppr_debug_walk_form)
     int sg_wave_max = SG_WAVE_MAX;  // matched entries of a row up to which the wave that owns it places them (dppr_debug_subgraph_wave_max)
     int rk_piece = RK_PIECE;        // entries of a seed's row one wave of k_rk_mark walks (dppr_debug_rank_piece)
+    int pos_tile = 0;               // queries of a lane's order a workgroup of k_pos_count holds per pass; 0: the plan's choice (dppr_debug_position_tile)
     float query_ms = -1.0f;         // dppr_set_profiling: device time of the last top-k, changes, export or dot call, first to last kernel (dppr_debug_query_ms)
     std::vector<int32_t> h_tmp1, h_tmp2;
     std::vector<int32_t> h_tiles; // host copy of the tile edge prefix / group table

@@ -73,6 +73,7 @@ EXPORTS = [
     "dppr_add_target_group", "dppr_group_replace_target", "dppr_group_targets",
     "dppr_topk_ranked", "dppr_group_topk_ranked", "dppr_rank_score_at", "dppr_group_rank_score_at", "dppr_debug_rank_piece",
     "dppr_assign", "dppr_assign_at",
+    "dppr_position_at", "dppr_group_position_at", "dppr_debug_position_tile",
 ]
 
 DEST_HOST, DEST_DEVICE = 0, 1
@@ -91,6 +92,7 @@ MASK_NONE, MASK_ALLOW, MASK_DENY = 0, 1, 2
 EXCLUDE_SEEDS, EXCLUDE_IN_NEIGHBOURS, EXCLUDE_OUT_NEIGHBOURS = 1, 2, 4
 RANK_PIECE = 512
 ASSIGN_GROUPS_MAX, ASSIGN_CLASSES_MAX = 16, 256
+POSITION_MAX = 4096
 
 
 class RankSpec(C.Structure):
@@ -235,6 +237,9 @@ def lib():
     L.dppr_rank_score_at.argtypes = [vp, C.c_int32, C.c_int32, vp, ip, C.c_int32, dp]
     L.dppr_group_rank_score_at.argtypes = [vp, C.c_int32, C.c_int32, vp, ip, C.c_int32, dp]
     L.dppr_debug_rank_piece.argtypes = [vp, C.c_int]
+    L.dppr_position_at.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_double, ip, C.c_int32, ip, ip]
+    L.dppr_group_position_at.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_double, ip, C.c_int32, ip, ip]
+    L.dppr_debug_position_tile.argtypes = [vp, C.c_int]
     L.dppr_assign.argtypes = [vp, ip, C.c_int32, dp, C.c_double, C.c_int, vp, vp, vp, i64p, vp, C.c_int64, i64p, vp, vp, vp]
     L.dppr_assign_at.argtypes = [vp, ip, C.c_int32, dp, C.c_double, ip, C.c_int32, ip, dp, ip, dp]
     for name in EXPORTS:
@@ -242,6 +247,26 @@ def lib():
             getattr(L, name).restype = C.c_int
     _lib = L
     return L
+
+
+def rank_metrics(pos_column, ks):
+    """MRR and Hits@K of one column of positions (Engine.position_at / group_position_at): (mrr, {K: hits}). A position p >= 0
+    contributes 1 / (p + 1) to the mean reciprocal rank and a hit to every K > p; -1 is a miss for both. Host arithmetic, summed
+    in input order; an empty column gives zeros."""
+    pos = [int(p) for p in np.asarray(pos_column).reshape(-1)]
+    ks = [int(k) for k in ks]
+    rr, hits = 0.0, {k: 0 for k in ks}
+    for p in pos:
+        if p < 0:
+            continue
+        rr += 1.0 / (p + 1)
+        for k in ks:
+            if p < k:
+                hits[k] += 1
+    m = len(pos)
+    if m == 0:
+        return 0.0, {k: 0.0 for k in ks}
+    return rr / m, {k: hits[k] / m for k in ks}
 
 
 def _i32(a):
@@ -728,6 +753,33 @@ class Engine:
         """Test hook (dppr_debug_rank_piece): the rows of the seeds are marked in pieces of at most `edges` entries, one wave each;
         1 .. 512, default 512. The results do not depend on it."""
         self._ck(self._L.dppr_debug_rank_piece(self._h, int(edges)), "debug_rank_piece")
+
+    # ---- positions of given vertices in a lane's order ----
+    def _position_at(self, fn, which, n, ids, spec, min_score, epoch, what):
+        a, pa = _i32(ids)
+        pos = np.empty((len(a), n), dtype=np.int32)
+        cnt = np.empty(n, dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        self._ck(fn(self._h, int(which), int(epoch), C.byref(spec) if spec is not None else None, float(min_score), pa, len(a),
+                    pos.ctypes.data_as(ip), cnt.ctypes.data_as(ip)), what)
+        return pos, cnt
+
+    def position_at(self, slot, ids, spec=None, min_score=0.0, epoch=-1):
+        """Where the given external ids stand in the order of topk_ranked (include/dppr.h: the number of vertices of larger score,
+        or of equal score and smaller id; -1 where the id does not qualify): (pos int32 [len(ids)], the count of qualifying
+        vertices)."""
+        pos, cnt = self._position_at(self._L.dppr_position_at, slot, 1, ids, spec, min_score, epoch, "position_at")
+        return pos[:, 0].copy(), int(cnt[0])
+
+    def group_position_at(self, group, ids, spec=None, min_score=0.0, epoch=-1):
+        """position_at for every lane of a group at once: (pos int32 [len(ids)][n], vertex-major as the state, counts int32 [n])."""
+        return self._position_at(self._L.dppr_group_position_at, group, self._group_n.get(group, 1), ids, spec, min_score, epoch,
+                                 "group_position_at")
+
+    def debug_position_tile(self, queries):
+        """Test hook (dppr_debug_position_tile): the count pass holds at most `queries` positions of a lane's order per workgroup and
+        pass; 1 .. 4096, 0 (default): the plan's choice. The results do not depend on it."""
+        self._ck(self._L.dppr_debug_position_tile(self._h, int(queries)), "debug_position_tile")
 
     # ---- every vertex to its best lane, across groups ----
     def _assign_classes(self, groups, scale, what):

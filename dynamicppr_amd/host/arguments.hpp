@@ -131,7 +131,7 @@ inline bool load_target_sets(const char *path, std::vector<std::vector<std::pair
     }
     return !lanes.empty();
 }
-// --refine: one external vertex id per line (blank lines are skipped). false: unreadable, no id, or a token that is not an id >= 0.
+// --refine, --positions: one external vertex id per line (blank lines are skipped). false: unreadable, no id, or a token that is not an id >= 0.
 inline bool load_ids(const char *path, std::vector<int32_t> &ids) {
     std::ifstream in(path);
     if (!in) return false;
@@ -185,6 +185,10 @@ inline void PrintUsage() {
               << "--refine <file> --walks <W> [--walk-seed <S>]: <file> holds one vertex id per line (ids in [0, V), at most 4096, W in [1, 2^20],\n"
               << "            ids x W <= 2^26); after every batch print, per id and per source (index from 0, in source order), the pagerank\n"
               << "            refined by W random walks, its correction and its standard error: refined <vertex> <source index> <est> <corr> <stderr>\n"
+              << "--positions <file>: <file> holds one vertex id per line (ids in [0, V), at most 4096); after every batch print, per source in source\n"
+              << "            order, where every id stands in the source's order by pagerank -- by the score of --rank-factor / --rank-exclude if\n"
+              << "            given (no --topk needed) --, from 0, -1 if its score is not > 0: position <source> <vertex> <pos>, then the number\n"
+              << "            of vertices that have a position: positions <source> qualifying <count>   (not with --split)\n"
               << "--cluster <K> [--cluster-min <P>] [--cluster-min-size <M>]: after every batch print, per source in source order, the prefix of\n"
               << "            lowest conductance of the source's K vertices of largest pagerank > P (1 <= K <= 8192, P >= 0, 1 <= M <= K vertices\n"
               << "            at least): cluster <source> size <vertices> cut <edges leaving it> vol <its out-degrees> phi <conductance>\n"
@@ -244,12 +248,13 @@ inline void ArgumentsChecker() {
     if (!gRefineFile.empty() && !gRefineBad &&
         (gWalks < 1 || gWalks > DPPR_WALK_MAX_W || gRefineIds.size() > (size_t)DPPR_WALK_MAX_M || (long long)gRefineIds.size() * gWalks > (1ll << 26)))
         ok = false;
+    if (gPositionsBad || (!gPositionsFile.empty() && (gPositionIds.size() > (size_t)DPPR_POSITION_MAX || gSplitInterface))) ok = false;
     if (gClusterGiven && (gClusterK < 1 || gClusterK > DPPR_CLUSTER_MAX || !(gClusterMin >= 0.0) || gClusterMinSize < 1 || gClusterMinSize > gClusterK))
         ok = false;
     if (gClusterOptsGiven && !gClusterGiven) ok = false;
     if ((gSubgraphGiven && (gSubgraphK < 1 || gSubgraphK > DPPR_SUBGRAPH_MAX)) || (!gSubgraphOut.empty() && !gSubgraphGiven)) ok = false;
     if (gTopKWeightsGiven && (gTopK == 0 || gTopKWeights.empty())) ok = false; // (the count is checked against the sources in main)
-    if (gRankGiven && (gTopK == 0 || gRankFactor < 0 || gRankExclude < 0 || gSplitInterface)) ok = false;
+    if (gRankGiven && ((gTopK == 0 && gPositionsFile.empty()) || gRankFactor < 0 || gRankExclude < 0 || gSplitInterface)) ok = false;
     if (!gTargetSetsFile.empty() && (gTargetSetsBad || gTargetSets.empty() || !gSourcesFile.empty() || gSplitInterface || gNoGroups || gTopKWeightsGiven)) ok = false;
     if ((gAssignMinGiven || !gAssignOut.empty()) && !gAssign) ok = false;
     if (gAssign && (!(gAssignMin >= 0.0) || gSplitInterface || gNoGroups)) ok = false; // (one device, groups in use: checked against the sources in main)
@@ -309,6 +314,10 @@ inline void ArgumentsParser(int argc, char **argv) {
     if (const char *f = find(argc, argv, "--refine")) {
         gRefineFile = f;
         gRefineBad = !load_ids(f, gRefineIds);
+    }
+    if (const char *f = find(argc, argv, "--positions")) {
+        gPositionsFile = f;
+        gPositionsBad = !load_ids(f, gPositionIds);
     }
     gWalksGiven = find(argc, argv, "--walks") != nullptr;
     gWalks = as_int(argc, argv, "--walks", 0);

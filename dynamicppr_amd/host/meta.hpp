@@ -63,6 +63,9 @@ inline std::vector<double> gSeedW;
 inline std::string gRefineFile;       // --refine FILE : one external vertex id per line; after every batch print refined <v> <source index> <est> <corr> <stderr>
 inline bool gRefineBad = false;       //   FILE could not be read, holds no id, or a token is not an id >= 0
 inline std::vector<int32_t> gRefineIds;
+inline std::string gPositionsFile;    // --positions FILE : one external vertex id per line; after every batch print position <source> <v> <pos> and positions <source> qualifying <count>
+inline bool gPositionsBad = false;    //   FILE could not be read, holds no id, or a token is not an id >= 0
+inline std::vector<int32_t> gPositionIds;
 inline int gWalks = 0;                // --walks W : walks per refined vertex (with --refine)
 inline bool gWalksGiven = false;
 inline unsigned long long gWalkSeed = 0; // --walk-seed S

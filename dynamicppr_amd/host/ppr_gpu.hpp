@@ -270,6 +270,7 @@ public:
             if (gChangesK > 0) PrintChanges(stream_batch_count);
             if (gAssign) PrintAssign(stream_batch_count);
             if (!gRefineIds.empty()) PrintRefined(-1);
+            if (!gPositionIds.empty()) PrintPositions(-1);
             if (gClusterK > 0) PrintClusters(-1);
             if (gSubgraphK > 0) PrintSubgraphs(-1);
         }
@@ -366,6 +367,7 @@ public:
             if (gChangesK > 0) PrintChanges(stream_batch_count);
             if (gAssign) PrintAssign(stream_batch_count);
             if (!gRefineIds.empty()) PrintRefined(epoch); // (the epoch the states stand on: the helper may have built the next one)
+            if (!gPositionIds.empty()) PrintPositions(epoch);
             if (gClusterK > 0) PrintClusters(epoch);
             if (gSubgraphK > 0) PrintSubgraphs(epoch);
         }
@@ -680,6 +682,40 @@ public:
                     std::snprintf(line, sizeof(line), "refined %d %zu %.17g %.17g %.17g\n", (int)gRefineIds[q], first + j, est[at], corr[at], se);
                     out += line;
                 }
+        }
+        progress++;
+        static std::mutex print_mu;
+        std::lock_guard<std::mutex> lk(print_mu);
+        std::cout << out << std::flush;
+    }
+
+    // --positions: after a batch, where every listed vertex stands in the order of every source of this device (dppr_position_at /
+    // dppr_group_position_at: by pagerank, or by the score of --rank-factor / --rank-exclude over `epoch`), and how many vertices have
+    // a position at all. Outside the timed region, printed as one block like --changes.
+    void PrintPositions(int32_t epoch) {
+        const size_t n_src = source_vertex_ids.size(), m = gPositionIds.size();
+        std::vector<int32_t> pos, cnt;
+        dppr_rank_spec_t spec{};
+        spec.factor = gRankGiven ? gRankFactor : DPPR_FACTOR_NONE;
+        spec.exclude = gRankGiven ? (unsigned)gRankExclude : 0u;
+        std::string out;
+        char line[200];
+        for (size_t first = 0; first < n_src; first += use_groups ? kGroupMax : 1) {
+            const size_t n = use_groups ? std::min(kGroupMax, n_src - first) : 1;
+            pos.assign(m * n, -1);
+            cnt.assign(n, 0);
+            if (use_groups)
+                DPPR_CHECK(engine, dppr_group_position_at(engine, groups[first / kGroupMax], epoch, &spec, 0.0, gPositionIds.data(), (int32_t)m, pos.data(), cnt.data()));
+            else
+                DPPR_CHECK(engine, dppr_position_at(engine, slots[first], epoch, &spec, 0.0, gPositionIds.data(), (int32_t)m, pos.data(), cnt.data()));
+            for (size_t j = 0; j < n; ++j) {
+                for (size_t q = 0; q < m; ++q) {
+                    std::snprintf(line, sizeof(line), "position %d %d %d\n", (int)source_vertex_ids[first + j], (int)gPositionIds[q], (int)pos[q * n + j]);
+                    out += line;
+                }
+                std::snprintf(line, sizeof(line), "positions %d qualifying %d\n", (int)source_vertex_ids[first + j], (int)cnt[j]);
+                out += line;
+            }
         }
         progress++;
         static std::mutex print_mu;

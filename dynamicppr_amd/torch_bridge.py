@@ -167,46 +167,43 @@ _RANK_FACTORS = {None: _eng.FACTOR_NONE, "none": _eng.FACTOR_NONE, "deg": _eng.F
 _RANK_EXCLUDE = {"seeds": _eng.EXCLUDE_SEEDS, "in": _eng.EXCLUDE_IN_NEIGHBOURS, "out": _eng.EXCLUDE_OUT_NEIGHBOURS}
 
 
-def _rank_vector(engine, t, what, dtypes):
+def _rank_vector(engine, t, what, dtypes, who="group_topk_ranked"):
     """A per-vertex tensor of a ranked query: on the engine's device, V elements, contiguous, of one of `dtypes`."""
     if not isinstance(t, torch.Tensor) or t.layout != torch.strided:
-        raise ValueError(f"group_topk_ranked: {what} is a dense tensor")
+        raise ValueError(f"{who}: {what} is a dense tensor")
     if t.device != _device(engine):
-        raise ValueError(f"group_topk_ranked: {what} must be on the engine's device {_device(engine)}, not {t.device}")
+        raise ValueError(f"{who}: {what} must be on the engine's device {_device(engine)}, not {t.device}")
     if t.dim() != 1 or t.numel() != engine.V:
-        raise ValueError(f"group_topk_ranked: {what} holds V = {engine.V} elements, not {tuple(t.shape)}")
+        raise ValueError(f"{who}: {what} holds V = {engine.V} elements, not {tuple(t.shape)}")
     if t.dtype not in dtypes:
-        raise ValueError(f"group_topk_ranked: {what} is one of {[str(d) for d in dtypes]}, not {t.dtype}")
+        raise ValueError(f"{who}: {what} is one of {[str(d) for d in dtypes]}, not {t.dtype}")
     if not t.is_contiguous():
-        raise ValueError(f"group_topk_ranked: {what} must be contiguous")
+        raise ValueError(f"{who}: {what} must be contiguous")
     return t
 
 
-def group_topk_ranked(engine, gid, k, min_score=0.0, factor=None, allow=None, deny=None, exclude=(), epoch=-1):
-    """dppr_group_topk_ranked over torch tensors: a list of (ids, scores) numpy pairs, one per lane, as Engine.group_topk_ranked
-    returns them. factor: None, "deg", "inv_deg" or a float64 / float32 tensor g (score = p * g[v]); allow / deny: bool or uint8
-    tensors (nonzero = set; with both, a vertex takes part if it is allowed and not denied); exclude: any of "seeds", "in", "out".
-    Every tensor lives on the engine's device, is contiguous and holds V elements by external id: anything else raises ValueError
-    before the engine is called."""
+def _rank_spec(engine, factor, allow, deny, exclude, who):
+    """The dppr_rank_spec_t of a ranked call over torch tensors, and the tensors it points into (to be kept until the engine has
+    returned)."""
     flags = 0
     for name in ([exclude] if isinstance(exclude, str) else exclude):
         if name not in _RANK_EXCLUDE:
-            raise ValueError(f"group_topk_ranked: exclude holds any of {sorted(_RANK_EXCLUDE)}, not {name!r}")
+            raise ValueError(f"{who}: exclude holds any of {sorted(_RANK_EXCLUDE)}, not {name!r}")
         flags |= _RANK_EXCLUDE[name]
     kind, g_ptr, g_dtype = _eng.FACTOR_NONE, 0, _eng.F64
     keep = []   # (what the engine reads stays referenced until it has returned)
     if isinstance(factor, torch.Tensor):
-        g = _rank_vector(engine, factor, "factor", (torch.float64, torch.float32))
+        g = _rank_vector(engine, factor, "factor", (torch.float64, torch.float32), who)
         kind, g_ptr, g_dtype = _eng.FACTOR_DEV, g.data_ptr(), _DTYPES[g.dtype]
         keep.append(g)
     elif factor in _RANK_FACTORS:
         kind = _RANK_FACTORS[factor]
     else:
-        raise ValueError(f"group_topk_ranked: factor is None, 'deg', 'inv_deg' or a tensor, not {factor!r}")
+        raise ValueError(f"{who}: factor is None, 'deg', 'inv_deg' or a tensor, not {factor!r}")
     masks = {"allow": allow, "deny": deny}
     for what, m in masks.items():
         if m is not None:
-            m = _rank_vector(engine, m, what, (torch.bool, torch.uint8))
+            m = _rank_vector(engine, m, what, (torch.bool, torch.uint8), who)
             masks[what] = m.view(torch.uint8) if m.dtype == torch.bool else m
     mode, m_ptr = _eng.MASK_NONE, 0
     if masks["allow"] is not None and masks["deny"] is not None:
@@ -219,9 +216,32 @@ def group_topk_ranked(engine, gid, k, min_score=0.0, factor=None, allow=None, de
     elif masks["deny"] is not None:
         mode, m_ptr = _eng.MASK_DENY, masks["deny"].data_ptr()
         keep.append(masks["deny"])
-    spec = _eng.Engine.rank_spec(kind, g_ptr, g_dtype, mode, m_ptr, flags)
+    return _eng.Engine.rank_spec(kind, g_ptr, g_dtype, mode, m_ptr, flags), keep
+
+
+def group_topk_ranked(engine, gid, k, min_score=0.0, factor=None, allow=None, deny=None, exclude=(), epoch=-1):
+    """dppr_group_topk_ranked over torch tensors: a list of (ids, scores) numpy pairs, one per lane, as Engine.group_topk_ranked
+    returns them. factor: None, "deg", "inv_deg" or a float64 / float32 tensor g (score = p * g[v]); allow / deny: bool or uint8
+    tensors (nonzero = set; with both, a vertex takes part if it is allowed and not denied); exclude: any of "seeds", "in", "out".
+    Every tensor lives on the engine's device, is contiguous and holds V elements by external id: anything else raises ValueError
+    before the engine is called."""
+    spec, keep = _rank_spec(engine, factor, allow, deny, exclude, "group_topk_ranked")
     torch.cuda.synchronize(_device(engine))   # (the tensors are torch's; nothing of torch's is in flight on them when the engine reads)
     return engine.group_topk_ranked(gid, k, min_score, spec, epoch)
+
+
+def group_position_at(engine, gid, ids, min_score=0.0, factor=None, allow=None, deny=None, exclude=(), epoch=-1):
+    """dppr_group_position_at over torch tensors: where the external ids `ids` (a host sequence or an integer tensor, at most 4096)
+    stand in every lane's order under the factor, masks and exclusions of group_topk_ranked, which it takes in the same form.
+    Returns (pos, counts): int32 CPU tensors [len(ids)][n] (-1: the id does not qualify in the lane) and [n]."""
+    spec, keep = _rank_spec(engine, factor, allow, deny, exclude, "group_position_at")
+    if isinstance(ids, torch.Tensor):
+        if ids.is_floating_point() or ids.dtype == torch.bool or ids.dim() != 1:
+            raise ValueError(f"group_position_at: ids is a 1-D integer tensor or a sequence, not {ids.dtype} {tuple(ids.shape)}")
+        ids = ids.detach().cpu().numpy()
+    torch.cuda.synchronize(_device(engine))   # (the tensors are torch's; nothing of torch's is in flight on them when the engine reads)
+    pos, counts = engine.group_position_at(gid, ids, spec, min_score, epoch)
+    return torch.from_numpy(pos), torch.from_numpy(counts)
 
 
 def assign(engine, groups, scale=None, min_score=0.0, prev=None, want=("best", "margin")):

@@ -935,6 +935,54 @@ int dppr_group_rank_score_at(dppr_engine *e, int32_t group, int32_t epoch, const
                              double *out_score /* [m][n] */);
 int dppr_debug_rank_piece(dppr_engine *e, int edges);
 
+/* ---- positions of given vertices in a lane's order (backward-compatible additions, ABI 6) ----
+ * dppr_topk_ranked returns the head of every lane's order. These calls answer the inverse question: WHERE DOES VERTEX v STAND in
+ * lane i's order -- the input of MRR, Hits@K and the percentile of a held-out edge, and the "rank of item v for user s" shown
+ * beside a score. Without them the answer is a selection at k = DPPR_TOPK_MAX searched on the host, blind below position 8192, or
+ * a dense read of every column and a host sort.
+ *
+ * THE SCORE score_i[v] is THE SCORE of dppr_topk_ranked for lane i, unchanged: the same factor, mask and exclusion, the same NO ID
+ * rule, the same EPOCH rule (a spec that reads no degree and no neighbour does not look at `epoch`); spec == NULL means the score
+ * is p.
+ * QUALIFYING. A vertex qualifies in lane i iff score_i[v] > min_score, with min_score >= 0: a score of +-0, a negative or a NaN
+ * score never qualifies, +inf does.
+ * POSITION. pos[j][i] = -1 if ids[j] does not qualify in lane i. Otherwise it is the number of external ids u with
+ * score_i[u] > score_i[v], or score_i[u] == score_i[v] and u < v: the 0-based position of v in the order of dppr_topk_ranked.
+ * Every such u qualifies by itself. Every output is an integer defined by comparisons alone.
+ * COUNTS. out_counts[i] is the number of qualifying vertices of lane i, the denominator of a percentile: the count
+ * dppr_group_topk_ranked would report at unlimited k.
+ * ZONES. The live and the parked zone are both counted. A vertex without an internal id never qualifies and never precedes
+ * anything.
+ * DUPLICATE IDS. A duplicate id gives the same answer in each of its places.
+ * ANCHORS. (a) For every (i, j) with 0 <= pos[j][i] < k, dppr_group_topk_ranked(k, min_score, spec) returns ids[j] at
+ * [i][pos[j][i]]. (b) Conversely, the positions of the ids that call returns for lane i are 0, 1, .., count - 1 in column i.
+ * (c) With spec == NULL the same holds against dppr_group_topk(k, min_p = min_score).
+ *
+ * Outputs: dppr_position_at out_pos [m] and one count; dppr_group_position_at out_pos [m][n], vertex-major like the state, and
+ * out_counts [n]. The count pointer may be NULL. m == 0 is valid: only the counts are computed if asked, a no-op if they are not.
+ *
+ * Rejected with DPPR_ERR_INVALID before any device work, nothing written: m < 0 or m > DPPR_POSITION_MAX; a NULL ids or a NULL
+ * out_pos with m > 0; an id outside [0, V); min_score negative or NaN; every spec and epoch rejection of dppr_topk_ranked; a bad
+ * slot / group.
+ * Threading and stream as dppr_topk_ranked: the id-map lock for the whole call (safe beside dppr_slide_concurrent), the solver
+ * stream, any state (converged or not), never part of the update path or of a timed region. Every stage is enqueued before the
+ * single copy back of 64 + 4 m n bytes. Work space beyond dppr_topk_ranked's (whose scratch state it is, not a second one):
+ * 12 m n bytes of keys and permutation, 4 (m + 1) n bytes of slots, the result block and its pinned twin; all of it is the
+ * engine's, obtained before the first kernel, grown on demand and released with the engine: after DPPR_ERR_NOMEM the states and the
+ * engine are as before. With dppr_set_profiling on, dppr_debug_query_ms reports the device time of the last of these calls.
+ * OUT OF SCOPE: weight vectors (the scores of dppr_group_topk_weighted), positions by |p - mark|, device-resident ids or outputs,
+ * more than DPPR_POSITION_MAX ids per call.
+ * dppr_debug_position_tile: a test hook, as dppr_debug_rank_piece. The count pass holds at most `queries` consecutive positions of
+ * a lane's order per workgroup and pass (smallest value 1, largest 4096; 0, the default: the plan's choice), so a small m can be
+ * made to take several passes and lane blocks. The results do not depend on it. */
+#define DPPR_POSITION_MAX 4096   /* ids per call, the limit of dppr_refine_at */
+int dppr_position_at(dppr_engine *e, int32_t slot, int32_t epoch, const dppr_rank_spec_t *spec, double min_score,
+                     const int32_t *ids, int32_t m, int32_t *out_pos /* [m] */, int32_t *out_count /* [1], may be NULL */);
+int dppr_group_position_at(dppr_engine *e, int32_t group, int32_t epoch, const dppr_rank_spec_t *spec, double min_score,
+                           const int32_t *ids, int32_t m, int32_t *out_pos /* [m][n], vertex-major like the state */,
+                           int32_t *out_counts /* [n], may be NULL */);
+int dppr_debug_position_tile(dppr_engine *e, int queries);
+
 /* ---- every vertex to its best lane, across groups (backward-compatible additions, ABI 6) ----
  * The queries above answer per lane. With one lane per class -- sources or target sets -- the question per VERTEX is which lane
  * holds it best: label propagation on a live stream. dppr_assign reduces over the lane axis in one pass over the states, across
