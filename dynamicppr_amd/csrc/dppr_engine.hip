@@ -54,6 +54,7 @@
 #include "dppr_rank.hpp"
 #include "dppr_assign.hpp"
 #include "dppr_position.hpp"
+#include "dppr_explain.hpp"
 
 using namespace dppr;
 
@@ -1638,6 +1639,26 @@ int dppr_debug_position_tile(dppr_engine *e, int queries) {
     if (!e || !position_tile_ok(queries))
         return fail(e, DPPR_ERR_INVALID, "debug_position_tile: 1 .. 4096 queries of a lane's order per workgroup and pass, 0: the plan's choice");
     e->pos_tile = queries;
+    return DPPR_OK;
+}
+
+int dppr_explain_at(dppr_engine *e, int32_t slot, int32_t epoch, const int32_t *ids, int32_t m, int32_t f, int32_t depth,
+                    const dppr_explain_out_t *out) {
+    GET_SLOT(e, slot);
+    return explain_call(e, s, epoch, ids, m, f, depth, out);
+}
+
+int dppr_group_explain_at(dppr_engine *e, int32_t group, int32_t epoch, const int32_t *ids, int32_t m, int32_t f, int32_t depth,
+                          const dppr_explain_out_t *out) {
+    GET_GROUP(e, group);
+    return explain_call(e, g, epoch, ids, m, f, depth, out);
+}
+
+int dppr_debug_explain(dppr_engine *e, int memo, int wave_rows) {
+    if (!e || !ex_hook_ok(memo, wave_rows))
+        return fail(e, DPPR_ERR_INVALID, "debug_explain: memo -1 (the plan's choice), 0 or 1; 1 .. 64 entries of a row per wave and step");
+    e->ex_memo = memo;
+    e->ex_wave_rows = wave_rows;
     return DPPR_OK;
 }
 

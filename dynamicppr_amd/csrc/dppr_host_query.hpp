@@ -1417,4 +1417,76 @@ int assign_at_call(dppr_engine *e, const int32_t *groups, int32_t n_groups, cons
     return run_assign_at(e, d, team, scale, min_score, ids, m, out_label, out_best, out_second_label, out_margin);
 }
 
+// ---- explain a score: top contributors and the path to the seeds (dppr_explain.hpp, dppr_explain_plan.hpp) -------------------------
+// Contributors and paths of m external ids in every lane (arguments and the epoch validated by the caller, m > 0, `which` names at
+// least one output). Every buffer is in place before the first kernel -- the block, its pinned twin and, with the memo on, the
+// first plane of the scratch state of the ranked family -- and both kernels are enqueued before the one copy back.
+int run_explain(dppr_engine *e, const StateView &v, const RkLanes &l, const Epoch &ep, const int32_t *ids, int m, int f, int depth,
+                uint32_t which, const dppr_explain_out_t &out) {
+    if (int rc = query_begin(e, MAP_E2I | MAP_I2E)) return rc;
+    QueryWork::Explain &xq = e->q.exq;
+    const int n = v.n;
+    const ExplainLayout lay = ex_layout(m, n, f, depth, which);
+    const bool memo = ex_memo_on(m, n, depth, which, e->ex_memo);
+    const size_t memo_elems = ex_memo_elems((size_t)e->n_int, n);
+    Grow grow{e};
+    int rc = grow(xq.blk, lay.total_bytes);
+    if (!rc) rc = grow(xq.pin, lay.total_bytes);
+    if (!rc && memo) rc = grow(e->q.sc.a, memo_elems, with_slack(memo_elems));
+    if (rc) return rc;
+    unsigned char *blk = xq.blk.get();
+    auto ints = [&](uint32_t bit, size_t off) { return (which & bit) ? reinterpret_cast<int *>(blk + off) : nullptr; };
+    auto dbls = [&](uint32_t bit, size_t off) { return (which & bit) ? reinterpret_cast<double *>(blk + off) : nullptr; };
+    int *d_ids = reinterpret_cast<int *>(blk + lay.off_ids);
+    const ExIn in{v.p, v.gw, n, e->d_ext2int.get(), e->d_int2ext.get(), d_ids, m, rank_graph(e, &ep), l};
+    const ExFirstOut fo{ints(EX_DEG, lay.off_deg),     ints(EX_DISTINCT, lay.off_distinct), dbls(EX_SELF, lay.off_self), ints(EX_NBR_COUNT, lay.off_nbr_count),
+                        ints(EX_NBR, lay.off_nbr),     ints(EX_NBR_MULT, lay.off_nbr_mult), dbls(EX_NBR_C, lay.off_nbr_c)};
+    const ExPathOut po{ints(EX_LEN, lay.off_len), ints(EX_END, lay.off_end), ints(EX_PATH, lay.off_path), dbls(EX_PATH_P, lay.off_path_p),
+                       dbls(EX_PATH_C, lay.off_path_c)};
+    HIP_TRY(hipMemcpyAsync(d_ids, ids, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, e->stream));
+    if (int rc2 = DeviceTime{e}.open()) return rc2;
+    const dim3 grid((unsigned)ex_grid(m, n)), block(EX_BLOCK);
+    if (which & EX_FIRST) hipLaunchKernelGGL(k_ex_first, grid, block, 0, e->stream, in, f, e->ex_wave_rows, fo);
+    if (which & EX_WALK) {
+        unsigned long long *d_memo = memo ? reinterpret_cast<unsigned long long *>(e->q.sc.a.get()) : nullptr;
+        if (memo) HIP_TRY(hipMemsetAsync(d_memo, 0xff, sizeof(unsigned long long) * memo_elems, e->stream)); // (every entry: unknown)
+        hipLaunchKernelGGL(k_ex_path, grid, block, 0, e->stream, in, depth, e->ex_wave_rows, d_memo, po);
+    }
+    HIP_TRY(hipGetLastError());
+    if (int rc2 = fetch_block(e, xq.blk, xq.pin, lay.copy_bytes)) return rc2;
+    const size_t mn = (size_t)m * (size_t)n;
+    auto back = [&](uint32_t bit, void *dst, size_t off, size_t bytes) {
+        if (which & bit) memcpy(dst, xq.pin + off, bytes);
+    };
+    back(EX_DEG, out.deg, lay.off_deg, sizeof(int32_t) * (size_t)m);
+    back(EX_DISTINCT, out.distinct, lay.off_distinct, sizeof(int32_t) * (size_t)m);
+    back(EX_SELF, out.self, lay.off_self, sizeof(double) * mn);
+    back(EX_NBR_COUNT, out.nbr_count, lay.off_nbr_count, sizeof(int32_t) * mn);
+    back(EX_NBR, out.nbr, lay.off_nbr, sizeof(int32_t) * mn * (size_t)f);
+    back(EX_NBR_MULT, out.nbr_mult, lay.off_nbr_mult, sizeof(int32_t) * mn * (size_t)f);
+    back(EX_NBR_C, out.nbr_c, lay.off_nbr_c, sizeof(double) * mn * (size_t)f);
+    back(EX_LEN, out.len, lay.off_len, sizeof(int32_t) * mn);
+    back(EX_END, out.end, lay.off_end, sizeof(int32_t) * mn);
+    back(EX_PATH, out.path, lay.off_path, sizeof(int32_t) * mn * ((size_t)depth + 1));
+    back(EX_PATH_P, out.path_p, lay.off_path_p, sizeof(double) * mn * ((size_t)depth + 1));
+    back(EX_PATH_C, out.path_c, lay.off_path_c, sizeof(double) * mn * (size_t)depth);
+    return DPPR_OK;
+}
+
+// (Owner: a Slot or a Group. Its seeds are read under map_mu: a renumbering beside the call renames them)
+template <class Owner>
+int explain_call(dppr_engine *e, Owner &o, int32_t epoch, const int32_t *ids, int32_t m, int32_t f, int32_t depth, const dppr_explain_out_t *out) {
+    const StateView v = view(o);
+    if (!ex_args_ok(ids, m, f, depth, e->V, out))
+        return fail(e, DPPR_ERR_INVALID, "explain_at: m in [0, DPPR_EXPLAIN_MAX_M], f in [0, DPPR_EXPLAIN_MAX_F], depth in [0, DPPR_EXPLAIN_MAX_DEPTH], f + depth >= 1, ids in [0, V), non-null ids / out when m > 0");
+    const Epoch *ep = find_epoch(e, epoch);
+    if (!ep) return fail(e, DPPR_ERR_INVALID, "explain_at: epoch not resident (evicted or never built)");
+    if (!refine_epoch_ok(v.st.last_epoch, ep->id))
+        return fail(e, DPPR_ERR_INVALID, "explain_at: the state stands on another epoch than the one given: the out-edges of another graph do not decompose its scores");
+    const uint32_t which = ex_which(out, f, depth);
+    if (m == 0 || !which) return DPPR_OK;
+    std::lock_guard<std::mutex> map_lk(e->map_mu); // (as dppr_read: one state of the id space for the whole query)
+    return run_explain(e, v, rank_lanes(o), *ep, ids, m, f, depth, which, *out);
+}
+
 } // namespace

@@ -246,6 +246,9 @@ struct QueryWork {
         DevBuf<unsigned char> blk; PinBuf<unsigned char> pin; // counts, positions: device / pinned host
         bool lds_set = false;       // the count pass was given its dynamic LDS limit
     } pos;
+    struct Explain { // top contributors and the path to the seeds (dppr_explain.hpp, dppr_explain_plan.hpp); its memo: the first plane of sc
+        DevBuf<unsigned char> blk; PinBuf<unsigned char> pin; // the planes asked for, then the queried ids: device / pinned host
+    } exq;
     struct Assign { // every vertex to its best lane across groups (dppr_assign.hpp, dppr_assign_plan.hpp); the block grows with a host destination
         DevBuf<double> scale; // [256] the scales of the call
         DevBuf<int> cnt;      // [tiles] flips per tile
@@ -428,6 +431,8 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     int sg_wave_max = SG_WAVE_MAX;  // matched entries of a row up to which the wave that owns it places them (dppr_debug_subgraph_wave_max)
     int rk_piece = RK_PIECE;        // entries of a seed's row one wave of k_rk_mark walks (dppr_debug_rank_piece)
     int pos_tile = 0;               // queries of a lane's order a workgroup of k_pos_count holds per pass; 0: the plan's choice (dppr_debug_position_tile)
+    int ex_memo = -1;               // the memo of k_ex_path: -1 the plan's choice, 0 off, 1 on (dppr_debug_explain)
+    int ex_wave_rows = EX_WAVE_ROWS; // entries of a row a wave of dppr_explain.hpp takes per step (dppr_debug_explain)
     float query_ms = -1.0f;         // dppr_set_profiling: device time of the last top-k, changes, export or dot call, first to last kernel (dppr_debug_query_ms)
     std::vector<int32_t> h_tmp1, h_tmp2;
     std::vector<int32_t> h_tiles; // host copy of the tile edge prefix / group table

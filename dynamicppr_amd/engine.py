@@ -74,6 +74,7 @@ EXPORTS = [
     "dppr_topk_ranked", "dppr_group_topk_ranked", "dppr_rank_score_at", "dppr_group_rank_score_at", "dppr_debug_rank_piece",
     "dppr_assign", "dppr_assign_at",
     "dppr_position_at", "dppr_group_position_at", "dppr_debug_position_tile",
+    "dppr_explain_at", "dppr_group_explain_at", "dppr_debug_explain",
 ]
 
 DEST_HOST, DEST_DEVICE = 0, 1
@@ -93,12 +94,21 @@ EXCLUDE_SEEDS, EXCLUDE_IN_NEIGHBOURS, EXCLUDE_OUT_NEIGHBOURS = 1, 2, 4
 RANK_PIECE = 512
 ASSIGN_GROUPS_MAX, ASSIGN_CLASSES_MAX = 16, 256
 POSITION_MAX = 4096
+EXPLAIN_MAX_M, EXPLAIN_MAX_F, EXPLAIN_MAX_DEPTH = 4096, 16, 64
+END_SEED, END_DEPTH, END_DEAD, END_CYCLE = 0, 1, 2, 3
 
 
 class RankSpec(C.Structure):
     """dppr_rank_spec_t: the factor, the mask and the exclusions of a ranked query."""
     _fields_ = [("factor", C.c_int32), ("factor_dtype", C.c_int32), ("factor_dev", C.c_void_p), ("mask", C.c_int32),
                 ("mask_dev", C.c_void_p), ("exclude", C.c_uint32)]
+
+
+class ExplainOut(C.Structure):
+    """dppr_explain_out_t: where the outputs of an explain call go (host memory; a NULL is not computed)."""
+    _ip, _dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    _fields_ = [("deg", _ip), ("distinct", _ip), ("self", _dp), ("nbr_count", _ip), ("nbr", _ip), ("nbr_mult", _ip), ("nbr_c", _dp),
+                ("len", _ip), ("end", _ip), ("path", _ip), ("path_p", _dp), ("path_c", _dp)]
 
 
 class Cluster(C.Structure):
@@ -240,6 +250,9 @@ def lib():
     L.dppr_position_at.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_double, ip, C.c_int32, ip, ip]
     L.dppr_group_position_at.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_double, ip, C.c_int32, ip, ip]
     L.dppr_debug_position_tile.argtypes = [vp, C.c_int]
+    L.dppr_explain_at.argtypes = [vp, C.c_int32, C.c_int32, ip, C.c_int32, C.c_int32, C.c_int32, vp]
+    L.dppr_group_explain_at.argtypes = [vp, C.c_int32, C.c_int32, ip, C.c_int32, C.c_int32, C.c_int32, vp]
+    L.dppr_debug_explain.argtypes = [vp, C.c_int, C.c_int]
     L.dppr_assign.argtypes = [vp, ip, C.c_int32, dp, C.c_double, C.c_int, vp, vp, vp, i64p, vp, C.c_int64, i64p, vp, vp, vp]
     L.dppr_assign_at.argtypes = [vp, ip, C.c_int32, dp, C.c_double, ip, C.c_int32, ip, dp, ip, dp]
     for name in EXPORTS:
@@ -780,6 +793,48 @@ class Engine:
         """Test hook (dppr_debug_position_tile): the count pass holds at most `queries` positions of a lane's order per workgroup and
         pass; 1 .. 4096, 0 (default): the plan's choice. The results do not depend on it."""
         self._ck(self._L.dppr_debug_position_tile(self._h, int(queries)), "debug_position_tile")
+
+    # ---- explain a score: top contributing out-edges and the path to the seeds ----
+    def _explain_at(self, fn, which, n, ids, f, depth, epoch, what, want=None):
+        a, pa = _i32(ids)
+        m, f, depth = len(a), int(f), int(depth)
+        shapes = {"deg": ((m,), np.int32), "distinct": ((m,), np.int32), "self": ((m, n), np.float64),
+                  "nbr_count": ((m, n), np.int32), "nbr": ((m, n, max(f, 0)), np.int32), "nbr_mult": ((m, n, max(f, 0)), np.int32),
+                  "nbr_c": ((m, n, max(f, 0)), np.float64), "len": ((m, n), np.int32), "end": ((m, n), np.int32),
+                  "path": ((m, n, max(depth, 0) + 1), np.int32), "path_p": ((m, n, max(depth, 0) + 1), np.float64),
+                  "path_c": ((m, n, max(depth, 0)), np.float64)}
+        if want is not None:   # (only what is asked for is computed and copied back: the other pointers stay NULL)
+            want = [want] if isinstance(want, str) else list(want)
+            unknown = [k for k in want if k not in shapes]
+            if unknown:
+                raise ValueError(f"{what}: unknown outputs {unknown}; the outputs are {list(shapes)}")
+            shapes = {k: v for k, v in shapes.items() if k in want}
+        res = {k: np.zeros(shape, dtype=dt) for k, (shape, dt) in shapes.items()}
+        out = ExplainOut()
+        for k, arr in res.items():
+            ptr = C.POINTER(C.c_int32 if arr.dtype == np.int32 else C.c_double)
+            setattr(out, k, arr.ctypes.data_as(ptr))
+        self._ck(fn(self._h, int(which), int(epoch), pa, m, f, depth, C.byref(out)), what)
+        return res
+
+    def explain_at(self, slot, ids, f=4, depth=16, epoch=-1, want=None):
+        """Why the given external ids have the score they have (include/dppr.h: dppr_explain_at): a dict of numpy arrays -- deg,
+        distinct [m]; self, nbr_count, len, end [m]; nbr, nbr_mult, nbr_c [m][f]; path, path_p [m][depth + 1]; path_c [m][depth].
+        want: the names of the outputs to compute and return (default: all twelve)."""
+        res = self._explain_at(self._L.dppr_explain_at, slot, 1, ids, f, depth, epoch, "explain_at", want)
+        return {k: (v if v.ndim == 1 else v[:, 0].copy()) for k, v in res.items()}
+
+    def group_explain_at(self, group, ids, f=4, depth=16, epoch=-1, want=None):
+        """explain_at for every lane of a group at once: the same dict with a lane axis after the vertex axis -- self, nbr_count,
+        len, end [m][n]; nbr, nbr_mult, nbr_c [m][n][f]; path, path_p [m][n][depth + 1]; path_c [m][n][depth]; deg, distinct [m].
+        want: the names of the outputs to compute and return (default: all twelve)."""
+        return self._explain_at(self._L.dppr_group_explain_at, group, self._group_n.get(group, 1), ids, f, depth, epoch, "group_explain_at",
+                                want)
+
+    def debug_explain(self, memo=-1, wave_rows=64):
+        """Test hook (dppr_debug_explain): memo -1 the plan's choice, 0 off, 1 on; wave_rows 1 .. 64 entries of a row per wave and
+        step. The results depend on neither."""
+        self._ck(self._L.dppr_debug_explain(self._h, int(memo), int(wave_rows)), "debug_explain")
 
     # ---- every vertex to its best lane, across groups ----
     def _assign_classes(self, groups, scale, what):

@@ -131,7 +131,7 @@ inline bool load_target_sets(const char *path, std::vector<std::vector<std::pair
     }
     return !lanes.empty();
 }
-// --refine, --positions: one external vertex id per line (blank lines are skipped). false: unreadable, no id, or a token that is not an id >= 0.
+// --refine, --positions, --explain: one external vertex id per line (blank lines are skipped). false: unreadable, no id, or a token that is not an id >= 0.
 inline bool load_ids(const char *path, std::vector<int32_t> &ids) {
     std::ifstream in(path);
     if (!in) return false;
@@ -189,6 +189,11 @@ inline void PrintUsage() {
               << "            order, where every id stands in the source's order by pagerank -- by the score of --rank-factor / --rank-exclude if\n"
               << "            given (no --topk needed) --, from 0, -1 if its score is not > 0: position <source> <vertex> <pos>, then the number\n"
               << "            of vertices that have a position: positions <source> qualifying <count>   (not with --split)\n"
+              << "--explain <file> [--explain-top <F>] [--explain-depth <D>]: <file> holds one vertex id per line (ids in [0, V), at most 4096); after every\n"
+              << "            batch print, per source in source order and per id, the path of largest contributions towards the source, at most D hops\n"
+              << "            (0 <= D <= 64, default 16): explain <source> <vertex> <end> <len> <v0> <v1> ...  (end 0 seed, 1 depth, 2 dead end, 3 cycle),\n"
+              << "            then the F out-neighbours that contribute most to its pagerank (0 <= F <= 16, default 3, F + D >= 1):\n"
+              << "            because <source> <vertex> <neighbour> <stored copies> <contribution>   (not with --split)\n"
               << "--cluster <K> [--cluster-min <P>] [--cluster-min-size <M>]: after every batch print, per source in source order, the prefix of\n"
               << "            lowest conductance of the source's K vertices of largest pagerank > P (1 <= K <= 8192, P >= 0, 1 <= M <= K vertices\n"
               << "            at least): cluster <source> size <vertices> cut <edges leaving it> vol <its out-degrees> phi <conductance>\n"
@@ -249,6 +254,10 @@ inline void ArgumentsChecker() {
         (gWalks < 1 || gWalks > DPPR_WALK_MAX_W || gRefineIds.size() > (size_t)DPPR_WALK_MAX_M || (long long)gRefineIds.size() * gWalks > (1ll << 26)))
         ok = false;
     if (gPositionsBad || (!gPositionsFile.empty() && (gPositionIds.size() > (size_t)DPPR_POSITION_MAX || gSplitInterface))) ok = false;
+    if (gExplainBad || (gExplainOptsGiven && gExplainFile.empty())) ok = false;
+    if (!gExplainFile.empty() && (gExplainIds.size() > (size_t)DPPR_EXPLAIN_MAX_M || gSplitInterface || gExplainTop < 0 || gExplainTop > DPPR_EXPLAIN_MAX_F ||
+                                  gExplainDepth < 0 || gExplainDepth > DPPR_EXPLAIN_MAX_DEPTH || gExplainTop + gExplainDepth < 1))
+        ok = false;
     if (gClusterGiven && (gClusterK < 1 || gClusterK > DPPR_CLUSTER_MAX || !(gClusterMin >= 0.0) || gClusterMinSize < 1 || gClusterMinSize > gClusterK))
         ok = false;
     if (gClusterOptsGiven && !gClusterGiven) ok = false;
@@ -319,6 +328,13 @@ inline void ArgumentsParser(int argc, char **argv) {
         gPositionsFile = f;
         gPositionsBad = !load_ids(f, gPositionIds);
     }
+    if (const char *f = find(argc, argv, "--explain")) {
+        gExplainFile = f;
+        gExplainBad = !load_ids(f, gExplainIds);
+    }
+    gExplainOptsGiven = find(argc, argv, "--explain-top") != nullptr || find(argc, argv, "--explain-depth") != nullptr;
+    gExplainTop = as_int(argc, argv, "--explain-top", 3);
+    gExplainDepth = as_int(argc, argv, "--explain-depth", 16);
     gWalksGiven = find(argc, argv, "--walks") != nullptr;
     gWalks = as_int(argc, argv, "--walks", 0);
     if (const char *v = find(argc, argv, "--walk-seed")) gWalkSeed = std::strtoull(v, nullptr, 0);

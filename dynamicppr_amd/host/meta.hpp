@@ -66,6 +66,12 @@ inline std::vector<int32_t> gRefineIds;
 inline std::string gPositionsFile;    // --positions FILE : one external vertex id per line; after every batch print position <source> <v> <pos> and positions <source> qualifying <count>
 inline bool gPositionsBad = false;    //   FILE could not be read, holds no id, or a token is not an id >= 0
 inline std::vector<int32_t> gPositionIds;
+inline std::string gExplainFile;      // --explain FILE : one external vertex id per line; after every batch print explain <source> <v> <end> <len> <v0> <v1> ... and because <source> <v> <w> <mult> <c>
+inline bool gExplainBad = false;      //   FILE could not be read, holds no id, or a token is not an id >= 0
+inline std::vector<int32_t> gExplainIds;
+inline int gExplainTop = 3;           // --explain-top F : contributors listed per id and source
+inline int gExplainDepth = 16;        // --explain-depth D : hops of the path at the most
+inline bool gExplainOptsGiven = false;
 inline int gWalks = 0;                // --walks W : walks per refined vertex (with --refine)
 inline bool gWalksGiven = false;
 inline unsigned long long gWalkSeed = 0; // --walk-seed S

@@ -82,11 +82,12 @@ int main(int argc, char *argv[]) {
             }
         }
         graphs[(size_t)d].reset(new SlidingGraphVec(gDataFileName, gIsDirected != 0));
-        if (d == 0) { // --seeds, --refine, --positions: an id the graph does not have is an argument error, found before any device work
+        if (d == 0) { // --seeds, --refine, --positions, --explain: an id the graph does not have is an argument error, found before any device work
             bool ok = true;
             for (int32_t v : gSeedIds) ok = ok && v < (int32_t)graphs[0]->vertex_count;
             for (int32_t v : gRefineIds) ok = ok && v < (int32_t)graphs[0]->vertex_count;
             for (int32_t v : gPositionIds) ok = ok && v < (int32_t)graphs[0]->vertex_count;
+            for (int32_t v : gExplainIds) ok = ok && v < (int32_t)graphs[0]->vertex_count;
             if (!ok) {
                 std::cout << "invalid arguments" << std::endl;
                 PrintUsage();

@@ -271,6 +271,7 @@ public:
             if (gAssign) PrintAssign(stream_batch_count);
             if (!gRefineIds.empty()) PrintRefined(-1);
             if (!gPositionIds.empty()) PrintPositions(-1);
+            if (!gExplainIds.empty()) PrintExplained(-1);
             if (gClusterK > 0) PrintClusters(-1);
             if (gSubgraphK > 0) PrintSubgraphs(-1);
         }
@@ -368,6 +369,7 @@ public:
             if (gAssign) PrintAssign(stream_batch_count);
             if (!gRefineIds.empty()) PrintRefined(epoch); // (the epoch the states stand on: the helper may have built the next one)
             if (!gPositionIds.empty()) PrintPositions(epoch);
+            if (!gExplainIds.empty()) PrintExplained(epoch);
             if (gClusterK > 0) PrintClusters(epoch);
             if (gSubgraphK > 0) PrintSubgraphs(epoch);
         }
@@ -716,6 +718,50 @@ public:
                 std::snprintf(line, sizeof(line), "positions %d qualifying %d\n", (int)source_vertex_ids[first + j], (int)cnt[j]);
                 out += line;
             }
+        }
+        progress++;
+        static std::mutex print_mu;
+        std::lock_guard<std::mutex> lk(print_mu);
+        std::cout << out << std::flush;
+    }
+
+    // --explain: after a batch, per source of this device and per listed vertex, the path of largest contributions towards the source
+    // and the out-neighbours that contribute most (dppr_explain_at / dppr_group_explain_at over `epoch`). Outside the timed region,
+    // printed as one block like --changes.
+    void PrintExplained(int32_t epoch) {
+        const size_t n_src = source_vertex_ids.size(), m = gExplainIds.size();
+        const size_t f = (size_t)gExplainTop, dp = (size_t)gExplainDepth + 1;
+        std::vector<int32_t> cnt, nbr, mult, len, end, path;
+        std::vector<double> c;
+        std::string out;
+        char line[200];
+        for (size_t first = 0; first < n_src; first += use_groups ? kGroupMax : 1) {
+            const size_t n = use_groups ? std::min(kGroupMax, n_src - first) : 1;
+            cnt.assign(m * n, 0), len.assign(m * n, 0), end.assign(m * n, 0);
+            nbr.assign(m * n * f + 1, -1), mult.assign(m * n * f + 1, 0), c.assign(m * n * f + 1, 0.0), path.assign(m * n * dp, -1);
+            dppr_explain_out_t o{};
+            o.nbr_count = cnt.data(), o.nbr = nbr.data(), o.nbr_mult = mult.data(), o.nbr_c = c.data();
+            o.len = len.data(), o.end = end.data(), o.path = path.data();
+            if (use_groups)
+                DPPR_CHECK(engine, dppr_group_explain_at(engine, groups[first / kGroupMax], epoch, gExplainIds.data(), (int32_t)m, gExplainTop, gExplainDepth, &o));
+            else
+                DPPR_CHECK(engine, dppr_explain_at(engine, slots[first], epoch, gExplainIds.data(), (int32_t)m, gExplainTop, gExplainDepth, &o));
+            for (size_t j = 0; j < n; ++j)
+                for (size_t q = 0; q < m; ++q) {
+                    const size_t at = q * n + j;
+                    const int src = (int)source_vertex_ids[first + j], v = (int)gExplainIds[q];
+                    std::snprintf(line, sizeof(line), "explain %d %d %d %d", src, v, (int)end[at], (int)len[at]);
+                    out += line;
+                    for (int t = 0; t < len[at]; ++t) {
+                        std::snprintf(line, sizeof(line), " %d", (int)path[at * dp + (size_t)t]);
+                        out += line;
+                    }
+                    out += "\n";
+                    for (int k = 0; k < cnt[at]; ++k) {
+                        std::snprintf(line, sizeof(line), "because %d %d %d %d %.17g\n", src, v, (int)nbr[at * f + (size_t)k], (int)mult[at * f + (size_t)k], c[at * f + (size_t)k]);
+                        out += line;
+                    }
+                }
         }
         progress++;
         static std::mutex print_mu;

@@ -983,6 +983,79 @@ int dppr_group_position_at(dppr_engine *e, int32_t group, int32_t epoch, const d
                            int32_t *out_counts /* [n], may be NULL */);
 int dppr_debug_position_tile(dppr_engine *e, int queries);
 
+/* ---- explain a score: top contributing out-edges and the path to the seeds (backward-compatible additions, ABI 6) ----
+ * The queries above answer WHAT is near a lane's target. These answer WHY a vertex has the score it has. The invariant every lane
+ * keeps,
+ *     p_i[u] + alpha r_i[u] = alpha h_i[u] + sum over stored out-edges u -> w of (1 - alpha) p_i[w] / (outdeg(u) + 1),
+ * is an exact decomposition of p_i[u] into its own seed term and one term per out-neighbour; following the largest term hop by
+ * hop gives the strongest chain from u to the lane's seeds. Without these calls the answer is dppr_group_read of every column,
+ * dppr_read_out_graph and a group-by on the host. Every value below is reproducible by numpy bit for bit.
+ *
+ * For lane i and a vertex u with a row in `epoch`:
+ *   DEGREE        d(u) is the stored out-degree, duplicates counted, as dppr_read_out_graph shows it. A vertex without an internal
+ *                 id, or parked, has d = 0 and no heads.
+ *   HEADS         the DISTINCT heads w of u's out-row; mult(u, w) is the number of stored copies. A self loop is a head like any
+ *                 other.
+ *   CONTRIBUTION  c_i(u, w) = (((1.0 - 0.15) * p_i[w]) * (double)mult) / (double)(d(u) + 1): two multiplications and one IEEE
+ *                 division, in this order, never contracted. 1.0 - 0.15 is the double 0x1.b333333333333p-1 (the literal 0.85).
+ *   CONTRIBUTOR ORDER of (u, i): the heads with c > 0 (false for a NaN and for negatives), c descending, external id of the head
+ *                 ascending.
+ *   OWN TERM      self_i[u] = 0.15 * h_i[u]: h is the indicator of the source for a source lane, the seed weight for a set lane,
+ *                 0.0 otherwise.
+ * Outputs are vertex-major [m][n] as the state and as dppr_position_at (a slot is n = 1). Per query id ids[j]:
+ *   deg[j], distinct[j]   d and the number of distinct heads (they do not depend on the lane)
+ *   self[j][i]            the own term
+ *   TOP f CONTRIBUTORS    nbr_count[j][i] = min(f, #heads with c > 0); nbr[j][i][0..f) holds external ids, -1 past the count;
+ *                         nbr_mult holds 0 and nbr_c 0.0 past the count; all three follow the contributor order.
+ *   PATH of at most `depth` hops. path[j][i][0] = ids[j] always. At u = path[t] the first rule that applies decides:
+ *       1. h_i[u] > 0                                  -> DPPR_EXPLAIN_END_SEED (0)
+ *       2. t == depth                                  -> DPPR_EXPLAIN_END_DEPTH (1)
+ *       3. the contributor order of (u, i) is empty    -> DPPR_EXPLAIN_END_DEAD (2)
+ *       4. its first head is already on the path (u itself included: a self loop) -> DPPR_EXPLAIN_END_CYCLE (3)
+ *       5. otherwise that head becomes path[t + 1], path_c[j][i][t] is its contribution, and t advances.
+ *     len[j][i] = t + 1 in [1, depth + 1]; end[j][i] the code above; path is -1 past len; path_c is 0.0 past len - 1;
+ *     path_p[j][i][t] = p_i[path[t]] is the stored double (0.0 for a vertex without a row), 0.0 past len.
+ * A duplicate id gives the same answer in each of its places. Prefix property: the path for depth' < depth is the head of the
+ * longer one, with END_DEPTH where it was cut.
+ *
+ * Limits: m in [0, DPPR_EXPLAIN_MAX_M], f in [0, DPPR_EXPLAIN_MAX_F], depth in [0, DPPR_EXPLAIN_MAX_DEPTH], f + depth >= 1.
+ * m == 0 is valid and writes nothing. Every pointer of dppr_explain_out_t may be NULL: only what is asked for is computed and
+ * copied back; all of them are HOST memory.
+ * Epoch rule as dppr_cluster: the epoch must be resident (-1: the newest) and must be the one the state stands on, if that is
+ * known. Convergence is NOT required: the decomposition holds for every state the solver leaves, with r in it.
+ * Rejected with DPPR_ERR_INVALID before any device work, nothing written: m, f or depth outside the limits, f + depth == 0, a NULL
+ * ids or a NULL out with m > 0, an id outside [0, V), a bad slot / group, an epoch that is not resident or not the state's.
+ * Threading and stream as dppr_read: the id-map lock for the whole call (safe beside dppr_slide_concurrent), the solver stream,
+ * never part of the update path or of a timed region. Determinism: the result is a function of the state and the epoch alone; no
+ * output position comes from an atomic. Work space: the result block and its pinned twin, and -- with the memo on -- the one
+ * scratch state of the ranked family; all of it is the engine's, obtained before the first kernel, grown on demand and released
+ * with the engine: after DPPR_ERR_NOMEM the states and the engine are as before. With dppr_set_profiling on, dppr_debug_query_ms
+ * reports the device time of the last of these calls.
+ * dppr_debug_explain: a test hook. memo: -1 the plan decides, 0 off, 1 on -- the table of next hops the path waves share;
+ * wave_rows in [1, 64]: the entries of a row a wave takes per step. The results depend on neither.
+ * OUT OF SCOPE: device destinations, contributors at hops beyond the first, the whole next-hop forest, the in-CSR. */
+#define DPPR_EXPLAIN_MAX_M 4096
+#define DPPR_EXPLAIN_MAX_F 16
+#define DPPR_EXPLAIN_MAX_DEPTH 64
+#define DPPR_EXPLAIN_END_SEED 0
+#define DPPR_EXPLAIN_END_DEPTH 1
+#define DPPR_EXPLAIN_END_DEAD 2
+#define DPPR_EXPLAIN_END_CYCLE 3
+typedef struct { /* every pointer may be NULL: only what is asked for is copied back; HOST memory */
+    int32_t *deg, *distinct;                /* [m]                 */
+    double *self;                           /* [m][n]              */
+    int32_t *nbr_count;                     /* [m][n]              */
+    int32_t *nbr, *nbr_mult; double *nbr_c; /* [m][n][f]           */
+    int32_t *len, *end;                     /* [m][n]              */
+    int32_t *path; double *path_p;          /* [m][n][depth + 1]   */
+    double *path_c;                         /* [m][n][depth] (depth 0: unused) */
+} dppr_explain_out_t;
+int dppr_explain_at(dppr_engine *e, int32_t slot, int32_t epoch, const int32_t *ids, int32_t m, int32_t f, int32_t depth,
+                    const dppr_explain_out_t *out);
+int dppr_group_explain_at(dppr_engine *e, int32_t group, int32_t epoch, const int32_t *ids, int32_t m, int32_t f, int32_t depth,
+                          const dppr_explain_out_t *out);
+int dppr_debug_explain(dppr_engine *e, int memo /* -1 plan decides, 0 off, 1 on */, int wave_rows /* 1 .. 64 */);
+
 /* ---- every vertex to its best lane, across groups (backward-compatible additions, ABI 6) ----
  * The queries above answer per lane. With one lane per class -- sources or target sets -- the question per VERTEX is which lane
  * holds it best: label propagation on a live stream. dppr_assign reduces over the lane axis in one pass over the states, across
