@@ -1662,6 +1662,24 @@ int dppr_debug_explain(dppr_engine *e, int memo, int wave_rows) {
     return DPPR_OK;
 }
 
+int dppr_certify(dppr_engine *e, int32_t slot, int32_t epoch, double eps, int flags, dppr_certify_out_t *out) {
+    GET_SLOT(e, slot);
+    return certify_call(e, s, epoch, eps, flags, out);
+}
+
+int dppr_group_certify(dppr_engine *e, int32_t group, int32_t epoch, double eps, int flags, dppr_certify_out_t *out) {
+    GET_GROUP(e, group);
+    return certify_call(e, g, epoch, eps, flags, out);
+}
+
+int dppr_debug_certify(dppr_engine *e, int piece_edges, int wave_rows) {
+    if (!e || !cert_hook_ok(piece_edges, wave_rows))
+        return fail(e, DPPR_ERR_INVALID, "debug_certify: piece_edges in [0, 2^20], wave_rows 0 or a power of two up to 64 (0: the plan's choice)");
+    e->cert_piece = piece_edges;
+    e->cert_wave_rows = wave_rows;
+    return DPPR_OK;
+}
+
 int dppr_debug_id_map(dppr_engine *e, int32_t *out_ext2int) {
     if (!e || e->broken || !out_ext2int) return fail(e, DPPR_ERR_INVALID, "debug_id_map: non-null out_ext2int");
     std::lock_guard<std::mutex> map_lk(e->map_mu);

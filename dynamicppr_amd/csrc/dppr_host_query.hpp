@@ -1489,4 +1489,103 @@ int explain_call(dppr_engine *e, Owner &o, int32_t epoch, const int32_t *ids, in
     return run_explain(e, v, rank_lanes(o), *ep, ids, m, f, depth, which, *out);
 }
 
+// ---- the certificate of a state: residual norms and the loop invariant (dppr_certify.hpp, dppr_certify_plan.hpp) ----------------
+// The parts `which` names (arguments and the epoch validated by the caller, at least one output). Every buffer is in place before
+// the first kernel -- the block, its pinned twin, the head and the partials, and for the invariant the queue of pieces, their
+// partials and the first plane of the scratch state of the ranked family for S -- and every kernel is enqueued before the one
+// copy back.
+int run_certify(dppr_engine *e, const StateView &v, const RkLanes &l, const Epoch &ep, double eps, uint32_t which, dppr_certify_out_t &out) {
+    if (int rc = query_begin(e, MAP_E2I)) return rc;
+    QueryWork::Certify &cq = e->q.cert;
+    const int n = v.n, gw = v.gw, V = e->V;
+    const bool res = (which & CERT_RES) != 0, inv = (which & CERT_INV) != 0;
+    const CertLayout lay = cert_layout(n, which);
+    const CertWork wk = cert_work();
+    const int piece = cert_piece(e->cert_piece), wave_rows = cert_wave_rows(gw, e->cert_wave_rows);
+    const size_t part_elems = cert_part_elems(V, n), s_elems = scratch_plane_elems((size_t)e->n_int, gw);
+    const size_t cap = cert_list_cap(ep.Ed, piece);
+    Grow grow{e};
+    int rc = grow(cq.blk, lay.total_bytes);
+    if (!rc) rc = grow(cq.pin, lay.total_bytes);
+    if (!rc) rc = grow(cq.ws, wk.bytes);
+    if (!rc && res) rc = grow(cq.part, part_elems);
+    if (!rc && inv) rc = grow(e->q.sc.a, s_elems, with_slack(s_elems));
+    if (!rc && inv) rc = grow(cq.list, cap);
+    if (!rc && inv) rc = grow(cq.pp, cap * (size_t)gw);
+    if (rc) return rc;
+    unsigned char *blk = cq.blk.get();
+    CertHead *head = reinterpret_cast<CertHead *>(cq.ws + wk.off_head);
+    double *sums = reinterpret_cast<double *>(cq.ws + wk.off_sums);
+    CertMax *max_r = reinterpret_cast<CertMax *>(cq.ws + wk.off_max_r), *max_inv = reinterpret_cast<CertMax *>(cq.ws + wk.off_max_inv);
+    auto dbls = [&](uint32_t bit, size_t off) { return (which & bit) ? reinterpret_cast<double *>(blk + off) : nullptr; };
+    auto i64s = [&](uint32_t bit, size_t off) { return (which & bit) ? reinterpret_cast<long long *>(blk + off) : nullptr; };
+    auto ints = [&](uint32_t bit, size_t off) { return (which & bit) ? reinterpret_cast<int *>(blk + off) : nullptr; };
+    const CertOut co{dbls(CERT_MAX_R, lay.off_max_r),      dbls(CERT_SUM_R, lay.off_sum_r),  dbls(CERT_SUM_P, lay.off_sum_p),
+                     dbls(CERT_INV_ERR, lay.off_inv_err),  i64s(CERT_N_POS, lay.off_n_pos),  i64s(CERT_N_NEG, lay.off_n_neg),
+                     i64s(CERT_N_NONFINITE, lay.off_n_nonfinite), i64s(CERT_N_P_NONZERO, lay.off_n_p_nonzero),
+                     ints(CERT_ARGMAX_R, lay.off_argmax_r), ints(CERT_INV_ARG, lay.off_inv_arg)};
+    const int *x2i = e->d_ext2int.get();
+    const dim3 block(CERT_BLOCK);
+    int nwg_r = 0, nwg_inv = 0;
+    if (int rc2 = DeviceTime{e}.open()) return rc2;
+    HIP_TRY(hipMemsetAsync(head, 0, sizeof(CertHead), e->stream));
+    if (res) {
+        const long long stride = dot_cols(V) > 0 ? dot_cols(V) : DOT_TPB;
+        nwg_r = cert_stream_grid(V);
+        HIP_TRY(hipMemsetAsync(cq.part, 0, sizeof(double) * part_elems, e->stream)); // (+0.0: the tiles of padding)
+        hipLaunchKernelGGL(k_cert_residual, dim3((unsigned)nwg_r), block, dot_lds_bytes(n, 1), e->stream, v.p, v.r, gw, n, x2i, V, eps,
+                           cq.part.get(), stride, head, max_r);
+        hipLaunchKernelGGL(k_dot_combine, dim3((2 * n + DOT_CB_WAVES - 1) / DOT_CB_WAVES), dim3(DOT_CB_WAVES * WAVE), 0, e->stream,
+                           cq.part.get(), (const long long *)nullptr, stride, 2 * n, n, &head->dot, sums);
+    }
+    if (inv) {
+        const CertGraph g{ep.out_row_ptr.get(), ep.out_col.get(), e->n_int, V};
+        double *S = e->q.sc.a.get();
+        const unsigned ucap = (unsigned)std::min<size_t>(cap, 0xffffffffu);
+        const int rows_per_wg = CERT_BLOCK / cert_lane_stride(n);
+        nwg_inv = (int)std::max<long long>(1, std::min<long long>(((long long)V + rows_per_wg - 1) / rows_per_wg, CERT_GRID_MAX));
+        hipLaunchKernelGGL(k_cert_rows, dim3((unsigned)cert_rows_grid(e->n_int, wave_rows)), block, 0, e->stream, v.p, gw, g, piece, wave_rows, S,
+                           head, cq.list.get(), ucap);
+        hipLaunchKernelGGL(k_cert_pieces, dim3((unsigned)std::min<size_t>((cap + CERT_WAVES - 1) / CERT_WAVES, 4096)), block, 0, e->stream, v.p,
+                           gw, g, piece, head, cq.list.get(), ucap, cq.pp.get());
+        hipLaunchKernelGGL(k_cert_long, dim3((unsigned)std::min<size_t>((cap * (size_t)gw + CERT_BLOCK - 1) / CERT_BLOCK, 4096)), block, 0,
+                           e->stream, gw, g, piece, head, cq.list.get(), ucap, cq.pp.get(), S);
+        hipLaunchKernelGGL(k_cert_err, dim3((unsigned)nwg_inv), block, 0, e->stream, v.p, v.r, gw, n, x2i, V, g, l, S, max_inv);
+    }
+    hipLaunchKernelGGL(k_cert_finish, dim3((unsigned)n), dim3(WAVE), 0, e->stream, head, sums, n, max_r, nwg_r, max_inv, nwg_inv, co);
+    HIP_TRY(hipGetLastError());
+    if (int rc2 = fetch_block(e, cq.blk, cq.pin, lay.copy_bytes)) return rc2;
+    auto back = [&](uint32_t bit, void *dst, size_t off, size_t elem_bytes) {
+        if (which & bit) memcpy(dst, cq.pin + off, elem_bytes * (size_t)n);
+    };
+    back(CERT_MAX_R, out.max_abs_r, lay.off_max_r, sizeof(double));
+    back(CERT_SUM_R, out.sum_abs_r, lay.off_sum_r, sizeof(double));
+    back(CERT_SUM_P, out.sum_p, lay.off_sum_p, sizeof(double));
+    back(CERT_INV_ERR, out.inv_max_err, lay.off_inv_err, sizeof(double));
+    back(CERT_N_POS, out.n_pos, lay.off_n_pos, sizeof(int64_t));
+    back(CERT_N_NEG, out.n_neg, lay.off_n_neg, sizeof(int64_t));
+    back(CERT_N_NONFINITE, out.n_nonfinite, lay.off_n_nonfinite, sizeof(int64_t));
+    back(CERT_N_P_NONZERO, out.n_p_nonzero, lay.off_n_p_nonzero, sizeof(int64_t));
+    back(CERT_ARGMAX_R, out.argmax_r, lay.off_argmax_r, sizeof(int32_t));
+    back(CERT_INV_ARG, out.inv_argmax, lay.off_inv_arg, sizeof(int32_t));
+    return DPPR_OK;
+}
+
+// (Owner: a Slot or a Group. Its seeds are read under map_mu: a renumbering beside the call renames them)
+template <class Owner>
+int certify_call(dppr_engine *e, Owner &o, int32_t epoch, double eps, int flags, dppr_certify_out_t *out) {
+    const StateView v = view(o);
+    if (!cert_args_ok(eps, flags, out))
+        return fail(e, DPPR_ERR_INVALID, "certify: non-null out, flags DPPR_CERT_RESIDUAL | DPPR_CERT_INVARIANT (1 .. 3), eps > 0");
+    const Epoch *ep = find_epoch(e, epoch);
+    if (!ep) return fail(e, DPPR_ERR_INVALID, "certify: epoch not resident (evicted or never built)");
+    out->state_epoch = v.st.last_epoch;
+    out->converged = v.st.converged ? 1 : 0;
+    out->conv_eps = v.st.conv_eps;
+    const uint32_t which = cert_which(out, flags);
+    if (!which) return DPPR_OK;
+    std::lock_guard<std::mutex> map_lk(e->map_mu); // (as dppr_read: one state of the id space for the whole query)
+    return run_certify(e, v, rank_lanes(o), *ep, eps, which, *out);
+}
+
 } // namespace

@@ -249,6 +249,13 @@ struct QueryWork {
     struct Explain { // top contributors and the path to the seeds (dppr_explain.hpp, dppr_explain_plan.hpp); its memo: the first plane of sc
         DevBuf<unsigned char> blk; PinBuf<unsigned char> pin; // the planes asked for, then the queried ids: device / pinned host
     } exq;
+    struct Certify { // the certificate of a state (dppr_certify.hpp, dppr_certify_plan.hpp); the gathered sums S: the first plane of sc
+        DevBuf<unsigned char> blk; PinBuf<unsigned char> pin; // the planes asked for: device / pinned host
+        DevBuf<unsigned char> ws;        // the head (counters, queued pieces), the two sums, the workgroups' (word, id) partials (cert_work)
+        DevBuf<double> part;             // the partials of the two sums, as the dot family lays them out
+        DevBuf<unsigned long long> list; // the queued pieces of the long rows (cert_list_cap)
+        DevBuf<double> pp;               // [queued pieces][gw] one partial per piece
+    } cert;
     struct Assign { // every vertex to its best lane across groups (dppr_assign.hpp, dppr_assign_plan.hpp); the block grows with a host destination
         DevBuf<double> scale; // [256] the scales of the call
         DevBuf<int> cnt;      // [tiles] flips per tile
@@ -433,6 +440,8 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     int pos_tile = 0;               // queries of a lane's order a workgroup of k_pos_count holds per pass; 0: the plan's choice (dppr_debug_position_tile)
     int ex_memo = -1;               // the memo of k_ex_path: -1 the plan's choice, 0 off, 1 on (dppr_debug_explain)
     int ex_wave_rows = EX_WAVE_ROWS; // entries of a row a wave of dppr_explain.hpp takes per step (dppr_debug_explain)
+    int cert_piece = 0;             // edges of a piece of a long row in k_cert_rows; 0: the plan's choice (dppr_debug_certify)
+    int cert_wave_rows = 0;         // short rows that share a wave of k_cert_rows; 0: the plan's choice (dppr_debug_certify)
     float query_ms = -1.0f;         // dppr_set_profiling: device time of the last top-k, changes, export or dot call, first to last kernel (dppr_debug_query_ms)
     std::vector<int32_t> h_tmp1, h_tmp2;
     std::vector<int32_t> h_tiles; // host copy of the tile edge prefix / group table

@@ -25,6 +25,7 @@
 //   dppr_churn.hpp    a source group changes its sources: column init, row re-interleaving
 //   dppr_targets.hpp  weighted vertex sets as a group's targets: seed table lookup, seeded Init (included by dppr_update.hpp)
 //   dppr_multi.hpp    multi-source batched sweeps (included separately by the engine)
+//   dppr_certify.hpp  the certificate of a state: residual norms and the loop invariant against an epoch's out-CSR (a query)
 #pragma once
 
 #include "dppr_common.hpp"
@@ -34,3 +35,4 @@
 #include "dppr_update.hpp"
 #include "dppr_builder.hpp"
 #include "dppr_churn.hpp"
+#include "dppr_certify.hpp"

@@ -75,6 +75,7 @@ EXPORTS = [
     "dppr_assign", "dppr_assign_at",
     "dppr_position_at", "dppr_group_position_at", "dppr_debug_position_tile",
     "dppr_explain_at", "dppr_group_explain_at", "dppr_debug_explain",
+    "dppr_certify", "dppr_group_certify", "dppr_debug_certify",
 ]
 
 DEST_HOST, DEST_DEVICE = 0, 1
@@ -96,6 +97,7 @@ ASSIGN_GROUPS_MAX, ASSIGN_CLASSES_MAX = 16, 256
 POSITION_MAX = 4096
 EXPLAIN_MAX_M, EXPLAIN_MAX_F, EXPLAIN_MAX_DEPTH = 4096, 16, 64
 END_SEED, END_DEPTH, END_DEAD, END_CYCLE = 0, 1, 2, 3
+CERT_RESIDUAL, CERT_INVARIANT = 1, 2
 
 
 class RankSpec(C.Structure):
@@ -109,6 +111,15 @@ class ExplainOut(C.Structure):
     _ip, _dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
     _fields_ = [("deg", _ip), ("distinct", _ip), ("self", _dp), ("nbr_count", _ip), ("nbr", _ip), ("nbr_mult", _ip), ("nbr_c", _dp),
                 ("len", _ip), ("end", _ip), ("path", _ip), ("path_p", _dp), ("path_c", _dp)]
+
+
+class CertifyOut(C.Structure):
+    """dppr_certify_out_t: where the outputs of a certify call go (host memory, [n]; a NULL is not computed), and what the last
+    solve left, written by the call."""
+    _ip, _dp, _lp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int64)
+    _fields_ = [("max_abs_r", _dp), ("argmax_r", _ip), ("sum_abs_r", _dp), ("sum_p", _dp), ("n_pos", _lp), ("n_neg", _lp),
+                ("n_nonfinite", _lp), ("n_p_nonzero", _lp), ("inv_max_err", _dp), ("inv_argmax", _ip),
+                ("state_epoch", C.c_int32), ("converged", C.c_int32), ("conv_eps", C.c_double)]
 
 
 class Cluster(C.Structure):
@@ -253,6 +264,9 @@ def lib():
     L.dppr_explain_at.argtypes = [vp, C.c_int32, C.c_int32, ip, C.c_int32, C.c_int32, C.c_int32, vp]
     L.dppr_group_explain_at.argtypes = [vp, C.c_int32, C.c_int32, ip, C.c_int32, C.c_int32, C.c_int32, vp]
     L.dppr_debug_explain.argtypes = [vp, C.c_int, C.c_int]
+    L.dppr_certify.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int, vp]
+    L.dppr_group_certify.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int, vp]
+    L.dppr_debug_certify.argtypes = [vp, C.c_int, C.c_int]
     L.dppr_assign.argtypes = [vp, ip, C.c_int32, dp, C.c_double, C.c_int, vp, vp, vp, i64p, vp, C.c_int64, i64p, vp, vp, vp]
     L.dppr_assign_at.argtypes = [vp, ip, C.c_int32, dp, C.c_double, ip, C.c_int32, ip, dp, ip, dp]
     for name in EXPORTS:
@@ -835,6 +849,39 @@ class Engine:
         """Test hook (dppr_debug_explain): memo -1 the plan's choice, 0 off, 1 on; wave_rows 1 .. 64 entries of a row per wave and
         step. The results depend on neither."""
         self._ck(self._L.dppr_debug_explain(self._h, int(memo), int(wave_rows)), "debug_explain")
+
+    # ---- certify a state: residual norms and the loop invariant ----
+    _CERT_RESIDUAL = {"max_abs_r": np.float64, "argmax_r": np.int32, "sum_abs_r": np.float64, "sum_p": np.float64, "n_pos": np.int64,
+                      "n_neg": np.int64, "n_nonfinite": np.int64, "n_p_nonzero": np.int64}
+    _CERT_INVARIANT = {"inv_max_err": np.float64, "inv_argmax": np.int32}
+
+    def _certify(self, fn, which, n, eps, epoch, residual, invariant, what):
+        names = dict(self._CERT_RESIDUAL if residual else {})
+        names.update(self._CERT_INVARIANT if invariant else {})
+        res = {k: np.zeros(n, dtype=dt) for k, dt in names.items()}
+        out = CertifyOut()
+        for k, arr in res.items():
+            ctype = {np.dtype(np.float64): C.c_double, np.dtype(np.int32): C.c_int32, np.dtype(np.int64): C.c_int64}[arr.dtype]
+            setattr(out, k, arr.ctypes.data_as(C.POINTER(ctype)))
+        flags = (CERT_RESIDUAL if residual else 0) | (CERT_INVARIANT if invariant else 0)
+        self._ck(fn(self._h, int(which), int(epoch), float(eps), flags, C.byref(out)), what)
+        res.update(state_epoch=int(out.state_epoch), converged=int(out.converged), conv_eps=float(out.conv_eps))
+        return res
+
+    def certify(self, slot, eps, epoch=-1, residual=True, invariant=True):
+        """Whether a slot's state is still right, decided on the device (include/dppr.h: dppr_certify): a dict of numpy arrays of
+        one entry -- max_abs_r, argmax_r, sum_abs_r, sum_p, n_pos, n_neg, n_nonfinite, n_p_nonzero (residual), inv_max_err,
+        inv_argmax (invariant, against the out-edges of `epoch`) -- plus state_epoch, converged and conv_eps of the last solve."""
+        return self._certify(self._L.dppr_certify, slot, 1, eps, epoch, residual, invariant, "certify")
+
+    def group_certify(self, group, eps, epoch=-1, residual=True, invariant=True):
+        """certify for every lane of a group at once: the same dict, every array with one entry per lane."""
+        return self._certify(self._L.dppr_group_certify, group, self._group_n.get(group, 1), eps, epoch, residual, invariant, "group_certify")
+
+    def debug_certify(self, piece_edges=0, wave_rows=0):
+        """Test hook (dppr_debug_certify): out-rows longer than piece_edges are summed in pieces; wave_rows short rows share a wave
+        (a power of two up to 64); 0: the plan's choice. Both change the order of the additions inside the invariant's sums only."""
+        self._ck(self._L.dppr_debug_certify(self._h, int(piece_edges), int(wave_rows)), "debug_certify")
 
     # ---- every vertex to its best lane, across groups ----
     def _assign_classes(self, groups, scale, what):

@@ -194,6 +194,11 @@ inline void PrintUsage() {
               << "            (0 <= D <= 64, default 16): explain <source> <vertex> <end> <len> <v0> <v1> ...  (end 0 seed, 1 depth, 2 dead end, 3 cycle),\n"
               << "            then the F out-neighbours that contribute most to its pagerank (0 <= F <= 16, default 3, F + D >= 1):\n"
               << "            because <source> <vertex> <neighbour> <stored copies> <contribution>   (not with --split)\n"
+              << "--certify <N>: after the initial solve and after every N-th batch (N >= 1) certify every source's state on the device, against the\n"
+              << "            batch's own graph: certify <source> epoch=<id> max_r=<largest |r|> at=<vertex> sum_r=<sum of |r|> legal=<vertices still\n"
+              << "            legal to push> nonfinite=<rows with a NaN or inf> inv=<largest violation of the invariant> inv_at=<vertex>; the program\n"
+              << "            prints CERTIFY FAILED: ... and exits non-zero if legal > 0, nonfinite > 0 or inv >= 1e-13 * max(1, sum of the lane's\n"
+              << "            seed weights)   (not with --split)\n"
               << "--cluster <K> [--cluster-min <P>] [--cluster-min-size <M>]: after every batch print, per source in source order, the prefix of\n"
               << "            lowest conductance of the source's K vertices of largest pagerank > P (1 <= K <= 8192, P >= 0, 1 <= M <= K vertices\n"
               << "            at least): cluster <source> size <vertices> cut <edges leaving it> vol <its out-degrees> phi <conductance>\n"
@@ -258,6 +263,7 @@ inline void ArgumentsChecker() {
     if (!gExplainFile.empty() && (gExplainIds.size() > (size_t)DPPR_EXPLAIN_MAX_M || gSplitInterface || gExplainTop < 0 || gExplainTop > DPPR_EXPLAIN_MAX_F ||
                                   gExplainDepth < 0 || gExplainDepth > DPPR_EXPLAIN_MAX_DEPTH || gExplainTop + gExplainDepth < 1))
         ok = false;
+    if (gCertifyGiven && (gCertifyBad || gCertify < 1 || gSplitInterface)) ok = false;
     if (gClusterGiven && (gClusterK < 1 || gClusterK > DPPR_CLUSTER_MAX || !(gClusterMin >= 0.0) || gClusterMinSize < 1 || gClusterMinSize > gClusterK))
         ok = false;
     if (gClusterOptsGiven && !gClusterGiven) ok = false;
@@ -335,6 +341,13 @@ inline void ArgumentsParser(int argc, char **argv) {
     gExplainOptsGiven = find(argc, argv, "--explain-top") != nullptr || find(argc, argv, "--explain-depth") != nullptr;
     gExplainTop = as_int(argc, argv, "--explain-top", 3);
     gExplainDepth = as_int(argc, argv, "--explain-depth", 16);
+    if (const char *v = find(argc, argv, "--certify")) { // (a whole number, all of the token)
+        gCertifyGiven = true;
+        char *end = nullptr;
+        const long x = std::strtol(v, &end, 10);
+        gCertifyBad = end == v || *end != '\0' || x > 1000000000l;
+        gCertify = gCertifyBad || x < 0 ? 0 : (int)x;
+    }
     gWalksGiven = find(argc, argv, "--walks") != nullptr;
     gWalks = as_int(argc, argv, "--walks", 0);
     if (const char *v = find(argc, argv, "--walk-seed")) gWalkSeed = std::strtoull(v, nullptr, 0);

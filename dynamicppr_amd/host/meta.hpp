@@ -72,6 +72,9 @@ inline std::vector<int32_t> gExplainIds;
 inline int gExplainTop = 3;           // --explain-top F : contributors listed per id and source
 inline int gExplainDepth = 16;        // --explain-depth D : hops of the path at the most
 inline bool gExplainOptsGiven = false;
+inline int gCertify = 0;              // --certify N : after the initial solve and after every N-th batch print certify <source> epoch=.. max_r=.. ... (dppr_certify / dppr_group_certify)
+inline bool gCertifyGiven = false;
+inline bool gCertifyBad = false;      //   N is not a whole number
 inline int gWalks = 0;                // --walks W : walks per refined vertex (with --refine)
 inline bool gWalksGiven = false;
 inline unsigned long long gWalkSeed = 0; // --walk-seed S

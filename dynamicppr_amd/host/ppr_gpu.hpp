@@ -150,6 +150,7 @@ public:
             for (int32_t gid : groups) DPPR_CHECK(engine, dppr_group_mark(engine, gid));
             for (int32_t sl : slots) DPPR_CHECK(engine, dppr_mark(engine, sl));
         }
+        if (gCertify > 0) PrintCertify(-1); // --certify: the from-scratch solution first
         prof.End(HostProfile::INIT_GRAPH_CALC);
         prof.Start(HostProfile::DYNA_GRAPH_CALC);
         if (overlap_) SlidingWindowExecuteOverlapped();
@@ -272,6 +273,7 @@ public:
             if (!gRefineIds.empty()) PrintRefined(-1);
             if (!gPositionIds.empty()) PrintPositions(-1);
             if (!gExplainIds.empty()) PrintExplained(-1);
+            if (gCertify > 0 && stream_batch_count % (size_t)gCertify == 0) PrintCertify(-1);
             if (gClusterK > 0) PrintClusters(-1);
             if (gSubgraphK > 0) PrintSubgraphs(-1);
         }
@@ -370,6 +372,7 @@ public:
             if (!gRefineIds.empty()) PrintRefined(epoch); // (the epoch the states stand on: the helper may have built the next one)
             if (!gPositionIds.empty()) PrintPositions(epoch);
             if (!gExplainIds.empty()) PrintExplained(epoch);
+            if (gCertify > 0 && stream_batch_count % (size_t)gCertify == 0) PrintCertify(epoch); // (the explicit epoch: the helper may have built the next one)
             if (gClusterK > 0) PrintClusters(epoch);
             if (gSubgraphK > 0) PrintSubgraphs(epoch);
         }
@@ -767,6 +770,51 @@ public:
         static std::mutex print_mu;
         std::lock_guard<std::mutex> lk(print_mu);
         std::cout << out << std::flush;
+    }
+
+    // --certify: the certificate of every source's state over `epoch` (dppr_certify / dppr_group_certify, both parts): one line per
+    // source in source order; legal > 0, nonfinite > 0 or inv >= 1e-13 * max(1, sum of the lane's seed weights) -- the bound
+    // ValidateResult holds set lanes to -- ends the program. Outside the timed region, printed as one block like --changes.
+    void PrintCertify(int32_t epoch) {
+        const size_t n_src = source_vertex_ids.size();
+        std::string out, failed;
+        char line[400];
+        for (size_t first = 0; first < n_src; first += use_groups ? kGroupMax : 1) {
+            const size_t n = use_groups ? std::min(kGroupMax, n_src - first) : 1;
+            std::vector<double> max_r(n), sum_r(n), inv(n);
+            std::vector<int32_t> at(n), inv_at(n);
+            std::vector<int64_t> pos(n), neg(n), nonfinite(n);
+            dppr_certify_out_t o{};
+            o.max_abs_r = max_r.data(), o.argmax_r = at.data(), o.sum_abs_r = sum_r.data();
+            o.n_pos = pos.data(), o.n_neg = neg.data(), o.n_nonfinite = nonfinite.data();
+            o.inv_max_err = inv.data(), o.inv_argmax = inv_at.data();
+            const int flags = DPPR_CERT_RESIDUAL | DPPR_CERT_INVARIANT;
+            if (use_groups) DPPR_CHECK(engine, dppr_group_certify(engine, groups[first / kGroupMax], epoch, gTolerance, flags, &o));
+            else DPPR_CHECK(engine, dppr_certify(engine, slots[first], epoch, gTolerance, flags, &o));
+            for (size_t j = 0; j < n; ++j) {
+                double total = 1.0; // (sum of h: a source lane's indicator)
+                if (!target_lanes.empty()) {
+                    total = 0.0;
+                    for (const auto &sd : gTargetSets[target_lanes[first + j]]) total += sd.second;
+                }
+                const double bound = 1e-13 * std::max(1.0, total);
+                const long long legal = (long long)(pos[j] + neg[j]);
+                std::snprintf(line, sizeof(line), "certify %d epoch=%d max_r=%.17g at=%d sum_r=%.17g legal=%lld nonfinite=%lld inv=%.17g inv_at=%d\n",
+                              (int)source_vertex_ids[first + j], (int)o.state_epoch, max_r[j], (int)at[j], sum_r[j], legal, (long long)nonfinite[j],
+                              inv[j], (int)inv_at[j]);
+                out += line;
+                if (failed.empty() && (legal > 0 || nonfinite[j] > 0 || !(inv[j] < bound))) {
+                    std::snprintf(line, sizeof(line), "CERTIFY FAILED: source %d legal=%lld nonfinite=%lld inv=%.17g bound=%.17g\n",
+                                  (int)source_vertex_ids[first + j], legal, (long long)nonfinite[j], inv[j], bound);
+                    failed = line;
+                }
+            }
+        }
+        progress++;
+        static std::mutex print_mu;
+        std::lock_guard<std::mutex> lk(print_mu);
+        std::cout << out << failed << std::flush;
+        if (!failed.empty()) std::exit(-1);
     }
 
     // --cluster: after a batch, the prefix of lowest conductance of every source's top-K order over `epoch` (dppr_cluster /

@@ -1056,6 +1056,67 @@ int dppr_group_explain_at(dppr_engine *e, int32_t group, int32_t epoch, const in
                           const dppr_explain_out_t *out);
 int dppr_debug_explain(dppr_engine *e, int memo /* -1 plan decides, 0 off, 1 on */, int wave_rows /* 1 .. 64 */);
 
+/* ---- certify a state: residual norms and the loop invariant (backward-compatible additions, ABI 6) ----
+ * The queries above read a state. These say whether it is still RIGHT, without a dense read: any state that keeps the invariant
+ *     p_i + alpha r_i = alpha h_i + M p_i
+ * satisfies |p - p*|inf <= max_abs_r (p* = alpha h + M p* is the fixed point, so p - p* = M (p - p*) - alpha r; M has
+ * non-negative entries and row sums <= 1 - alpha, hence |p - p*|inf <= (1 - alpha) |p - p*|inf + alpha |r|inf). "max |r| per
+ * lane" plus "the invariant holds to rounding" is therefore a complete certificate of accuracy; no fixed point is computed and
+ * the state is only read.
+ *
+ * ROWS. Every external id that has an internal id takes part, in the live zone and the parked zone, as dppr_topk sees them. A
+ * vertex without an id has p = r = 0 and contributes nothing. Outputs are [n], one entry per lane (a slot: n = 1).
+ * RESIDUAL PART (DPPR_CERT_RESIDUAL).
+ *   n_pos[i], n_neg[i]   rows with r > eps and with r < -eps. The inequalities are strict: the test of the solver's loops (phase 0
+ *                        and phase 1), so r == eps is not counted.
+ *   n_nonfinite[i]       rows where p or r is NaN or +-inf. Such a row counts here only: it takes no part in any other output
+ *                        of this part, and its slot in the two sums holds +0.0.
+ *   max_abs_r[i]         the largest |r_i[v]|; 0.0 with argmax_r[i] = -1 if the lane has no finite row. argmax_r[i] is the
+ *                        SMALLEST external id that attains it.
+ *   sum_abs_r[i], sum_p[i]  the fold of the dot family (section dot above): the term |r_i[v]| (respectively p_i[v]) sits at slot
+ *                        v, blocks of 2^16 slots, a block summed by the balanced tree that adds neighbours, the blocks added in
+ *                        ascending order; the slot of a vertex without an id holds +0.0. sum_p[i] is bit for bit what
+ *                        dppr_dot_dense_dev returns for h = 1, and numpy reproduces both sums bit for bit.
+ *   n_p_nonzero[i]       rows with p != 0.
+ * INVARIANT PART (DPPR_CERT_INVARIANT), against the out-CSR of `epoch` (-1: the newest). For every row u and lane i
+ *     err_i[u] = | (p_i[u] + 0.15 * r_i[u]) - (0.15 * h_i[u] + (0.85 * S_i[u]) / (double)(d(u) + 1)) |
+ *   S_i[u] is the sum of p_i[w] over the STORED out-edges u -> w: duplicates count as stored, self loops count. d(u) is the number
+ *   of stored out-edges. h_i is the lane's seed vector: 1.0 at the source of a source lane, the seed weights of a set lane. A
+ *   parked row has d = 0 and S = 0. inv_max_err[i] is the largest err_i[u] (an err that is not finite takes no part; 0.0 and
+ *   inv_argmax[i] = -1 if there is none); inv_argmax[i] is the smallest external id among the rows that attain the device's own
+ *   maximum. The ORDER of the additions inside S is the device's and is not part of the contract (rows are stored by internal id):
+ *   two calls on the same state with the same dppr_debug_certify setting return identical bits, and any setting agrees with the
+ *   plain sum to rounding. The call does NOT require that the state stands on `epoch`: state_epoch tells which epoch it stands on
+ *   (-2: unknown, e.g. after dppr_write); against another epoch the result is simply the violation that graph implies.
+ *   Convergence is not required.
+ * state_epoch, converged and conv_eps are written by every accepted call: what the last solve left.
+ * Rejected with DPPR_ERR_INVALID before any device work, nothing written: a NULL out, flags outside 1..3, an eps that is not
+ * positive (a NaN is not), a bad slot / group, an epoch that is not resident, an engine that is broken. Every pointer of
+ * dppr_certify_out_t may be NULL; a part all of whose pointers are NULL is simply not run.
+ * Threading and stream as dppr_explain_at: the id-map lock for the whole call (safe beside dppr_slide_concurrent with an explicit
+ * epoch <= k), the solver stream, never part of the update path or of a timed region. Work space: the result block, its pinned
+ * twin, the partials and the queue of pieces, and the one scratch state of the ranked family for S; all of it is the engine's,
+ * obtained before the first kernel, grown on demand and released with the engine: after DPPR_ERR_NOMEM the states and the engine
+ * are as before. With dppr_set_profiling on, dppr_debug_query_ms reports the device time. Results do not depend on the grid size
+ * or on scheduling; no output value comes from a floating-point atomic.
+ * dppr_debug_certify: a test hook. piece_edges in [0, 2^20]: out-rows longer than this are summed in pieces of this many edges;
+ * wave_rows in {0, 1, 2, 4, .. 64}: the short rows that share a wave (never more than the wave has teams). 0: the plan decides.
+ * OUT OF SCOPE: the fixed point or any power iteration, repairing a state, several groups in one call. */
+#define DPPR_CERT_RESIDUAL  1
+#define DPPR_CERT_INVARIANT 2
+typedef struct {            /* every pointer is HOST memory, [n] (a slot: n = 1), any may be NULL */
+    double  *max_abs_r;   int32_t *argmax_r;    /* external id; -1 if the lane has no finite r */
+    double  *sum_abs_r;   double  *sum_p;
+    int64_t *n_pos;       int64_t *n_neg;       /* r > eps, r < -eps: dppr::legal, phase 0 and phase 1 */
+    int64_t *n_nonfinite;                       /* rows where p or r is NaN or +-inf */
+    int64_t *n_p_nonzero;
+    double  *inv_max_err; int32_t *inv_argmax;  /* DPPR_CERT_INVARIANT only */
+    int32_t state_epoch;  int32_t converged;  double conv_eps;   /* written by the call: what the last solve left (SolveState) */
+} dppr_certify_out_t;
+int dppr_certify(dppr_engine *e, int32_t slot, int32_t epoch, double eps, int flags, dppr_certify_out_t *out);
+int dppr_group_certify(dppr_engine *e, int32_t group, int32_t epoch, double eps, int flags, dppr_certify_out_t *out);
+int dppr_debug_certify(dppr_engine *e, int piece_edges /* 0: the plan decides */, int wave_rows /* 0: the plan decides */);
+
 /* ---- every vertex to its best lane, across groups (backward-compatible additions, ABI 6) ----
  * The queries above answer per lane. With one lane per class -- sources or target sets -- the question per VERTEX is which lane
  * holds it best: label propagation on a live stream. dppr_assign reduces over the lane axis in one pass over the states, across
