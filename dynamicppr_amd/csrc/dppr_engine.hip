@@ -47,6 +47,7 @@
 #include "dppr_wquery.hpp"
 #include "dppr_changes.hpp"
 #include "dppr_export.hpp"
+#include "dppr_patch.hpp"
 #include "dppr_dot.hpp"
 #include "dppr_walk.hpp"
 #include "dppr_cluster.hpp"
@@ -1491,6 +1492,18 @@ int dppr_group_export_sparse(dppr_engine *e, int32_t group, double min_p, int64_
                              int32_t *out_ids, double *out_p, double *out_r) {
     GET_GROUP(e, group);
     return export_sparse_call(e, view(g), min_p, cap, dest, out_offsets, out_ids, out_p, out_r);
+}
+
+int dppr_patch(dppr_engine *e, int32_t slot, double min_p, double min_delta, int64_t cap_up, int64_t cap_del, int dest, int remark,
+               dppr_patch_out_t *out) {
+    GET_SLOT(e, slot);
+    return patch_call(e, view(s), min_p, min_delta, cap_up, cap_del, dest, remark, out);
+}
+
+int dppr_group_patch(dppr_engine *e, int32_t group, double min_p, double min_delta, int64_t cap_up, int64_t cap_del, int dest,
+                     int remark, dppr_patch_out_t *out) {
+    GET_GROUP(e, group);
+    return patch_call(e, view(g), min_p, min_delta, cap_up, cap_del, dest, remark, out);
 }
 
 int dppr_export_dense_dev(dppr_engine *e, int32_t slot, int which, int dtype, void *dst_device) {

@@ -511,6 +511,86 @@ int export_dense_call(dppr_engine *e, const StateView &v, int which, int dtype, 
     return run_export_dense(e, v, which, dtype, layout, dst);
 }
 
+// ---- the patch feed (dppr_patch.hpp, dppr_patch_plan.hpp) ---------------------------------------------------------------------
+// workspace by V, the block by what the call copies back: in place before anything is written
+int patch_workspace(dppr_engine *e, size_t block_bytes) {
+    QueryWork::Patch &pt = e->q.pt;
+    const PtWork w = pt_workspace(e->V);
+    Grow grow{e};
+    int rc = grow(pt.mask, w.mask_elems);
+    if (!rc) rc = grow(pt.cnt, w.cnt_elems);
+    if (!rc) rc = grow(pt.base, w.base_elems);
+    if (!rc) rc = grow(pt.blk, block_bytes);
+    if (!rc) rc = grow(pt.pin, block_bytes);
+    return rc;
+}
+
+// The patch of every lane of a state against its mark (arguments, the mark and a device destination validated by the caller).
+// The offsets are decided on the device and so is whether the fill and the re-mark run: nothing is read back between the kernels;
+// one copy brings the head -- and a host destination's ids and p -- back.
+int run_patch(dppr_engine *e, const StateView &v, double min_p, double min_delta, int64_t cap_up, int64_t cap_del, int dest, int remark,
+              dppr_patch_out_t *out) {
+    if (int rc = query_begin(e, MAP_E2I)) return rc;
+    QueryWork::Patch &pt = e->q.pt;
+    const int n = v.n;
+    const bool host = dest == DPPR_DEST_HOST;
+    const int64_t cu = ex_cap_clamped(cap_up, e->V, n), cd = ex_cap_clamped(cap_del, e->V, n);
+    const PtLayout lay = pt_layout(host ? cu : 0, host ? cd : 0);
+    if (int rc = patch_workspace(e, lay.total_bytes)) return rc;
+    unsigned char *blk = pt.blk.get();
+    PtHead *head = reinterpret_cast<PtHead *>(blk);
+    int *d_up_ids = host ? reinterpret_cast<int *>(blk + lay.off_up_ids) : out->up_ids;
+    double *d_up_p = host ? reinterpret_cast<double *>(blk + lay.off_up_p) : out->up_p;
+    int *d_del_ids = host ? reinterpret_cast<int *>(blk + lay.off_del_ids) : out->del_ids;
+    const int tiles = (int)ex_tiles(e->V), grid = std::min(tiles, 2048);
+    if (int rc = DeviceTime{e}.open()) return rc;
+    hipLaunchKernelGGL(k_pt_classify, dim3(grid), dim3(EX_TILE), 0, e->stream, v.p, v.gw, n, e->d_ext2int.get(), e->V, v.mark.get(), min_p,
+                       min_delta, pt.mask.get(), pt.cnt.get());
+    hipLaunchKernelGGL(k_pt_scan, dim3(1), dim3(PT_LANES * WAVE), 0, e->stream, pt.cnt.get(), n, tiles, (long long)cu, (long long)cd,
+                       pt.base.get(), head);
+    if (cu > 0 || cd > 0 || remark != DPPR_PATCH_KEEP_MARK) // (the size query has nothing to fill and nothing to mark)
+        hipLaunchKernelGGL(k_pt_fill, dim3(grid), dim3(EX_TILE), 0, e->stream, v.p, v.gw, n, e->d_ext2int.get(), e->V, v.mark.get(),
+                           pt.mask.get(), pt.base.get(), head, remark, d_up_ids, d_up_p, d_del_ids);
+    HIP_TRY(hipGetLastError());
+    if (int rc = fetch_block(e, pt.blk, pt.pin, lay.total_bytes)) return rc; // (a device destination is complete here: any stream of the caller may read it)
+    const PtHead *h = reinterpret_cast<const PtHead *>(pt.pin.get());
+    for (int i = 0; i <= n; ++i) {
+        out->up_offsets[i] = h->up_offsets[i];
+        out->del_offsets[i] = h->del_offsets[i];
+    }
+    out->written = h->written;
+    if (host && h->go) {
+        const size_t ups = (size_t)h->up_offsets[n], dels = (size_t)h->del_offsets[n];
+        if (ups > 0) {
+            memcpy(out->up_ids, pt.pin + lay.off_up_ids, sizeof(int32_t) * ups);
+            memcpy(out->up_p, pt.pin + lay.off_up_p, sizeof(double) * ups);
+        }
+        if (dels > 0) memcpy(out->del_ids, pt.pin + lay.off_del_ids, sizeof(int32_t) * dels);
+    }
+    return DPPR_OK;
+}
+
+int patch_call(dppr_engine *e, const StateView &v, double min_p, double min_delta, int64_t cap_up, int64_t cap_del, int dest, int remark,
+               dppr_patch_out_t *out) {
+    if (!pt_args_ok(min_p, min_delta, cap_up, cap_del, dest, remark, out))
+        return fail(e, DPPR_ERR_INVALID, "patch: min_p >= 0, min_delta >= 0, caps >= 0, dest 0 or 1, remark 0, 1 or 2, non-null out and offsets, "
+                                         "non-null up_ids / up_p when cap_up > 0, non-null del_ids when cap_del > 0");
+    if (!v.mark)
+        return fail(e, DPPR_ERR_INVALID, v.group ? "patch: the group has no mark (dppr_group_mark; a change of the sources drops it)"
+                                                 : "patch: the slot has no mark (dppr_mark)");
+    HIP_TRY(hipSetDevice(e->device));
+    if (dest == DPPR_DEST_DEVICE) {
+        const size_t cu = (size_t)ex_cap_clamped(cap_up, e->V, v.n), cd = (size_t)ex_cap_clamped(cap_del, e->V, v.n);
+        const bool up_ok = cap_up == 0 || (dev_range_ok(e, out->up_ids, sizeof(int32_t) * cu, sizeof(int32_t)) &&
+                                           dev_range_ok(e, out->up_p, sizeof(double) * cu, sizeof(double)));
+        const bool del_ok = cap_del == 0 || dev_range_ok(e, out->del_ids, sizeof(int32_t) * cd, sizeof(int32_t));
+        if (!up_ok || !del_ok)
+            return fail(e, DPPR_ERR_INVALID, "patch: up_ids / up_p / del_ids must be aligned device memory of the engine's device, cap entries inside one allocation");
+    }
+    std::lock_guard<std::mutex> map_lk(e->map_mu); // (as dppr_read)
+    return run_patch(e, v, min_p, min_delta, cap_up, cap_del, dest, remark, out);
+}
+
 // ---- the state folded over the vertex axis (dppr_dot.hpp, dppr_dot_plan.hpp) ----------------------------------------------------
 // partials, the device input of a sparse call, the block and its pinned twin: in place before the first kernel
 int dot_workspace(dppr_engine *e, Grow &grow, size_t part_elems, size_t in_bytes, size_t block_bytes) {

@@ -211,6 +211,12 @@ struct QueryWork {
         DevBuf<long long> base;      // [tiles][16] first output position of a tile's entries of a lane
         DevBuf<unsigned char> blk; PinBuf<unsigned char> pin; // head (offsets, go), then ids / p / r of a host destination: device / pinned host
     } ex;
+    struct Patch { // dppr_patch.hpp, dppr_patch_plan.hpp; the block grows with a host destination's caps
+        DevBuf<unsigned> mask;  // [V] upserts (low half) and deletes (high half) of every lane at every external id
+        DevBuf<int> cnt;        // [tiles][2][16] upserts and deletes per tile and lane
+        DevBuf<long long> base; // [tiles][2][16] first output position of a tile's entries of a kind and lane
+        DevBuf<unsigned char> blk; PinBuf<unsigned char> pin; // head (offsets, go, written), then up_ids / up_p / del_ids of a host destination
+    } pt;
     struct Dot { // the state folded over the vertex axis (dppr_dot.hpp, dppr_dot_plan.hpp)
         DevBuf<double> part;      // one partial per (tile, output), output-major
         DevBuf<unsigned char> in; // a sparse call: its tile table and columns, and the ids / w of a host source

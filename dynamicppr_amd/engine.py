@@ -66,6 +66,7 @@ EXPORTS = [
     "dppr_mark", "dppr_group_mark", "dppr_unmark", "dppr_group_unmark", "dppr_changes", "dppr_group_changes",
     "dppr_support", "dppr_group_support", "dppr_export_sparse", "dppr_group_export_sparse", "dppr_export_dense_dev",
     "dppr_group_export_dense_dev",
+    "dppr_patch", "dppr_group_patch",
     "dppr_dot_dense_dev", "dppr_group_dot_dense_dev", "dppr_dot_sparse", "dppr_group_dot_sparse",
     "dppr_walks", "dppr_refine_at", "dppr_group_refine_at", "dppr_debug_id_map", "dppr_debug_walk_form",
     "dppr_cluster", "dppr_group_cluster",
@@ -98,6 +99,7 @@ POSITION_MAX = 4096
 EXPLAIN_MAX_M, EXPLAIN_MAX_F, EXPLAIN_MAX_DEPTH = 4096, 16, 64
 END_SEED, END_DEPTH, END_DEAD, END_CYCLE = 0, 1, 2, 3
 CERT_RESIDUAL, CERT_INVARIANT = 1, 2
+PATCH_KEEP_MARK, PATCH_REMARK_ALL, PATCH_REMARK_EMITTED = 0, 1, 2
 
 
 class RankSpec(C.Structure):
@@ -120,6 +122,36 @@ class CertifyOut(C.Structure):
     _fields_ = [("max_abs_r", _dp), ("argmax_r", _ip), ("sum_abs_r", _dp), ("sum_p", _dp), ("n_pos", _lp), ("n_neg", _lp),
                 ("n_nonfinite", _lp), ("n_p_nonzero", _lp), ("inv_max_err", _dp), ("inv_argmax", _ip),
                 ("state_epoch", C.c_int32), ("converged", C.c_int32), ("conv_eps", C.c_double)]
+
+
+class PatchOut(C.Structure):
+    """dppr_patch_out_t: where the two CSRs of a patch go (the offsets in host memory, the arrays where `dest` says), and whether
+    the call wrote them."""
+    _fields_ = [("up_offsets", C.POINTER(C.c_int64)), ("up_ids", C.c_void_p), ("up_p", C.c_void_p),
+                ("del_offsets", C.POINTER(C.c_int64)), ("del_ids", C.c_void_p), ("written", C.c_int32)]
+
+
+def apply_patch(replica, patch):
+    """Merge a patch (the dict Engine.patch / Engine.group_patch returns) into a replica held in the (offsets, ids, p) form of
+    group_export_sparse: per lane the deletes leave, the upserts overwrite or enter, the ids stay ascending. Pure numpy; returns a
+    new (offsets, ids, p)."""
+    off, ids, p = (np.asarray(a) for a in replica[:3])
+    n = len(off) - 1
+    uo, do = patch["up_offsets"], patch["del_offsets"]
+    if len(uo) != n + 1 or len(do) != n + 1:
+        raise ValueError(f"apply_patch: the replica has {n} lanes, the patch {len(uo) - 1}")
+    out_ids, out_p, out_off = [], [], np.zeros(n + 1, dtype=np.int64)
+    for i in range(n):
+        li, lp = ids[off[i]:off[i + 1]], p[off[i]:off[i + 1]]
+        ui, up = patch["up_ids"][uo[i]:uo[i + 1]], patch["up_p"][uo[i]:uo[i + 1]]
+        di = patch["del_ids"][do[i]:do[i + 1]]
+        keep = ~np.isin(li, di) & ~np.isin(li, ui)
+        mi, mp = np.concatenate([li[keep], ui]), np.concatenate([lp[keep], up])
+        order = np.argsort(mi, kind="stable")
+        out_ids.append(mi[order])
+        out_p.append(mp[order])
+        out_off[i + 1] = out_off[i] + len(mi)
+    return out_off, np.concatenate(out_ids).astype(np.int32), np.concatenate(out_p).astype(np.float64)
 
 
 class Cluster(C.Structure):
@@ -232,6 +264,8 @@ def lib():
     L.dppr_export_sparse.argtypes = [vp, C.c_int32, C.c_double, C.c_int64, C.c_int, i64p, vp, vp, vp]
     L.dppr_group_export_sparse.argtypes = [vp, C.c_int32, C.c_double, C.c_int64, C.c_int, i64p, vp, vp, vp]
     L.dppr_export_dense_dev.argtypes = [vp, C.c_int32, C.c_int, C.c_int, vp]
+    L.dppr_patch.argtypes = [vp, C.c_int32, C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_int, C.c_int, vp]
+    L.dppr_group_patch.argtypes = [vp, C.c_int32, C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_int, C.c_int, vp]
     L.dppr_group_export_dense_dev.argtypes = [vp, C.c_int32, C.c_int, C.c_int, C.c_int, vp]
     L.dppr_dot_dense_dev.argtypes = [vp, C.c_int32, C.c_int, vp, C.c_int, C.c_int, C.c_int32, C.c_int, vp]
     L.dppr_group_dot_dense_dev.argtypes = [vp, C.c_int32, C.c_int, vp, C.c_int, C.c_int, C.c_int32, C.c_int, vp]
@@ -1059,6 +1093,51 @@ class Engine:
         """p (or r) of every source of the group by external id, [V][n] or [n][V] elements of `dtype`, into device memory at dst_ptr."""
         self._ck(self._L.dppr_group_export_dense_dev(self._h, int(group), int(which), int(dtype), int(layout), dst_ptr or None),
                  "group_export_dense_dev")
+
+    # ---- the patch feed: what to write into and remove from a replica of {p > min_p} ----
+    def patch(self, slot, min_p, min_delta=0.0, remark=PATCH_KEEP_MARK):
+        """The patch of a slot against its mark (include/dppr.h: dppr_patch): a dict of up_offsets [2], up_ids, up_p, del_offsets
+        [2], del_ids. remark: PATCH_KEEP_MARK, PATCH_REMARK_ALL or PATCH_REMARK_EMITTED (the per-batch feed)."""
+        return self._patch(self._L.dppr_patch, slot, 1, min_p, min_delta, remark, "patch")
+
+    def group_patch(self, group, min_p, min_delta=0.0, remark=PATCH_KEEP_MARK):
+        """patch for every source of a group at once: two CSRs over the lanes, every lane by id ascending."""
+        return self._patch(self._L.dppr_group_patch, group, self._group_n.get(group, 1), min_p, min_delta, remark, "group_patch")
+
+    def _patch(self, fn, which, n, min_p, min_delta, remark, what):
+        i64p = C.POINTER(C.c_int64)
+        uo, do = np.zeros(n + 1, dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
+        out = PatchOut(uo.ctypes.data_as(i64p), None, None, do.ctypes.data_as(i64p), None, -1)
+        self._ck(fn(self._h, int(which), float(min_p), float(min_delta), 0, 0, DEST_HOST, PATCH_KEEP_MARK, C.byref(out)), what)   # the size call
+        ups, dels = int(uo[n]), int(do[n])
+        up_ids, up_p = np.empty(ups, dtype=np.int32), np.empty(ups, dtype=np.float64)
+        del_ids = np.empty(dels, dtype=np.int32)
+        if ups or dels or int(remark) != PATCH_KEEP_MARK:   # the fill and the re-mark (the state does not change between the two calls of one thread)
+            out = PatchOut(uo.ctypes.data_as(i64p), up_ids.ctypes.data if ups else None, up_p.ctypes.data if ups else None,
+                           do.ctypes.data_as(i64p), del_ids.ctypes.data if dels else None, -1)
+            self._ck(fn(self._h, int(which), float(min_p), float(min_delta), ups, dels, DEST_HOST, int(remark), C.byref(out)), what)
+            if out.written != 1 or int(uo[n]) != ups or int(do[n]) != dels:
+                raise DpprError(f"{what}: the state changed between the size call and the fill")
+        return {"up_offsets": uo, "up_ids": up_ids, "up_p": up_p, "del_offsets": do, "del_ids": del_ids}
+
+    def patch_dev(self, slot, min_p, min_delta, cap_up, cap_del, up_ids_ptr, up_p_ptr, del_ids_ptr, remark=PATCH_KEEP_MARK):
+        """dppr_patch into device memory at the given raw addresses (cap_up / cap_del entries): (up_offsets [2], del_offsets [2],
+        written). Nothing is written and the mark is not touched if a total exceeds its cap."""
+        return self._patch_dev(self._L.dppr_patch, slot, 1, min_p, min_delta, cap_up, cap_del, up_ids_ptr, up_p_ptr, del_ids_ptr, remark,
+                               "patch_dev")
+
+    def group_patch_dev(self, group, min_p, min_delta, cap_up, cap_del, up_ids_ptr, up_p_ptr, del_ids_ptr, remark=PATCH_KEEP_MARK):
+        """dppr_group_patch into device memory at the given raw addresses: (up_offsets [n + 1], del_offsets [n + 1], written)."""
+        return self._patch_dev(self._L.dppr_group_patch, group, self._group_n.get(group, 1), min_p, min_delta, cap_up, cap_del, up_ids_ptr,
+                               up_p_ptr, del_ids_ptr, remark, "group_patch_dev")
+
+    def _patch_dev(self, fn, which, n, min_p, min_delta, cap_up, cap_del, up_ids_ptr, up_p_ptr, del_ids_ptr, remark, what):
+        i64p = C.POINTER(C.c_int64)
+        uo, do = np.zeros(n + 1, dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
+        out = PatchOut(uo.ctypes.data_as(i64p), up_ids_ptr or None, up_p_ptr or None, do.ctypes.data_as(i64p), del_ids_ptr or None, -1)
+        self._ck(fn(self._h, int(which), float(min_p), float(min_delta), int(cap_up), int(cap_del), DEST_DEVICE, int(remark), C.byref(out)),
+                 what)
+        return uo, do, int(out.written)
 
     # ---- the sources scored under a seed distribution: h . p over the vertex axis ----
     def dot_dense_dev(self, slot, h_ptr, F, which=DENSE_P, dtype=F64, layout=H_FEATURE_MAJOR, out_ptr=None):

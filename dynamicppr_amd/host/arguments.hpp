@@ -51,6 +51,14 @@ inline double as_double(int argc, char **argv, const char *flag, double dflt) {
     }
     return x;
 }
+// a flag whose value must be a number and nothing else: NaN for a missing or non-numeric value (rejected by ArgumentsChecker)
+inline double as_whole_double(int argc, char **argv, const char *flag, double dflt) {
+    if (!has(argc, argv, flag)) return dflt;
+    const char *v = find(argc, argv, flag);
+    char *end = nullptr;
+    const double x = v ? std::strtod(v, &end) : 0.0;
+    return v && end != v && *end == '\0' ? x : std::nan("");
+}
 // "w1,w2,..": finite numbers separated by commas; anything else gives an empty list (rejected by ArgumentsChecker)
 inline std::vector<double> parse_weights(const char *v) {
     std::vector<double> w;
@@ -179,6 +187,10 @@ inline void PrintUsage() {
               << "--sparse-min <P> [--sparse-out <file>]: after the last batch print, per source in source order, the number of vertices\n"
               << "            with pagerank > P (P >= 0): support <source> <count>; with --sparse-out also write them to <file>,\n"
               << "            one line each, by source then vertex id: <source> <vertex> <pagerank>\n"
+              << "--patch-min <P> [--patch-delta <D>] [--patch-out <file>]: after every batch print, per source in source order, the size of the patch\n"
+              << "            that brings a replica of {pagerank > P} up to date (P >= 0, D >= 0; not with --changes): patch <source> upserts <a> deletes <b>;\n"
+              << "            an entry that stays above P is sent again only once it has moved by more than D since it was last sent. With --patch-out\n"
+              << "            also append the entries to <file>, by source then vertex id: U <batch> <source> <vertex> <pagerank> / D <batch> <source> <vertex>\n"
               << "--seeds <file>: every line of <file> is one seed set `id[:weight] id[:weight] ...` (weight 1 by default, ids in [0, V));\n"
               << "            after the last batch print, per line (from 1) and per source in source order, the source's PPR under that seed\n"
               << "            distribution, sum_v weight[v] * pagerank_source[v]: seedscore <line> <source> <score>\n"
@@ -253,6 +265,8 @@ inline void ArgumentsChecker() {
     if (gTopK < 0 || gTopK > DPPR_TOPK_MAX) ok = false;
     if (gChangesK < 0 || gChangesK > DPPR_TOPK_MAX || !(gChangesMin >= 0.0) || (gChangesMinGiven && gChangesK == 0)) ok = false;
     if ((gSparseGiven && !(gSparseMin >= 0.0)) || (!gSparseOut.empty() && !gSparseGiven)) ok = false;
+    // (a value that is no number was read as NaN and fails `>=`; --patch-min and --changes would share one mark)
+    if ((gPatchGiven && (!(gPatchMin >= 0.0) || !(gPatchDelta >= 0.0) || gChangesK > 0)) || ((gPatchDeltaGiven || !gPatchOut.empty()) && !gPatchGiven)) ok = false;
     if (gSeedsBad) ok = false;
     if (gRefineBad || gRefineFile.empty() != !gWalksGiven) ok = false;
     if (!gRefineFile.empty() && !gRefineBad &&
@@ -322,6 +336,11 @@ inline void ArgumentsParser(int argc, char **argv) {
     gSparseGiven = find(argc, argv, "--sparse-min") != nullptr;
     gSparseMin = as_double(argc, argv, "--sparse-min", 0.0);
     if (const char *f = find(argc, argv, "--sparse-out")) gSparseOut = f;
+    gPatchGiven = has(argc, argv, "--patch-min");
+    gPatchDeltaGiven = has(argc, argv, "--patch-delta");
+    gPatchMin = as_whole_double(argc, argv, "--patch-min", 0.0);
+    gPatchDelta = as_whole_double(argc, argv, "--patch-delta", 0.0);
+    if (const char *f = find(argc, argv, "--patch-out")) gPatchOut = f;
     if (const char *f = find(argc, argv, "--seeds")) {
         gSeedsFile = f;
         gSeedsBad = !load_seeds(f, gSeedOff, gSeedIds, gSeedW);

@@ -55,6 +55,11 @@ inline bool gSparseGiven = false;     // --sparse-min P : after the last batch p
 inline double gSparseMin = 0.0;
 inline std::string gSparseOut;        // --sparse-out FILE : ... and write them, one text line `source id pagerank` each, by source then id
 inline bool gChangesMinGiven = false;
+inline bool gPatchGiven = false;      // --patch-min P : after every batch print, per source, the size of the patch of {pagerank > P} (patch <source> upserts <a> deletes <b>)
+inline double gPatchMin = 0.0;
+inline bool gPatchDeltaGiven = false; // --patch-delta D : an entry that stays above P is sent again only once it has moved by more than D since it was last sent
+inline double gPatchDelta = 0.0;
+inline std::string gPatchOut;         // --patch-out FILE : ... and append the patch, one text line `U batch source id pagerank` or `D batch source id` per entry
 inline std::string gSeedsFile;        // --seeds FILE : every line one seed set `id[:weight] ...`; after the last batch print seedscore <line> <source> <score>
 inline bool gSeedsBad = false;        //   FILE could not be read, holds no line, or a token is not id[:weight] with id >= 0
 inline std::vector<int64_t> gSeedOff; //   the seed sets as one CSR over the lines: offsets [lines + 1], external ids, weights

@@ -61,6 +61,15 @@ int main(int argc, char *argv[]) {
         return -1;
     }
 
+    if (!gPatchOut.empty()) { // --patch-out: the file starts empty; every batch appends to it
+        std::FILE *f = std::fopen(gPatchOut.c_str(), "w");
+        if (!f) {
+            std::cout << "cannot write " << gPatchOut << std::endl;
+            return -1;
+        }
+        std::fclose(f);
+    }
+
     // Every device thread streams the same file through its own SlidingGraphVec (a position in
     // a shared read-only mapping of the page cache) and owns one engine.
     // --share-device / DPPR_DEVICE_ALIAS=1: the N device threads (each with its own engine, stream and graph replica) run on the

@@ -150,6 +150,10 @@ public:
             for (int32_t gid : groups) DPPR_CHECK(engine, dppr_group_mark(engine, gid));
             for (int32_t sl : slots) DPPR_CHECK(engine, dppr_mark(engine, sl));
         }
+        if (gPatchGiven) { // --patch-min: the from-scratch solution is the mark the first patch is taken against
+            for (int32_t gid : groups) DPPR_CHECK(engine, dppr_group_mark(engine, gid));
+            for (int32_t sl : slots) DPPR_CHECK(engine, dppr_mark(engine, sl));
+        }
         if (gCertify > 0) PrintCertify(-1); // --certify: the from-scratch solution first
         prof.End(HostProfile::INIT_GRAPH_CALC);
         prof.Start(HostProfile::DYNA_GRAPH_CALC);
@@ -269,6 +273,7 @@ public:
                 DPPR_CHECK(engine, ahead_rc);
             }
             if (gChangesK > 0) PrintChanges(stream_batch_count);
+            if (gPatchGiven) PrintPatch(stream_batch_count);
             if (gAssign) PrintAssign(stream_batch_count);
             if (!gRefineIds.empty()) PrintRefined(-1);
             if (!gPositionIds.empty()) PrintPositions(-1);
@@ -368,6 +373,7 @@ public:
                 build_beside_ms += nxt.ms;
             }
             if (gChangesK > 0) PrintChanges(stream_batch_count);
+            if (gPatchGiven) PrintPatch(stream_batch_count);
             if (gAssign) PrintAssign(stream_batch_count);
             if (!gRefineIds.empty()) PrintRefined(epoch); // (the epoch the states stand on: the helper may have built the next one)
             if (!gPositionIds.empty()) PrintPositions(epoch);
@@ -634,6 +640,66 @@ public:
         static std::mutex print_mu;
         std::lock_guard<std::mutex> lk(print_mu);
         std::cout << out << std::flush;
+    }
+
+    // --patch-min: the patch of batch `batch` (from 1) that brings a replica of {p > gPatchMin} up to date, per source of this device in
+    // this device's source order (dppr_patch / dppr_group_patch: the size call, which leaves the mark alone, then the fill with
+    // DPPR_PATCH_REMARK_EMITTED, so that the mark is what the replica holds). Outside the timed region, printed as one block like
+    // --changes; the entries are appended to --patch-out under the same lock.
+    void PrintPatch(size_t batch) {
+        const size_t n_src = source_vertex_ids.size();
+        std::vector<int32_t> up_ids, del_ids;
+        std::vector<double> up_p;
+        std::string out, file;
+        char line[200];
+        for (size_t first = 0; first < n_src; first += use_groups ? kGroupMax : 1) {
+            const size_t n = use_groups ? std::min(kGroupMax, n_src - first) : 1;
+            std::vector<int64_t> uo(n + 1, 0), dl(n + 1, 0);
+            dppr_patch_out_t po{uo.data(), nullptr, nullptr, dl.data(), nullptr, 0};
+            auto call = [&](int64_t cap_up, int64_t cap_del, int remark) {
+                if (use_groups)
+                    DPPR_CHECK(engine, dppr_group_patch(engine, groups[first / kGroupMax], gPatchMin, gPatchDelta, cap_up, cap_del, DPPR_DEST_HOST, remark, &po));
+                else
+                    DPPR_CHECK(engine, dppr_patch(engine, slots[first], gPatchMin, gPatchDelta, cap_up, cap_del, DPPR_DEST_HOST, remark, &po));
+            };
+            call(0, 0, DPPR_PATCH_KEEP_MARK);
+            up_ids.assign((size_t)uo[n] + 1, -1);
+            up_p.assign((size_t)uo[n] + 1, 0.0);
+            del_ids.assign((size_t)dl[n] + 1, -1);
+            po.up_ids = up_ids.data();
+            po.up_p = up_p.data();
+            po.del_ids = del_ids.data();
+            call(uo[n], dl[n], DPPR_PATCH_REMARK_EMITTED);
+            if (po.written != 1) {
+                std::cout << "patch: the state changed between the size call and the fill" << std::endl;
+                std::exit(-1);
+            }
+            for (size_t j = 0; j < n; ++j) {
+                const int src = (int)source_vertex_ids[first + j];
+                std::snprintf(line, sizeof(line), "patch %d upserts %lld deletes %lld\n", src, (long long)(uo[j + 1] - uo[j]), (long long)(dl[j + 1] - dl[j]));
+                out += line;
+                if (gPatchOut.empty()) continue;
+                for (int64_t t = uo[j]; t < uo[j + 1]; ++t) {
+                    std::snprintf(line, sizeof(line), "U %zu %d %d %.17g\n", batch, src, (int)up_ids[(size_t)t], up_p[(size_t)t]);
+                    file += line;
+                }
+                for (int64_t t = dl[j]; t < dl[j + 1]; ++t) {
+                    std::snprintf(line, sizeof(line), "D %zu %d %d\n", batch, src, (int)del_ids[(size_t)t]);
+                    file += line;
+                }
+            }
+        }
+        progress++;
+        static std::mutex print_mu;
+        std::lock_guard<std::mutex> lk(print_mu);
+        std::cout << out << std::flush;
+        if (!gPatchOut.empty()) {
+            std::FILE *f = std::fopen(gPatchOut.c_str(), "a");
+            if (!f || std::fwrite(file.data(), 1, file.size(), f) != file.size() || std::fclose(f) != 0) {
+                std::cout << "cannot write " << gPatchOut << std::endl;
+                std::exit(-1);
+            }
+        }
     }
 
     // --assign: after a batch, every vertex to the lane that holds it best over ALL groups of this device (dppr_assign, host

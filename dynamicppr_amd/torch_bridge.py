@@ -1,5 +1,5 @@
 """The engine's state as torch tensors on the engine's device: the device-side exports of include/dppr.h
-(dppr_group_export_sparse / dppr_group_export_dense_dev, dppr_group_subgraph, dppr_assign) written straight into memory that torch
+(dppr_group_export_sparse / dppr_group_export_dense_dev, dppr_group_subgraph, dppr_assign, dppr_group_patch) written straight into memory that torch
 allocated.
 
 The engine binding itself (``engine.py``) stays torch-free: nothing there imports torch, and importing this module puts no
@@ -273,3 +273,51 @@ def assign(engine, groups, scale=None, min_score=0.0, prev=None, want=("best", "
                                         V if prev is not None else 0, tuple(t.data_ptr() if t is not None else None for t in lists))
     flips = tuple(t[:n_flips] for t in lists) if prev is not None else None
     return {"label": label, "best": best, "margin": margin, "counts": counts, "n_flips": n_flips, "flips": flips}
+
+
+def group_patch(engine, gid, min_p, min_delta=0.0, remark=_eng.PATCH_REMARK_EMITTED):
+    """dppr_group_patch with tensors on the engine's device, written in place: a dict of up_offsets / del_offsets (int64 CPU
+    tensors [n + 1]), up_ids (int32), up_p (float64) and del_ids (int32). Two calls: the size query, which leaves the mark alone,
+    then the fill with exactly those caps, which applies `remark`."""
+    n = len(engine.group_sources(gid))
+    dev = _device(engine)
+    uo, do, _ = engine.group_patch_dev(gid, min_p, min_delta, 0, 0, None, None, None, _eng.PATCH_KEEP_MARK)
+    ups, dels = int(uo[n]), int(do[n])
+    up_ids = torch.empty(max(ups, 1), dtype=torch.int32, device=dev)
+    up_p = torch.empty(max(ups, 1), dtype=torch.float64, device=dev)
+    del_ids = torch.empty(max(dels, 1), dtype=torch.int32, device=dev)
+    if ups or dels or int(remark) != _eng.PATCH_KEEP_MARK:
+        torch.cuda.synchronize(dev)   # (the allocations are torch's; nothing of torch's is in flight on them when the engine writes)
+        uo, do, written = engine.group_patch_dev(gid, min_p, min_delta, ups, dels, up_ids.data_ptr() if ups else None,
+                                                 up_p.data_ptr() if ups else None, del_ids.data_ptr() if dels else None, remark)
+        if written != 1 or int(uo[n]) != ups or int(do[n]) != dels:
+            raise _eng.DpprError("group_patch: the state changed between the size call and the fill")
+    return {"up_offsets": torch.from_numpy(uo), "up_ids": up_ids[:ups], "up_p": up_p[:ups], "del_offsets": torch.from_numpy(do),
+            "del_ids": del_ids[:dels]}
+
+
+def _lanes(offsets, dev):
+    """The lane of every entry of a CSR over the lanes, from its host offsets."""
+    counts = (offsets[1:] - offsets[:-1]).to(dev)
+    return torch.repeat_interleave(torch.arange(len(counts), dtype=torch.int64, device=dev), counts)
+
+
+def apply_patch(replica, patch, V):
+    """Merge a patch of group_patch into a replica held as tensors -- (offsets int64 CPU [n + 1], ids int32, p float64), the
+    form of group_export_sparse with ids and p on one device -- from torch ops alone: every entry gets the key lane * V + id, the
+    replica's entries whose key is deleted or upserted leave, the upserts enter, one sort puts the keys back in order. Returns a
+    new (offsets, ids, p)."""
+    off, ids, p = replica
+    dev = ids.device
+    n = len(off) - 1
+    key = _lanes(off, dev) * V + ids.to(torch.int64)
+    up_key = _lanes(patch["up_offsets"], dev) * V + patch["up_ids"].to(torch.int64)
+    del_key = _lanes(patch["del_offsets"], dev) * V + patch["del_ids"].to(torch.int64)
+    keep = ~torch.isin(key, torch.cat([up_key, del_key]))
+    all_key, all_p = torch.cat([key[keep], up_key]), torch.cat([p[keep], patch["up_p"]])
+    all_key, order = torch.sort(all_key)   # (the keys are distinct: the order is total)
+    lane = torch.div(all_key, V, rounding_mode="floor")
+    counts = torch.bincount(lane, minlength=n).cpu()
+    new_off = torch.zeros(n + 1, dtype=torch.int64)
+    new_off[1:] = torch.cumsum(counts, 0)
+    return new_off, (all_key - lane * V).to(torch.int32), all_p[order]

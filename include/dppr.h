@@ -1174,6 +1174,77 @@ int dppr_assign_at(dppr_engine *e, const int32_t *groups, int32_t n_groups, cons
                    int32_t m, int32_t *out_label /* [m] */, double *out_best /* [m] */, int32_t *out_second_label /* [m] */,
                    double *out_margin /* [m] */);
 
+/* ---- the patch feed: keep a replica of the thresholded state current, batch by batch (backward-compatible additions, ABI 6) ----
+ * A consumer holds a copy of the thresholded vectors {p_i[v] > min_p} downstream (a feature store, a candidate index, a tensor
+ * beside a model). dppr_group_export_sparse costs the whole support whatever a batch moved, and dppr_group_changes knows neither
+ * the threshold nor which entries left the support. A PATCH is the entries to write and the entries to remove that make the
+ * replica equal to the thresholded state; its size follows the change, not the support. It is the first query about the step
+ * from one state to the next: it compares the state with the MARK of dppr_mark / dppr_group_mark (the same mark dppr_changes uses).
+ *
+ * For lane i (lane order as dppr_group_sources reports it) and external id v in [0, V):
+ *     p   = p_i[v], exactly what dppr_read / dppr_group_read returns now (0.0 for a vertex without an internal id)
+ *     m   = mark_i[v]
+ *     d   = p - m, ONE double subtraction rounded to nearest even (the delta of dppr_changes)
+ *     now = (p > min_p), then = (m > min_p), min_p >= 0: a negative value, -0.0 and NaN never qualify (the rule of
+ *           dppr_export_sparse)
+ *     UPSERT (v, i):  now && (!then || |d| > min_delta), min_delta >= 0.   Carries the id and p, bit for bit.
+ *     DELETE (v, i):  then && !now.                                       Carries the id.
+ * So a NaN p over a qualifying mark is a delete, a qualifying p over a NaN mark is an upsert, and |d| == min_delta is suppressed.
+ * r is not part of a patch: it can move where p does not.
+ *
+ * Layout: two CSRs over the lanes in a dppr_patch_out_t -- up_offsets [n + 1], up_ids, up_p and del_offsets [n + 1], del_ids.
+ * Lane i's upserts occupy [up_offsets[i], up_offsets[i + 1]) of up_ids and up_p, its deletes [del_offsets[i], del_offsets[i + 1])
+ * of del_ids; each lane is in ascending external id. A slot is n = 1 (offsets [2]).
+ * Offsets: up_offsets and del_offsets are always HOST memory and are always written with the TRUE counts.
+ * Capacity: the caller gives cap_up and cap_del (entries). If up_offsets[n] > cap_up or del_offsets[n] > cap_del nothing is
+ * written to the arrays, the mark is not touched, and the call returns DPPR_OK with written = 0; otherwise written = 1. Caps of 0
+ * with NULL arrays are the size query; the pattern is two calls, the first with DPPR_PATCH_KEEP_MARK.
+ * dest: where up_ids, up_p and del_ids live, DPPR_DEST_HOST or DPPR_DEST_DEVICE, with the device-pointer checks of the exports
+ * (cap_up entries of up_ids and up_p, cap_del entries of del_ids, each cap taken as at most n * V).
+ * Determinism: no output position and no value comes from an atomic. The result is a function of the state, the mark, min_p and
+ * min_delta alone.
+ *
+ * RE-MARK, applied in the same call and only when written = 1:
+ *     DPPR_PATCH_KEEP_MARK      leaves the mark alone.
+ *     DPPR_PATCH_REMARK_ALL     sets the mark to p everywhere, as dppr_mark / dppr_group_mark would.
+ *     DPPR_PATCH_REMARK_EMITTED sets mark_i[v] = p_i[v] only at the emitted upserts and deletes (v, i).
+ * DPPR_PATCH_REMARK_EMITTED is the mode that BOUNDS DRIFT. Under it the mark is what the replica holds: where the replica has an
+ * entry the mark is the value last sent, where it has none the mark does not qualify. After every applied patch the replica's
+ * support equals {p > min_p} exactly, and every value it holds is within min_delta of the current p -- for any number of
+ * batches, because a value is suppressed only while |p - (the value the replica holds)| <= min_delta. Under
+ * DPPR_PATCH_REMARK_ALL with min_delta > 0 the mark follows p where nothing was sent, so moves below min_delta accumulate
+ * unseen: the support stays exact, the values may drift without bound. With min_delta = 0 the replica is exact under either mode.
+ * (If a call with a re-mark fails with DPPR_ERR_HIP the mark is undefined: mark again.)
+ *
+ * The initial sync is dppr_group_mark followed by dppr_group_export_sparse(min_p). A call on a slot or group without a mark is
+ * DPPR_ERR_INVALID; dppr_group_replace_source, dppr_group_add_source and dppr_group_remove_source drop the mark, the consumer
+ * then marks and exports again.
+ *
+ * Rejected with DPPR_ERR_INVALID before any device work, nothing written and the mark untouched: min_p or min_delta negative or
+ * NaN, a negative cap, cap_up > 0 with a NULL up_ids or up_p, cap_del > 0 with a NULL del_ids, dest or remark outside its
+ * values, a NULL out, up_offsets or del_offsets, a device destination that fails the checks, no mark, a bad slot / group.
+ * Threading and stream as dppr_export_sparse: the call holds the id-map lock as dppr_read does (safe beside
+ * dppr_slide_concurrent), runs on the solver stream, works on any state, sees the live and the parked zone and is never part of
+ * the update path or of a timed region. The work space is 4 bytes per external id plus 384 bytes per 256 external ids, and the
+ * block of a host destination 12 bytes per entry of cap_up and 4 per entry of cap_del, device and pinned host; all of it is the
+ * engine's, obtained before anything is written, grown on demand and released with the engine. With dppr_set_profiling on,
+ * dppr_debug_query_ms also reports the device time of the last of these calls, first to last kernel. */
+#define DPPR_PATCH_KEEP_MARK 0
+#define DPPR_PATCH_REMARK_ALL 1
+#define DPPR_PATCH_REMARK_EMITTED 2
+typedef struct {
+    int64_t *up_offsets;  /* [n + 1], HOST */
+    int32_t *up_ids;      /* cap_up entries, dest */
+    double *up_p;         /* cap_up entries, dest */
+    int64_t *del_offsets; /* [n + 1], HOST */
+    int32_t *del_ids;     /* cap_del entries, dest */
+    int32_t written;      /* set by the call: 1 the arrays hold the patch and the re-mark was applied, 0 a cap was too small */
+} dppr_patch_out_t;
+int dppr_patch(dppr_engine *e, int32_t slot, double min_p, double min_delta, int64_t cap_up, int64_t cap_del, int dest, int remark,
+               dppr_patch_out_t *out);
+int dppr_group_patch(dppr_engine *e, int32_t group, double min_p, double min_delta, int64_t cap_up, int64_t cap_del, int dest,
+                     int remark, dppr_patch_out_t *out);
+
 /* Windows whose sweep groups are all resident at once run a frontier loop of a source group as
  * multi-sweep launches (grid barrier between sweeps, row tables kept in LDS; dppr_multi.hpp). on by
  * default; 0 = one launch per sweep everywhere. The roll-call / time-out rules are those of
