@@ -55,6 +55,7 @@
 #include "dppr_rank.hpp"
 #include "dppr_assign.hpp"
 #include "dppr_position.hpp"
+#include "dppr_sample.hpp"
 #include "dppr_explain.hpp"
 
 using namespace dppr;
@@ -1690,6 +1691,25 @@ int dppr_debug_certify(dppr_engine *e, int piece_edges, int wave_rows) {
         return fail(e, DPPR_ERR_INVALID, "debug_certify: piece_edges in [0, 2^20], wave_rows 0 or a power of two up to 64 (0: the plan's choice)");
     e->cert_piece = piece_edges;
     e->cert_wave_rows = wave_rows;
+    return DPPR_OK;
+}
+
+int dppr_sample(dppr_engine *e, int32_t slot, int32_t epoch, const dppr_rank_spec_t *spec, double min_score, uint64_t seed, uint64_t first, int32_t S,
+                int dest, int32_t *out_ids, double *out_w, double *out_total, int32_t *out_support, int32_t *out_status) {
+    GET_SLOT(e, slot);
+    return sample_call(e, s, epoch, spec, min_score, seed, first, S, dest, out_ids, out_w, out_total, out_support, out_status);
+}
+
+int dppr_group_sample(dppr_engine *e, int32_t group, int32_t epoch, const dppr_rank_spec_t *spec, double min_score, uint64_t seed, uint64_t first,
+                      int32_t S, int dest, int32_t *out_ids, double *out_w, double *out_total, int32_t *out_support, int32_t *out_status) {
+    GET_GROUP(e, group);
+    return sample_call(e, g, epoch, spec, min_score, seed, first, S, dest, out_ids, out_w, out_total, out_support, out_status);
+}
+
+int dppr_debug_sample_form(dppr_engine *e, int form) {
+    if (!e || !sample_form_ok(form))
+        return fail(e, DPPR_ERR_INVALID, "debug_sample_form: 0 (a wave rebuilds the lowest levels) or 1 (one draw per thread, every level stored)");
+    e->sample_form = form;
     return DPPR_OK;
 }
 

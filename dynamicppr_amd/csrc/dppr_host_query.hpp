@@ -1306,6 +1306,88 @@ int position_call(dppr_engine *e, Owner &o, int32_t epoch, const dppr_rank_spec_
     return run_position(e, v, rank_lanes(o), ep, rank_spec(spec), min_score, ids, m, out_pos, out_counts);
 }
 
+// ---- vertices drawn in proportion to a lane's score (dppr_sample.hpp, dppr_sample_plan.hpp) ---------------------------------------
+// the leaves, the nodes, the low levels of the plain form, the block and its pinned twin: in place before the first kernel
+int sample_workspace(dppr_engine *e, Grow &grow, int n, const SmTree &t, size_t blk_bytes) {
+    QueryWork::Sample &sm = e->q.sm;
+    int rc = grow(sm.leaves, sample_leaf_elems(n, t.Vt));
+    if (!rc) rc = grow(sm.nodes, sample_node_elems(n, t));
+    if (!rc && e->sample_form == 1) rc = grow(sm.low, sample_leaf_elems(n, t.Vt));
+    if (!rc) rc = grow(sm.blk, blk_bytes);
+    if (!rc) rc = grow(sm.pin, blk_bytes);
+    return rc;
+}
+
+// S draws of every lane by the spec's score, with the totals, supports and statuses (arguments, the spec's device pointers, the
+// epoch and a device destination validated by the caller; S == 0: the tree alone). Every buffer is in place before the first
+// kernel, every stage is enqueued before the one copy back: the marking of run_topk_ranked, the leaves and the tiles' nodes, the
+// upper levels, the draws.
+int run_sample(dppr_engine *e, const StateView &v, const RkLanes &l, const Epoch *ep, const RkSpec &sp, double min_score, uint64_t seed,
+               uint64_t first, int S, int dest, int32_t *out_ids, double *out_w, double *out_total, int32_t *out_support, int32_t *out_status) {
+    if (int rc = query_begin(e, MAP_E2I)) return rc;
+    QueryWork::Sample &sm = e->q.sm;
+    const int n = v.n;
+    const bool host = dest == DPPR_DEST_HOST;
+    const SmTree t = sample_tree(e->V);
+    const SmLayout lay = sample_layout(n, S, host, out_w != nullptr);
+    Grow grow{e};
+    if (int rc = rank_mark_workspace(e, grow, l, sp, ep)) return rc;
+    if (int rc = sample_workspace(e, grow, n, t, lay.total_bytes)) return rc;
+    const RkGraph g = rank_graph(e, ep);
+    const RkRule rule = rank_rule(sp);
+    const SmOut head{reinterpret_cast<double *>(sm.blk + lay.off_total), reinterpret_cast<int *>(sm.blk + lay.off_support),
+                     reinterpret_cast<int *>(sm.blk + lay.off_status)};
+    int *d_ids = host ? reinterpret_cast<int *>(sm.blk + lay.off_ids) : out_ids;
+    double *d_w = !out_w ? nullptr : host ? reinterpret_cast<double *>(sm.blk + lay.off_w) : out_w;
+    const bool plain = e->sample_form == 1;
+    if (int rc = DeviceTime{e}.open()) return rc;
+    const unsigned *excl = nullptr;
+    if (int rc = rank_mark_enqueue(e, l, sp, g, &excl)) return rc;
+    HIP_TRY(hipMemsetAsync(sm.blk, 0, SM_HEAD_BYTES, e->stream));
+    by_factor(sp, [&](auto kind, auto elem) -> int {
+        using T = decltype(elem);
+        hipLaunchKernelGGL((k_sm_leaves<decltype(kind)::value, T>), dim3(t.tiles), dim3(SM_BLOCK), 0, e->stream, v.p, v.gw, n, e->d_ext2int.get(),
+                           excl, rule, g, min_score, t, sm.leaves.get(), sm.nodes.get(), plain ? sm.low.get() : nullptr, head.support);
+        return DPPR_OK;
+    });
+    hipLaunchKernelGGL(k_sm_upper, dim3(n), dim3(SM_BLOCK), 0, e->stream, sm.nodes.get(), t, head);
+    if (S > 0) {
+        const int64_t total = (int64_t)n * S;
+        if (plain)
+            hipLaunchKernelGGL(k_sm_draw_plain, dim3((unsigned)sample_plain_blocks(total)), dim3(SM_BLOCK), 0, e->stream, sm.leaves.get(),
+                               sm.nodes.get(), sm.low.get(), t, head.total, head.status, (int64_t)S, total, first, seed, d_ids, d_w);
+        else
+            hipLaunchKernelGGL(k_sm_draw, dim3((unsigned)sample_draw_blocks(total)), dim3(SM_BLOCK), 0, e->stream, sm.leaves.get(), sm.nodes.get(), t,
+                               head.total, head.status, (int64_t)S, total, first, seed, d_ids, d_w);
+    }
+    HIP_TRY(hipGetLastError());
+    if (int rc = fetch_block(e, sm.blk, sm.pin, lay.total_bytes)) return rc; // (a device destination is complete here: any stream of the caller may read it)
+    memcpy(out_total, sm.pin + lay.off_total, sizeof(double) * (size_t)n);
+    if (out_support) memcpy(out_support, sm.pin + lay.off_support, sizeof(int32_t) * (size_t)n);
+    memcpy(out_status, sm.pin + lay.off_status, sizeof(int32_t) * (size_t)n);
+    if (host && S > 0) {
+        memcpy(out_ids, sm.pin + lay.off_ids, sample_ids_bytes(n, S));
+        if (out_w) memcpy(out_w, sm.pin + lay.off_w, sample_w_bytes(n, S));
+    }
+    return DPPR_OK;
+}
+
+template <class Owner>
+int sample_call(dppr_engine *e, Owner &o, int32_t epoch, const dppr_rank_spec_t *spec, double min_score, uint64_t seed, uint64_t first, int32_t S,
+                int dest, int32_t *out_ids, double *out_w, double *out_total, int32_t *out_support, int32_t *out_status) {
+    const StateView v = view(o);
+    if (!sample_args_ok(spec, min_score, v.n, first, S, dest, out_ids, out_total, out_status))
+        return fail(e, DPPR_ERR_INVALID, "sample: factor 0..3, factor_dtype 0 or 1, mask 0..2, exclude bits 1 | 2 | 4, min_score >= 0, S in [0, DPPR_SAMPLE_MAX], n * S <= DPPR_SAMPLE_MAX_TOTAL, first + S without a wrap, dest 0 or 1, non-null ids when S > 0, non-null total / status");
+    HIP_TRY(hipSetDevice(e->device));
+    const Epoch *ep = nullptr;
+    if (const char *why = rank_spec_refused(e, v, epoch, spec, &ep)) return fail(e, DPPR_ERR_INVALID, why);
+    if (dest == DPPR_DEST_DEVICE && S > 0 &&
+        (!dev_range_ok(e, out_ids, sample_ids_bytes(v.n, S), sizeof(int32_t)) || (out_w && !dev_range_ok(e, out_w, sample_w_bytes(v.n, S), sizeof(double)))))
+        return fail(e, DPPR_ERR_INVALID, "sample: a device destination is aligned device memory of the engine's device, n * S elements inside one allocation");
+    std::lock_guard<std::mutex> map_lk(e->map_mu); // (as dppr_read: one state of the id space for the whole query)
+    return run_sample(e, v, rank_lanes(o), ep, rank_spec(spec), min_score, seed, first, S, dest, out_ids, out_w, out_total, out_support, out_status);
+}
+
 // ---- every vertex to its best lane, across groups (dppr_assign.hpp, dppr_assign_plan.hpp) --------------------------------------
 static_assert(AS_TEAM_MAX * 2 == GS_MAX, "the widest row of a group is one step of the widest team");
 

@@ -252,6 +252,12 @@ struct QueryWork {
         DevBuf<unsigned char> blk; PinBuf<unsigned char> pin; // counts, positions: device / pinned host
         bool lds_set = false;       // the count pass was given its dynamic LDS limit
     } pos;
+    struct Sample { // vertices drawn in proportion to a lane's score (dppr_sample.hpp, dppr_sample_plan.hpp); its exclusion words: rk
+        DevBuf<double> leaves; // [n][Vt] the weights by external id, lane-major
+        DevBuf<double> nodes;  // [n][node_stride] the levels 8 .. top of every lane's tree
+        DevBuf<double> low;    // [n][Vt] the levels 1 .. 7 (dppr_debug_sample_form(1) alone)
+        DevBuf<unsigned char> blk; PinBuf<unsigned char> pin; // head (totals, supports, statuses), then ids / w of a host destination: device / pinned host
+    } sm;
     struct Explain { // top contributors and the path to the seeds (dppr_explain.hpp, dppr_explain_plan.hpp); its memo: the first plane of sc
         DevBuf<unsigned char> blk; PinBuf<unsigned char> pin; // the planes asked for, then the queried ids: device / pinned host
     } exq;
@@ -443,6 +449,7 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     int walk_form = 0;              // 0: lane refill, 1: one walk per thread (dppr_debug_walk_form)
     int sg_wave_max = SG_WAVE_MAX;  // matched entries of a row up to which the wave that owns it places them (dppr_debug_subgraph_wave_max)
     int rk_piece = RK_PIECE;        // entries of a seed's row one wave of k_rk_mark walks (dppr_debug_rank_piece)
+    int sample_form = 0;            // 0: a wave rebuilds a draw's lowest 8 levels, 1: one draw per thread over a fully stored tree (dppr_debug_sample_form)
     int pos_tile = 0;               // queries of a lane's order a workgroup of k_pos_count holds per pass; 0: the plan's choice (dppr_debug_position_tile)
     int ex_memo = -1;               // the memo of k_ex_path: -1 the plan's choice, 0 off, 1 on (dppr_debug_explain)
     int ex_wave_rows = EX_WAVE_ROWS; // entries of a row a wave of dppr_explain.hpp takes per step (dppr_debug_explain)

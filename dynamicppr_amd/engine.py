@@ -77,6 +77,7 @@ EXPORTS = [
     "dppr_position_at", "dppr_group_position_at", "dppr_debug_position_tile",
     "dppr_explain_at", "dppr_group_explain_at", "dppr_debug_explain",
     "dppr_certify", "dppr_group_certify", "dppr_debug_certify",
+    "dppr_sample", "dppr_group_sample", "dppr_debug_sample_form",
 ]
 
 DEST_HOST, DEST_DEVICE = 0, 1
@@ -100,6 +101,9 @@ EXPLAIN_MAX_M, EXPLAIN_MAX_F, EXPLAIN_MAX_DEPTH = 4096, 16, 64
 END_SEED, END_DEPTH, END_DEAD, END_CYCLE = 0, 1, 2, 3
 CERT_RESIDUAL, CERT_INVARIANT = 1, 2
 PATCH_KEEP_MARK, PATCH_REMARK_ALL, PATCH_REMARK_EMITTED = 0, 1, 2
+SAMPLE_MAX, SAMPLE_MAX_TOTAL = 1 << 20, 1 << 24
+SAMPLE_OK, SAMPLE_EMPTY, SAMPLE_NONFINITE = 0, 1, 2
+SAMPLE_WAVE, SAMPLE_PER_THREAD = 0, 1
 
 
 class RankSpec(C.Structure):
@@ -295,6 +299,10 @@ def lib():
     L.dppr_position_at.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_double, ip, C.c_int32, ip, ip]
     L.dppr_group_position_at.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_double, ip, C.c_int32, ip, ip]
     L.dppr_debug_position_tile.argtypes = [vp, C.c_int]
+    # (out_ids / out_w as plain addresses: host arrays or device memory, as `dest` says; out_w and out_support may be NULL)
+    L.dppr_sample.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_double, C.c_uint64, C.c_uint64, C.c_int32, C.c_int, vp, vp, dp, ip, ip]
+    L.dppr_group_sample.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_double, C.c_uint64, C.c_uint64, C.c_int32, C.c_int, vp, vp, dp, ip, ip]
+    L.dppr_debug_sample_form.argtypes = [vp, C.c_int]
     L.dppr_explain_at.argtypes = [vp, C.c_int32, C.c_int32, ip, C.c_int32, C.c_int32, C.c_int32, vp]
     L.dppr_group_explain_at.argtypes = [vp, C.c_int32, C.c_int32, ip, C.c_int32, C.c_int32, C.c_int32, vp]
     L.dppr_debug_explain.argtypes = [vp, C.c_int, C.c_int]
@@ -916,6 +924,46 @@ class Engine:
         """Test hook (dppr_debug_certify): out-rows longer than piece_edges are summed in pieces; wave_rows short rows share a wave
         (a power of two up to 64); 0: the plan's choice. Both change the order of the additions inside the invariant's sums only."""
         self._ck(self._L.dppr_debug_certify(self._h, int(piece_edges), int(wave_rows)), "debug_certify")
+
+    # ---- vertices drawn in proportion to a lane's score ----
+    def _sample(self, fn, which, n, S, spec, min_score, seed, first, epoch, dest, ids_ptr, w_ptr, what):
+        total = np.empty(n, dtype=np.float64)
+        support = np.empty(n, dtype=np.int32)
+        status = np.empty(n, dtype=np.int32)
+        self._ck(fn(self._h, int(which), int(epoch), C.byref(spec) if spec is not None else None, float(min_score), int(seed), int(first),
+                    int(S), dest, ids_ptr, w_ptr, total.ctypes.data_as(C.POINTER(C.c_double)), support.ctypes.data_as(C.POINTER(C.c_int32)),
+                    status.ctypes.data_as(C.POINTER(C.c_int32))), what)
+        return total, support, status
+
+    def _sample_host(self, fn, which, n, S, spec, min_score, seed, first, with_w, epoch, what):
+        ids = np.empty((n, max(int(S), 0)), dtype=np.int32)
+        w = np.empty((n, max(int(S), 0)), dtype=np.float64) if with_w else None
+        total, support, status = self._sample(fn, which, n, S, spec, min_score, seed, first, epoch, DEST_HOST, ids.ctypes.data,
+                                              w.ctypes.data if with_w else None, what)
+        return ids, w, total, support, status
+
+    def sample(self, slot, S, spec=None, min_score=0.0, seed=0, first=0, with_w=True, epoch=-1):
+        """S external ids drawn with replacement in proportion to the slot's score (include/dppr.h: THE SCORE of topk_ranked above
+        min_score, a sum tree in external-id order, Philox draws number first .. first + S - 1): (ids int32 [S], w float64 [S] or
+        None, total, support, status). ids are -1 where status is not SAMPLE_OK."""
+        ids, w, total, support, status = self._sample_host(self._L.dppr_sample, slot, 1, S, spec, min_score, seed, first, with_w, epoch, "sample")
+        return ids[0], None if w is None else w[0], float(total[0]), int(support[0]), int(status[0])
+
+    def group_sample(self, group, S, spec=None, min_score=0.0, seed=0, first=0, with_w=True, epoch=-1):
+        """sample for every lane of a group at once: (ids int32 [n][S], w float64 [n][S] or None, total [n], support [n], status [n]).
+        A lane's draws depend on its own weights, its lane index, seed and the draw number alone."""
+        return self._sample_host(self._L.dppr_group_sample, group, self._group_n.get(group, 1), S, spec, min_score, seed, first, with_w, epoch,
+                                 "group_sample")
+
+    def group_sample_dev(self, group, S, ids_ptr, w_ptr=None, spec=None, min_score=0.0, seed=0, first=0, epoch=-1):
+        """... into device memory of the caller: n * S int32 at the raw address ids_ptr and, unless w_ptr is None, n * S float64 at
+        w_ptr, lane-major. Returns (total, support, status)."""
+        return self._sample(self._L.dppr_group_sample, group, self._group_n.get(group, 1), S, spec, min_score, seed, first, epoch, DEST_DEVICE,
+                            ids_ptr, w_ptr, "group_sample")
+
+    def debug_sample_form(self, form):
+        """Test hook (dppr_debug_sample_form): SAMPLE_WAVE (default) or SAMPLE_PER_THREAD. The results do not depend on it."""
+        self._ck(self._L.dppr_debug_sample_form(self._h, int(form)), "debug_sample_form")
 
     # ---- every vertex to its best lane, across groups ----
     def _assign_classes(self, groups, scale, what):

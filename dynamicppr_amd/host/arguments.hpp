@@ -211,6 +211,11 @@ inline void PrintUsage() {
               << "            legal to push> nonfinite=<rows with a NaN or inf> inv=<largest violation of the invariant> inv_at=<vertex>; the program\n"
               << "            prints CERTIFY FAILED: ... and exits non-zero if legal > 0, nonfinite > 0 or inv >= 1e-13 * max(1, sum of the lane's\n"
               << "            seed weights)   (not with --split)\n"
+              << "--sample <S> [--sample-seed <X>]: after every batch draw, per source in source order, S vertices with replacement in proportion to\n"
+              << "            the source's pagerank -- to the score of --rank-factor / --rank-exclude if given (no --topk needed) -- (1 <= S <= 2^20;\n"
+              << "            the draws are a function of the scores, the source's lane, X and the draw number alone): sample <source> lane <lane>\n"
+              << "            total <sum of the weights> support <vertices of positive weight> status <0 ok, 1 empty, 2 not finite> distinct <ids drawn>\n"
+              << "            ids <the first 8>   (not with --split)\n"
               << "--cluster <K> [--cluster-min <P>] [--cluster-min-size <M>]: after every batch print, per source in source order, the prefix of\n"
               << "            lowest conductance of the source's K vertices of largest pagerank > P (1 <= K <= 8192, P >= 0, 1 <= M <= K vertices\n"
               << "            at least): cluster <source> size <vertices> cut <edges leaving it> vol <its out-degrees> phi <conductance>\n"
@@ -283,7 +288,8 @@ inline void ArgumentsChecker() {
     if (gClusterOptsGiven && !gClusterGiven) ok = false;
     if ((gSubgraphGiven && (gSubgraphK < 1 || gSubgraphK > DPPR_SUBGRAPH_MAX)) || (!gSubgraphOut.empty() && !gSubgraphGiven)) ok = false;
     if (gTopKWeightsGiven && (gTopK == 0 || gTopKWeights.empty())) ok = false; // (the count is checked against the sources in main)
-    if (gRankGiven && ((gTopK == 0 && gPositionsFile.empty()) || gRankFactor < 0 || gRankExclude < 0 || gSplitInterface)) ok = false;
+    if ((gSampleGiven && (gSample < 1 || gSample > DPPR_SAMPLE_MAX || gSplitInterface)) || (gSampleSeedGiven && !gSampleGiven)) ok = false;
+    if (gRankGiven && ((gTopK == 0 && gPositionsFile.empty() && !gSampleGiven) || gRankFactor < 0 || gRankExclude < 0 || gSplitInterface)) ok = false;
     if (!gTargetSetsFile.empty() && (gTargetSetsBad || gTargetSets.empty() || !gSourcesFile.empty() || gSplitInterface || gNoGroups || gTopKWeightsGiven)) ok = false;
     if ((gAssignMinGiven || !gAssignOut.empty()) && !gAssign) ok = false;
     if (gAssign && (!(gAssignMin >= 0.0) || gSplitInterface || gNoGroups)) ok = false; // (one device, groups in use: checked against the sources in main)
@@ -367,6 +373,10 @@ inline void ArgumentsParser(int argc, char **argv) {
         gCertifyBad = end == v || *end != '\0' || x > 1000000000l;
         gCertify = gCertifyBad || x < 0 ? 0 : (int)x;
     }
+    gSampleGiven = has(argc, argv, "--sample");
+    gSample = as_int(argc, argv, "--sample", 0);
+    gSampleSeedGiven = has(argc, argv, "--sample-seed");
+    if (const char *v = find(argc, argv, "--sample-seed")) gSampleSeed = std::strtoull(v, nullptr, 0);
     gWalksGiven = find(argc, argv, "--walks") != nullptr;
     gWalks = as_int(argc, argv, "--walks", 0);
     if (const char *v = find(argc, argv, "--walk-seed")) gWalkSeed = std::strtoull(v, nullptr, 0);

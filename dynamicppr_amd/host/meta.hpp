@@ -80,6 +80,10 @@ inline bool gExplainOptsGiven = false;
 inline int gCertify = 0;              // --certify N : after the initial solve and after every N-th batch print certify <source> epoch=.. max_r=.. ... (dppr_certify / dppr_group_certify)
 inline bool gCertifyGiven = false;
 inline bool gCertifyBad = false;      //   N is not a whole number
+inline int gSample = 0;               // --sample S : after every batch print one sample line per source (S draws in proportion to its score)
+inline bool gSampleGiven = false;
+inline bool gSampleSeedGiven = false;
+inline unsigned long long gSampleSeed = 0; // --sample-seed X
 inline int gWalks = 0;                // --walks W : walks per refined vertex (with --refine)
 inline bool gWalksGiven = false;
 inline unsigned long long gWalkSeed = 0; // --walk-seed S

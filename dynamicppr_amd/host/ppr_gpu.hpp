@@ -277,6 +277,7 @@ public:
             if (gAssign) PrintAssign(stream_batch_count);
             if (!gRefineIds.empty()) PrintRefined(-1);
             if (!gPositionIds.empty()) PrintPositions(-1);
+            if (gSample > 0) PrintSamples(-1);
             if (!gExplainIds.empty()) PrintExplained(-1);
             if (gCertify > 0 && stream_batch_count % (size_t)gCertify == 0) PrintCertify(-1);
             if (gClusterK > 0) PrintClusters(-1);
@@ -377,6 +378,7 @@ public:
             if (gAssign) PrintAssign(stream_batch_count);
             if (!gRefineIds.empty()) PrintRefined(epoch); // (the epoch the states stand on: the helper may have built the next one)
             if (!gPositionIds.empty()) PrintPositions(epoch);
+            if (gSample > 0) PrintSamples(epoch);
             if (!gExplainIds.empty()) PrintExplained(epoch);
             if (gCertify > 0 && stream_batch_count % (size_t)gCertify == 0) PrintCertify(epoch); // (the explicit epoch: the helper may have built the next one)
             if (gClusterK > 0) PrintClusters(epoch);
@@ -881,6 +883,51 @@ public:
         std::lock_guard<std::mutex> lk(print_mu);
         std::cout << out << failed << std::flush;
         if (!failed.empty()) std::exit(-1);
+    }
+
+    // --sample: after a batch, gSample vertices drawn in proportion to the score of every source of this device (dppr_sample /
+    // dppr_group_sample: by pagerank, or by the score of --rank-factor / --rank-exclude over `epoch`). Outside the timed region,
+    // printed as one block like --changes.
+    void PrintSamples(int32_t epoch) {
+        const size_t n_src = source_vertex_ids.size(), S = (size_t)gSample;
+        std::vector<int32_t> ids, support, status, seen;
+        std::vector<double> total;
+        dppr_rank_spec_t spec{};
+        spec.factor = gRankGiven ? gRankFactor : DPPR_FACTOR_NONE;
+        spec.exclude = gRankGiven ? (unsigned)gRankExclude : 0u;
+        std::string out;
+        char line[200];
+        for (size_t first = 0; first < n_src; first += use_groups ? kGroupMax : 1) {
+            const size_t n = use_groups ? std::min(kGroupMax, n_src - first) : 1;
+            ids.assign(n * S, -1);
+            total.assign(n, 0.0);
+            support.assign(n, 0);
+            status.assign(n, 0);
+            if (use_groups)
+                DPPR_CHECK(engine, dppr_group_sample(engine, groups[first / kGroupMax], epoch, &spec, 0.0, gSampleSeed, 0, (int32_t)S, DPPR_DEST_HOST, ids.data(),
+                                                     nullptr, total.data(), support.data(), status.data()));
+            else
+                DPPR_CHECK(engine, dppr_sample(engine, slots[first], epoch, &spec, 0.0, gSampleSeed, 0, (int32_t)S, DPPR_DEST_HOST, ids.data(), nullptr,
+                                               total.data(), support.data(), status.data()));
+            for (size_t j = 0; j < n; ++j) {
+                seen.assign(ids.begin() + (long)(j * S), ids.begin() + (long)((j + 1) * S));
+                std::sort(seen.begin(), seen.end());
+                size_t distinct = 0;
+                for (size_t q = 0; q < S; ++q) distinct += seen[q] >= 0 && (q == 0 || seen[q] != seen[q - 1]) ? 1 : 0;
+                std::snprintf(line, sizeof(line), "sample %d lane %d total %.17g support %d status %d distinct %zu ids", (int)source_vertex_ids[first + j], (int)j,
+                              total[j], (int)support[j], (int)status[j], distinct);
+                out += line;
+                for (size_t q = 0; q < std::min<size_t>(S, 8); ++q) {
+                    std::snprintf(line, sizeof(line), " %d", (int)ids[j * S + q]);
+                    out += line;
+                }
+                out += "\n";
+            }
+        }
+        progress++;
+        static std::mutex print_mu;
+        std::lock_guard<std::mutex> lk(print_mu);
+        std::cout << out << std::flush;
     }
 
     // --cluster: after a batch, the prefix of lowest conductance of every source's top-K order over `epoch` (dppr_cluster /

@@ -244,6 +244,25 @@ def group_position_at(engine, gid, ids, min_score=0.0, factor=None, allow=None, 
     return torch.from_numpy(pos), torch.from_numpy(counts)
 
 
+def group_sample(engine, gid, S, min_score=0.0, seed=0, first=0, factor=None, allow=None, deny=None, exclude=(), with_w=True, epoch=-1):
+    """dppr_group_sample over torch tensors: S external ids per lane drawn with replacement in proportion to the lane's score under
+    the factor, masks and exclusions of group_topk_ranked, which it takes in the same form. Returns (ids, w, total, support,
+    status): ids int32 [n, S] and w float64 [n, S] (None without with_w) on the engine's device, filled in place; total float64
+    [n], support int32 [n] and status int32 [n] as CPU tensors. ids are -1 where a lane's status is not SAMPLE_OK."""
+    spec, keep = _rank_spec(engine, factor, allow, deny, exclude, "group_sample")
+    S = int(S)
+    if not 0 <= S <= _eng.SAMPLE_MAX:
+        raise _eng.DpprError(f"group_sample: 0 <= S <= {_eng.SAMPLE_MAX}, not {S}")
+    n = len(engine.group_sources(gid))
+    dev = _device(engine)
+    ids = torch.empty((n, S), dtype=torch.int32, device=dev)
+    w = torch.empty((n, S), dtype=torch.float64, device=dev) if with_w else None
+    torch.cuda.synchronize(dev)   # (the tensors are torch's; nothing of torch's is in flight on them when the engine reads or writes)
+    total, support, status = engine.group_sample_dev(gid, S, ids.data_ptr() if S else None, w.data_ptr() if with_w and S else None, spec,
+                                                     min_score, seed, first, epoch)
+    return ids, w, torch.from_numpy(total), torch.from_numpy(support), torch.from_numpy(status)
+
+
 def assign(engine, groups, scale=None, min_score=0.0, prev=None, want=("best", "margin")):
     """dppr_assign over torch tensors on the engine's device: every external id gets the smallest class of largest score =
     scale[c] * p_c above min_score, or -1; the classes are the lanes of `groups` (handles of this engine) in call order. Returns a

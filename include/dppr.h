@@ -1245,6 +1245,72 @@ int dppr_patch(dppr_engine *e, int32_t slot, double min_p, double min_delta, int
 int dppr_group_patch(dppr_engine *e, int32_t group, double min_p, double min_delta, int64_t cap_up, int64_t cap_del, int dest,
                      int remark, dppr_patch_out_t *out);
 
+/* ---- vertices drawn in proportion to a lane's score (backward-compatible additions, ABI 6) ----
+ * Every query above is a deterministic read. Consumers that TRAIN on the index need draws: negative and candidate sampling for a
+ * recommender or a link predictor (vertices in proportion to p_i[v], the lane's seeds and their neighbours left out, one vertex
+ * type allowed), importance sampling of a GNN mini-batch, Monte Carlo estimates of a sum over a lane's distribution. These calls
+ * draw S external ids per lane WITH replacement, in proportion to a weight that is THE SCORE of the ranked queries, from a sum
+ * tree built on the device; nothing of size V leaves the engine.
+ *
+ * THE DEFINITION. Lane i is in lane order; a slot is n = 1, lane 0. Every step is one addition, one subtraction, one
+ * multiplication or one comparison of IEEE doubles, so a host program reproduces every draw exactly.
+ * 1. WEIGHT. score_i[v] is THE SCORE of dppr_topk_ranked, unchanged: the same factor, mask and exclusion, the same NO ID rule,
+ *    the same EPOCH rule (a spec that reads no degree and no neighbour does not look at `epoch`); spec == NULL means the score is
+ *    p. w_i[v] = score_i[v] if score_i[v] > min_score (min_score >= 0), otherwise w_i[v] = +0.0: a NaN, a negative or a zero score
+ *    weighs nothing.
+ * 2. TREE. P is the smallest power of two >= V. Level 0 is y0[j] = w_i[j] for j < V and +0.0 for V <= j < P, in EXTERNAL id
+ *    order. Level l + 1 is y[j] = y_l[2j] + y_l[2j + 1], one rounding. The root is out_total[i]; out_support[i] is the number of
+ *    positive leaves. A root == 0 gives status DPPR_SAMPLE_EMPTY, a root that is not finite DPPR_SAMPLE_NONFINITE: in both
+ *    cases every draw of the lane is -1 and its out_w is +0.0. Otherwise the status is DPPR_SAMPLE_OK.
+ * 3. UNIFORM. Draw number j = first + 0 .. first + S - 1, in 64-bit arithmetic (first + S must not wrap):
+ *    (x0, x1, x2, x3) = Philox4x32-10(counter = (lo32 j, hi32 j, i, 0x53414D50), key = (lo32 seed, hi32 seed)),
+ *    u = ((x0 * 2^32 + x1) >> 11) * 2^-53, x = u * root, one rounding.
+ * 4. DESCENT. From the root to a leaf. At a node with children L (even) and R (odd): if x >= L and R > 0 then x = x - L (one
+ *    rounding) and go right; otherwise go left. The draw is the leaf's external id and out_w is that leaf's weight.
+ * CONSEQUENCES. The descent only ever enters a node of positive value: a draw never returns a masked, excluded or
+ * below-threshold vertex, whatever the roundings did (x may even be rounded up to the root itself). A lane's draws are a function
+ * of its own leaves, its lane index, seed and j alone: not of n, S, the other lanes, or the form of the kernels. The contract is
+ * the definition: the probability of v is w[v] / total up to the rounding of the sums, of relative order log2(P) * 2^-52.
+ * ANCHORS. (a) Every drawn id v has dppr_group_rank_score_at(v) in that lane equal to out_w bit for bit, and > min_score.
+ * (b) The draws of (first, S = a + b) are those of (first, a) followed by those of (first + a, b). (c) A lane with one positive
+ * leaf returns it S times. (d) S == 0 is valid: only totals, supports and statuses are computed.
+ *
+ * dest (DPPR_DEST_HOST / DPPR_DEST_DEVICE) governs out_ids and out_w: a device pointer is checked as the destinations of the
+ * exports are (aligned device memory of the engine's device, n * S elements inside one allocation), and is complete when the call
+ * returns. out_w and out_support may be NULL. out_total, out_support and out_status are always host memory. Outputs:
+ * dppr_sample out_ids [S], out_w [S], one total, support and status; dppr_group_sample out_ids [n][S] and out_w [n][S],
+ * lane-major, out_total [n], out_support [n], out_status [n].
+ *
+ * Rejected with DPPR_ERR_INVALID before any device work, nothing written: every spec and epoch rejection of dppr_topk_ranked;
+ * min_score negative or NaN; S < 0, S > DPPR_SAMPLE_MAX or n * S > DPPR_SAMPLE_MAX_TOTAL; first + S wrapping; an unknown dest;
+ * a NULL out_ids with S > 0; a NULL out_total or out_status; a device out_ids or out_w that the range check refuses; a bad slot
+ * / group.
+ * Threading and stream as dppr_topk_ranked: the id-map lock for the whole call (safe beside dppr_slide_concurrent), the solver
+ * stream, any state (converged or not), never part of the update path or of a timed region. Every stage is enqueued before the
+ * single copy back. WORK SPACE: 8 n Vt bytes of leaves (Vt = V rounded up to 2048) and 8 n (Vt / 128 + 2 per level) bytes of
+ * nodes -- about 8 n V (1 + 1/128) --, dppr_topk_ranked's exclusion words where the spec excludes, and the result block with its
+ * pinned twin: 256 bytes, and 12 n S more for a host destination. All of it is the engine's, obtained before the first kernel,
+ * grown on demand and released with the engine: after DPPR_ERR_NOMEM the states and the engine are as before. With
+ * dppr_set_profiling on, dppr_debug_query_ms reports the device time of the last of these calls.
+ * OUT OF SCOPE: sampling without replacement; weight vectors across lanes (the scores of dppr_group_topk_weighted); sampling by r
+ * or by |delta p|; alias tables.
+ * dppr_debug_sample_form: a test hook, as dppr_debug_walk_form. 0 (default): a wave rebuilds the lowest 8 levels of a draw from
+ * the 256 leaves under it; 1: one thread per draw reads every level from a fully stored tree (8 n Vt bytes more). The results do
+ * not depend on the form. */
+#define DPPR_SAMPLE_MAX        (1 << 20)  /* draws per lane and call */
+#define DPPR_SAMPLE_MAX_TOTAL  (1 << 24)  /* n * S per call */
+#define DPPR_SAMPLE_OK         0
+#define DPPR_SAMPLE_EMPTY      1          /* no vertex has a positive weight: every draw is -1 */
+#define DPPR_SAMPLE_NONFINITE  2          /* the lane's total is not finite: every draw is -1 */
+int dppr_sample(dppr_engine *e, int32_t slot, int32_t epoch, const dppr_rank_spec_t *spec, double min_score, uint64_t seed,
+                uint64_t first, int32_t S, int dest, int32_t *out_ids /* [S] */, double *out_w /* [S], may be NULL */,
+                double *out_total /* [1] */, int32_t *out_support /* [1], may be NULL */, int32_t *out_status /* [1] */);
+int dppr_group_sample(dppr_engine *e, int32_t group, int32_t epoch, const dppr_rank_spec_t *spec, double min_score, uint64_t seed,
+                      uint64_t first, int32_t S, int dest, int32_t *out_ids /* [n][S], lane-major */,
+                      double *out_w /* [n][S], may be NULL */, double *out_total /* [n] */,
+                      int32_t *out_support /* [n], may be NULL */, int32_t *out_status /* [n] */);
+int dppr_debug_sample_form(dppr_engine *e, int form);
+
 /* Windows whose sweep groups are all resident at once run a frontier loop of a source group as
  * multi-sweep launches (grid barrier between sweeps, row tables kept in LDS; dppr_multi.hpp). on by
  * default; 0 = one launch per sweep everywhere. The roll-call / time-out rules are those of
