@@ -57,6 +57,7 @@
 #include "dppr_position.hpp"
 #include "dppr_sample.hpp"
 #include "dppr_explain.hpp"
+#include "dppr_forward.hpp"
 
 using namespace dppr;
 
@@ -1691,6 +1692,19 @@ int dppr_debug_certify(dppr_engine *e, int piece_edges, int wave_rows) {
         return fail(e, DPPR_ERR_INVALID, "debug_certify: piece_edges in [0, 2^20], wave_rows 0 or a power of two up to 64 (0: the plan's choice)");
     e->cert_piece = piece_edges;
     e->cert_wave_rows = wave_rows;
+    return DPPR_OK;
+}
+
+int dppr_forward(dppr_engine *e, int32_t epoch, const int32_t *starts, int32_t m, int32_t iters, double tol, const dppr_forward_out_t *out) {
+    if (!e || e->broken) return fail(e, DPPR_ERR_INVALID, "forward: no usable engine");
+    return forward_call(e, epoch, starts, m, iters, tol, out);
+}
+
+int dppr_debug_forward(dppr_engine *e, int piece_edges, int team) {
+    if (!e || !fw_hook_ok(piece_edges, team))
+        return fail(e, DPPR_ERR_INVALID, "debug_forward: piece_edges 0 or a power of two in [64, 4096], team 0, 1, 2, 4 or 8 (0: the plan's choice)");
+    e->fw_piece = piece_edges;
+    e->fw_team = team;
     return DPPR_OK;
 }
 

@@ -1750,4 +1750,153 @@ int certify_call(dppr_engine *e, Owner &o, int32_t epoch, double eps, int flags,
     return run_certify(e, v, rank_lanes(o), *ep, eps, which, *out);
 }
 
+// ---- the forward sweep of any vertex (dppr_forward.hpp, dppr_forward_plan.hpp) -----------------------------------------------------
+// One of the four instantiations of a sweep kernel template <PP, LEVELS>: f(pieces of a row per lane, levels of the counter)
+template <class F> int by_fw_shape(int lane_pieces, int levels, F &&f) {
+    using I1 = std::integral_constant<int, 1>;
+    using I2 = std::integral_constant<int, 2>;
+    using LS = std::integral_constant<int, FW_LEVELS_SHORT>;
+    using LL = std::integral_constant<int, FW_LEVELS_LONG>;
+    if (lane_pieces == 1) return levels == FW_LEVELS_SHORT ? f(I1(), LS()) : f(I1(), LL());
+    return levels == FW_LEVELS_SHORT ? f(I2(), LS()) : f(I2(), LL());
+}
+
+// The sweeps and the parts `which` names (arguments, ids, a device destination and the epoch validated by the caller). Every buffer
+// is in place before the first kernel. Per chunk the host enqueues up to 8 sweeps, the rem fold and the freeze update and reads
+// back the freeze word; the whole head comes back once, after the last chunk.
+int run_forward(dppr_engine *e, const Epoch &ep, const int32_t *starts, int m, int iters, double tol, uint32_t which,
+                const dppr_forward_out_t &out) {
+    if (int rc = query_begin(e, MAP_E2I | ((which & FW_TOPK) ? MAP_I2E : 0u))) return rc;
+    QueryWork::Forward &fq = e->q.fw;
+    const int V = e->V, gw = fw_row_width(m);
+    const int piece = fw_piece(e->fw_piece), T = fw_team(gw, e->fw_team), PP = fw_lane_pieces(gw, T), levels = fw_levels(piece);
+    const size_t plane = fw_plane_elems(V, gw), part_elems = fw_part_elems(V, m);
+    const size_t item_cap = fw_item_cap(ep.Ed, piece), long_cap = fw_long_cap(ep.Ed, piece);
+    const long long stride = fw_part_stride(V);
+    Grow grow{e};
+    int rc = grow(fq.planes, 4 * plane);
+    if (!rc) rc = grow(fq.head, sizeof(FwHead));
+    if (!rc) rc = grow(fq.pin, sizeof(FwHead));
+    if (!rc) rc = grow(fq.part, part_elems);
+    if (!rc) rc = grow(fq.items, item_cap);
+    if (!rc) rc = grow(fq.longs, sizeof(FwLong) * long_cap);
+    if (!rc) rc = grow(fq.pp, item_cap * (size_t)gw);
+    if (!rc && (which & FW_TOPK)) rc = topk_workspace(e, grow, m, (size_t)(e->n_int + e->n_parked));
+    if (!rc && (which & FW_AT)) rc = grow(e->q.ra.buf, ra_layout(out.n_at, m, 2).total_bytes);
+    if (rc) return rc;
+    double *y = fq.planes.get(), *yn = y + plane, *f = yn + plane, *x = f + plane;
+    FwHead *head = reinterpret_cast<FwHead *>(fq.head.get());
+    const FwHead *pin = reinterpret_cast<const FwHead *>(fq.pin.get());
+    FwLong *longs = reinterpret_cast<FwLong *>(fq.longs.get());
+    const unsigned icap = (unsigned)std::min<size_t>(item_cap, 0xffffffffu), lcap = (unsigned)std::min<size_t>(long_cap, 0xffffffffu);
+    const FwGraph g{ep.row_ptr.get(), ep.adj.get(), ep.out_row_ptr.get(), e->n_int, V};
+    const int *x2i = e->d_ext2int.get();
+    const dim3 block(FW_BLOCK);
+    const dim3 rows_grid((unsigned)fw_units_grid(e->n_int, T)), piece_grid((unsigned)fw_units_grid((long long)std::min<size_t>(item_cap, 1u << 20), T));
+    const dim3 long_grid((unsigned)grid_for((int64_t)std::min<size_t>(long_cap, 1u << 16) * m, FW_BLOCK, 1024));
+
+    HIP_TRY(hipMemsetAsync(head, 0, sizeof(FwHead), e->stream));
+    HIP_TRY(hipMemcpyAsync(head->starts, starts, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemsetAsync(fq.planes, 0, sizeof(double) * 4 * plane, e->stream));
+    HIP_TRY(hipMemsetAsync(fq.part, 0, sizeof(double) * part_elems, e->stream)); // (+0.0: the tiles of padding)
+    if (int rc2 = DeviceTime{e}.open()) return rc2;
+    hipLaunchKernelGGL(k_fw_init, dim3(1), dim3(WAVE), 0, e->stream, head, m, iters, x2i, g, y, f, gw);
+    hipLaunchKernelGGL(k_fw_list, dim3((unsigned)grid_for(e->n_int, FW_BLOCK, 1024)), block, 0, e->stream, g, piece, head, fq.items.get(), icap,
+                       longs, lcap);
+    HIP_TRY(hipGetLastError());
+    unsigned frozen = 0;
+    for (int k = 0; k < iters && (frozen & fw_all(m)) != fw_all(m);) {
+        const int end = fw_next_check(k, iters);
+        for (++k; k <= end; ++k) {
+            const FwPlanes pl{y, yn, f, x, gw, m, k == end ? 1 : 0};
+            by_fw_shape(PP, levels, [&](auto pp_c, auto lv_c) -> int {
+                constexpr int P = decltype(pp_c)::value, L = decltype(lv_c)::value;
+                hipLaunchKernelGGL((k_fw_sweep<P, L>), rows_grid, block, 0, e->stream, g, pl, T, piece, head);
+                hipLaunchKernelGGL((k_fw_pieces<P, L>), piece_grid, block, 0, e->stream, g, pl.y, gw, m, T, piece, head, fq.items.get(), icap,
+                                   fq.pp.get());
+                return DPPR_OK;
+            });
+            hipLaunchKernelGGL(k_fw_long, long_grid, block, 0, e->stream, g, pl, piece, head, longs, lcap, fq.pp.get());
+            std::swap(y, yn);
+        }
+        k = end;
+        hipLaunchKernelGGL(k_fw_rem, dim3((unsigned)fw_rem_grid(V)), block, dot_lds_bytes(gw, 1), e->stream, x, gw, m, x2i, V, fq.part.get(), stride);
+        hipLaunchKernelGGL(k_dot_combine, dim3((m + DOT_CB_WAVES - 1) / DOT_CB_WAVES), dim3(DOT_CB_WAVES * WAVE), 0, e->stream, fq.part.get(),
+                           (const long long *)nullptr, stride, m, m, &head->dot, head->cur);
+        hipLaunchKernelGGL(k_fw_check, dim3(1), dim3(WAVE), 0, e->stream, head, m, k, tol, k == iters ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(fq.pin, head, sizeof(unsigned), hipMemcpyDeviceToHost, e->stream)); // THE word of the chunk
+        HIP_TRY(loop_wait(e));
+        frozen = pin->frozen;
+    }
+    if (int rc2 = DeviceTime{e}.close()) return rc2;
+    HIP_TRY(hipMemcpyAsync(fq.pin, head, sizeof(FwHead), hipMemcpyDeviceToHost, e->stream));
+    if (int rc2 = run_end(e)) return rc2;
+    const float sweep_ms = e->query_ms;
+    if (pin->overflow) return fail(e, DPPR_ERR_HIP, "forward: the list of the long rows' pieces was too short (fw_item_cap)");
+    const FwHead hd = *pin; // (the parts below reuse nothing of it, but the pinned twin is the engine's)
+    if (out.iters_used) memcpy(out.iters_used, hd.iters_used, sizeof(int32_t) * (size_t)m);
+    if (out.rem) memcpy(out.rem, hd.rem, sizeof(double) * (size_t)m);
+
+    if (which & FW_DENSE) {
+        const bool sm = out.dense_layout == DPPR_SOURCE_MAJOR;
+        const dim3 grid(sm ? std::min((int)ex_tiles(V), 2048) : grid_for((int64_t)V * m, EX_TILE));
+        by_dtype_layout(out.dense_dtype, sm, [&](auto elem, auto source_major) -> int {
+            using E = decltype(elem);
+            hipLaunchKernelGGL((k_ex_dense<E, decltype(source_major)::value>), grid, dim3(EX_TILE), 0, e->stream, f, gw, m, x2i, V,
+                               static_cast<E *>(out.dense_dev));
+            for (int c = 0; c < m; ++c)
+                if (hd.rowless[c])
+                    hipLaunchKernelGGL(k_fw_poke<E>, dim3(1), dim3(WAVE), 0, e->stream, static_cast<E *>(out.dense_dev),
+                                       (long long)ex_dense_index(out.dense_layout, m, V, starts[c], c));
+            return DPPR_OK;
+        });
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(e->stream)); // (the destination is complete here: any stream of the caller may read it)
+    }
+    if (which & FW_AT) {
+        const int n_at = out.n_at;
+        if (int rc2 = point_read(e, grow, out.at_ids, n_at, m, 2, out.at_f, nullptr, [&](const int *d_ids, double *d_a, double *d_b) {
+                hipLaunchKernelGGL(k_read_at, dim3(grid_for((int64_t)n_at * m)), dim3(BLOCK), 0, e->stream, f, f, gw, m, x2i, d_ids, n_at, d_a, d_b);
+                return DPPR_OK;
+            }))
+            return rc2;
+        for (int c = 0; c < m; ++c)
+            if (hd.rowless[c])
+                for (int j = 0; j < n_at; ++j)
+                    if (out.at_ids[j] == starts[c]) out.at_f[(size_t)j * m + c] = FW_ALPHA;
+    }
+    if (which & FW_TOPK) {
+        const TkState st = tk_state(e, f, f, gw, m);
+        if (int rc2 = run_select(e, st, e->d_int2ext, out.k, out.min_f, out.topk_ids, out.topk_f, nullptr, out.topk_counts)) return rc2;
+        for (int c = 0; c < m; ++c)
+            if (hd.rowless[c] && FW_ALPHA > out.min_f) { // (the column holds nothing else)
+                out.topk_counts[c] = 1;
+                out.topk_ids[(size_t)c * out.k] = starts[c];
+                out.topk_f[(size_t)c * out.k] = FW_ALPHA;
+            }
+    }
+    if (e->profiling) e->query_ms = sweep_ms; // (the parts opened brackets of their own)
+    return DPPR_OK;
+}
+
+int forward_call(dppr_engine *e, int32_t epoch, const int32_t *starts, int32_t m, int32_t iters, double tol, const dppr_forward_out_t *out) {
+    if (!fw_args_ok(starts, m, iters, tol, out))
+        return fail(e, DPPR_ERR_INVALID, "forward: m in [1, 16], iters in [1, 256], tol >= 0 and finite, non-null starts / out");
+    if (!fw_parts_ok(out))
+        return fail(e, DPPR_ERR_INVALID,
+                    "forward: a part asked for needs all its pointers; k in [1, DPPR_TOPK_MAX], min_f >= 0; n_at in [1, DPPR_FORWARD_AT_MAX]; dtype 0 or 1, layout 0 or 1");
+    const uint32_t which = fw_which(out);
+    if (!dppr::ids_in_range(starts, m, e->V)) return fail(e, DPPR_ERR_INVALID, "forward: starts in [0, V)");
+    if ((which & FW_AT) && !dppr::ids_in_range(out->at_ids, out->n_at, e->V)) return fail(e, DPPR_ERR_INVALID, "forward: at_ids in [0, V)");
+    const Epoch *ep = find_epoch(e, epoch);
+    if (!ep) return fail(e, DPPR_ERR_INVALID, "forward: epoch not resident (evicted or never built)");
+    HIP_TRY(hipSetDevice(e->device));
+    if ((which & FW_DENSE) && !dev_range_ok(e, out->dense_dev, ex_dense_bytes(out->dense_dtype, m, e->V), ex_elem_bytes(out->dense_dtype)))
+        return fail(e, DPPR_ERR_INVALID, "forward: dense_dev must be aligned device memory of the engine's device, m x V elements inside one allocation");
+    if (!which) return DPPR_OK;
+    std::lock_guard<std::mutex> map_lk(e->map_mu); // (as dppr_read: one state of the id space for the whole call)
+    return run_forward(e, *ep, starts, m, iters, tol, which, *out);
+}
+
 } // namespace

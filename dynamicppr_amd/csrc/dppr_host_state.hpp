@@ -268,6 +268,14 @@ struct QueryWork {
         DevBuf<unsigned long long> list; // the queued pieces of the long rows (cert_list_cap)
         DevBuf<double> pp;               // [queued pieces][gw] one partial per piece
     } cert;
+    struct Forward { // the forward sweep of any vertex (dppr_forward.hpp, dppr_forward_plan.hpp); its selection: tk, its point reads: ra
+        DevBuf<double> planes;            // y | y' | f | x, each [V][row width]
+        DevBuf<unsigned char> head; PinBuf<unsigned char> pin; // FwHead: device / pinned host (the freeze word per chunk, the whole head at the end)
+        DevBuf<double> part;              // the partials of the rem fold, as the dot family lays them out
+        DevBuf<unsigned long long> items; // the queued pieces of the long in-rows (fw_item_cap)
+        DevBuf<unsigned char> longs;      // the long rows (FwLong, fw_long_cap)
+        DevBuf<double> pp;                // [queued pieces][row width] one partial per piece
+    } fw;
     struct Assign { // every vertex to its best lane across groups (dppr_assign.hpp, dppr_assign_plan.hpp); the block grows with a host destination
         DevBuf<double> scale; // [256] the scales of the call
         DevBuf<int> cnt;      // [tiles] flips per tile
@@ -455,6 +463,8 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     int ex_wave_rows = EX_WAVE_ROWS; // entries of a row a wave of dppr_explain.hpp takes per step (dppr_debug_explain)
     int cert_piece = 0;             // edges of a piece of a long row in k_cert_rows; 0: the plan's choice (dppr_debug_certify)
     int cert_wave_rows = 0;         // short rows that share a wave of k_cert_rows; 0: the plan's choice (dppr_debug_certify)
+    int fw_piece = 0;               // entries of a piece of a long in-row of the forward sweep; 0: the plan's choice (dppr_debug_forward)
+    int fw_team = 0;                // lanes that share a gathered row there; 0: the plan's choice (dppr_debug_forward)
     float query_ms = -1.0f;         // dppr_set_profiling: device time of the last top-k, changes, export or dot call, first to last kernel (dppr_debug_query_ms)
     std::vector<int32_t> h_tmp1, h_tmp2;
     std::vector<int32_t> h_tiles; // host copy of the tile edge prefix / group table

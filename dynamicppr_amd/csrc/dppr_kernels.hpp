@@ -26,6 +26,7 @@
 //   dppr_targets.hpp  weighted vertex sets as a group's targets: seed table lookup, seeded Init (included by dppr_update.hpp)
 //   dppr_multi.hpp    multi-source batched sweeps (included separately by the engine)
 //   dppr_certify.hpp  the certificate of a state: residual norms and the loop invariant against an epoch's out-CSR (a query)
+//   dppr_forward.hpp  the forward sweep of any vertex: a pull over an epoch's in-CSR for up to 16 starts (a query; included by the engine)
 #pragma once
 
 #include "dppr_common.hpp"

@@ -78,6 +78,7 @@ EXPORTS = [
     "dppr_explain_at", "dppr_group_explain_at", "dppr_debug_explain",
     "dppr_certify", "dppr_group_certify", "dppr_debug_certify",
     "dppr_sample", "dppr_group_sample", "dppr_debug_sample_form",
+    "dppr_forward", "dppr_debug_forward",
 ]
 
 DEST_HOST, DEST_DEVICE = 0, 1
@@ -104,6 +105,7 @@ PATCH_KEEP_MARK, PATCH_REMARK_ALL, PATCH_REMARK_EMITTED = 0, 1, 2
 SAMPLE_MAX, SAMPLE_MAX_TOTAL = 1 << 20, 1 << 24
 SAMPLE_OK, SAMPLE_EMPTY, SAMPLE_NONFINITE = 0, 1, 2
 SAMPLE_WAVE, SAMPLE_PER_THREAD = 0, 1
+FORWARD_MAX_M, FORWARD_MAX_ITERS, FORWARD_CHECK, FORWARD_AT_MAX = 16, 256, 8, 4096
 
 
 class RankSpec(C.Structure):
@@ -126,6 +128,14 @@ class CertifyOut(C.Structure):
     _fields_ = [("max_abs_r", _dp), ("argmax_r", _ip), ("sum_abs_r", _dp), ("sum_p", _dp), ("n_pos", _lp), ("n_neg", _lp),
                 ("n_nonfinite", _lp), ("n_p_nonzero", _lp), ("inv_max_err", _dp), ("inv_argmax", _ip),
                 ("state_epoch", C.c_int32), ("converged", C.c_int32), ("conv_eps", C.c_double)]
+
+
+class ForwardOut(C.Structure):
+    """dppr_forward_out_t: where the parts of a forward call go (a part whose pointers are all NULL is not run)."""
+    _ip, _dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    _fields_ = [("iters_used", _ip), ("rem", _dp), ("k", C.c_int32), ("min_f", C.c_double), ("topk_ids", _ip), ("topk_f", _dp),
+                ("topk_counts", _ip), ("at_ids", _ip), ("n_at", C.c_int32), ("at_f", _dp), ("dense_dev", C.c_void_p),
+                ("dense_dtype", C.c_int32), ("dense_layout", C.c_int32)]
 
 
 class PatchOut(C.Structure):
@@ -309,6 +319,8 @@ def lib():
     L.dppr_certify.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int, vp]
     L.dppr_group_certify.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int, vp]
     L.dppr_debug_certify.argtypes = [vp, C.c_int, C.c_int]
+    L.dppr_forward.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_double, vp]
+    L.dppr_debug_forward.argtypes = [vp, C.c_int, C.c_int]
     L.dppr_assign.argtypes = [vp, ip, C.c_int32, dp, C.c_double, C.c_int, vp, vp, vp, i64p, vp, C.c_int64, i64p, vp, vp, vp]
     L.dppr_assign_at.argtypes = [vp, ip, C.c_int32, dp, C.c_double, ip, C.c_int32, ip, dp, ip, dp]
     for name in EXPORTS:
@@ -964,6 +976,42 @@ class Engine:
     def debug_sample_form(self, form):
         """Test hook (dppr_debug_sample_form): SAMPLE_WAVE (default) or SAMPLE_PER_THREAD. The results do not depend on it."""
         self._ck(self._L.dppr_debug_sample_form(self._h, int(form)), "debug_sample_form")
+
+    # ---- forward PPR of any vertex on the resident window ----
+    def forward(self, starts, iters=64, tol=0.0, k=0, min_f=0.0, at=None, epoch=-1, dense_ptr=None, dtype=F64, layout=VERTEX_MAJOR):
+        """f^K of the walk from each of the external ids `starts` (at most 16) over the in-CSR of `epoch` (include/dppr.h:
+        dppr_forward). Returns a dict: iters_used [m] int32 and rem [m]; with k > 0, topk = a list of (ids, f) per start, f
+        descending, ties by id ascending, f > min_f; with `at`, at = f at those external ids, [m][len(at)]. dense_ptr: a raw
+        device address that takes f by external id, [V][m] (VERTEX_MAJOR) or [m][V] (SOURCE_MAJOR) elements of `dtype`."""
+        a, pa = _i32(starts)
+        m = len(a)
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        res = {"iters_used": np.full(max(m, 1), -1, dtype=np.int32), "rem": np.full(max(m, 1), np.nan)}
+        out = ForwardOut()
+        out.iters_used, out.rem = res["iters_used"].ctypes.data_as(ip), res["rem"].ctypes.data_as(dp)
+        if k:
+            kk = max(int(k), 1)
+            ids, f, cnt = np.empty((max(m, 1), kk), dtype=np.int32), np.empty((max(m, 1), kk)), np.empty(max(m, 1), dtype=np.int32)
+            out.k, out.min_f = int(k), float(min_f)
+            out.topk_ids, out.topk_f, out.topk_counts = ids.ctypes.data_as(ip), f.ctypes.data_as(dp), cnt.ctypes.data_as(ip)
+        if at is not None:
+            b, _ = _i32(at)
+            at_f = np.empty((max(len(b), 1), max(m, 1)))
+            out.at_ids, out.n_at, out.at_f = b.ctypes.data_as(ip), len(b), at_f.ctypes.data_as(dp)
+        if dense_ptr:
+            out.dense_dev, out.dense_dtype, out.dense_layout = dense_ptr, int(dtype), int(layout)
+        self._ck(self._L.dppr_forward(self._h, int(epoch), pa, m, int(iters), float(tol), C.byref(out)), "forward")
+        res["iters_used"], res["rem"] = res["iters_used"][:m], res["rem"][:m]
+        if k:
+            res["topk"] = [(ids[i, :c].copy(), f[i, :c].copy()) for i, c in enumerate(cnt[:m])]
+        if at is not None:
+            res["at"] = np.ascontiguousarray(at_f[:len(b), :m].T)
+        return res
+
+    def debug_forward(self, piece_edges=0, team=0):
+        """Test hook (dppr_debug_forward): in-rows longer than piece_edges are summed in pieces; `team` lanes share a gathered
+        row. 0: the plan's choice. The results do not depend on either."""
+        self._ck(self._L.dppr_debug_forward(self._h, int(piece_edges), int(team)), "debug_forward")
 
     # ---- every vertex to its best lane, across groups ----
     def _assign_classes(self, groups, scale, what):

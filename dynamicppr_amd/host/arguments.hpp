@@ -211,6 +211,11 @@ inline void PrintUsage() {
               << "            legal to push> nonfinite=<rows with a NaN or inf> inv=<largest violation of the invariant> inv_at=<vertex>; the program\n"
               << "            prints CERTIFY FAILED: ... and exits non-zero if legal > 0, nonfinite > 0 or inv >= 1e-13 * max(1, sum of the lane's\n"
               << "            seed weights)   (not with --split)\n"
+              << "--forward <file> [--forward-iters <N>] [--forward-tol <T>] [--forward-topk <K>]: <file> holds one vertex id per line; after every\n"
+              << "            batch sweep the walk FROM each of them forward over the batch's own graph (any vertex, tracked or not; 1 <= N <= 256\n"
+              << "            iterations, default 64; a start stops at a check -- every 8 iterations -- once less than T of its mass remains, default\n"
+              << "            0; the K vertices it reaches most, 0 <= K <= 64, default 5): forward <vertex> iters <used> rem <mass remaining> top <found>\n"
+              << "            <v0>:<f0> <v1>:<f1> ...   (starts beyond 16 go in calls of 16; not with --split)\n"
               << "--sample <S> [--sample-seed <X>]: after every batch draw, per source in source order, S vertices with replacement in proportion to\n"
               << "            the source's pagerank -- to the score of --rank-factor / --rank-exclude if given (no --topk needed) -- (1 <= S <= 2^20;\n"
               << "            the draws are a function of the scores, the source's lane, X and the draw number alone): sample <source> lane <lane>\n"
@@ -288,6 +293,10 @@ inline void ArgumentsChecker() {
     if (gClusterOptsGiven && !gClusterGiven) ok = false;
     if ((gSubgraphGiven && (gSubgraphK < 1 || gSubgraphK > DPPR_SUBGRAPH_MAX)) || (!gSubgraphOut.empty() && !gSubgraphGiven)) ok = false;
     if (gTopKWeightsGiven && (gTopK == 0 || gTopKWeights.empty())) ok = false; // (the count is checked against the sources in main)
+    if (gForwardBad || (gForwardOptsGiven && gForwardFile.empty())) ok = false;
+    if (!gForwardFile.empty() && (gSplitInterface || gForwardIters < 1 || gForwardIters > DPPR_FORWARD_MAX_ITERS || !(gForwardTol >= 0.0) ||
+                                  !std::isfinite(gForwardTol) || gForwardTopK < 0 || gForwardTopK > 64))
+        ok = false;
     if ((gSampleGiven && (gSample < 1 || gSample > DPPR_SAMPLE_MAX || gSplitInterface)) || (gSampleSeedGiven && !gSampleGiven)) ok = false;
     if (gRankGiven && ((gTopK == 0 && gPositionsFile.empty() && !gSampleGiven) || gRankFactor < 0 || gRankExclude < 0 || gSplitInterface)) ok = false;
     if (!gTargetSetsFile.empty() && (gTargetSetsBad || gTargetSets.empty() || !gSourcesFile.empty() || gSplitInterface || gNoGroups || gTopKWeightsGiven)) ok = false;
@@ -373,6 +382,14 @@ inline void ArgumentsParser(int argc, char **argv) {
         gCertifyBad = end == v || *end != '\0' || x > 1000000000l;
         gCertify = gCertifyBad || x < 0 ? 0 : (int)x;
     }
+    if (const char *f = find(argc, argv, "--forward")) {
+        gForwardFile = f;
+        gForwardBad = !load_ids(f, gForwardIds);
+    }
+    gForwardOptsGiven = has(argc, argv, "--forward-iters") || has(argc, argv, "--forward-tol") || has(argc, argv, "--forward-topk");
+    gForwardIters = as_int(argc, argv, "--forward-iters", 64);
+    gForwardTol = as_whole_double(argc, argv, "--forward-tol", 0.0);
+    gForwardTopK = as_int(argc, argv, "--forward-topk", 5);
     gSampleGiven = has(argc, argv, "--sample");
     gSample = as_int(argc, argv, "--sample", 0);
     gSampleSeedGiven = has(argc, argv, "--sample-seed");

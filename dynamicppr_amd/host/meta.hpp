@@ -80,6 +80,13 @@ inline bool gExplainOptsGiven = false;
 inline int gCertify = 0;              // --certify N : after the initial solve and after every N-th batch print certify <source> epoch=.. max_r=.. ... (dppr_certify / dppr_group_certify)
 inline bool gCertifyGiven = false;
 inline bool gCertifyBad = false;      //   N is not a whole number
+inline std::string gForwardFile;      // --forward FILE : one external vertex id per line; after every batch print one forward line per start (dppr_forward)
+inline bool gForwardBad = false;      //   FILE could not be read, holds no id, or a token is not an id >= 0
+inline std::vector<int32_t> gForwardIds;
+inline bool gForwardOptsGiven = false; // --forward-iters / --forward-tol / --forward-topk
+inline int gForwardIters = 64;        // --forward-iters N (1 <= N <= 256)
+inline double gForwardTol = 0.0;      // --forward-tol T (T >= 0)
+inline int gForwardTopK = 5;          // --forward-topk K (0 <= K <= 64: 0 prints no vertex)
 inline int gSample = 0;               // --sample S : after every batch print one sample line per source (S draws in proportion to its score)
 inline bool gSampleGiven = false;
 inline bool gSampleSeedGiven = false;

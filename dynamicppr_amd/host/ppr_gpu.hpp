@@ -278,6 +278,7 @@ public:
             if (!gRefineIds.empty()) PrintRefined(-1);
             if (!gPositionIds.empty()) PrintPositions(-1);
             if (gSample > 0) PrintSamples(-1);
+            if (!gForwardIds.empty()) PrintForward(-1);
             if (!gExplainIds.empty()) PrintExplained(-1);
             if (gCertify > 0 && stream_batch_count % (size_t)gCertify == 0) PrintCertify(-1);
             if (gClusterK > 0) PrintClusters(-1);
@@ -379,6 +380,7 @@ public:
             if (!gRefineIds.empty()) PrintRefined(epoch); // (the epoch the states stand on: the helper may have built the next one)
             if (!gPositionIds.empty()) PrintPositions(epoch);
             if (gSample > 0) PrintSamples(epoch);
+            if (!gForwardIds.empty()) PrintForward(epoch);
             if (!gExplainIds.empty()) PrintExplained(epoch);
             if (gCertify > 0 && stream_batch_count % (size_t)gCertify == 0) PrintCertify(epoch); // (the explicit epoch: the helper may have built the next one)
             if (gClusterK > 0) PrintClusters(epoch);
@@ -919,6 +921,44 @@ public:
                 out += line;
                 for (size_t q = 0; q < std::min<size_t>(S, 8); ++q) {
                     std::snprintf(line, sizeof(line), " %d", (int)ids[j * S + q]);
+                    out += line;
+                }
+                out += "\n";
+            }
+        }
+        progress++;
+        static std::mutex print_mu;
+        std::lock_guard<std::mutex> lk(print_mu);
+        std::cout << out << std::flush;
+    }
+
+    // --forward: after a batch, the forward sweep from every id of the file over `epoch` (dppr_forward: any vertex, tracked or not), in
+    // calls of at most 16 starts. Outside the timed region, printed as one block like --changes.
+    void PrintForward(int32_t epoch) {
+        const size_t n_ids = gForwardIds.size(), K = (size_t)gForwardTopK;
+        std::vector<int32_t> used(DPPR_FORWARD_MAX_M), ids(DPPR_FORWARD_MAX_M * std::max<size_t>(K, 1)), counts(DPPR_FORWARD_MAX_M);
+        std::vector<double> rem(DPPR_FORWARD_MAX_M), f(DPPR_FORWARD_MAX_M * std::max<size_t>(K, 1));
+        std::string out;
+        char line[200];
+        for (size_t first = 0; first < n_ids; first += DPPR_FORWARD_MAX_M) {
+            const size_t m = std::min<size_t>(DPPR_FORWARD_MAX_M, n_ids - first);
+            dppr_forward_out_t o{};
+            o.iters_used = used.data();
+            o.rem = rem.data();
+            std::fill(counts.begin(), counts.end(), 0);
+            if (K > 0) {
+                o.k = (int32_t)K;
+                o.min_f = 0.0;
+                o.topk_ids = ids.data();
+                o.topk_f = f.data();
+                o.topk_counts = counts.data();
+            }
+            DPPR_CHECK(engine, dppr_forward(engine, epoch, gForwardIds.data() + first, (int32_t)m, gForwardIters, gForwardTol, &o));
+            for (size_t j = 0; j < m; ++j) {
+                std::snprintf(line, sizeof(line), "forward %d iters %d rem %.17g top %d", (int)gForwardIds[first + j], (int)used[j], rem[j], (int)counts[j]);
+                out += line;
+                for (size_t q = 0; q < (size_t)counts[j]; ++q) {
+                    std::snprintf(line, sizeof(line), " %d:%.17g", (int)ids[j * K + q], f[j * K + q]);
                     out += line;
                 }
                 out += "\n";

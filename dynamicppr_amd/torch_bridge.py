@@ -95,6 +95,22 @@ def group_dense(engine, gid, which="p", dtype=torch.float64, layout="source_majo
     return out
 
 
+def forward(engine, starts, iters=64, tol=0.0, dtype=torch.float64, layout="source_major", epoch=-1):
+    """dppr_forward over torch tensors: f^K of the walk from each of the external ids `starts` (at most 16) as a dense tensor on
+    the engine's device, [m, V] (source_major) or [V, m] (vertex_major), float64 (bit for bit) or float32 (rounded once). Returns
+    (f, iters_used, rem), the last two as CPU tensors [m]."""
+    if dtype not in _DTYPES or layout not in _LAYOUTS:
+        raise _eng.DpprError(f"forward: dtype float64 or float32, layout in {sorted(_LAYOUTS)}")
+    m = len(starts)
+    if not 1 <= m <= _eng.FORWARD_MAX_M:
+        raise _eng.DpprError(f"forward: 1 <= len(starts) <= {_eng.FORWARD_MAX_M}, not {m}")
+    shape = (m, engine.V) if layout == "source_major" else (engine.V, m)
+    out = torch.empty(shape, dtype=dtype, device=_device(engine))
+    torch.cuda.synchronize(out.device)   # (the tensor is torch's; nothing of torch's is in flight on it when the engine writes)
+    res = engine.forward(starts, iters, tol, epoch=epoch, dense_ptr=out.data_ptr(), dtype=_DTYPES[dtype], layout=_LAYOUTS[layout])
+    return out, torch.from_numpy(res["iters_used"].copy()), torch.from_numpy(res["rem"].copy())
+
+
 _H_LAYOUTS = {"feature_major": _eng.H_FEATURE_MAJOR, "vertex_major": _eng.H_VERTEX_MAJOR}
 
 

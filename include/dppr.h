@@ -1311,6 +1311,77 @@ int dppr_group_sample(dppr_engine *e, int32_t group, int32_t epoch, const dppr_r
                       int32_t *out_support /* [n], may be NULL */, int32_t *out_status /* [n] */);
 int dppr_debug_sample_form(dppr_engine *e, int form);
 
+/* ---- forward PPR of any vertex on the resident window (backward-compatible additions, ABI 6) ----
+ * Every score above is a column of the reverse problem: p_i[v] ~ pi_v(s_i) for a tracked target s_i. dppr_forward answers the
+ * other direction, "where does the walk from q go?", for up to 16 starts q that need not be tracked: a ROW of the PPR matrix,
+ * swept on the device over the in-CSR of a resident epoch. Read side only: no state is read or changed.
+ *
+ * DEFINITION. M[u][w] = 0.85 * mult(u -> w) / (d(u) + 1) over the STORED out-edges of epoch `epoch` (-1: the newest): d(u) is
+ * the number of stored out-edges of u, duplicates count as stored, self loops count, the + 1 is death. For a start q
+ *     x_0 = e_q,   x_{k+1}[w] = sum over the stored edges u -> w of x_k[u] * M[u][w],   f^K = 0.15 * sum_{k = 0 .. K} x_k
+ * so that pihat_q(t) = lim f^K[t] and 0 <= pihat_q(t) - f^K[t] <= |x_{K+1}|_1 =: rem (0.15 * sum_{j > K} 0.85^(j-K-1) <= 1).
+ * Every rounding is fixed; numpy reproduces every output bit for bit (tests/forward_ref.py):
+ *   per-vertex term  y_k[u] = (0.85 * x_k[u]) / (double)(d(u) + 1): one multiplication, one division, once per vertex and
+ *                    iteration.
+ *   row sum          x_{k+1}[w] is THE FOLD of the dot family (section dot above) over the terms y_k[tail] of w's in-row in the
+ *                    order the device stores it -- ascending internal tail id, duplicates as stored, self loops kept: blocks of
+ *                    2^16 slots, a block summed by the balanced tree that adds neighbours (missing slots +0.0), the blocks added
+ *                    in ascending order. Every term is >= +0.0, so padding is exact.
+ *   accumulation     f[w] = f[w] + 0.15 * x_{k+1}[w]: one multiplication and one addition, k ascending; f starts as 0.15 * e_q.
+ *   remaining mass   rem is the same fold of the last computed x over the external ids 0 .. V - 1; the slot of a vertex without
+ *                    an internal id holds +0.0.
+ *   stopping         iters in [1, 256], tol >= 0. After the iterations 8, 16, 24, .. below iters and after iteration iters every
+ *                    column's rem is evaluated; a column whose rem <= tol is FROZEN at that check: its f and rem stand, its
+ *                    iters_used is that k, it takes no further part. tol = 0 stops only a column whose mass has died out. After
+ *                    iteration iters every column still running stops with iters_used = iters and the rem it has.
+ *   independence     a column is a function of the epoch's rows, q, iters and tol alone: not of the other starts of the call, of
+ *                    m, of the grid, of a team or piece size (dppr_debug_forward), or of what the solver has done.
+ *   no internal id   a start without an internal id, and a parked one, has d = 0: f = 0.15 * e_q, rem = 0.0, iters_used =
+ *                    min(8, iters).
+ *   renumberings     results are by external id; like a walk, the order of a row's terms follows the rows the device holds, so a
+ *                    renumbering may move last bits (it invalidates older epochs anyway).
+ * OUTPUTS (dppr_forward_out_t; a part whose pointers are all NULL is not run):
+ *   iters_used[m], rem[m]          HOST memory, either may be NULL.
+ *   top k per start                topk_ids / topk_f [m][k], topk_counts [m], HOST memory: the vertices with f > min_f, f
+ *                                  descending, ties by external id ascending (the order of dppr_topk); entries past a count: id
+ *                                  -1, f 0.0. Asked for when any of the three is not NULL; then all three, k in
+ *                                  [1, DPPR_TOPK_MAX] and min_f >= 0 are required.
+ *   f at given ids                 at_f[j * m + i] = f_i[at_ids[j]], HOST memory, n_at in [1, DPPR_FORWARD_AT_MAX]. Asked for
+ *                                  when at_ids or at_f is not NULL; then both are required.
+ *   dense copy                     dense_dev: DEVICE memory of the caller, f by external id, dense_dtype DPPR_F64 (bit for bit)
+ *                                  or DPPR_F32 (rounded once, to nearest even), dense_layout DPPR_VERTEX_MAJOR [V][m] or
+ *                                  DPPR_SOURCE_MAJOR [m][V]; the pointer is checked as dppr_export_dense_dev checks its own.
+ * starts: m in [1, DPPR_FORWARD_MAX_M] external ids in HOST memory; a start may repeat. The columns are interleaved as a group's
+ * state is ([rows][row width of m]), so one gathered row serves every start.
+ * Rejected with DPPR_ERR_INVALID before any device work, nothing written: m outside [1, 16], iters outside [1, 256], a tol that
+ * is negative or not finite, a NULL starts or out, a start or an at id outside [0, V), a part asked for with a pointer missing
+ * or a bad k / min_f / n_at / dtype / layout / device pointer, an epoch that is not resident, an engine that is broken.
+ * Threading and stream as dppr_certify: the id-map lock for the whole call (safe beside dppr_slide_concurrent with an explicit
+ * epoch <= k), the solver stream, never part of the update path or of a timed region. The host enqueues up to 8 sweeps, the rem
+ * fold and the freeze update and then reads back ONE word; nothing is read back between sweeps. Work space: four planes of
+ * [V][row width] doubles, the partials of the fold and the queue of the long rows' pieces; all of it is the engine's, obtained
+ * before the first kernel, grown on demand and released with the engine: after DPPR_ERR_NOMEM the engine is as before. With
+ * dppr_set_profiling on, dppr_debug_query_ms reports the time from the first sweep to the last check (read-backs included).
+ * No output value comes from a floating-point atomic.
+ * dppr_debug_forward: a test hook. piece_edges 0 or a power of two in [64, 4096]: in-rows longer than this are summed in pieces
+ * of this many entries; team in {0, 1, 2, 4, 8}: the lanes that share one gathered row (raised to the fewest the row width
+ * allows). 0: the plan decides. Every setting gives the same bits.
+ * OUT OF SCOPE: weighted start distributions, a forward push with a frontier, keeping a forward vector current under the stream,
+ * the ranked, cluster or subgraph families over f. */
+#define DPPR_FORWARD_MAX_M 16
+#define DPPR_FORWARD_MAX_ITERS 256
+#define DPPR_FORWARD_CHECK 8          /* iterations between two evaluations of rem */
+#define DPPR_FORWARD_AT_MAX 4096
+typedef struct {
+    int32_t *iters_used; double *rem;                                   /* [m], HOST; either may be NULL */
+    int32_t k; double min_f; int32_t *topk_ids; double *topk_f; int32_t *topk_counts; /* [m][k], [m][k], [m], HOST */
+    const int32_t *at_ids; int32_t n_at; double *at_f;                  /* [n_at], [n_at][m], HOST */
+    void *dense_dev; int32_t dense_dtype, dense_layout;                 /* DEVICE; DPPR_F64 | DPPR_F32; DPPR_VERTEX_MAJOR | DPPR_SOURCE_MAJOR */
+} dppr_forward_out_t;
+int dppr_forward(dppr_engine *e, int32_t epoch, const int32_t *starts /* [m] external, HOST */, int32_t m, int32_t iters, double tol,
+                 const dppr_forward_out_t *out);
+int dppr_debug_forward(dppr_engine *e, int piece_edges /* 0: the plan decides */, int team /* 0: the plan decides */);
+
 /* Windows whose sweep groups are all resident at once run a frontier loop of a source group as
  * multi-sweep launches (grid barrier between sweeps, row tables kept in LDS; dppr_multi.hpp). on by
  * default; 0 = one launch per sweep everywhere. The roll-call / time-out rules are those of
