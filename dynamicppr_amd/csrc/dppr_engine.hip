@@ -58,6 +58,7 @@
 #include "dppr_sample.hpp"
 #include "dppr_explain.hpp"
 #include "dppr_forward.hpp"
+#include "dppr_fpush.hpp"
 
 using namespace dppr;
 
@@ -1705,6 +1706,22 @@ int dppr_debug_forward(dppr_engine *e, int piece_edges, int team) {
         return fail(e, DPPR_ERR_INVALID, "debug_forward: piece_edges 0 or a power of two in [64, 4096], team 0, 1, 2, 4 or 8 (0: the plan's choice)");
     e->fw_piece = piece_edges;
     e->fw_team = team;
+    return DPPR_OK;
+}
+
+int dppr_forward_push(dppr_engine *e, int32_t epoch, const int64_t *offsets, const int32_t *ids, const double *weights, int32_t m, double eps,
+                      int32_t max_rounds, const dppr_forward_push_out_t *out) {
+    if (!e || e->broken) return fail(e, DPPR_ERR_INVALID, "forward_push: no usable engine");
+    return forward_push_call(e, epoch, offsets, ids, weights, m, eps, max_rounds, out);
+}
+
+int dppr_debug_forward_push(dppr_engine *e, int piece_edges, int team, int chunk_rounds) {
+    if (!e || !fp_hook_ok(piece_edges, team, chunk_rounds))
+        return fail(e, DPPR_ERR_INVALID,
+                    "debug_forward_push: piece_edges 0 or a power of two in [64, 4096], team 0, 1, 2, 4 or 8, chunk_rounds in [0, 256] (0: the plan's choice)");
+    e->fp_piece = piece_edges;
+    e->fp_team = team;
+    e->fp_chunk = chunk_rounds;
     return DPPR_OK;
 }
 

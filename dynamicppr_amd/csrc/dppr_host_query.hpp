@@ -1899,4 +1899,184 @@ int forward_call(dppr_engine *e, int32_t epoch, const int32_t *starts, int32_t m
     return run_forward(e, *ep, starts, m, iters, tol, which, *out);
 }
 
+// ---- the forward push from weighted start sets (dppr_fpush.hpp, dppr_fpush_plan.hpp) -----------------------------------------------
+// The rounds and the parts `which` names (arguments, the CSR, ids, device destinations and the epoch validated by the caller).
+// Every buffer is in place before the first kernel. Per chunk the host enqueues a few rounds -- select, mark, gather, the pieces
+// of the long receivers and their sums -- and reads back ONE word: the columns that pushed in the chunk's last round.
+int run_fpush(dppr_engine *e, const Epoch &ep, const int64_t *offsets, const int32_t *ids, const double *weights, int m, double eps, int max_rounds,
+              uint32_t which, const dppr_forward_push_out_t &out) {
+    if (int rc = query_begin(e, MAP_E2I | ((which & FP_TOPK) ? MAP_I2E : 0u))) return rc;
+    QueryWork::Forward &fq = e->q.fw;
+    const int V = e->V, gw = fw_row_width(m), n_seeds = (int)offsets[m];
+    const int piece = fw_piece(e->fp_piece), T = fw_team(gw, e->fp_team), PP = fw_lane_pieces(gw, T), levels = fw_levels(piece);
+    const int chunk = fp_chunk(e->fp_chunk);
+    const size_t plane = fw_plane_elems(V, gw), part_elems = fw_part_elems(V, m);
+    const size_t item_cap = fw_item_cap(ep.Ed, piece), long_cap = fw_long_cap(ep.Ed, piece);
+    const size_t list_cap = fp_list_cap(V), mark_cap = fp_mark_cap(V, ep.Ed), words = fp_bitmap_words(V);
+    const long long stride = fw_part_stride(V);
+    Grow grow{e};
+    int rc = grow(fq.planes, 4 * plane);
+    if (!rc) rc = grow(fq.fp_head, sizeof(FpHead));
+    if (!rc) rc = grow(fq.fp_pin, sizeof(FpHead));
+    if (!rc) rc = grow(fq.fp_seeds, sizeof(FpSeed) * (size_t)n_seeds);
+    if (!rc) rc = grow(fq.fp_seeds_pin, sizeof(FpSeed) * (size_t)n_seeds);
+    if (!rc) rc = grow(fq.fp_lists, 4 * list_cap);
+    if (!rc) rc = grow(fq.fp_bits, words);
+    if (!rc) rc = grow(fq.fp_mark, mark_cap);
+    if (!rc) rc = grow(fq.part, part_elems);
+    if (!rc) rc = grow(fq.items, item_cap);
+    if (!rc) rc = grow(fq.longs, sizeof(FwLong) * long_cap);
+    if (!rc) rc = grow(fq.pp, item_cap * (size_t)gw);
+    if (!rc && (which & FP_TOPK)) rc = topk_workspace(e, grow, m, (size_t)(e->n_int + e->n_parked));
+    if (!rc && (which & FP_AT)) rc = grow(e->q.ra.buf, ra_layout(out.n_at, m, 2).total_bytes);
+    if (rc) return rc;
+    double *p = fq.planes.get(), *r = p + plane, *y[2] = {r + plane, r + 2 * plane};
+    FpHead *head = reinterpret_cast<FpHead *>(fq.fp_head.get());
+    const FpHead *pin = reinterpret_cast<const FpHead *>(fq.fp_pin.get());
+    FpSeed *seeds = reinterpret_cast<FpSeed *>(fq.fp_seeds.get()), *h_seeds = reinterpret_cast<FpSeed *>(fq.fp_seeds_pin.get());
+    FwLong *longs = reinterpret_cast<FwLong *>(fq.longs.get());
+    const unsigned icap = (unsigned)std::min<size_t>(item_cap, 0xffffffffu), lcap = (unsigned)std::min<size_t>(long_cap, 0xffffffffu);
+    const FwGraph g{ep.row_ptr.get(), ep.adj.get(), ep.out_row_ptr.get(), e->n_int, V};
+    FpLists ls;
+    for (int i = 0; i < 2; ++i) {
+        ls.front[i] = fq.fp_lists.get() + (size_t)i * list_cap;
+        ls.recv[i] = fq.fp_lists.get() + (size_t)(2 + i) * list_cap;
+    }
+    ls.bits = fq.fp_bits.get();
+    ls.mark = fq.fp_mark.get();
+    ls.list_cap = (unsigned)std::min<size_t>(list_cap, 0xffffffffu);
+    ls.mark_cap = (unsigned)std::min<size_t>(mark_cap, 0xffffffffu);
+    const int *x2i = e->d_ext2int.get();
+    const dim3 block(FW_BLOCK);
+    const dim3 thread_grid((unsigned)fp_grid(e->n_int, FW_BLOCK)), mark_grid((unsigned)fp_grid(e->n_int, FW_WAVES * (WAVE / FP_MARK_LANES)));
+    const dim3 rows_grid((unsigned)std::min(fw_units_grid(e->n_int, T), FP_GRID_MAX));
+    const dim3 piece_grid((unsigned)std::min(fw_units_grid((long long)std::min<size_t>(item_cap, 1u << 20), T), FP_GRID_MAX));
+    const dim3 long_grid((unsigned)grid_for((int64_t)std::min<size_t>(long_cap, 1u << 16) * m, FW_BLOCK, FP_GRID_MAX));
+
+    for (int c = 0; c < m; ++c)
+        for (int64_t j = offsets[c]; j < offsets[c + 1]; ++j) h_seeds[j] = FpSeed{ids[j], c, weights[j], -1, 0};
+    HIP_TRY(hipMemsetAsync(head, 0, sizeof(FpHead), e->stream));
+    HIP_TRY(hipMemcpyAsync(seeds, h_seeds, sizeof(FpSeed) * (size_t)n_seeds, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemsetAsync(fq.planes, 0, sizeof(double) * 4 * plane, e->stream));
+    HIP_TRY(hipMemsetAsync(fq.fp_bits, 0, sizeof(unsigned) * words, e->stream));
+    HIP_TRY(hipMemsetAsync(fq.part, 0, sizeof(double) * part_elems, e->stream)); // (+0.0: the tiles of padding)
+    if (int rc2 = DeviceTime{e}.open()) return rc2;
+    hipLaunchKernelGGL(k_fp_init, dim3((unsigned)grid_for(n_seeds, FW_BLOCK, FP_GRID_MAX)), block, 0, e->stream, head, seeds, n_seeds, x2i, g, r, gw, ls);
+    HIP_TRY(hipGetLastError());
+    int k = 0;
+    while (k < max_rounds) {
+        const int end = fp_chunk_end(k, max_rounds, chunk);
+        for (++k; k <= end; ++k) {
+            const int b = k & 1;
+            hipLaunchKernelGGL(k_fp_select, thread_grid, block, 0, e->stream, head, g, eps, p, r, y[b], y[b ^ 1], gw, m, ls, b);
+            hipLaunchKernelGGL(k_fp_mark, mark_grid, block, 0, e->stream, head, g, ep.out_col.get(), ls, b, piece, fq.items.get(), icap, longs, lcap);
+            by_fw_shape(PP, levels, [&](auto pp_c, auto lv_c) -> int {
+                constexpr int P = decltype(pp_c)::value, L = decltype(lv_c)::value;
+                hipLaunchKernelGGL((k_fp_gather<P, L>), rows_grid, block, 0, e->stream, head, g, y[b], r, gw, m, T, piece, ls, b);
+                hipLaunchKernelGGL((k_fw_pieces<P, L>), piece_grid, block, 0, e->stream, g, y[b], gw, m, T, piece, &head->fw, fq.items.get(), icap,
+                                   fq.pp.get());
+                return DPPR_OK;
+            });
+            hipLaunchKernelGGL(k_fp_long, long_grid, block, 0, e->stream, head, r, gw, m, piece, longs, lcap, fq.pp.get());
+        }
+        k = end;
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(fq.fp_pin.get() + offsetof(FpHead, last_act), reinterpret_cast<unsigned char *>(head) + offsetof(FpHead, last_act),
+                               sizeof(unsigned), hipMemcpyDeviceToHost, e->stream)); // THE word of the chunk
+        HIP_TRY(loop_wait(e));
+        if (!pin->last_act) break; // (no column pushed: every later round is empty)
+    }
+    hipLaunchKernelGGL(k_fp_left, thread_grid, block, 0, e->stream, head, g, eps, r, gw, m, ls, k & 1);
+    hipLaunchKernelGGL(k_fw_rem, dim3((unsigned)fw_rem_grid(V)), block, dot_lds_bytes(gw, 1), e->stream, r, gw, m, x2i, V, fq.part.get(), stride);
+    hipLaunchKernelGGL(k_dot_combine, dim3((m + DOT_CB_WAVES - 1) / DOT_CB_WAVES), dim3(DOT_CB_WAVES * WAVE), 0, e->stream, fq.part.get(),
+                       (const long long *)nullptr, stride, m, m, &head->fw.dot, head->rem);
+    HIP_TRY(hipGetLastError());
+    if (int rc2 = DeviceTime{e}.close()) return rc2;
+    HIP_TRY(hipMemcpyAsync(fq.fp_pin, head, sizeof(FpHead), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(h_seeds, seeds, sizeof(FpSeed) * (size_t)n_seeds, hipMemcpyDeviceToHost, e->stream));
+    if (int rc2 = run_end(e)) return rc2;
+    const float push_ms = e->query_ms;
+    if (pin->overflow || pin->fw.overflow) return fail(e, DPPR_ERR_HIP, "forward_push: a list was too short (fp_list_cap, fp_mark_cap, fw_item_cap)");
+    const FpHead hd = *pin;
+    struct Rowless { int id, col; double p; };
+    std::vector<Rowless> rowless; // the seeds the host answers: p = 0.15 w
+    for (int j = 0; j < n_seeds; ++j)
+        if (h_seeds[j].row < 0) rowless.push_back({h_seeds[j].id, h_seeds[j].col, fp_rowless_p(h_seeds[j].w)});
+    for (int c = 0; c < m; ++c) {
+        if (out.rounds_used) out.rounds_used[c] = hd.rounds_used[c];
+        if (out.converged) out.converged[c] = hd.left[c] == 0 ? 1 : 0;
+        if (out.rem) out.rem[c] = hd.rem[c];
+        if (out.pushes) out.pushes[c] = (int64_t)hd.pushes[c];
+        if (out.left) out.left[c] = (int64_t)hd.left[c];
+    }
+    if (out.work)
+        for (int i = 0; i < 3; ++i) out.work[i] = (int64_t)hd.work[i];
+
+    if (which & FP_DENSE) {
+        const bool sm = out.dense_layout == DPPR_SOURCE_MAJOR;
+        const dim3 grid(sm ? std::min((int)ex_tiles(V), 2048) : grid_for((int64_t)V * m, EX_TILE));
+        by_dtype_layout(out.dense_dtype, sm, [&](auto elem, auto source_major) -> int {
+            using E = decltype(elem);
+            if (out.dense_p_dev) {
+                hipLaunchKernelGGL((k_ex_dense<E, decltype(source_major)::value>), grid, dim3(EX_TILE), 0, e->stream, p, gw, m, x2i, V,
+                                   static_cast<E *>(out.dense_p_dev));
+                for (const Rowless &s : rowless)
+                    hipLaunchKernelGGL(k_fp_poke<E>, dim3(1), dim3(WAVE), 0, e->stream, static_cast<E *>(out.dense_p_dev),
+                                       (long long)ex_dense_index(out.dense_layout, m, V, s.id, s.col), s.p);
+            }
+            if (out.dense_r_dev)
+                hipLaunchKernelGGL((k_ex_dense<E, decltype(source_major)::value>), grid, dim3(EX_TILE), 0, e->stream, r, gw, m, x2i, V,
+                                   static_cast<E *>(out.dense_r_dev));
+            return DPPR_OK;
+        });
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(e->stream)); // (the destinations are complete here: any stream of the caller may read them)
+    }
+    if (which & FP_AT) {
+        const int n_at = out.n_at;
+        std::vector<double> spare(out.at_p && out.at_r ? 0 : (size_t)n_at * m);
+        double *at_p = out.at_p ? out.at_p : spare.data(), *at_r = out.at_r ? out.at_r : spare.data();
+        if (int rc2 = point_read(e, grow, out.at_ids, n_at, m, 2, at_p, at_r, [&](const int *d_ids, double *d_a, double *d_b) {
+                hipLaunchKernelGGL(k_read_at, dim3(grid_for((int64_t)n_at * m)), dim3(BLOCK), 0, e->stream, p, r, gw, m, x2i, d_ids, n_at, d_a, d_b);
+                return DPPR_OK;
+            }))
+            return rc2;
+        if (out.at_p)
+            for (const Rowless &s : rowless)
+                for (int j = 0; j < n_at; ++j)
+                    if (out.at_ids[j] == s.id) out.at_p[(size_t)j * m + s.col] = s.p;
+    }
+    if (which & FP_TOPK) {
+        const TkState st = tk_state(e, p, p, gw, m);
+        if (int rc2 = run_select(e, st, e->d_int2ext, out.k, out.min_p, out.topk_ids, out.topk_p, nullptr, out.topk_counts)) return rc2;
+        for (const Rowless &s : rowless) // (a row of the device holds +0.0 there: the seed is not in the column's list yet)
+            out.topk_counts[s.col] = fp_topk_insert(out.topk_ids + (size_t)s.col * out.k, out.topk_p + (size_t)s.col * out.k, out.topk_counts[s.col],
+                                                    out.k, out.min_p, s.id, s.p);
+    }
+    if (e->profiling) e->query_ms = push_ms; // (the parts opened brackets of their own)
+    return DPPR_OK;
+}
+
+int forward_push_call(dppr_engine *e, int32_t epoch, const int64_t *offsets, const int32_t *ids, const double *weights, int32_t m, double eps,
+                      int32_t max_rounds, const dppr_forward_push_out_t *out) {
+    if (!fp_args_ok(m, eps, max_rounds, out))
+        return fail(e, DPPR_ERR_INVALID, "forward_push: m in [1, 16], eps > 0 and finite, max_rounds in [1, 256], non-null out");
+    if (!fp_parts_ok(out))
+        return fail(e, DPPR_ERR_INVALID,
+                    "forward_push: a part asked for needs its pointers; k in [1, DPPR_TOPK_MAX], min_p >= 0; n_at in [1, DPPR_FORWARD_AT_MAX]; dtype 0 or 1, layout 0 or 1");
+    if (TgCheck c = fp_csr_check(offsets, ids, weights, m, e->V)) return fail(e, DPPR_ERR_INVALID, (std::string("forward_push: ") + tg_check_text(c)).c_str());
+    const uint32_t which = fp_which(out);
+    if ((which & FP_AT) && !dppr::ids_in_range(out->at_ids, out->n_at, e->V)) return fail(e, DPPR_ERR_INVALID, "forward_push: at_ids in [0, V)");
+    const Epoch *ep = find_epoch(e, epoch);
+    if (!ep) return fail(e, DPPR_ERR_INVALID, "forward_push: epoch not resident (evicted or never built)");
+    HIP_TRY(hipSetDevice(e->device));
+    for (void *dst : {out->dense_p_dev, out->dense_r_dev})
+        if (dst && !dev_range_ok(e, dst, ex_dense_bytes(out->dense_dtype, m, e->V), ex_elem_bytes(out->dense_dtype)))
+            return fail(e, DPPR_ERR_INVALID,
+                        "forward_push: a dense destination must be aligned device memory of the engine's device, m x V elements inside one allocation");
+    if (!which) return DPPR_OK;
+    std::lock_guard<std::mutex> map_lk(e->map_mu); // (as dppr_read: one state of the id space for the whole call)
+    return run_fpush(e, *ep, offsets, ids, weights, m, eps, max_rounds, which, *out);
+}
+
 } // namespace

@@ -275,6 +275,12 @@ struct QueryWork {
         DevBuf<unsigned long long> items; // the queued pieces of the long in-rows (fw_item_cap)
         DevBuf<unsigned char> longs;      // the long rows (FwLong, fw_long_cap)
         DevBuf<double> pp;                // [queued pieces][row width] one partial per piece
+        // the forward push (dppr_fpush.hpp, dppr_fpush_plan.hpp) shares everything above (its planes: p | r | y0 | y1) and adds:
+        DevBuf<unsigned char> fp_head; PinBuf<unsigned char> fp_pin; // FpHead: device / pinned host (one word per chunk, the whole head at the end)
+        DevBuf<unsigned char> fp_seeds; PinBuf<unsigned char> fp_seeds_pin; // the seed table (FpSeed): device / pinned host (the rows come back)
+        DevBuf<int> fp_lists;             // front[2] | recv[2], each fp_list_cap rows
+        DevBuf<unsigned> fp_bits;         // a bit per row: already a receiver of the round
+        DevBuf<unsigned long long> fp_mark; // the queued pieces of the frontier's out-rows (fp_mark_cap)
     } fw;
     struct Assign { // every vertex to its best lane across groups (dppr_assign.hpp, dppr_assign_plan.hpp); the block grows with a host destination
         DevBuf<double> scale; // [256] the scales of the call
@@ -465,6 +471,8 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     int cert_wave_rows = 0;         // short rows that share a wave of k_cert_rows; 0: the plan's choice (dppr_debug_certify)
     int fw_piece = 0;               // entries of a piece of a long in-row of the forward sweep; 0: the plan's choice (dppr_debug_forward)
     int fw_team = 0;                // lanes that share a gathered row there; 0: the plan's choice (dppr_debug_forward)
+    int fp_piece = 0, fp_team = 0;  // the same two for the forward push (dppr_debug_forward_push)
+    int fp_chunk = 0;               // rounds of the forward push between two read-backs; 0: the plan's choice (dppr_debug_forward_push)
     float query_ms = -1.0f;         // dppr_set_profiling: device time of the last top-k, changes, export or dot call, first to last kernel (dppr_debug_query_ms)
     std::vector<int32_t> h_tmp1, h_tmp2;
     std::vector<int32_t> h_tiles; // host copy of the tile edge prefix / group table

@@ -79,6 +79,7 @@ EXPORTS = [
     "dppr_certify", "dppr_group_certify", "dppr_debug_certify",
     "dppr_sample", "dppr_group_sample", "dppr_debug_sample_form",
     "dppr_forward", "dppr_debug_forward",
+    "dppr_forward_push", "dppr_debug_forward_push",
 ]
 
 DEST_HOST, DEST_DEVICE = 0, 1
@@ -106,6 +107,7 @@ SAMPLE_MAX, SAMPLE_MAX_TOTAL = 1 << 20, 1 << 24
 SAMPLE_OK, SAMPLE_EMPTY, SAMPLE_NONFINITE = 0, 1, 2
 SAMPLE_WAVE, SAMPLE_PER_THREAD = 0, 1
 FORWARD_MAX_M, FORWARD_MAX_ITERS, FORWARD_CHECK, FORWARD_AT_MAX = 16, 256, 8, 4096
+FPUSH_SET_MAX, FPUSH_MAX_ROUNDS = 4096, 256
 
 
 class RankSpec(C.Structure):
@@ -136,6 +138,15 @@ class ForwardOut(C.Structure):
     _fields_ = [("iters_used", _ip), ("rem", _dp), ("k", C.c_int32), ("min_f", C.c_double), ("topk_ids", _ip), ("topk_f", _dp),
                 ("topk_counts", _ip), ("at_ids", _ip), ("n_at", C.c_int32), ("at_f", _dp), ("dense_dev", C.c_void_p),
                 ("dense_dtype", C.c_int32), ("dense_layout", C.c_int32)]
+
+
+class ForwardPushOut(C.Structure):
+    """dppr_forward_push_out_t: where the parts of a forward push go (a part whose pointers are all NULL is not run)."""
+    _ip, _dp, _lp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int64)
+    _fields_ = [("rounds_used", _ip), ("converged", _ip), ("rem", _dp), ("pushes", _lp), ("left", _lp), ("work", _lp),
+                ("k", C.c_int32), ("min_p", C.c_double), ("topk_ids", _ip), ("topk_p", _dp), ("topk_counts", _ip),
+                ("at_ids", _ip), ("n_at", C.c_int32), ("at_p", _dp), ("at_r", _dp), ("dense_p_dev", C.c_void_p),
+                ("dense_r_dev", C.c_void_p), ("dense_dtype", C.c_int32), ("dense_layout", C.c_int32)]
 
 
 class PatchOut(C.Structure):
@@ -320,6 +331,9 @@ def lib():
     L.dppr_group_certify.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int, vp]
     L.dppr_debug_certify.argtypes = [vp, C.c_int, C.c_int]
     L.dppr_forward.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_double, vp]
+    L.dppr_forward_push.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32,
+                                    C.c_double, C.c_int32, vp]
+    L.dppr_debug_forward_push.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     L.dppr_debug_forward.argtypes = [vp, C.c_int, C.c_int]
     L.dppr_assign.argtypes = [vp, ip, C.c_int32, dp, C.c_double, C.c_int, vp, vp, vp, i64p, vp, C.c_int64, i64p, vp, vp, vp]
     L.dppr_assign_at.argtypes = [vp, ip, C.c_int32, dp, C.c_double, ip, C.c_int32, ip, dp, ip, dp]
@@ -1012,6 +1026,56 @@ class Engine:
         """Test hook (dppr_debug_forward): in-rows longer than piece_edges are summed in pieces; `team` lanes share a gathered
         row. 0: the plan's choice. The results do not depend on either."""
         self._ck(self._L.dppr_debug_forward(self._h, int(piece_edges), int(team)), "debug_forward")
+
+    # ---- forward push: local forward PPR from weighted start sets ----
+    def forward_push(self, sets, eps, max_rounds=64, k=0, min_p=0.0, at=None, epoch=-1, dense_p_ptr=None, dense_r_ptr=None, dtype=F64,
+                     layout=VERTEX_MAJOR):
+        """The frontier-driven forward push from each of the start sets `sets` (at most 16) over `epoch` (include/dppr.h:
+        dppr_forward_push). A set is a vertex id (one seed of weight 1.0) or a pair (ids, weights). Returns a dict: rounds_used,
+        converged [m] int32, rem [m], pushes, left [m] int64, work [3] int64; with k > 0, topk = a list of (ids, p) per set; with
+        `at`, at_p and at_r = p and r at those external ids, [m][len(at)]. dense_p_ptr / dense_r_ptr: raw device addresses that
+        take p / r by external id, [V][m] (VERTEX_MAJOR) or [m][V] (SOURCE_MAJOR) elements of `dtype`."""
+        lanes = [(np.array([s], dtype=np.int32), np.ones(1)) if np.isscalar(s) else s for s in sets]
+        m = len(lanes)
+        off = np.zeros(m + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(np.atleast_1d(l[0])) for l in lanes])
+        ids = np.ascontiguousarray(np.concatenate([np.atleast_1d(l[0]) for l in lanes]) if m else [], dtype=np.int32)
+        w = np.ascontiguousarray(np.concatenate([np.atleast_1d(l[1]) for l in lanes]) if m else [], dtype=np.float64)
+        if len(w) != len(ids):
+            raise ValueError("forward_push: a set needs one weight per id")
+        ip, dp, lp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int64)
+        n = max(m, 1)
+        res = {"rounds_used": np.full(n, -1, dtype=np.int32), "converged": np.full(n, -1, dtype=np.int32), "rem": np.full(n, np.nan),
+               "pushes": np.full(n, -1, dtype=np.int64), "left": np.full(n, -1, dtype=np.int64), "work": np.full(3, -1, dtype=np.int64)}
+        out = ForwardPushOut()
+        out.rounds_used, out.converged, out.rem = res["rounds_used"].ctypes.data_as(ip), res["converged"].ctypes.data_as(ip), res["rem"].ctypes.data_as(dp)
+        out.pushes, out.left, out.work = res["pushes"].ctypes.data_as(lp), res["left"].ctypes.data_as(lp), res["work"].ctypes.data_as(lp)
+        if k:
+            kk = max(int(k), 1)
+            tid, tp, cnt = np.empty((n, kk), dtype=np.int32), np.empty((n, kk)), np.empty(n, dtype=np.int32)
+            out.k, out.min_p = int(k), float(min_p)
+            out.topk_ids, out.topk_p, out.topk_counts = tid.ctypes.data_as(ip), tp.ctypes.data_as(dp), cnt.ctypes.data_as(ip)
+        if at is not None:
+            b, _ = _i32(at)
+            at_p, at_r = np.empty((max(len(b), 1), n)), np.empty((max(len(b), 1), n))
+            out.at_ids, out.n_at, out.at_p, out.at_r = b.ctypes.data_as(ip), len(b), at_p.ctypes.data_as(dp), at_r.ctypes.data_as(dp)
+        if dense_p_ptr or dense_r_ptr:
+            out.dense_p_dev, out.dense_r_dev, out.dense_dtype, out.dense_layout = dense_p_ptr, dense_r_ptr, int(dtype), int(layout)
+        self._ck(self._L.dppr_forward_push(self._h, int(epoch), off.ctypes.data_as(lp), ids.ctypes.data_as(ip), w.ctypes.data_as(dp), m,
+                                           float(eps), int(max_rounds), C.byref(out)), "forward_push")
+        for key in ("rounds_used", "converged", "rem", "pushes", "left"):
+            res[key] = res[key][:m]
+        if k:
+            res["topk"] = [(tid[i, :c].copy(), tp[i, :c].copy()) for i, c in enumerate(cnt[:m])]
+        if at is not None:
+            res["at_p"] = np.ascontiguousarray(at_p[:len(b), :m].T)
+            res["at_r"] = np.ascontiguousarray(at_r[:len(b), :m].T)
+        return res
+
+    def debug_forward_push(self, piece_edges=0, team=0, chunk_rounds=0):
+        """Test hook (dppr_debug_forward_push): piece_edges and team as debug_forward; chunk_rounds rounds are enqueued between
+        two read-backs. 0: the plan's choice. The results do not depend on any of them."""
+        self._ck(self._L.dppr_debug_forward_push(self._h, int(piece_edges), int(team), int(chunk_rounds)), "debug_forward_push")
 
     # ---- every vertex to its best lane, across groups ----
     def _assign_classes(self, groups, scale, what):

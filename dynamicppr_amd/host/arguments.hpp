@@ -216,6 +216,11 @@ inline void PrintUsage() {
               << "            iterations, default 64; a start stops at a check -- every 8 iterations -- once less than T of its mass remains, default\n"
               << "            0; the K vertices it reaches most, 0 <= K <= 64, default 5): forward <vertex> iters <used> rem <mass remaining> top <found>\n"
               << "            <v0>:<f0> <v1>:<f1> ...   (starts beyond 16 go in calls of 16; not with --split)\n"
+              << "--forward-push <file> --push-eps <E> [--push-rounds <N>]: <file> holds one weighted vertex set per line as --target-sets; after\n"
+              << "            every batch run the frontier-driven forward push from each set over the batch's own graph (E > 0: a vertex is pushed\n"
+              << "            while its residual exceeds E * (outdeg + 1); at most N rounds, 1 <= N <= 256, default 64; the --forward-topk K vertices\n"
+              << "            it reaches most): fpush <first id> seeds <count> rounds <used> converged <0|1> rem <mass remaining> pushes <count> left\n"
+              << "            <count> top <found> <v0>:<p0> ...   (sets beyond 16 go in calls of 16; not with --split)\n"
               << "--sample <S> [--sample-seed <X>]: after every batch draw, per source in source order, S vertices with replacement in proportion to\n"
               << "            the source's pagerank -- to the score of --rank-factor / --rank-exclude if given (no --topk needed) -- (1 <= S <= 2^20;\n"
               << "            the draws are a function of the scores, the source's lane, X and the draw number alone): sample <source> lane <lane>\n"
@@ -296,6 +301,10 @@ inline void ArgumentsChecker() {
     if (gForwardBad || (gForwardOptsGiven && gForwardFile.empty())) ok = false;
     if (!gForwardFile.empty() && (gSplitInterface || gForwardIters < 1 || gForwardIters > DPPR_FORWARD_MAX_ITERS || !(gForwardTol >= 0.0) ||
                                   !std::isfinite(gForwardTol) || gForwardTopK < 0 || gForwardTopK > 64))
+        ok = false;
+    if (gPushBad || (gPushOptsGiven && gPushFile.empty())) ok = false;
+    if (!gPushFile.empty() && (gSplitInterface || !(gPushEps > 0.0) || !std::isfinite(gPushEps) || gPushRounds < 1 || gPushRounds > DPPR_FPUSH_MAX_ROUNDS ||
+                               gForwardTopK < 0 || gForwardTopK > 64))
         ok = false;
     if ((gSampleGiven && (gSample < 1 || gSample > DPPR_SAMPLE_MAX || gSplitInterface)) || (gSampleSeedGiven && !gSampleGiven)) ok = false;
     if (gRankGiven && ((gTopK == 0 && gPositionsFile.empty() && !gSampleGiven) || gRankFactor < 0 || gRankExclude < 0 || gSplitInterface)) ok = false;
@@ -386,7 +395,14 @@ inline void ArgumentsParser(int argc, char **argv) {
         gForwardFile = f;
         gForwardBad = !load_ids(f, gForwardIds);
     }
-    gForwardOptsGiven = has(argc, argv, "--forward-iters") || has(argc, argv, "--forward-tol") || has(argc, argv, "--forward-topk");
+    if (const char *f = find(argc, argv, "--forward-push")) {
+        gPushFile = f;
+        gPushBad = !load_target_sets(f, gPushSets);
+    }
+    gPushOptsGiven = has(argc, argv, "--push-eps") || has(argc, argv, "--push-rounds");
+    gPushEps = as_whole_double(argc, argv, "--push-eps", 0.0);
+    gPushRounds = as_int(argc, argv, "--push-rounds", 64);
+    gForwardOptsGiven = has(argc, argv, "--forward-iters") || has(argc, argv, "--forward-tol") || (has(argc, argv, "--forward-topk") && gPushFile.empty());
     gForwardIters = as_int(argc, argv, "--forward-iters", 64);
     gForwardTol = as_whole_double(argc, argv, "--forward-tol", 0.0);
     gForwardTopK = as_int(argc, argv, "--forward-topk", 5);

@@ -86,6 +86,12 @@ inline std::vector<int32_t> gForwardIds;
 inline bool gForwardOptsGiven = false; // --forward-iters / --forward-tol / --forward-topk
 inline int gForwardIters = 64;        // --forward-iters N (1 <= N <= 256)
 inline double gForwardTol = 0.0;      // --forward-tol T (T >= 0)
+inline std::string gPushFile;         // --forward-push FILE : one weighted vertex set per line (the format of --target-sets); after every batch print one fpush line per set (dppr_forward_push)
+inline bool gPushBad = false;         //   FILE could not be read, holds no set, or a token is not `id` or `id:weight`
+inline std::vector<std::vector<std::pair<int32_t, double>>> gPushSets;
+inline bool gPushOptsGiven = false;   // --push-eps / --push-rounds
+inline double gPushEps = 0.0;         // --push-eps E (E > 0; required with --forward-push)
+inline int gPushRounds = 64;          // --push-rounds N (1 <= N <= 256)
 inline int gForwardTopK = 5;          // --forward-topk K (0 <= K <= 64: 0 prints no vertex)
 inline int gSample = 0;               // --sample S : after every batch print one sample line per source (S draws in proportion to its score)
 inline bool gSampleGiven = false;

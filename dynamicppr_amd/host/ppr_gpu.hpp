@@ -279,6 +279,7 @@ public:
             if (!gPositionIds.empty()) PrintPositions(-1);
             if (gSample > 0) PrintSamples(-1);
             if (!gForwardIds.empty()) PrintForward(-1);
+            if (!gPushSets.empty()) PrintForwardPush(-1);
             if (!gExplainIds.empty()) PrintExplained(-1);
             if (gCertify > 0 && stream_batch_count % (size_t)gCertify == 0) PrintCertify(-1);
             if (gClusterK > 0) PrintClusters(-1);
@@ -381,6 +382,7 @@ public:
             if (!gPositionIds.empty()) PrintPositions(epoch);
             if (gSample > 0) PrintSamples(epoch);
             if (!gForwardIds.empty()) PrintForward(epoch);
+            if (!gPushSets.empty()) PrintForwardPush(epoch);
             if (!gExplainIds.empty()) PrintExplained(epoch);
             if (gCertify > 0 && stream_batch_count % (size_t)gCertify == 0) PrintCertify(epoch); // (the explicit epoch: the helper may have built the next one)
             if (gClusterK > 0) PrintClusters(epoch);
@@ -959,6 +961,60 @@ public:
                 out += line;
                 for (size_t q = 0; q < (size_t)counts[j]; ++q) {
                     std::snprintf(line, sizeof(line), " %d:%.17g", (int)ids[j * K + q], f[j * K + q]);
+                    out += line;
+                }
+                out += "\n";
+            }
+        }
+        progress++;
+        static std::mutex print_mu;
+        std::lock_guard<std::mutex> lk(print_mu);
+        std::cout << out << std::flush;
+    }
+
+    // --forward-push: after a batch, the forward push from every set of the file over `epoch` (dppr_forward_push), in calls of at most
+    // 16 sets. Outside the timed region, printed as one block like --changes.
+    void PrintForwardPush(int32_t epoch) {
+        const size_t n_sets = gPushSets.size(), K = (size_t)gForwardTopK;
+        std::vector<int32_t> used(DPPR_FORWARD_MAX_M), conv(DPPR_FORWARD_MAX_M), ids(DPPR_FORWARD_MAX_M * std::max<size_t>(K, 1)), counts(DPPR_FORWARD_MAX_M);
+        std::vector<int64_t> pushes(DPPR_FORWARD_MAX_M), left(DPPR_FORWARD_MAX_M);
+        std::vector<double> rem(DPPR_FORWARD_MAX_M), p(DPPR_FORWARD_MAX_M * std::max<size_t>(K, 1));
+        std::string out;
+        char line[240];
+        for (size_t first = 0; first < n_sets; first += DPPR_FORWARD_MAX_M) {
+            const size_t m = std::min<size_t>(DPPR_FORWARD_MAX_M, n_sets - first);
+            std::vector<int64_t> off(1, 0);
+            std::vector<int32_t> sid;
+            std::vector<double> sw;
+            for (size_t j = 0; j < m; ++j) {
+                for (const auto &s : gPushSets[first + j]) {
+                    sid.push_back(s.first);
+                    sw.push_back(s.second);
+                }
+                off.push_back((int64_t)sid.size());
+            }
+            dppr_forward_push_out_t o{};
+            o.rounds_used = used.data();
+            o.converged = conv.data();
+            o.rem = rem.data();
+            o.pushes = pushes.data();
+            o.left = left.data();
+            std::fill(counts.begin(), counts.end(), 0);
+            if (K > 0) {
+                o.k = (int32_t)K;
+                o.min_p = 0.0;
+                o.topk_ids = ids.data();
+                o.topk_p = p.data();
+                o.topk_counts = counts.data();
+            }
+            DPPR_CHECK(engine, dppr_forward_push(engine, epoch, off.data(), sid.data(), sw.data(), (int32_t)m, gPushEps, gPushRounds, &o));
+            for (size_t j = 0; j < m; ++j) {
+                std::snprintf(line, sizeof(line), "fpush %d seeds %d rounds %d converged %d rem %.17g pushes %lld left %lld top %d",
+                              (int)gPushSets[first + j][0].first, (int)gPushSets[first + j].size(), (int)used[j], (int)conv[j], rem[j], (long long)pushes[j],
+                              (long long)left[j], (int)counts[j]);
+                out += line;
+                for (size_t q = 0; q < (size_t)counts[j]; ++q) {
+                    std::snprintf(line, sizeof(line), " %d:%.17g", (int)ids[j * K + q], p[j * K + q]);
                     out += line;
                 }
                 out += "\n";

@@ -111,6 +111,25 @@ def forward(engine, starts, iters=64, tol=0.0, dtype=torch.float64, layout="sour
     return out, torch.from_numpy(res["iters_used"].copy()), torch.from_numpy(res["rem"].copy())
 
 
+def forward_push(engine, sets, eps, max_rounds=64, dtype=torch.float64, layout="source_major", epoch=-1):
+    """dppr_forward_push over torch tensors: p and r of the forward push from each of the start sets `sets` (at most 16; a vertex
+    id or a pair (ids, weights)) as dense tensors on the engine's device, [m, V] (source_major) or [V, m] (vertex_major), float64
+    (bit for bit) or float32 (rounded once). r is what group_dot takes for the bidirectional estimate. Returns (p, r, info): info
+    holds rounds_used, converged, rem, pushes, left [m] and work [3] as CPU tensors."""
+    if dtype not in _DTYPES or layout not in _LAYOUTS:
+        raise _eng.DpprError(f"forward_push: dtype float64 or float32, layout in {sorted(_LAYOUTS)}")
+    m = len(sets)
+    if not 1 <= m <= _eng.FORWARD_MAX_M:
+        raise _eng.DpprError(f"forward_push: 1 <= len(sets) <= {_eng.FORWARD_MAX_M}, not {m}")
+    shape = (m, engine.V) if layout == "source_major" else (engine.V, m)
+    p = torch.empty(shape, dtype=dtype, device=_device(engine))
+    r = torch.empty(shape, dtype=dtype, device=p.device)
+    torch.cuda.synchronize(p.device)   # (the tensors are torch's; nothing of torch's is in flight on them when the engine writes)
+    res = engine.forward_push(sets, eps, max_rounds, epoch=epoch, dense_p_ptr=p.data_ptr(), dense_r_ptr=r.data_ptr(), dtype=_DTYPES[dtype],
+                              layout=_LAYOUTS[layout])
+    return p, r, {k: torch.from_numpy(v.copy()) for k, v in res.items()}
+
+
 _H_LAYOUTS = {"feature_major": _eng.H_FEATURE_MAJOR, "vertex_major": _eng.H_VERTEX_MAJOR}
 
 

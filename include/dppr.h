@@ -1382,6 +1382,73 @@ int dppr_forward(dppr_engine *e, int32_t epoch, const int32_t *starts /* [m] ext
                  const dppr_forward_out_t *out);
 int dppr_debug_forward(dppr_engine *e, int piece_edges /* 0: the plan decides */, int team /* 0: the plan decides */);
 
+/* ---- forward push: local forward PPR from a weighted start set (backward-compatible additions, ABI 6) ----
+ * dppr_forward sweeps the whole window whatever the answer looks like. dppr_forward_push is the frontier-driven forward push of
+ * Andersen, Chung and Lang on the device: its work follows the mass, not the window. Read side only: no state is read or changed,
+ * no id is assigned.
+ *
+ * DEFINITION. M, d(u), stored edges, duplicates, self loops and epochs are exactly those of dppr_forward. A call has m in
+ * [1, DPPR_FORWARD_MAX_M] columns. Column c starts from a weighted set h_c, a CSR in HOST memory (offsets[m + 1], ids, weights)
+ * under the rules of dppr_add_target_group: offsets start at 0 and never decrease, a column has 1 .. DPPR_FPUSH_SET_MAX seeds, no
+ * id twice within a column, every weight finite and > 0, weights are not normalised. A single vertex is one seed of weight 1.0.
+ * Per column, by the device's rows: p = 0, r = h_c, thr[u] = eps * (double)(d(u) + 1) (one multiplication). Round k = 1, 2, ..:
+ *   frontier         F = { u : r[u] > thr[u] }, a strict comparison. If F is empty the column is CONVERGED, rounds_used = k - 1,
+ *                    and it never changes again.
+ *   push             for u in F: p[u] = p[u] + 0.15 * r[u] (one multiplication, one addition), y[u] = (0.85 * r[u]) /
+ *                    (double)(d(u) + 1) (the per-vertex term of dppr_forward), r[u] = +0.0. For u not in F: y[u] = +0.0.
+ *   gather           for every vertex w: r[w] = r[w] + s[w], s[w] the row sum of dppr_forward: THE FOLD of the dot family over
+ *                    y[tail] along w's whole in-row in stored order. Every term is >= +0.0: a row with no tail in F has
+ *                    s = +0.0 and r[w] keeps its bits, so the device skips every row without a frontier in-neighbour. The
+ *                    definition stays the dense one that numpy runs (tests/fpush_ref.py), bit for bit.
+ *   stopping         max_rounds in [1, DPPR_FPUSH_MAX_ROUNDS]. After round max_rounds F is evaluated once more: a column whose F
+ *                    is empty then is converged with rounds_used = max_rounds; any other stops with converged = 0 and
+ *                    rounds_used = max_rounds.
+ *   rowless seeds    a seed without an internal id, or a parked one, has no row: it is settled exactly whatever eps is,
+ *                    p[q] = 0.15 * w and r[q] = +0.0; it takes no part in the rounds and counts in no statistic (the host
+ *                    answers it, as dppr_forward answers a start without a row). So that a column is a function of the epoch
+ *                    alone -- whether a vertex without an edge is parked is not one -- the same holds for every seed that no
+ *                    stored edge of the epoch names.
+ *   independence     a column is a function of the epoch's rows, its set, eps and max_rounds alone: not of the other columns,
+ *                    of m, of the grid, of the chunking of rounds or of dppr_debug_forward_push.
+ * GUARANTEE. With pihat_h = sum_q h[q] * pihat_q and rem = sum r: 0 <= pihat_h[t] - p[t] <= rem entrywise; a converged column
+ * has r[u] <= eps * (d(u) + 1) everywhere; pihat_h(s) = p[s] + sum_u r[u] * pihat_u(s) exactly, so r handed to
+ * dppr_group_dot_dense_dev over a solved group gives the bidirectional estimate of pihat_h(s_i) with error <= rem * max|r_reverse|.
+ * OUTPUTS (dppr_forward_push_out_t; a part whose pointers are all NULL is not run):
+ *   per column, HOST, each may be NULL   rounds_used[m], converged[m], rem[m] (the fold of r over the external ids 0 .. V - 1,
+ *                                  as dppr_forward's rem), pushes[m] (int64: the sum of |F_k| over the rounds), left[m] (int64:
+ *                                  the vertices with r > thr at the end; 0 if and only if converged).
+ *   work[3]                        int64, HOST, over the UNION of the columns' frontiers per round, summed over the rounds: rows
+ *                                  pushed; rows gathered (vertices with at least one in-neighbour in the union frontier); the
+ *                                  in-edges of those rows. Exact integers: what the device walked.
+ *   top k of p per column          topk_ids / topk_p [m][k], topk_counts [m], HOST: order and layout of dppr_forward's top k.
+ *   p and r at given ids           at_p / at_r [j * m + i], HOST, n_at in [1, DPPR_FORWARD_AT_MAX]. Asked for when at_ids, at_p
+ *                                  or at_r is not NULL; then at_ids and at least one of the two are required.
+ *   dense copies                   dense_p_dev and / or dense_r_dev: DEVICE memory of the caller, by external id, one dtype and
+ *                                  layout for both under the rules of dppr_forward's dense copy.
+ * Rejected with DPPR_ERR_INVALID before any device work, nothing written: what dppr_forward rejects, an eps that is not finite or
+ * not > 0, max_rounds outside [1, DPPR_FPUSH_MAX_ROUNDS], a bad CSR (NULL, offsets, sizes, an id outside [0, V), an id twice in a
+ * column, a bad weight).
+ * Threading, stream, work-space ownership and DPPR_ERR_NOMEM behave as for dppr_forward; the planes are shared with it. Nothing is
+ * read back between the rounds of a chunk: the host enqueues a few rounds, then reads ONE word. Every kernel takes its counts from
+ * device memory, so a round after convergence is a few empty launches. No output value comes from a floating-point atomic; the
+ * order of the frontier and receiver lists enters no value.
+ * dppr_debug_forward_push: a test hook. piece_edges and team as dppr_debug_forward; chunk_rounds in [0, 256]: the rounds enqueued
+ * between two read-backs. 0: the plan decides. Every setting gives the same bits.
+ * OUT OF SCOPE: a true scatter push (a hub that receives anything is gathered whole: the price of determinism), keeping a forward
+ * vector current under the stream, dense start vectors, the ranked, cluster and subgraph families over p. */
+#define DPPR_FPUSH_SET_MAX 4096
+#define DPPR_FPUSH_MAX_ROUNDS 256
+typedef struct {
+    int32_t *rounds_used; int32_t *converged; double *rem; int64_t *pushes; int64_t *left; /* [m], HOST; each may be NULL */
+    int64_t *work;                                                      /* [3], HOST; may be NULL */
+    int32_t k; double min_p; int32_t *topk_ids; double *topk_p; int32_t *topk_counts; /* [m][k], [m][k], [m], HOST */
+    const int32_t *at_ids; int32_t n_at; double *at_p; double *at_r;    /* [n_at], [n_at][m], [n_at][m], HOST */
+    void *dense_p_dev; void *dense_r_dev; int32_t dense_dtype, dense_layout; /* DEVICE; as dppr_forward_out_t */
+} dppr_forward_push_out_t;
+int dppr_forward_push(dppr_engine *e, int32_t epoch, const int64_t *offsets /* [m + 1], HOST */, const int32_t *ids, const double *weights,
+                      int32_t m, double eps, int32_t max_rounds, const dppr_forward_push_out_t *out);
+int dppr_debug_forward_push(dppr_engine *e, int piece_edges, int team, int chunk_rounds /* 0: the plan decides */);
+
 /* Windows whose sweep groups are all resident at once run a frontier loop of a source group as
  * multi-sweep launches (grid barrier between sweeps, row tables kept in LDS; dppr_multi.hpp). on by
  * default; 0 = one launch per sweep everywhere. The roll-call / time-out rules are those of
