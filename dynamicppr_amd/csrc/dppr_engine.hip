@@ -59,6 +59,7 @@
 #include "dppr_explain.hpp"
 #include "dppr_forward.hpp"
 #include "dppr_fpush.hpp"
+#include "dppr_ftrack.hpp"
 
 using namespace dppr;
 
@@ -67,6 +68,7 @@ using namespace dppr;
 #include "dppr_host_loop.hpp"
 #include "dppr_host_group.hpp"
 #include "dppr_host_query.hpp"
+#include "dppr_host_ftrack.hpp"
 
 
 extern "C" {
@@ -1722,6 +1724,56 @@ int dppr_debug_forward_push(dppr_engine *e, int piece_edges, int team, int chunk
     e->fp_piece = piece_edges;
     e->fp_team = team;
     e->fp_chunk = chunk_rounds;
+    return DPPR_OK;
+}
+
+int dppr_ftrack_create(dppr_engine *e, int32_t epoch, const int64_t *offsets, const int32_t *ids, const double *weights, int32_t m, double eps,
+                       int32_t max_rounds, const dppr_ftrack_out_t *out, int32_t *out_track) {
+    if (!e || e->broken) return fail(e, DPPR_ERR_INVALID, "ftrack_create: no usable engine");
+    return ftrack_create_call(e, epoch, offsets, ids, weights, m, eps, max_rounds, out, out_track);
+}
+
+int dppr_ftrack_update(dppr_engine *e, int32_t track, int32_t epoch, int32_t max_rounds, const dppr_ftrack_out_t *out) {
+    if (!e || e->broken) return fail(e, DPPR_ERR_INVALID, "ftrack_update: no usable engine");
+    return ftrack_update_call(e, track, epoch, max_rounds, out);
+}
+
+int dppr_ftrack_read(dppr_engine *e, int32_t track, const dppr_ftrack_out_t *out) {
+    if (!e || e->broken) return fail(e, DPPR_ERR_INVALID, "ftrack_read: no usable engine");
+    return ftrack_read_call(e, track, out);
+}
+
+int dppr_ftrack_info(dppr_engine *e, int32_t track, int32_t *epoch, int32_t *m, double *eps, int64_t *offsets, int32_t *ids, double *weights,
+                     int64_t cap) {
+    if (!e || e->broken) return fail(e, DPPR_ERR_INVALID, "ftrack_info: no usable engine");
+    const FTrack *tk = find_ftrack(e, track);
+    if (!tk) return fail(e, DPPR_ERR_INVALID, "ftrack_info: no such track");
+    if (epoch) *epoch = tk->epoch;
+    if (m) *m = tk->m;
+    if (eps) *eps = tk->eps;
+    if (offsets) std::copy(tk->offsets.begin(), tk->offsets.end(), offsets);
+    if (ids || weights) {
+        if (cap < (int64_t)tk->ids.size()) return fail(e, DPPR_ERR_INVALID, "ftrack_info: cap is smaller than the sets (offsets[m])");
+        if (ids) std::copy(tk->ids.begin(), tk->ids.end(), ids);
+        if (weights) std::copy(tk->weights.begin(), tk->weights.end(), weights);
+    }
+    return DPPR_OK;
+}
+
+int dppr_debug_ftrack_ms(dppr_engine *e, float *out_ms) {
+    if (!e || !out_ms) return fail(e, DPPR_ERR_INVALID, "debug_ftrack_ms: non-null engine and out_ms");
+    for (int i = 0; i < 4; ++i) out_ms[i] = e->ft_ms[i];
+    return DPPR_OK;
+}
+
+int dppr_ftrack_destroy(dppr_engine *e, int32_t track) {
+    if (!e || e->broken) return fail(e, DPPR_ERR_INVALID, "ftrack_destroy: no usable engine");
+    FTrack *tk = find_ftrack(e, track);
+    if (!tk) return fail(e, DPPR_ERR_INVALID, "ftrack_destroy: no such track");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    tk->state.reset();
+    *tk = FTrack();
     return DPPR_OK;
 }
 

@@ -73,7 +73,9 @@ __global__ __launch_bounds__(FW_BLOCK) void k_fp_init(FpHead *__restrict__ head,
     }
 }
 
-// round k, b = k & 1: candidates recv[b ^ 1] -> front[b], the mark list; y[b ^ 1] of front[b ^ 1] cleared
+// round k, b = k & 1: candidates recv[b ^ 1] -> front[b], the mark list; y[b ^ 1] of front[b ^ 1] cleared.
+// SIGNED (the forward track, dppr_ftrack.hpp): the test is |r| > thr; the push is the same three assignments.
+template <bool SIGNED>
 __global__ __launch_bounds__(FW_BLOCK) void k_fp_select(FpHead *__restrict__ head, FwGraph g, double eps, double *__restrict__ p,
                                                         double *__restrict__ r, double *__restrict__ y, double *__restrict__ y_old, int gw, int m,
                                                         FpLists ls, int b) {
@@ -100,7 +102,7 @@ __global__ __launch_bounds__(FW_BLOCK) void k_fp_select(FpHead *__restrict__ hea
             const size_t at = (size_t)u * gw;
             for (int c = 0; c < m; ++c) {
                 const double rv = r[at + c];
-                if (rv > thr) {
+                if ((SIGNED ? fabs(rv) : rv) > thr) {
                     p[at + c] = __dadd_rn(p[at + c], __dmul_rn(FW_ALPHA, rv));
                     y[at + c] = __ddiv_rn(__dmul_rn(FW_DAMP, rv), den);
                     r[at + c] = 0.0;
@@ -286,6 +288,7 @@ __global__ __launch_bounds__(FW_BLOCK) void k_fp_long(const FpHead *__restrict__
 }
 
 // after the last round: a row above thr is a receiver of that round (recv[b])
+template <bool SIGNED>
 __global__ __launch_bounds__(FW_BLOCK) void k_fp_left(FpHead *__restrict__ head, FwGraph g, double eps, const double *__restrict__ r, int gw, int m,
                                                       FpLists ls, int b) {
     const unsigned n = min(head->n_recv[b], ls.list_cap);
@@ -297,8 +300,10 @@ __global__ __launch_bounds__(FW_BLOCK) void k_fp_left(FpHead *__restrict__ head,
             const int u = ls.recv[b][i];
             if ((unsigned)u < (unsigned)g.n_int) {
                 const double thr = __dmul_rn(eps, (double)(g.out_row_ptr[u + 1] - g.out_row_ptr[u] + 1));
-                for (int c = 0; c < m; ++c)
-                    if (r[(size_t)u * gw + c] > thr) mask |= 1u << c;
+                for (int c = 0; c < m; ++c) {
+                    const double rv = r[(size_t)u * gw + c];
+                    if ((SIGNED ? fabs(rv) : rv) > thr) mask |= 1u << c;
+                }
             }
         }
         if (!__any(mask != 0)) continue;

@@ -1968,7 +1968,7 @@ int run_fpush(dppr_engine *e, const Epoch &ep, const int64_t *offsets, const int
         const int end = fp_chunk_end(k, max_rounds, chunk);
         for (++k; k <= end; ++k) {
             const int b = k & 1;
-            hipLaunchKernelGGL(k_fp_select, thread_grid, block, 0, e->stream, head, g, eps, p, r, y[b], y[b ^ 1], gw, m, ls, b);
+            hipLaunchKernelGGL(k_fp_select<false>, thread_grid, block, 0, e->stream, head, g, eps, p, r, y[b], y[b ^ 1], gw, m, ls, b);
             hipLaunchKernelGGL(k_fp_mark, mark_grid, block, 0, e->stream, head, g, ep.out_col.get(), ls, b, piece, fq.items.get(), icap, longs, lcap);
             by_fw_shape(PP, levels, [&](auto pp_c, auto lv_c) -> int {
                 constexpr int P = decltype(pp_c)::value, L = decltype(lv_c)::value;
@@ -1986,7 +1986,7 @@ int run_fpush(dppr_engine *e, const Epoch &ep, const int64_t *offsets, const int
         HIP_TRY(loop_wait(e));
         if (!pin->last_act) break; // (no column pushed: every later round is empty)
     }
-    hipLaunchKernelGGL(k_fp_left, thread_grid, block, 0, e->stream, head, g, eps, r, gw, m, ls, k & 1);
+    hipLaunchKernelGGL(k_fp_left<false>, thread_grid, block, 0, e->stream, head, g, eps, r, gw, m, ls, k & 1);
     hipLaunchKernelGGL(k_fw_rem, dim3((unsigned)fw_rem_grid(V)), block, dot_lds_bytes(gw, 1), e->stream, r, gw, m, x2i, V, fq.part.get(), stride);
     hipLaunchKernelGGL(k_dot_combine, dim3((m + DOT_CB_WAVES - 1) / DOT_CB_WAVES), dim3(DOT_CB_WAVES * WAVE), 0, e->stream, fq.part.get(),
                        (const long long *)nullptr, stride, m, m, &head->fw.dot, head->rem);

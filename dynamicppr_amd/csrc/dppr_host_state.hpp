@@ -281,6 +281,10 @@ struct QueryWork {
         DevBuf<int> fp_lists;             // front[2] | recv[2], each fp_list_cap rows
         DevBuf<unsigned> fp_bits;         // a bit per row: already a receiver of the round
         DevBuf<unsigned long long> fp_mark; // the queued pieces of the frontier's out-rows (fp_mark_cap)
+        // the forward track (dppr_ftrack.hpp, dppr_ftrack_plan.hpp) runs the rounds of the push over all of the above and adds:
+        DevBuf<uint32_t> ft_sort;         // the records' keys and indices, in and sorted by tail and by head (ft_sort_words)
+        DevBuf<unsigned char> ft_tmp;     // the device radix sort's own scratch
+        DevBuf<double> ft_c;              // [records][row width] c of step T, by record
     } fw;
     struct Assign { // every vertex to its best lane across groups (dppr_assign.hpp, dppr_assign_plan.hpp); the block grows with a host destination
         DevBuf<double> scale; // [256] the scales of the call
@@ -292,6 +296,24 @@ struct QueryWork {
 };
 
 } // namespace
+
+namespace dppr {
+// A forward track (dppr_ftrack_*): the push state of up to 16 weighted start sets, by EXTERNAL id, and what the last create or
+// update call counted. Owned by the engine; touched by the track calls alone.
+struct FTrack {
+    bool used = false;
+    int epoch = -1, m = 0, gw = 0;
+    double eps = 0.0;
+    std::vector<int64_t> offsets;
+    std::vector<int32_t> ids;
+    std::vector<double> weights;
+    DevBuf<double> state;   // p | r, each [V][gw]
+    bool converged = false; // every column of the last call
+    int rounds_used[Q_LANES] = {};
+    long long pushes[Q_LANES] = {}, left[Q_LANES] = {}, work[3] = {}, fix[3] = {};
+    double rem[Q_LANES] = {};
+};
+} // namespace dppr
 
 struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pending row moves: dppr_idspace.hpp)
     int device = 0;
@@ -473,6 +495,8 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     int fw_team = 0;                // lanes that share a gathered row there; 0: the plan's choice (dppr_debug_forward)
     int fp_piece = 0, fp_team = 0;  // the same two for the forward push (dppr_debug_forward_push)
     int fp_chunk = 0;               // rounds of the forward push between two read-backs; 0: the plan's choice (dppr_debug_forward_push)
+    dppr::FTrack ftracks[16];       // the forward tracks (DPPR_FTRACK_MAX)
+    float ft_ms[4] = {-1.0f, -1.0f, -1.0f, -1.0f}; // dppr_set_profiling: device time of the last track call's load, fix-up, rounds, store (dppr_debug_ftrack_ms)
     float query_ms = -1.0f;         // dppr_set_profiling: device time of the last top-k, changes, export or dot call, first to last kernel (dppr_debug_query_ms)
     std::vector<int32_t> h_tmp1, h_tmp2;
     std::vector<int32_t> h_tiles; // host copy of the tile edge prefix / group table

@@ -80,6 +80,7 @@ EXPORTS = [
     "dppr_sample", "dppr_group_sample", "dppr_debug_sample_form",
     "dppr_forward", "dppr_debug_forward",
     "dppr_forward_push", "dppr_debug_forward_push",
+    "dppr_ftrack_create", "dppr_ftrack_update", "dppr_ftrack_read", "dppr_ftrack_info", "dppr_ftrack_destroy", "dppr_debug_ftrack_ms",
 ]
 
 DEST_HOST, DEST_DEVICE = 0, 1
@@ -108,6 +109,7 @@ SAMPLE_OK, SAMPLE_EMPTY, SAMPLE_NONFINITE = 0, 1, 2
 SAMPLE_WAVE, SAMPLE_PER_THREAD = 0, 1
 FORWARD_MAX_M, FORWARD_MAX_ITERS, FORWARD_CHECK, FORWARD_AT_MAX = 16, 256, 8, 4096
 FPUSH_SET_MAX, FPUSH_MAX_ROUNDS = 4096, 256
+FTRACK_MAX = 16
 
 
 class RankSpec(C.Structure):
@@ -147,6 +149,11 @@ class ForwardPushOut(C.Structure):
                 ("k", C.c_int32), ("min_p", C.c_double), ("topk_ids", _ip), ("topk_p", _dp), ("topk_counts", _ip),
                 ("at_ids", _ip), ("n_at", C.c_int32), ("at_p", _dp), ("at_r", _dp), ("dense_p_dev", C.c_void_p),
                 ("dense_r_dev", C.c_void_p), ("dense_dtype", C.c_int32), ("dense_layout", C.c_int32)]
+
+
+class FtrackOut(C.Structure):
+    """dppr_ftrack_out_t: dppr_forward_push_out_t with fix [3] behind it."""
+    _fields_ = ForwardPushOut._fields_ + [("fix", C.POINTER(C.c_int64))]
 
 
 class PatchOut(C.Structure):
@@ -334,6 +341,14 @@ def lib():
     L.dppr_forward_push.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32,
                                     C.c_double, C.c_int32, vp]
     L.dppr_debug_forward_push.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    L.dppr_ftrack_create.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32,
+                                     C.c_double, C.c_int32, vp, C.POINTER(C.c_int32)]
+    L.dppr_ftrack_update.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp]
+    L.dppr_ftrack_read.argtypes = [vp, C.c_int32, vp]
+    L.dppr_ftrack_info.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int64),
+                                   C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int64]
+    L.dppr_ftrack_destroy.argtypes = [vp, C.c_int32]
+    L.dppr_debug_ftrack_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.dppr_debug_forward.argtypes = [vp, C.c_int, C.c_int]
     L.dppr_assign.argtypes = [vp, ip, C.c_int32, dp, C.c_double, C.c_int, vp, vp, vp, i64p, vp, C.c_int64, i64p, vp, vp, vp]
     L.dppr_assign_at.argtypes = [vp, ip, C.c_int32, dp, C.c_double, ip, C.c_int32, ip, dp, ip, dp]
@@ -367,6 +382,87 @@ def rank_metrics(pos_column, ks):
 def _i32(a):
     a = np.ascontiguousarray(a, dtype=np.int32)
     return a, a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+class ForwardTrack:
+    """A forward track of an Engine (dppr_ftrack_*). update / read return the dict of Engine.forward_push plus fix [3] int64
+    (records applied, distinct tails, distinct heads); the counts are those of the last create or update call."""
+
+    def __init__(self, engine, handle, m):
+        self._e, self.handle, self.m, self.created = engine, handle, m, None
+
+    def _out(self, k, min_p, at, dense_p_ptr, dense_r_ptr, dtype, layout):
+        """(the FtrackOut of a call, a function that returns the call's dict once it has run)"""
+        ip, dp, lp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int64)
+        m, n = self.m, max(self.m, 1)
+        res = {"rounds_used": np.full(n, -1, dtype=np.int32), "converged": np.full(n, -1, dtype=np.int32), "rem": np.full(n, np.nan),
+               "pushes": np.full(n, -1, dtype=np.int64), "left": np.full(n, -1, dtype=np.int64), "work": np.full(3, -1, dtype=np.int64),
+               "fix": np.full(3, -1, dtype=np.int64)}
+        out = FtrackOut()
+        out.rounds_used, out.converged, out.rem = res["rounds_used"].ctypes.data_as(ip), res["converged"].ctypes.data_as(ip), res["rem"].ctypes.data_as(dp)
+        out.pushes, out.left, out.work = res["pushes"].ctypes.data_as(lp), res["left"].ctypes.data_as(lp), res["work"].ctypes.data_as(lp)
+        out.fix = res["fix"].ctypes.data_as(lp)
+        keep = [res]
+        if k:
+            kk = max(int(k), 1)
+            tid, tp, cnt = np.empty((n, kk), dtype=np.int32), np.empty((n, kk)), np.empty(n, dtype=np.int32)
+            out.k, out.min_p = int(k), float(min_p)
+            out.topk_ids, out.topk_p, out.topk_counts = tid.ctypes.data_as(ip), tp.ctypes.data_as(dp), cnt.ctypes.data_as(ip)
+        if at is not None:
+            b, _ = _i32(at)
+            at_p, at_r = np.empty((max(len(b), 1), n)), np.empty((max(len(b), 1), n))
+            out.at_ids, out.n_at, out.at_p, out.at_r = b.ctypes.data_as(ip), len(b), at_p.ctypes.data_as(dp), at_r.ctypes.data_as(dp)
+            keep.append(b)
+        if dense_p_ptr or dense_r_ptr:
+            out.dense_p_dev, out.dense_r_dev, out.dense_dtype, out.dense_layout = dense_p_ptr, dense_r_ptr, int(dtype), int(layout)
+
+        def finish():
+            for key in ("rounds_used", "converged", "rem", "pushes", "left"):
+                res[key] = res[key][:m]
+            if k:
+                res["topk"] = [(tid[i, :c].copy(), tp[i, :c].copy()) for i, c in enumerate(cnt[:m])]
+            if at is not None:
+                res["at_p"] = np.ascontiguousarray(at_p[:len(b), :m].T)
+                res["at_r"] = np.ascontiguousarray(at_r[:len(b), :m].T)
+            return res
+        return out, finish
+
+    def update(self, epoch=-1, max_rounds=64, k=0, min_p=0.0, at=None, dense_p_ptr=None, dense_r_ptr=None, dtype=F64, layout=VERTEX_MAJOR):
+        """dppr_ftrack_update: to `epoch`, the track's own (more rounds) or the next one (fix-up, then rounds)."""
+        out, finish = self._out(k, min_p, at, dense_p_ptr, dense_r_ptr, dtype, layout)
+        self._e._ck(self._e._L.dppr_ftrack_update(self._e._h, self.handle, int(epoch), int(max_rounds), C.byref(out)), "ftrack_update")
+        return finish()
+
+    def read(self, k=0, min_p=0.0, at=None, dense_p_ptr=None, dense_r_ptr=None, dtype=F64, layout=VERTEX_MAJOR):
+        """dppr_ftrack_read: the outputs of the state as it stands."""
+        out, finish = self._out(k, min_p, at, dense_p_ptr, dense_r_ptr, dtype, layout)
+        self._e._ck(self._e._L.dppr_ftrack_read(self._e._h, self.handle, C.byref(out)), "ftrack_read")
+        return finish()
+
+    def info(self):
+        """dict(epoch=, m=, eps=, sets=[(ids, weights), ..])"""
+        ep, m, eps = C.c_int32(), C.c_int32(), C.c_double()
+        off = np.zeros(FTRACK_MAX + 1, dtype=np.int64)
+        L, h = self._e._L, self._e._h
+        self._e._ck(L.dppr_ftrack_info(h, self.handle, C.byref(ep), C.byref(m), C.byref(eps), off.ctypes.data_as(C.POINTER(C.c_int64)), None, None, 0),
+                    "ftrack_info")
+        n = int(off[m.value])
+        ids, w = np.empty(max(n, 1), dtype=np.int32), np.empty(max(n, 1))
+        self._e._ck(L.dppr_ftrack_info(h, self.handle, None, None, None, None, ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                       w.ctypes.data_as(C.POINTER(C.c_double)), n), "ftrack_info")
+        return {"epoch": ep.value, "m": m.value, "eps": eps.value,
+                "sets": [(ids[off[i]:off[i + 1]].copy(), w[off[i]:off[i + 1]].copy()) for i in range(m.value)]}
+
+    def times_ms(self):
+        """With Engine.set_profiling(1): device ms of the engine's last track create / update: [load, fix-up, rounds, store]."""
+        out = (C.c_float * 4)()
+        self._e._ck(self._e._L.dppr_debug_ftrack_ms(self._e._h, out), "debug_ftrack_ms")
+        return [float(x) for x in out]
+
+    def close(self):
+        if self.handle >= 0:
+            self._e._ck(self._e._L.dppr_ftrack_destroy(self._e._h, self.handle), "ftrack_destroy")
+            self.handle = -1
 
 
 class Engine:
@@ -1076,6 +1172,29 @@ class Engine:
         """Test hook (dppr_debug_forward_push): piece_edges and team as debug_forward; chunk_rounds rounds are enqueued between
         two read-backs. 0: the plan's choice. The results do not depend on any of them."""
         self._ck(self._L.dppr_debug_forward_push(self._h, int(piece_edges), int(team), int(chunk_rounds)), "debug_forward_push")
+
+    # ---- forward track: forward PPR of weighted start sets kept current under the stream ----
+    def ftrack(self, sets, eps, max_rounds=64, k=0, min_p=0.0, at=None, epoch=-1, dense_p_ptr=None, dense_r_ptr=None, dtype=F64,
+               layout=VERTEX_MAJOR):
+        """A forward track over the start sets `sets` (include/dppr.h: dppr_ftrack_create), created on `epoch`: the arguments of
+        forward_push. Returns a ForwardTrack; its `.created` is the result dict of the create call (that of forward_push, plus fix)."""
+        lanes = [(np.array([s], dtype=np.int32), np.ones(1)) if np.isscalar(s) else s for s in sets]
+        m = len(lanes)
+        off = np.zeros(m + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(np.atleast_1d(l[0])) for l in lanes])
+        ids = np.ascontiguousarray(np.concatenate([np.atleast_1d(l[0]) for l in lanes]) if m else [], dtype=np.int32)
+        w = np.ascontiguousarray(np.concatenate([np.atleast_1d(l[1]) for l in lanes]) if m else [], dtype=np.float64)
+        if len(w) != len(ids):
+            raise ValueError("ftrack: a set needs one weight per id")
+        ip, dp, lp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int64)
+        tr = ForwardTrack(self, -1, m)
+        out, finish = tr._out(k, min_p, at, dense_p_ptr, dense_r_ptr, dtype, layout)
+        handle = C.c_int32(-1)
+        self._ck(self._L.dppr_ftrack_create(self._h, int(epoch), off.ctypes.data_as(lp), ids.ctypes.data_as(ip), w.ctypes.data_as(dp), m,
+                                            float(eps), int(max_rounds), C.byref(out), C.byref(handle)), "ftrack_create")
+        tr.handle = handle.value
+        tr.created = finish()
+        return tr
 
     # ---- every vertex to its best lane, across groups ----
     def _assign_classes(self, groups, scale, what):

@@ -221,6 +221,10 @@ inline void PrintUsage() {
               << "            while its residual exceeds E * (outdeg + 1); at most N rounds, 1 <= N <= 256, default 64; the --forward-topk K vertices\n"
               << "            it reaches most): fpush <first id> seeds <count> rounds <used> converged <0|1> rem <mass remaining> pushes <count> left\n"
               << "            <count> top <found> <v0>:<p0> ...   (sets beyond 16 go in calls of 16; not with --split)\n"
+              << "--forward-track <file> --push-eps <E> [--push-rounds <N>]: <file> as --forward-push (at most 256 sets); a forward track per 16\n"
+              << "            sets is created after the initial solve and moved to every batch's graph by a fix-up over the batch's records and\n"
+              << "            signed push rounds, instead of a push from zero: ftrack <first id> seeds <count> epoch <e> rounds <used> converged <0|1>\n"
+              << "            rem <fold of |r|> pushes <count> fix <records> <tails> <heads> top <found> <v0>:<p0> ...   (not with --split)\n"
               << "--sample <S> [--sample-seed <X>]: after every batch draw, per source in source order, S vertices with replacement in proportion to\n"
               << "            the source's pagerank -- to the score of --rank-factor / --rank-exclude if given (no --topk needed) -- (1 <= S <= 2^20;\n"
               << "            the draws are a function of the scores, the source's lane, X and the draw number alone): sample <source> lane <lane>\n"
@@ -302,7 +306,10 @@ inline void ArgumentsChecker() {
     if (!gForwardFile.empty() && (gSplitInterface || gForwardIters < 1 || gForwardIters > DPPR_FORWARD_MAX_ITERS || !(gForwardTol >= 0.0) ||
                                   !std::isfinite(gForwardTol) || gForwardTopK < 0 || gForwardTopK > 64))
         ok = false;
-    if (gPushBad || (gPushOptsGiven && gPushFile.empty())) ok = false;
+    if (gPushBad || gTrackBad || (gPushOptsGiven && gPushFile.empty() && gTrackFile.empty())) ok = false;
+    if (!gTrackFile.empty() && (gSplitInterface || !(gPushEps > 0.0) || !std::isfinite(gPushEps) || gPushRounds < 1 || gPushRounds > DPPR_FPUSH_MAX_ROUNDS ||
+                                gForwardTopK < 0 || gForwardTopK > 64 || gTrackSets.size() > (size_t)DPPR_FTRACK_MAX * DPPR_FORWARD_MAX_M))
+        ok = false;
     if (!gPushFile.empty() && (gSplitInterface || !(gPushEps > 0.0) || !std::isfinite(gPushEps) || gPushRounds < 1 || gPushRounds > DPPR_FPUSH_MAX_ROUNDS ||
                                gForwardTopK < 0 || gForwardTopK > 64))
         ok = false;
@@ -399,10 +406,14 @@ inline void ArgumentsParser(int argc, char **argv) {
         gPushFile = f;
         gPushBad = !load_target_sets(f, gPushSets);
     }
+    if (const char *f = find(argc, argv, "--forward-track")) {
+        gTrackFile = f;
+        gTrackBad = !load_target_sets(f, gTrackSets);
+    }
     gPushOptsGiven = has(argc, argv, "--push-eps") || has(argc, argv, "--push-rounds");
     gPushEps = as_whole_double(argc, argv, "--push-eps", 0.0);
     gPushRounds = as_int(argc, argv, "--push-rounds", 64);
-    gForwardOptsGiven = has(argc, argv, "--forward-iters") || has(argc, argv, "--forward-tol") || (has(argc, argv, "--forward-topk") && gPushFile.empty());
+    gForwardOptsGiven = has(argc, argv, "--forward-iters") || has(argc, argv, "--forward-tol") || (has(argc, argv, "--forward-topk") && gPushFile.empty() && gTrackFile.empty());
     gForwardIters = as_int(argc, argv, "--forward-iters", 64);
     gForwardTol = as_whole_double(argc, argv, "--forward-tol", 0.0);
     gForwardTopK = as_int(argc, argv, "--forward-topk", 5);

@@ -155,6 +155,7 @@ public:
             for (int32_t sl : slots) DPPR_CHECK(engine, dppr_mark(engine, sl));
         }
         if (gCertify > 0) PrintCertify(-1); // --certify: the from-scratch solution first
+        if (!gTrackSets.empty()) PrintForwardTrack(-1, true); // --forward-track: created on the window the initial solve ran on
         prof.End(HostProfile::INIT_GRAPH_CALC);
         prof.Start(HostProfile::DYNA_GRAPH_CALC);
         if (overlap_) SlidingWindowExecuteOverlapped();
@@ -280,6 +281,7 @@ public:
             if (gSample > 0) PrintSamples(-1);
             if (!gForwardIds.empty()) PrintForward(-1);
             if (!gPushSets.empty()) PrintForwardPush(-1);
+            if (!gTrackSets.empty()) PrintForwardTrack(-1, false);
             if (!gExplainIds.empty()) PrintExplained(-1);
             if (gCertify > 0 && stream_batch_count % (size_t)gCertify == 0) PrintCertify(-1);
             if (gClusterK > 0) PrintClusters(-1);
@@ -383,6 +385,7 @@ public:
             if (gSample > 0) PrintSamples(epoch);
             if (!gForwardIds.empty()) PrintForward(epoch);
             if (!gPushSets.empty()) PrintForwardPush(epoch);
+            if (!gTrackSets.empty()) PrintForwardTrack(epoch, false);
             if (!gExplainIds.empty()) PrintExplained(epoch);
             if (gCertify > 0 && stream_batch_count % (size_t)gCertify == 0) PrintCertify(epoch); // (the explicit epoch: the helper may have built the next one)
             if (gClusterK > 0) PrintClusters(epoch);
@@ -1012,6 +1015,70 @@ public:
                 std::snprintf(line, sizeof(line), "fpush %d seeds %d rounds %d converged %d rem %.17g pushes %lld left %lld top %d",
                               (int)gPushSets[first + j][0].first, (int)gPushSets[first + j].size(), (int)used[j], (int)conv[j], rem[j], (long long)pushes[j],
                               (long long)left[j], (int)counts[j]);
+                out += line;
+                for (size_t q = 0; q < (size_t)counts[j]; ++q) {
+                    std::snprintf(line, sizeof(line), " %d:%.17g", (int)ids[j * K + q], p[j * K + q]);
+                    out += line;
+                }
+                out += "\n";
+            }
+        }
+        progress++;
+        static std::mutex print_mu;
+        std::lock_guard<std::mutex> lk(print_mu);
+        std::cout << out << std::flush;
+    }
+
+    // --forward-track: a forward track per 16 sets of the file (dppr_ftrack_*). create: on the loaded window, after the initial solve;
+    // else the tracks move to `epoch`, the batch's graph, by the fix-up and the signed rounds. Outside the timed region, printed as one
+    // block like --changes.
+    std::vector<int32_t> ftracks;
+    void PrintForwardTrack(int32_t epoch, bool create) {
+        const size_t n_sets = gTrackSets.size(), K = (size_t)gForwardTopK;
+        std::vector<int32_t> used(DPPR_FORWARD_MAX_M), conv(DPPR_FORWARD_MAX_M), ids(DPPR_FORWARD_MAX_M * std::max<size_t>(K, 1)), counts(DPPR_FORWARD_MAX_M);
+        std::vector<int64_t> pushes(DPPR_FORWARD_MAX_M), fix(3);
+        std::vector<double> rem(DPPR_FORWARD_MAX_M), p(DPPR_FORWARD_MAX_M * std::max<size_t>(K, 1));
+        std::string out;
+        char line[280];
+        for (size_t first = 0, t = 0; first < n_sets; first += DPPR_FORWARD_MAX_M, ++t) {
+            const size_t m = std::min<size_t>(DPPR_FORWARD_MAX_M, n_sets - first);
+            dppr_ftrack_out_t o{};
+            o.rounds_used = used.data();
+            o.converged = conv.data();
+            o.rem = rem.data();
+            o.pushes = pushes.data();
+            o.fix = fix.data();
+            std::fill(counts.begin(), counts.end(), 0);
+            if (K > 0) {
+                o.k = (int32_t)K;
+                o.min_p = 0.0;
+                o.topk_ids = ids.data();
+                o.topk_p = p.data();
+                o.topk_counts = counts.data();
+            }
+            if (create) {
+                std::vector<int64_t> off(1, 0);
+                std::vector<int32_t> sid;
+                std::vector<double> sw;
+                for (size_t j = 0; j < m; ++j) {
+                    for (const auto &s : gTrackSets[first + j]) {
+                        sid.push_back(s.first);
+                        sw.push_back(s.second);
+                    }
+                    off.push_back((int64_t)sid.size());
+                }
+                int32_t handle = -1;
+                DPPR_CHECK(engine, dppr_ftrack_create(engine, epoch, off.data(), sid.data(), sw.data(), (int32_t)m, gPushEps, gPushRounds, &o, &handle));
+                ftracks.push_back(handle);
+            } else {
+                DPPR_CHECK(engine, dppr_ftrack_update(engine, ftracks[t], epoch, gPushRounds, &o));
+            }
+            int32_t at = -1;
+            DPPR_CHECK(engine, dppr_ftrack_info(engine, ftracks[t], &at, nullptr, nullptr, nullptr, nullptr, nullptr, 0));
+            for (size_t j = 0; j < m; ++j) {
+                std::snprintf(line, sizeof(line), "ftrack %d seeds %d epoch %d rounds %d converged %d rem %.17g pushes %lld fix %lld %lld %lld top %d",
+                              (int)gTrackSets[first + j][0].first, (int)gTrackSets[first + j].size(), (int)at, (int)used[j], (int)conv[j], rem[j],
+                              (long long)pushes[j], (long long)fix[0], (long long)fix[1], (long long)fix[2], (int)counts[j]);
                 out += line;
                 for (size_t q = 0; q < (size_t)counts[j]; ++q) {
                     std::snprintf(line, sizeof(line), " %d:%.17g", (int)ids[j * K + q], p[j * K + q]);

@@ -130,6 +130,23 @@ def forward_push(engine, sets, eps, max_rounds=64, dtype=torch.float64, layout="
     return p, r, {k: torch.from_numpy(v.copy()) for k, v in res.items()}
 
 
+def ftrack_read(engine, track, dtype=torch.float64, layout="source_major"):
+    """dppr_ftrack_read over torch tensors: p and r of the forward track `track` (Engine.ftrack) as it stands, dense tensors on the
+    engine's device, [m, V] (source_major) or [V, m] (vertex_major), float64 (bit for bit) or float32 (rounded once). Returns
+    (p, r, info): info holds rounds_used, converged, rem, pushes, left [m], work and fix [3] of the last create or update call as
+    CPU tensors."""
+    if dtype not in _DTYPES or layout not in _LAYOUTS:
+        raise _eng.DpprError(f"ftrack_read: dtype float64 or float32, layout in {sorted(_LAYOUTS)}")
+    if not isinstance(track, _eng.ForwardTrack) or track.handle < 0:
+        raise _eng.DpprError("ftrack_read: an open ForwardTrack of Engine.ftrack")
+    shape = (track.m, engine.V) if layout == "source_major" else (engine.V, track.m)
+    p = torch.empty(shape, dtype=dtype, device=_device(engine))
+    r = torch.empty(shape, dtype=dtype, device=p.device)
+    torch.cuda.synchronize(p.device)   # (the tensors are torch's; nothing of torch's is in flight on them when the engine writes)
+    res = track.read(dense_p_ptr=p.data_ptr(), dense_r_ptr=r.data_ptr(), dtype=_DTYPES[dtype], layout=_LAYOUTS[layout])
+    return p, r, {k: torch.from_numpy(v.copy()) for k, v in res.items()}
+
+
 _H_LAYOUTS = {"feature_major": _eng.H_FEATURE_MAJOR, "vertex_major": _eng.H_VERTEX_MAJOR}
 
 

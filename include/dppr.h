@@ -1366,8 +1366,8 @@ int dppr_debug_sample_form(dppr_engine *e, int form);
  * dppr_debug_forward: a test hook. piece_edges 0 or a power of two in [64, 4096]: in-rows longer than this are summed in pieces
  * of this many entries; team in {0, 1, 2, 4, 8}: the lanes that share one gathered row (raised to the fewest the row width
  * allows). 0: the plan decides. Every setting gives the same bits.
- * OUT OF SCOPE: weighted start distributions, a forward push with a frontier, keeping a forward vector current under the stream,
- * the ranked, cluster or subgraph families over f. */
+ * OUT OF SCOPE: the ranked, cluster or subgraph families over f. (Weighted start sets and a push with a frontier: dppr_forward_push;
+ * a forward vector kept current under the stream: dppr_ftrack_create / dppr_ftrack_update.) */
 #define DPPR_FORWARD_MAX_M 16
 #define DPPR_FORWARD_MAX_ITERS 256
 #define DPPR_FORWARD_CHECK 8          /* iterations between two evaluations of rem */
@@ -1434,8 +1434,8 @@ int dppr_debug_forward(dppr_engine *e, int piece_edges /* 0: the plan decides */
  * order of the frontier and receiver lists enters no value.
  * dppr_debug_forward_push: a test hook. piece_edges and team as dppr_debug_forward; chunk_rounds in [0, 256]: the rounds enqueued
  * between two read-backs. 0: the plan decides. Every setting gives the same bits.
- * OUT OF SCOPE: a true scatter push (a hub that receives anything is gathered whole: the price of determinism), keeping a forward
- * vector current under the stream, dense start vectors, the ranked, cluster and subgraph families over p. */
+ * OUT OF SCOPE: a true scatter push (a hub that receives anything is gathered whole: the price of determinism), dense start
+ * vectors, the ranked, cluster and subgraph families over p. (A forward vector kept current under the stream: dppr_ftrack_*.) */
 #define DPPR_FPUSH_SET_MAX 4096
 #define DPPR_FPUSH_MAX_ROUNDS 256
 typedef struct {
@@ -1448,6 +1448,81 @@ typedef struct {
 int dppr_forward_push(dppr_engine *e, int32_t epoch, const int64_t *offsets /* [m + 1], HOST */, const int32_t *ids, const double *weights,
                       int32_t m, double eps, int32_t max_rounds, const dppr_forward_push_out_t *out);
 int dppr_debug_forward_push(dppr_engine *e, int piece_edges, int team, int chunk_rounds /* 0: the plan decides */);
+
+/* ---- forward track: forward PPR of weighted start sets kept current under the stream (backward-compatible additions, ABI 6) ----
+ * dppr_forward_push starts from zero on every call. A FORWARD TRACK keeps the push state (p, r) of up to DPPR_FORWARD_MAX_M weighted
+ * start sets inside the engine and moves it from epoch k to epoch k + 1 by a fix-up over that epoch's batch records and signed push
+ * rounds over the rows the fix-up disturbed. Read side only with respect to the solver: no slot or group state is read or changed,
+ * the call takes no part in dppr_update / dppr_group_update or in a timed region, no id is assigned. An engine holds at most
+ * DPPR_FTRACK_MAX tracks.
+ *
+ * DEFINITION. M, d(u), stored edges, duplicates, self loops, the per-vertex term, THE FOLD and the row order are those of
+ * dppr_forward / dppr_forward_push. Write P = p / 0.15 for the mass pushed at a vertex. The state of a column keeps
+ *     r[w] = h[w] - P[w] + sum over stored edges u -> w of 0.85 * P[u] * mult / (d(u) + 1)                                  (I)
+ * on the epoch it stands on, to rounding. (I) alone gives pihat_h = p + sum_u r[u] * pihat_u exactly, so
+ * |pihat_h[t] - p[t]| <= sum |r| entrywise; a converged column has |r[u]| <= eps * (d(u) + 1) everywhere.
+ *   create, on epoch k   p = 0, r = h, then the rounds below; the rowless-seed rule of dppr_forward_push applies (p = 0.15 * w,
+ *                    r = +0.0 at a seed that no stored edge of the epoch names). With non-negative r the signed test is the
+ *                    unsigned one: a fresh track equals dppr_forward_push with the same sets, eps and max_rounds bit for bit in
+ *                    p, r, rem, rounds_used, converged, pushes, left, work.
+ *   fix-up, k -> k + 1   over the records i = 0 .. L - 1 of epoch k + 1's batch as dppr_set_batch staged them (tail, head,
+ *                    is_insert; the mirrored copies of an undirected window are records like any other), per column, by
+ *                    external id.
+ *                    STEP T, for every vertex u that is the tail of at least one record: n_ins, n_del its insert and delete
+ *                    records, d1 = d(u) on epoch k + 1, d0 = d1 - n_ins + n_del. g[u] = p[u] / (0.15 * (double)(d0 + 1)) (one
+ *                    multiplication, one division, from p before any change), c[u] = 0.85 * g[u]. Only if d1 != d0:
+ *                    p[u] = (p[u] * (double)(d1 + 1)) / (double)(d0 + 1) and r[u] = r[u] - (double)(d1 - d0) * g[u] (one
+ *                    multiplication, one subtraction). A tail with d1 == d0 keeps p[u] and r[u] to the bit.
+ *                    STEP H, after step T is complete, for every vertex w that is the head of at least one record, the records
+ *                    in ascending i: r[w] = r[w] + c[tail_i] for an insert, r[w] = r[w] - c[tail_i] for a delete. The sum is
+ *                    sequential, one rounding per record.
+ *                    Rescaling P[u] by (d1 + 1) / (d0 + 1) leaves 0.85 * P[u] / (d(u) + 1) unchanged on every kept edge, so (I)
+ *                    changes only at u and at the heads of the changed edges. A vertex new in the batch has p = r = 0; a vertex
+ *                    whose last edge leaves gets d1 = 0 and keeps its values (the state is by external id).
+ *   rounds           those of dppr_forward_push with the frontier F = { u : |r[u]| > thr[u] }, strict; the push is the same three
+ *                    assignments, r, y and the fold's terms may be negative. r is never -0.0, so a row without a frontier
+ *                    in-neighbour keeps its bits and is skipped; the definition stays the dense one (tests/ftrack_ref.py).
+ *   rem              THE FOLD of |r| over the external ids 0 .. V - 1; dppr_forward_push's rem bit for bit while r >= 0.
+ *   independence     a column is a function of the epochs' rows, the batches, its own set, eps and the max_rounds of each call:
+ *                    not of the other columns, of m, of the grid, of the chunking, of dppr_debug_forward_push, of a renumbering
+ *                    of the internal ids beyond the row order the fold already follows, or of anything the solver did.
+ * CALLS. dppr_ftrack_create validates as dppr_forward_push does, runs the create step on `epoch` and hands out a track id in
+ * [0, DPPR_FTRACK_MAX); `out` may be NULL. dppr_ftrack_update accepts exactly two epochs: the track's own (no fix-up, up to
+ * max_rounds more rounds, for a column that stopped unconverged) and the next one (fix-up, then rounds): the sequence rule of
+ * dppr_update. Anything else -- a skipped epoch, an older one, one that is not resident (for instance after a renumbering slide
+ * the track did not follow: create a new track) -- is DPPR_ERR_INVALID with the track unchanged. dppr_ftrack_read writes the
+ * outputs of the state as it stands; dppr_ftrack_info returns the epoch, m, eps and the start sets (offsets [m + 1]; ids and
+ * weights when `cap` holds them all, else DPPR_ERR_INVALID with the size in offsets[m]); dppr_ftrack_destroy frees the track.
+ * OUTPUTS: dppr_ftrack_out_t is dppr_forward_push_out_t with rem as defined above and fix[3] (int64, HOST): records applied,
+ * distinct tails, distinct heads. rounds_used, pushes, left, work and fix are those of the last create or update call;
+ * dppr_ftrack_read returns them unchanged.
+ * The state is held as [V][row width] planes by EXTERNAL id: a renumbering, a parking or a revival never touches it, and a track
+ * never blocks a renumbering. Every call loads it into the planes of the forward family through the id map and stores it back:
+ * two whole-V copies, the fixed cost of a call.
+ * Input rules, rejection before any device work, the id-map lock, stream, work-space ownership and DPPR_ERR_NOMEM behave as for
+ * dppr_forward_push; dppr_debug_forward_push applies to the rounds unchanged, and every setting gives the same bits. No output
+ * value comes from a floating-point atomic; no output position or value depends on the order of a list.
+ * OUT OF SCOPE: changing a track's sets in place, tracks that span engines, the ranked, cluster and subgraph families over a
+ * track's p, any change to the reverse update path. */
+#define DPPR_FTRACK_MAX 16
+typedef struct {
+    int32_t *rounds_used; int32_t *converged; double *rem; int64_t *pushes; int64_t *left; /* [m], HOST; each may be NULL */
+    int64_t *work;                                                      /* [3], HOST; may be NULL */
+    int32_t k; double min_p; int32_t *topk_ids; double *topk_p; int32_t *topk_counts; /* [m][k], [m][k], [m], HOST */
+    const int32_t *at_ids; int32_t n_at; double *at_p; double *at_r;    /* [n_at], [n_at][m], [n_at][m], HOST */
+    void *dense_p_dev; void *dense_r_dev; int32_t dense_dtype, dense_layout; /* DEVICE; as dppr_forward_out_t */
+    int64_t *fix;                                                       /* [3], HOST; may be NULL */
+} dppr_ftrack_out_t;
+int dppr_ftrack_create(dppr_engine *e, int32_t epoch, const int64_t *offsets /* [m + 1], HOST */, const int32_t *ids, const double *weights,
+                       int32_t m, double eps, int32_t max_rounds, const dppr_ftrack_out_t *out /* may be NULL */, int32_t *out_track);
+int dppr_ftrack_update(dppr_engine *e, int32_t track, int32_t epoch, int32_t max_rounds, const dppr_ftrack_out_t *out /* may be NULL */);
+int dppr_ftrack_read(dppr_engine *e, int32_t track, const dppr_ftrack_out_t *out);
+int dppr_ftrack_info(dppr_engine *e, int32_t track, int32_t *epoch, int32_t *m, double *eps, int64_t *offsets /* [17] */, int32_t *ids,
+                     double *weights, int64_t cap);
+int dppr_ftrack_destroy(dppr_engine *e, int32_t track);
+/* With dppr_set_profiling on: the device time in ms of the last create or update call, cut into [4]: the load, the fix-up, the
+ * rounds (the scan of the candidates and the count of `left` with them), the store with the fold of rem. -1 before the first. */
+int dppr_debug_ftrack_ms(dppr_engine *e, float *out_ms /* [4] */);
 
 /* Windows whose sweep groups are all resident at once run a frontier loop of a source group as
  * multi-sweep launches (grid barrier between sweeps, row tables kept in LDS; dppr_multi.hpp). on by
