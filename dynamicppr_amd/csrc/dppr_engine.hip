@@ -60,6 +60,7 @@
 #include "dppr_forward.hpp"
 #include "dppr_fpush.hpp"
 #include "dppr_ftrack.hpp"
+#include "dppr_fcluster.hpp"
 
 using namespace dppr;
 
@@ -69,6 +70,7 @@ using namespace dppr;
 #include "dppr_host_group.hpp"
 #include "dppr_host_query.hpp"
 #include "dppr_host_ftrack.hpp"
+#include "dppr_host_fcluster.hpp"
 
 
 extern "C" {
@@ -1774,6 +1776,22 @@ int dppr_ftrack_destroy(dppr_engine *e, int32_t track) {
     HIP_TRY(hipStreamSynchronize(e->stream));
     tk->state.reset();
     *tk = FTrack();
+    return DPPR_OK;
+}
+
+int dppr_ftrack_cluster(dppr_engine *e, int32_t track, int32_t order, double min_score, int64_t max_len, int32_t min_size, int64_t cap, int dest,
+                        dppr_fcluster_t *out_best, int64_t *out_offsets, int32_t *out_ids, double *out_score, int64_t *out_cut_out,
+                        int64_t *out_cut_in, int64_t *out_vol) {
+    if (!e || e->broken) return fail(e, DPPR_ERR_INVALID, "ftrack_cluster: no usable engine");
+    return ftrack_cluster_call(e, track, order, min_score, max_len, min_size, cap, dest, out_best, out_offsets, out_ids, out_score, out_cut_out,
+                               out_cut_in, out_vol);
+}
+
+int dppr_debug_ftrack_cluster(dppr_engine *e, int scan_tile, int piece_edges) {
+    if (!e || !fc_hook_ok(scan_tile) || !fc_hook_ok(piece_edges))
+        return fail(e, DPPR_ERR_INVALID, "debug_ftrack_cluster: scan_tile and piece_edges 0 or a power of two in [64, 4096]");
+    e->fc_tile = scan_tile;
+    e->fc_piece = piece_edges;
     return DPPR_OK;
 }
 

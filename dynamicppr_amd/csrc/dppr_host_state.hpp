@@ -286,6 +286,20 @@ struct QueryWork {
         DevBuf<unsigned char> ft_tmp;     // the device radix sort's own scratch
         DevBuf<double> ft_c;              // [records][row width] c of step T, by record
     } fw;
+    struct FCluster { // the full-length conductance sweep of a forward track (dppr_fcluster.hpp, dppr_fcluster_plan.hpp); its planes: fw
+        DevBuf<unsigned short> mask;     // [V] which columns qualify at every external id
+        DevBuf<int> cnt;                 // [tiles][m] qualifying ids per tile and column
+        DevBuf<long long> base;          // [tiles][m] first position of a tile's entries of a column
+        DevBuf<unsigned char> head; PinBuf<unsigned char> head_pin; // ExHead (the qualifying offsets), the control words, the records: device / pinned host
+        DevBuf<unsigned long long> keys; // the score bits of the qualifying entries, in | sorted
+        DevBuf<int> vals;                // their external ids, in | sorted
+        DevBuf<unsigned char> tmp;       // the device radix sort's own scratch
+        DevBuf<int> rank;                // [live rows][m] position of a vertex in every column's order (-1: absent)
+        DevBuf<long long> d;             // d_out | d_in | deg by position, then the tiles' sums and carries
+        DevBuf<unsigned char> tbest;     // the tiles' first minima (FcBest)
+        DevBuf<unsigned char> list;      // the queued pieces of the long rows (FcItem, fc_list_cap)
+        DevBuf<unsigned char> blk; PinBuf<unsigned char> pin; // ids, score, cut_out, cut_in, vol by position: device / pinned host
+    } fc;
     struct Assign { // every vertex to its best lane across groups (dppr_assign.hpp, dppr_assign_plan.hpp); the block grows with a host destination
         DevBuf<double> scale; // [256] the scales of the call
         DevBuf<int> cnt;      // [tiles] flips per tile
@@ -494,6 +508,7 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     int fw_piece = 0;               // entries of a piece of a long in-row of the forward sweep; 0: the plan's choice (dppr_debug_forward)
     int fw_team = 0;                // lanes that share a gathered row there; 0: the plan's choice (dppr_debug_forward)
     int fp_piece = 0, fp_team = 0;  // the same two for the forward push (dppr_debug_forward_push)
+    int fc_tile = 0, fc_piece = 0;  // the scan tile and the row piece of the forward track's sweep (dppr_debug_ftrack_cluster; 0: the plan decides)
     int fp_chunk = 0;               // rounds of the forward push between two read-backs; 0: the plan's choice (dppr_debug_forward_push)
     dppr::FTrack ftracks[16];       // the forward tracks (DPPR_FTRACK_MAX)
     float ft_ms[4] = {-1.0f, -1.0f, -1.0f, -1.0f}; // dppr_set_profiling: device time of the last track call's load, fix-up, rounds, store (dppr_debug_ftrack_ms)

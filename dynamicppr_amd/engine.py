@@ -81,6 +81,7 @@ EXPORTS = [
     "dppr_forward", "dppr_debug_forward",
     "dppr_forward_push", "dppr_debug_forward_push",
     "dppr_ftrack_create", "dppr_ftrack_update", "dppr_ftrack_read", "dppr_ftrack_info", "dppr_ftrack_destroy", "dppr_debug_ftrack_ms",
+    "dppr_ftrack_cluster", "dppr_debug_ftrack_cluster",
 ]
 
 DEST_HOST, DEST_DEVICE = 0, 1
@@ -349,6 +350,9 @@ def lib():
                                    C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int64]
     L.dppr_ftrack_destroy.argtypes = [vp, C.c_int32]
     L.dppr_debug_ftrack_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    # (the five arrays as plain addresses: host arrays or device memory, as `dest` says; each may be NULL)
+    L.dppr_ftrack_cluster.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_int64, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.dppr_debug_ftrack_cluster.argtypes = [vp, C.c_int, C.c_int]
     L.dppr_debug_forward.argtypes = [vp, C.c_int, C.c_int]
     L.dppr_assign.argtypes = [vp, ip, C.c_int32, dp, C.c_double, C.c_int, vp, vp, vp, i64p, vp, C.c_int64, i64p, vp, vp, vp]
     L.dppr_assign_at.argtypes = [vp, ip, C.c_int32, dp, C.c_double, ip, C.c_int32, ip, dp, ip, dp]
@@ -382,6 +386,19 @@ def rank_metrics(pos_column, ks):
 def _i32(a):
     a = np.ascontiguousarray(a, dtype=np.int32)
     return a, a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+FCLUSTER_BY_P, FCLUSTER_BY_P_OVER_DEG = 0, 1
+FCLUSTER_ORDERS = {"p": FCLUSTER_BY_P, "deg": FCLUSTER_BY_P_OVER_DEG}
+
+
+class FCluster(C.Structure):
+    """dppr_fcluster_t"""
+    _fields_ = [("count", C.c_int64), ("best_size", C.c_int64), ("best_cut", C.c_int64), ("best_vol", C.c_int64), ("best_phi", C.c_double)]
+
+    def as_dict(self):
+        return {"count": int(self.count), "best_size": int(self.best_size), "best_cut": int(self.best_cut), "best_vol": int(self.best_vol),
+                "best_phi": float(self.best_phi)}
 
 
 class ForwardTrack:
@@ -452,6 +469,33 @@ class ForwardTrack:
                                        w.ctypes.data_as(C.POINTER(C.c_double)), n), "ftrack_info")
         return {"epoch": ep.value, "m": m.value, "eps": eps.value,
                 "sets": [(ids[off[i]:off[i + 1]].copy(), w[off[i]:off[i + 1]].copy()) for i in range(m.value)]}
+
+    def cluster(self, order="deg", min_score=0.0, max_len=0, min_size=1, profile=False, device_ptrs=None, cap=None):
+        """dppr_ftrack_cluster: the lowest-conductance prefix of every column's FULL order (order "deg": p / (outdeg + 1), "p": raw p;
+        score > min_score, at most max_len positions, 0 = all): a list of dicts (count, best_size, best_cut, best_vol, best_phi) in
+        column order. profile=True: (that list, offsets [m + 1], ids, score, cut_out, cut_in, vol), the five arrays one CSR over the
+        columns; the members of column c's best cluster are ids[offsets[c]:offsets[c] + best_size]. device_ptrs: a dict of raw
+        device addresses (ids, score, cut_out, cut_in, vol; each optional) with `cap` entries each: (that list, offsets); nothing is
+        written there if offsets[m] > cap."""
+        m = self.m
+        best, off = (FCluster * max(m, 1))(), np.zeros(max(m, 1) + 1, dtype=np.int64)
+        head = (self._e._h, self.handle, FCLUSTER_ORDERS.get(order, order), float(min_score), int(max_len), int(min_size))
+        fn, ck = self._e._L.dppr_ftrack_cluster, self._e._ck
+        names = ("ids", "score", "cut_out", "cut_in", "vol")
+        if device_ptrs is not None:
+            ck(fn(*head, int(cap or 0), DEST_DEVICE, C.addressof(best), off.ctypes.data, *[device_ptrs.get(k) for k in names]), "ftrack_cluster")
+            return [b.as_dict() for b in best[:m]], off[:m + 1]
+        if not profile:
+            ck(fn(*head, 0, DEST_HOST, C.addressof(best), off.ctypes.data, None, None, None, None, None), "ftrack_cluster")
+            return [b.as_dict() for b in best[:m]]
+        ck(fn(*head, 0, DEST_HOST, C.addressof(best), off.ctypes.data, None, None, None, None, None), "ftrack_cluster")  # the size call
+        total = int(off[m])
+        arrays = [np.empty(total, dtype=dt) for dt in (np.int32, np.float64, np.int64, np.int64, np.int64)]
+        if total:   # the fill (the state does not change between the two calls of one thread)
+            ck(fn(*head, total, DEST_HOST, C.addressof(best), off.ctypes.data, *[a.ctypes.data for a in arrays]), "ftrack_cluster")
+            if int(off[m]) != total:
+                raise DpprError("ftrack_cluster: the state changed between the size call and the fill")
+        return ([b.as_dict() for b in best[:m]], off[:m + 1].copy(), *arrays)
 
     def times_ms(self):
         """With Engine.set_profiling(1): device ms of the engine's last track create / update: [load, fix-up, rounds, store]."""
@@ -1167,6 +1211,11 @@ class Engine:
             res["at_p"] = np.ascontiguousarray(at_p[:len(b), :m].T)
             res["at_r"] = np.ascontiguousarray(at_r[:len(b), :m].T)
         return res
+
+    def debug_ftrack_cluster(self, scan_tile=0, piece_edges=0):
+        """Test hook of ForwardTrack.cluster: positions per tile of the prefix sum and entries per piece of a long row (0 or a power of
+        two in [64, 4096]; 0: the plan decides). Every setting gives the same bits."""
+        self._ck(self._L.dppr_debug_ftrack_cluster(self._h, int(scan_tile), int(piece_edges)), "debug_ftrack_cluster")
 
     def debug_forward_push(self, piece_edges=0, team=0, chunk_rounds=0):
         """Test hook (dppr_debug_forward_push): piece_edges and team as debug_forward; chunk_rounds rounds are enqueued between

@@ -225,6 +225,9 @@ inline void PrintUsage() {
               << "            sets is created after the initial solve and moved to every batch's graph by a fix-up over the batch's records and\n"
               << "            signed push rounds, instead of a push from zero: ftrack <first id> seeds <count> epoch <e> rounds <used> converged <0|1>\n"
               << "            rem <fold of |r|> pushes <count> fix <records> <tails> <heads> top <found> <v0>:<p0> ...   (not with --split)\n"
+              << "--forward-cluster deg|p: with --forward-track, after the create and after every batch sweep every set's WHOLE order -- every vertex an\n"
+              << "            edge names with a score > 0, by p / (outdeg + 1) (deg) or by p -- for its prefix of lowest conductance (dppr_ftrack_cluster):\n"
+              << "            fcluster <first id> size <best_size> of <count> cut <cut_out> vol <vol> phi <conductance, %.17g>\n"
               << "--sample <S> [--sample-seed <X>]: after every batch draw, per source in source order, S vertices with replacement in proportion to\n"
               << "            the source's pagerank -- to the score of --rank-factor / --rank-exclude if given (no --topk needed) -- (1 <= S <= 2^20;\n"
               << "            the draws are a function of the scores, the source's lane, X and the draw number alone): sample <source> lane <lane>\n"
@@ -306,6 +309,7 @@ inline void ArgumentsChecker() {
     if (!gForwardFile.empty() && (gSplitInterface || gForwardIters < 1 || gForwardIters > DPPR_FORWARD_MAX_ITERS || !(gForwardTol >= 0.0) ||
                                   !std::isfinite(gForwardTol) || gForwardTopK < 0 || gForwardTopK > 64))
         ok = false;
+    if (!gTrackCluster.empty() && (gTrackFile.empty() || (gTrackCluster != "deg" && gTrackCluster != "p"))) ok = false;
     if (gPushBad || gTrackBad || (gPushOptsGiven && gPushFile.empty() && gTrackFile.empty())) ok = false;
     if (!gTrackFile.empty() && (gSplitInterface || !(gPushEps > 0.0) || !std::isfinite(gPushEps) || gPushRounds < 1 || gPushRounds > DPPR_FPUSH_MAX_ROUNDS ||
                                 gForwardTopK < 0 || gForwardTopK > 64 || gTrackSets.size() > (size_t)DPPR_FTRACK_MAX * DPPR_FORWARD_MAX_M))
@@ -409,6 +413,10 @@ inline void ArgumentsParser(int argc, char **argv) {
     if (const char *f = find(argc, argv, "--forward-track")) {
         gTrackFile = f;
         gTrackBad = !load_target_sets(f, gTrackSets);
+    }
+    if (has(argc, argv, "--forward-cluster")) {
+        const char *v = find(argc, argv, "--forward-cluster");
+        gTrackCluster = v && *v ? v : "?"; // (no value, or an empty one: refused with the usage)
     }
     gPushOptsGiven = has(argc, argv, "--push-eps") || has(argc, argv, "--push-rounds");
     gPushEps = as_whole_double(argc, argv, "--push-eps", 0.0);

@@ -95,6 +95,7 @@ inline int gPushRounds = 64;          // --push-rounds N (1 <= N <= 256)
 inline std::string gTrackFile;        // --forward-track FILE : sets as --forward-push; a forward track per 16 sets is created after the initial solve and updated after every batch (dppr_ftrack_*; --push-eps, --push-rounds)
 inline bool gTrackBad = false;        //   FILE could not be read, holds no set or more than 256, or a token is not `id` or `id:weight`
 inline std::vector<std::vector<std::pair<int32_t, double>>> gTrackSets;
+inline std::string gTrackCluster;     // --forward-cluster deg|p : with --forward-track, the full-length conductance sweep of every set's p after the create and after every batch (dppr_ftrack_cluster)
 inline int gForwardTopK = 5;          // --forward-topk K (0 <= K <= 64: 0 prints no vertex)
 inline int gSample = 0;               // --sample S : after every batch print one sample line per source (S draws in proportion to its score)
 inline bool gSampleGiven = false;

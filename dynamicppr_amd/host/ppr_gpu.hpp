@@ -1087,6 +1087,23 @@ public:
                 out += "\n";
             }
         }
+        // --forward-cluster: the full-length sweep of every set's p on the epoch the tracks stand on now (the records alone)
+        if (!gTrackCluster.empty()) {
+            const int32_t order = gTrackCluster == "p" ? DPPR_FCLUSTER_BY_P : DPPR_FCLUSTER_BY_P_OVER_DEG;
+            for (size_t first = 0, t = 0; first < n_sets; first += DPPR_FORWARD_MAX_M, ++t) {
+                const size_t m = std::min<size_t>(DPPR_FORWARD_MAX_M, n_sets - first);
+                dppr_fcluster_t best[DPPR_FORWARD_MAX_M];
+                int64_t offsets[DPPR_FORWARD_MAX_M + 1];
+                DPPR_CHECK(engine, dppr_ftrack_cluster(engine, ftracks[t], order, 0.0, 0, 1, 0, DPPR_DEST_HOST, best, offsets, nullptr, nullptr, nullptr,
+                                                       nullptr, nullptr));
+                for (size_t j = 0; j < m; ++j) {
+                    std::snprintf(line, sizeof(line), "fcluster %d size %lld of %lld cut %lld vol %lld phi %.17g\n", (int)gTrackSets[first + j][0].first,
+                                  (long long)best[j].best_size, (long long)best[j].count, (long long)best[j].best_cut, (long long)best[j].best_vol,
+                                  best[j].best_phi);
+                    out += line;
+                }
+            }
+        }
         progress++;
         static std::mutex print_mu;
         std::lock_guard<std::mutex> lk(print_mu);

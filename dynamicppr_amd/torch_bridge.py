@@ -147,6 +147,31 @@ def ftrack_read(engine, track, dtype=torch.float64, layout="source_major"):
     return p, r, {k: torch.from_numpy(v.copy()) for k, v in res.items()}
 
 
+def ftrack_cluster(engine, track, order="deg", min_score=0.0, max_len=0, min_size=1):
+    """dppr_ftrack_cluster over torch tensors: the full-length conductance sweep of every column of the forward track `track`, one CSR
+    over the columns on the engine's device, filled in place (DPPR_DEST_DEVICE). Returns (best, offsets, ids, score, cut_out, cut_in,
+    vol): best a list of dicts (count, best_size, best_cut, best_vol, best_phi), offsets [m + 1] int64 on the CPU, ids int32, score
+    float64, the three prefix arrays int64. The best cluster of column c is ids[offsets[c]:offsets[c] + best[c]["best_size"]]. Two
+    calls: the size query, then the fill with exactly that many entries."""
+    if order not in _eng.FCLUSTER_ORDERS:
+        raise _eng.DpprError(f"ftrack_cluster: order in {sorted(_eng.FCLUSTER_ORDERS)}")
+    if not isinstance(track, _eng.ForwardTrack) or track.handle < 0:
+        raise _eng.DpprError("ftrack_cluster: an open ForwardTrack of Engine.ftrack")
+    dev = _device(engine)
+    kw = dict(order=order, min_score=min_score, max_len=max_len, min_size=min_size)
+    best, off = track.cluster(device_ptrs={}, cap=0, **kw)
+    total = int(off[-1])
+    dtypes = (torch.int32, torch.float64, torch.int64, torch.int64, torch.int64)
+    arrays = [torch.empty(max(total, 1), dtype=d, device=dev) for d in dtypes]
+    if total:
+        torch.cuda.synchronize(dev)   # (the allocations are torch's; nothing of torch's is in flight on them when the engine writes)
+        names = ("ids", "score", "cut_out", "cut_in", "vol")
+        best, off = track.cluster(device_ptrs={n: a.data_ptr() for n, a in zip(names, arrays)}, cap=total, **kw)
+        if int(off[-1]) != total:
+            raise _eng.DpprError("ftrack_cluster: the state changed between the size call and the fill")
+    return (best, torch.from_numpy(off.copy()), *[a[:total] for a in arrays])
+
+
 _H_LAYOUTS = {"feature_major": _eng.H_FEATURE_MAJOR, "vertex_major": _eng.H_VERTEX_MAJOR}
 
 

@@ -1366,8 +1366,9 @@ int dppr_debug_sample_form(dppr_engine *e, int form);
  * dppr_debug_forward: a test hook. piece_edges 0 or a power of two in [64, 4096]: in-rows longer than this are summed in pieces
  * of this many entries; team in {0, 1, 2, 4, 8}: the lanes that share one gathered row (raised to the fewest the row width
  * allows). 0: the plan decides. Every setting gives the same bits.
- * OUT OF SCOPE: the ranked, cluster or subgraph families over f. (Weighted start sets and a push with a frontier: dppr_forward_push;
- * a forward vector kept current under the stream: dppr_ftrack_create / dppr_ftrack_update.) */
+ * OUT OF SCOPE: the ranked or subgraph families over f. (Weighted start sets and a push with a frontier: dppr_forward_push;
+ * a forward vector kept current under the stream: dppr_ftrack_create / dppr_ftrack_update; the conductance sweep of a track's p:
+ * dppr_ftrack_cluster.) */
 #define DPPR_FORWARD_MAX_M 16
 #define DPPR_FORWARD_MAX_ITERS 256
 #define DPPR_FORWARD_CHECK 8          /* iterations between two evaluations of rem */
@@ -1435,7 +1436,8 @@ int dppr_debug_forward(dppr_engine *e, int piece_edges /* 0: the plan decides */
  * dppr_debug_forward_push: a test hook. piece_edges and team as dppr_debug_forward; chunk_rounds in [0, 256]: the rounds enqueued
  * between two read-backs. 0: the plan decides. Every setting gives the same bits.
  * OUT OF SCOPE: a true scatter push (a hub that receives anything is gathered whole: the price of determinism), dense start
- * vectors, the ranked, cluster and subgraph families over p. (A forward vector kept current under the stream: dppr_ftrack_*.) */
+ * vectors, the ranked and subgraph families over p. (A forward vector kept current under the stream: dppr_ftrack_*; the
+ * conductance sweep of a track's p, and a fresh track is the push bit for bit: dppr_ftrack_cluster.) */
 #define DPPR_FPUSH_SET_MAX 4096
 #define DPPR_FPUSH_MAX_ROUNDS 256
 typedef struct {
@@ -1502,8 +1504,8 @@ int dppr_debug_forward_push(dppr_engine *e, int piece_edges, int team, int chunk
  * Input rules, rejection before any device work, the id-map lock, stream, work-space ownership and DPPR_ERR_NOMEM behave as for
  * dppr_forward_push; dppr_debug_forward_push applies to the rounds unchanged, and every setting gives the same bits. No output
  * value comes from a floating-point atomic; no output position or value depends on the order of a list.
- * OUT OF SCOPE: changing a track's sets in place, tracks that span engines, the ranked, cluster and subgraph families over a
- * track's p, any change to the reverse update path. */
+ * OUT OF SCOPE: changing a track's sets in place, tracks that span engines, the ranked and subgraph families over a
+ * track's p, any change to the reverse update path. (The conductance sweep of a track's p: dppr_ftrack_cluster.) */
 #define DPPR_FTRACK_MAX 16
 typedef struct {
     int32_t *rounds_used; int32_t *converged; double *rem; int64_t *pushes; int64_t *left; /* [m], HOST; each may be NULL */
@@ -1523,6 +1525,71 @@ int dppr_ftrack_destroy(dppr_engine *e, int32_t track);
 /* With dppr_set_profiling on: the device time in ms of the last create or update call, cut into [4]: the load, the fix-up, the
  * rounds (the scan of the candidates and the count of `left` with them), the store with the fold of rem. -1 before the first. */
 int dppr_debug_ftrack_ms(dppr_engine *e, float *out_ms /* [4] */);
+
+/* ---- local cluster of a forward track: a full-length conductance sweep over p (backward-compatible additions, ABI 6) ----
+ * The forward push vector of a start set is what PageRank-Nibble sweeps for a low-conductance cut (Andersen, Chung, Lang, FOCS
+ * 2006), and the guarantee is about the sweep over the WHOLE support. dppr_cluster cannot be pointed at a track: its order is raw
+ * p where ACL needs p / degree, and it ends at DPPR_CLUSTER_MAX positions. dppr_ftrack_cluster orders every qualifying vertex of
+ * the window -- up to V per column -- and sweeps the order on the device, next to the state, instead of a dense read of p +
+ * dppr_read_out_graph + a sweep on the host. Read side only: the track, the solver's states and the epoch are not changed.
+ *
+ * For column c of the track, on the epoch the track stands on, every output is defined exactly:
+ *   SCORE     p[v] is what dppr_ftrack_read returns at v; outdeg(v) is the stored out-degree with multiplicity.
+ *             DPPR_FCLUSTER_BY_P: score = p[v]. DPPR_FCLUSTER_BY_P_OVER_DEG: score = p[v] / (double)(outdeg(v) + 1), ONE division,
+ *             nothing fused.
+ *   QUALIFIES v qualifies if at least one stored edge of the epoch names it as tail or head and score > min_score (min_score >= 0).
+ *             A track's p can be negative after deletes: a negative score, a +-0 score and a NaN score never qualify; +infinity
+ *             orders first. A seed that no stored edge names is in no order, whether or not it has an internal id (the
+ *             rowless-seed rule of dppr_forward_push: such a seed has no edge to cut, and the result stays a function of the
+ *             epoch alone).
+ *   ORDER     v_0 .. v_{L-1}: score descending, external id ascending. L = #qualifying if max_len == 0, else
+ *             min(max_len, #qualifying). count = L.
+ *   GRAPH, PREFIX, BEST   word for word those of dppr_cluster: the out-CSR of the epoch with multiplicity, a self loop never
+ *             crosses a cut, Ed is what dppr_graph_edges returns; with S_j = {v_0 .. v_j}: vol[j] = sum of outdeg over S_j,
+ *             cut_out[j] = #{stored edges u -> w : u in S_j, w not in S_j}, cut_in[j] = #{stored edges u -> w : u not in S_j,
+ *             w in S_j}; den[j] = min(vol[j], Ed - vol[j]); prefix j is eligible iff j + 1 >= min_size and den[j] > 0;
+ *             phi[j] = (double)cut_out[j] / (double)den[j], one IEEE division; the best prefix is the first minimum (the smallest
+ *             j among equal values); with no eligible prefix: best_size = 0, best_cut = best_vol = 0, best_phi = +infinity.
+ *   Prefix property: the arrays of a smaller max_len are the head of those of a larger one.
+ *   LAYOUT    one CSR over the columns under the capacity rule of dppr_export_sparse / dppr_subgraph: column c's entries occupy
+ *             [offsets[c], offsets[c + 1]) of the five arrays, offsets[0] = 0, offsets[c + 1] - offsets[c] = L of column c.
+ *             out_offsets [m + 1] and out_best [m] are HOST memory and are always written, with the TRUE counts. If
+ *             offsets[m] > cap nothing is written to the five arrays and the call still returns DPPR_OK. cap = 0 with all five
+ *             arrays NULL is the size-and-best query. dest (DPPR_DEST_HOST / DPPR_DEST_DEVICE): where the five arrays live; each
+ *             may be NULL. A device destination is checked as the exports check theirs, before any device work (cap entries of
+ *             the element type, cap taken as at most m * V, inside one allocation of the engine's device, aligned), and the call
+ *             returns after the solver stream has finished writing. out_score holds the scores the order was made by. The members
+ *             of the best cluster of column c are ids[offsets[c] .. offsets[c] + best_size).
+ *   Determinism: the result is a function of the track's state and the epoch alone: not of the other columns, of the grid or of
+ *             dppr_debug_ftrack_cluster. No output value or position comes from a floating-point atomic, and none from the return
+ *             value of an atomic (integer sums count; the order in which the pieces of a long row are queued enters nothing).
+ * Rejected with DPPR_ERR_INVALID before any device work, nothing written: no such track, an unknown order, min_score negative or
+ * NaN, max_len < 0 or > V, min_size < 1, cap < 0, cap > 0 with every array NULL, a bad dest, a NULL out_best or out_offsets, a
+ * bad device pointer, the track's epoch no longer resident, a broken engine.
+ * Threading and stream as dppr_ftrack_read: the id-map lock for the whole call (safe beside dppr_slide_concurrent), the solver
+ * stream, never part of an update or of a timed region. ONE read of the per-column counts by the host lies between the kernels,
+ * as in dppr_subgraph, to size the sort. Work space: the p | r planes of the forward family, a 16-bit mask per external id, and
+ * per qualifying (vertex, column) 24 bytes of sort keys and ids (in and out), per ordered position 60 bytes (ids, score, three
+ * differences, three prefix sums), 4 bytes per (live row, column) of rank table, the sort's own scratch and the list of the
+ * long rows' pieces; all of it is the engine's, grown on demand and released with the engine: after DPPR_ERR_NOMEM the track and
+ * the engine are as before. With dppr_set_profiling on, dppr_debug_query_ms reports the call, first to last kernel (the one read
+ * of the counts lies between them).
+ * dppr_debug_ftrack_cluster: a test hook. scan_tile 0 or a power of two in [64, 4096]: positions of a tile of the multi-tile
+ * prefix sum; piece_edges 0 or a power of two in [64, 4096]: rows longer than this are walked in pieces of this many entries.
+ * 0: the plan decides. Every setting gives the same bits.
+ * OUT OF SCOPE: masks, factors and exclusions over a track, the ranked and subgraph families over a track, the full-length sweep
+ * for slot and group states, sweeps over dppr_forward / dppr_forward_push results that are not tracks (a fresh track is the push
+ * bit for bit). */
+#define DPPR_FCLUSTER_BY_P           0   /* score = p[v]                              */
+#define DPPR_FCLUSTER_BY_P_OVER_DEG  1   /* score = p[v] / (double)(outdeg(v) + 1)    */
+typedef struct { int64_t count, best_size, best_cut, best_vol; double best_phi; } dppr_fcluster_t;
+int dppr_ftrack_cluster(dppr_engine *e, int32_t track, int32_t order, double min_score, int64_t max_len, int32_t min_size,
+                        int64_t cap, int dest,
+                        dppr_fcluster_t *out_best   /* [m], HOST */,
+                        int64_t *out_offsets        /* [m + 1], HOST */,
+                        int32_t *out_ids, double *out_score,
+                        int64_t *out_cut_out, int64_t *out_cut_in, int64_t *out_vol /* [cap] each, each may be NULL */);
+int dppr_debug_ftrack_cluster(dppr_engine *e, int scan_tile, int piece_edges);
 
 /* Windows whose sweep groups are all resident at once run a frontier loop of a source group as
  * multi-sweep launches (grid barrier between sweeps, row tables kept in LDS; dppr_multi.hpp). on by
