@@ -61,6 +61,7 @@
 #include "dppr_fpush.hpp"
 #include "dppr_ftrack.hpp"
 #include "dppr_fcluster.hpp"
+#include "dppr_ftrack_rank.hpp"
 
 using namespace dppr;
 
@@ -71,6 +72,7 @@ using namespace dppr;
 #include "dppr_host_query.hpp"
 #include "dppr_host_ftrack.hpp"
 #include "dppr_host_fcluster.hpp"
+#include "dppr_host_ftrack_rank.hpp"
 
 
 extern "C" {
@@ -1792,6 +1794,35 @@ int dppr_debug_ftrack_cluster(dppr_engine *e, int scan_tile, int piece_edges) {
         return fail(e, DPPR_ERR_INVALID, "debug_ftrack_cluster: scan_tile and piece_edges 0 or a power of two in [64, 4096]");
     e->fc_tile = scan_tile;
     e->fc_piece = piece_edges;
+    return DPPR_OK;
+}
+
+int dppr_ftrack_topk_ranked(dppr_engine *e, int32_t track, const dppr_rank_spec_t *spec, int32_t k, double min_score, int32_t *out_ids,
+                            double *out_score, int32_t *out_counts) {
+    if (!e || e->broken) return fail(e, DPPR_ERR_INVALID, "ftrack_topk_ranked: no usable engine");
+    return ftrack_topk_ranked_call(e, track, spec, k, min_score, out_ids, out_score, out_counts);
+}
+
+int dppr_ftrack_rank_score_at(dppr_engine *e, int32_t track, const dppr_rank_spec_t *spec, const int32_t *ids, int32_t n_ids, double *out_score) {
+    if (!e || e->broken) return fail(e, DPPR_ERR_INVALID, "ftrack_rank_score_at: no usable engine");
+    return ftrack_rank_score_at_call(e, track, spec, ids, n_ids, out_score);
+}
+
+int dppr_ftrack_position_at(dppr_engine *e, int32_t track, const dppr_rank_spec_t *spec, double min_score, const int32_t *ids, int32_t n_ids,
+                            int32_t *out_pos, int32_t *out_counts) {
+    if (!e || e->broken) return fail(e, DPPR_ERR_INVALID, "ftrack_position_at: no usable engine");
+    return ftrack_position_call(e, track, spec, min_score, ids, n_ids, out_pos, out_counts);
+}
+
+int dppr_ftrack_sample(dppr_engine *e, int32_t track, const dppr_rank_spec_t *spec, double min_score, uint64_t seed, uint64_t first, int32_t S, int dest,
+                       int32_t *out_ids, double *out_w, double *out_total, int32_t *out_support, int32_t *out_status) {
+    if (!e || e->broken) return fail(e, DPPR_ERR_INVALID, "ftrack_sample: no usable engine");
+    return ftrack_sample_call(e, track, spec, min_score, seed, first, S, dest, out_ids, out_w, out_total, out_support, out_status);
+}
+
+int dppr_debug_ftrack_rank(dppr_engine *e, int tile_rows) {
+    if (!e || !fr_tile_ok(tile_rows)) return fail(e, DPPR_ERR_INVALID, "debug_ftrack_rank: tile_rows 0 or a power of two in [64, 1024]");
+    e->fr_tile = tile_rows;
     return DPPR_OK;
 }
 

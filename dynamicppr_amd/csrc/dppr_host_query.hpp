@@ -1173,6 +1173,16 @@ int run_rank_score_at(dppr_engine *e, const StateView &v, const RkLanes &l, cons
     });
 }
 
+// the spec's device pointers (shared with the forms over a forward track). NULL: fine; otherwise the words of the rejection.
+const char *rank_spec_ptrs_refused(dppr_engine *e, const dppr_rank_spec_t *spec) {
+    if (rank_needs_factor_dev(spec) &&
+        !dev_range_ok(e, spec->factor_dev, rank_factor_bytes(spec->factor_dtype, e->V), rank_factor_elem_bytes(spec->factor_dtype)))
+        return "ranked: factor_dev must be aligned device memory of the engine's device, V elements inside one allocation";
+    if (rank_needs_mask_dev(spec) && !dev_range_ok(e, spec->mask_dev, rank_mask_bytes(e->V), 1))
+        return "ranked: mask_dev must be device memory of the engine's device, V bytes inside one allocation";
+    return nullptr;
+}
+
 // What both forms check after their own arguments: the epoch, where the spec needs one (*out_ep stays NULL otherwise), and the
 // spec's device pointers. NULL: fine; otherwise the words of the rejection.
 const char *rank_spec_refused(dppr_engine *e, const StateView &v, int32_t epoch, const dppr_rank_spec_t *spec, const Epoch **out_ep) {
@@ -1184,12 +1194,7 @@ const char *rank_spec_refused(dppr_engine *e, const StateView &v, int32_t epoch,
             return "ranked: the state stands on another epoch than the one given: the degrees and neighbours of another graph are not those its order was computed on";
         *out_ep = ep;
     }
-    if (rank_needs_factor_dev(spec) &&
-        !dev_range_ok(e, spec->factor_dev, rank_factor_bytes(spec->factor_dtype, e->V), rank_factor_elem_bytes(spec->factor_dtype)))
-        return "ranked: factor_dev must be aligned device memory of the engine's device, V elements inside one allocation";
-    if (rank_needs_mask_dev(spec) && !dev_range_ok(e, spec->mask_dev, rank_mask_bytes(e->V), 1))
-        return "ranked: mask_dev must be device memory of the engine's device, V bytes inside one allocation";
-    return nullptr;
+    return rank_spec_ptrs_refused(e, spec);
 }
 
 // (Owner: a Slot or a Group. Its seeds are read under map_mu: a renumbering beside the call renames them)
@@ -1238,6 +1243,35 @@ int position_workspace(dppr_engine *e, Grow &grow, int n, int m) {
     return rc;
 }
 
+// The back half of a position call, from the filled scratch state (sc: `rows` rows of n scores with their external ids) and the
+// query scores at the uploaded ids (the buffer of the point reads) to the caller's arrays: the order of the queries, the count
+// pass, the sums, the one copy back. Its workspace is in place (position_workspace), the slots are zeroed, the bracket is open.
+int position_finish(dppr_engine *e, int rows, int n, double min_score, int m, int32_t *out_pos, int32_t *out_counts) {
+    QueryWork::Scratch &sc = e->q.sc;
+    QueryWork::Position &ps = e->q.pos;
+    const PosShape shape = pos_shape(n, m, e->pos_tile);
+    const PosWork w = pos_work(n, m);
+    const PosLayout lay = pos_layout(n, m);
+    const RaLayout ra = ra_layout(m, n, 1);
+    int *d_ids = reinterpret_cast<int *>(e->q.ra.buf + ra.off_ids);
+    double *d_qs = reinterpret_cast<double *>(e->q.ra.buf + ra.off_a);
+    unsigned long long *d_key = reinterpret_cast<unsigned long long *>(ps.keys + w.off_key);
+    int *d_place = reinterpret_cast<int *>(ps.keys + w.off_place);
+    int *res_cnt = reinterpret_cast<int *>(ps.blk + lay.off_cnt), *res_pos = reinterpret_cast<int *>(ps.blk + lay.off_pos);
+    if (m > 0)
+        hipLaunchKernelGGL(k_pos_order, dim3((m + POS_ORDER_BLOCK - 1) / POS_ORDER_BLOCK, n), dim3(POS_ORDER_BLOCK), 0, e->stream, d_qs, d_ids, m, n,
+                           min_score, d_key, d_place);
+    hipLaunchKernelGGL(k_pos_count, dim3(pos_grid_x(rows, shape), shape.lane_blocks, shape.passes), dim3(POS_BLOCK),
+                       pos_lds_bytes(shape.lanes, shape.tile), e->stream, sc.a.get(), sc.ext.get(), rows, n, min_score, d_key, d_place, d_ids, m,
+                       shape.tile, shape.lanes, ps.slots.get());
+    hipLaunchKernelGGL(k_pos_finish, dim3(n), dim3(POS_BLOCK), 0, e->stream, ps.slots.get(), d_key, d_place, m, n, shape.tile, res_cnt, res_pos);
+    HIP_TRY(hipGetLastError());
+    if (int rc = fetch_block(e, ps.blk, ps.pin, lay.total_bytes)) return rc;
+    if (out_counts) memcpy(out_counts, ps.pin + lay.off_cnt, sizeof(int32_t) * (size_t)n);
+    if (m > 0) memcpy(out_pos, ps.pin + lay.off_pos, sizeof(int32_t) * (size_t)m * (size_t)n);
+    return DPPR_OK;
+}
+
 // Positions of m external ids in every lane's order by the spec's score, and every lane's count of qualifying vertices (arguments,
 // the spec's device pointers and the epoch validated by the caller; m == 0: the counts alone). Every buffer is in place before the
 // first kernel, every stage is enqueued before the one copy back: the marking and the scratch state of run_topk_ranked, the scores
@@ -1255,15 +1289,10 @@ int run_position(dppr_engine *e, const StateView &v, const RkLanes &l, const Epo
     if (int rc = position_workspace(e, grow, n, m)) return rc;
     const RkGraph g = rank_graph(e, ep);
     const RkRule rule = rank_rule(sp);
-    const PosShape shape = pos_shape(n, m, e->pos_tile);
     const PosWork w = pos_work(n, m);
-    const PosLayout lay = pos_layout(n, m);
     const RaLayout ra = ra_layout(m, n, 1);
     int *d_ids = reinterpret_cast<int *>(e->q.ra.buf + ra.off_ids);
     double *d_qs = reinterpret_cast<double *>(e->q.ra.buf + ra.off_a);
-    unsigned long long *d_key = reinterpret_cast<unsigned long long *>(ps.keys + w.off_key);
-    int *d_place = reinterpret_cast<int *>(ps.keys + w.off_place);
-    int *res_cnt = reinterpret_cast<int *>(ps.blk + lay.off_cnt), *res_pos = reinterpret_cast<int *>(ps.blk + lay.off_pos);
     if (m > 0) HIP_TRY(hipMemcpyAsync(d_ids, ids, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, e->stream));
     if (int rc = DeviceTime{e}.open()) return rc;
     const unsigned *excl = nullptr;
@@ -1278,18 +1307,7 @@ int run_position(dppr_engine *e, const StateView &v, const RkLanes &l, const Epo
                                v.p, v.gw, n, e->d_ext2int.get(), d_ids, m, excl, rule, g, d_qs);
         return DPPR_OK;
     });
-    if (m > 0)
-        hipLaunchKernelGGL(k_pos_order, dim3((m + POS_ORDER_BLOCK - 1) / POS_ORDER_BLOCK, n), dim3(POS_ORDER_BLOCK), 0, e->stream, d_qs, d_ids, m, n,
-                           min_score, d_key, d_place);
-    hipLaunchKernelGGL(k_pos_count, dim3(pos_grid_x(st.rows, shape), shape.lane_blocks, shape.passes), dim3(POS_BLOCK),
-                       pos_lds_bytes(shape.lanes, shape.tile), e->stream, sc.a.get(), sc.ext.get(), st.rows, n, min_score, d_key, d_place, d_ids, m,
-                       shape.tile, shape.lanes, ps.slots.get());
-    hipLaunchKernelGGL(k_pos_finish, dim3(n), dim3(POS_BLOCK), 0, e->stream, ps.slots.get(), d_key, d_place, m, n, shape.tile, res_cnt, res_pos);
-    HIP_TRY(hipGetLastError());
-    if (int rc = fetch_block(e, ps.blk, ps.pin, lay.total_bytes)) return rc;
-    if (out_counts) memcpy(out_counts, ps.pin + lay.off_cnt, sizeof(int32_t) * (size_t)n);
-    if (m > 0) memcpy(out_pos, ps.pin + lay.off_pos, sizeof(int32_t) * (size_t)m * (size_t)n);
-    return DPPR_OK;
+    return position_finish(e, st.rows, n, min_score, m, out_pos, out_counts);
 }
 
 template <class Owner>
@@ -1318,38 +1336,24 @@ int sample_workspace(dppr_engine *e, Grow &grow, int n, const SmTree &t, size_t 
     return rc;
 }
 
-// S draws of every lane by the spec's score, with the totals, supports and statuses (arguments, the spec's device pointers, the
-// epoch and a device destination validated by the caller; S == 0: the tree alone). Every buffer is in place before the first
-// kernel, every stage is enqueued before the one copy back: the marking of run_topk_ranked, the leaves and the tiles' nodes, the
-// upper levels, the draws.
-int run_sample(dppr_engine *e, const StateView &v, const RkLanes &l, const Epoch *ep, const RkSpec &sp, double min_score, uint64_t seed,
-               uint64_t first, int S, int dest, int32_t *out_ids, double *out_w, double *out_total, int32_t *out_support, int32_t *out_status) {
-    if (int rc = query_begin(e, MAP_E2I)) return rc;
+// the head of a call's result block
+SmOut sample_head(dppr_engine *e, const SmLayout &lay) {
     QueryWork::Sample &sm = e->q.sm;
-    const int n = v.n;
+    return {reinterpret_cast<double *>(sm.blk + lay.off_total), reinterpret_cast<int *>(sm.blk + lay.off_support), reinterpret_cast<int *>(sm.blk + lay.off_status)};
+}
+
+// The back half of a sample call, from the written leaves and tiles' nodes of n lanes to the caller's arrays: the upper levels,
+// the draws of the form in force, the one copy back. Its workspace is in place (sample_workspace), the head of the block is zeroed,
+// the bracket is open.
+int sample_finish(dppr_engine *e, int n, const SmTree &t, uint64_t seed, uint64_t first, int S, int dest, int32_t *out_ids, double *out_w,
+                  double *out_total, int32_t *out_support, int32_t *out_status) {
+    QueryWork::Sample &sm = e->q.sm;
     const bool host = dest == DPPR_DEST_HOST;
-    const SmTree t = sample_tree(e->V);
     const SmLayout lay = sample_layout(n, S, host, out_w != nullptr);
-    Grow grow{e};
-    if (int rc = rank_mark_workspace(e, grow, l, sp, ep)) return rc;
-    if (int rc = sample_workspace(e, grow, n, t, lay.total_bytes)) return rc;
-    const RkGraph g = rank_graph(e, ep);
-    const RkRule rule = rank_rule(sp);
-    const SmOut head{reinterpret_cast<double *>(sm.blk + lay.off_total), reinterpret_cast<int *>(sm.blk + lay.off_support),
-                     reinterpret_cast<int *>(sm.blk + lay.off_status)};
+    const SmOut head = sample_head(e, lay);
     int *d_ids = host ? reinterpret_cast<int *>(sm.blk + lay.off_ids) : out_ids;
     double *d_w = !out_w ? nullptr : host ? reinterpret_cast<double *>(sm.blk + lay.off_w) : out_w;
     const bool plain = e->sample_form == 1;
-    if (int rc = DeviceTime{e}.open()) return rc;
-    const unsigned *excl = nullptr;
-    if (int rc = rank_mark_enqueue(e, l, sp, g, &excl)) return rc;
-    HIP_TRY(hipMemsetAsync(sm.blk, 0, SM_HEAD_BYTES, e->stream));
-    by_factor(sp, [&](auto kind, auto elem) -> int {
-        using T = decltype(elem);
-        hipLaunchKernelGGL((k_sm_leaves<decltype(kind)::value, T>), dim3(t.tiles), dim3(SM_BLOCK), 0, e->stream, v.p, v.gw, n, e->d_ext2int.get(),
-                           excl, rule, g, min_score, t, sm.leaves.get(), sm.nodes.get(), plain ? sm.low.get() : nullptr, head.support);
-        return DPPR_OK;
-    });
     hipLaunchKernelGGL(k_sm_upper, dim3(n), dim3(SM_BLOCK), 0, e->stream, sm.nodes.get(), t, head);
     if (S > 0) {
         const int64_t total = (int64_t)n * S;
@@ -1370,6 +1374,38 @@ int run_sample(dppr_engine *e, const StateView &v, const RkLanes &l, const Epoch
         if (out_w) memcpy(out_w, sm.pin + lay.off_w, sample_w_bytes(n, S));
     }
     return DPPR_OK;
+}
+
+// S draws of every lane by the spec's score, with the totals, supports and statuses (arguments, the spec's device pointers, the
+// epoch and a device destination validated by the caller; S == 0: the tree alone). Every buffer is in place before the first
+// kernel, every stage is enqueued before the one copy back: the marking of run_topk_ranked, the leaves and the tiles' nodes, the
+// upper levels, the draws.
+int run_sample(dppr_engine *e, const StateView &v, const RkLanes &l, const Epoch *ep, const RkSpec &sp, double min_score, uint64_t seed,
+               uint64_t first, int S, int dest, int32_t *out_ids, double *out_w, double *out_total, int32_t *out_support, int32_t *out_status) {
+    if (int rc = query_begin(e, MAP_E2I)) return rc;
+    QueryWork::Sample &sm = e->q.sm;
+    const int n = v.n;
+    const bool host = dest == DPPR_DEST_HOST;
+    const SmTree t = sample_tree(e->V);
+    const SmLayout lay = sample_layout(n, S, host, out_w != nullptr);
+    Grow grow{e};
+    if (int rc = rank_mark_workspace(e, grow, l, sp, ep)) return rc;
+    if (int rc = sample_workspace(e, grow, n, t, lay.total_bytes)) return rc;
+    const RkGraph g = rank_graph(e, ep);
+    const RkRule rule = rank_rule(sp);
+    const SmOut head = sample_head(e, lay);
+    const bool plain = e->sample_form == 1;
+    if (int rc = DeviceTime{e}.open()) return rc;
+    const unsigned *excl = nullptr;
+    if (int rc = rank_mark_enqueue(e, l, sp, g, &excl)) return rc;
+    HIP_TRY(hipMemsetAsync(sm.blk, 0, SM_HEAD_BYTES, e->stream));
+    by_factor(sp, [&](auto kind, auto elem) -> int {
+        using T = decltype(elem);
+        hipLaunchKernelGGL((k_sm_leaves<decltype(kind)::value, T>), dim3(t.tiles), dim3(SM_BLOCK), 0, e->stream, v.p, v.gw, n, e->d_ext2int.get(),
+                           excl, rule, g, min_score, t, sm.leaves.get(), sm.nodes.get(), plain ? sm.low.get() : nullptr, head.support);
+        return DPPR_OK;
+    });
+    return sample_finish(e, n, t, seed, first, S, dest, out_ids, out_w, out_total, out_support, out_status);
 }
 
 template <class Owner>

@@ -241,7 +241,7 @@ struct QueryWork {
         DevBuf<unsigned char> blk; PinBuf<unsigned char> pin; // the head, ids, p, row_ptr and a host destination's col: device / pinned host
     } sg;
     struct Rank { // ranked candidates (dppr_rank.hpp, dppr_rank_plan.hpp); its scores: sc
-        DevBuf<unsigned> excl; // [live rows] bit i: excluded for lane i (zeroed per call)
+        DevBuf<unsigned> excl; // bit i: excluded for lane i (zeroed per call). A slot / group call: [live rows] by internal id; a call over a forward track: [V] by EXTERNAL id, bit c for column c
         DevBuf<int> len; PinBuf<int> len_pin;     // [seeds][2] out-row and in-row length of every seed: device / pinned host
         DevBuf<unsigned long long> list;          // the piece list of the call (rk_piece_cap)
         std::vector<unsigned long long> items;    // ... as the host builds it (kept for its capacity)
@@ -300,6 +300,12 @@ struct QueryWork {
         DevBuf<unsigned char> list;      // the queued pieces of the long rows (FcItem, fc_list_cap)
         DevBuf<unsigned char> blk; PinBuf<unsigned char> pin; // ids, score, cut_out, cut_in, vol by position: device / pinned host
     } fc;
+    struct FtrackRank { // the ranked, position and sample queries over a forward track (dppr_ftrack_rank.hpp, dppr_ftrack_rank_plan.hpp); its exclusion words, row lengths and pieces: rk (the words by EXTERNAL id here), its scores: sc
+        DevBuf<int> seeds;      // the flat table of the track's seeds, external ids
+        DevBuf<int> cnt;        // [tiles] kept ids per tile
+        DevBuf<long long> base; // [tiles] first row of a tile in the compacted scratch state
+        DevBuf<unsigned char> head; PinBuf<unsigned char> head_pin; // ExHead (offsets[1]: the kept rows): device / pinned host
+    } fr;
     struct Assign { // every vertex to its best lane across groups (dppr_assign.hpp, dppr_assign_plan.hpp); the block grows with a host destination
         DevBuf<double> scale; // [256] the scales of the call
         DevBuf<int> cnt;      // [tiles] flips per tile
@@ -509,6 +515,7 @@ struct dppr_engine : dppr::IdSpace { // (the id maps, the parked zone and the pe
     int fw_team = 0;                // lanes that share a gathered row there; 0: the plan's choice (dppr_debug_forward)
     int fp_piece = 0, fp_team = 0;  // the same two for the forward push (dppr_debug_forward_push)
     int fc_tile = 0, fc_piece = 0;  // the scan tile and the row piece of the forward track's sweep (dppr_debug_ftrack_cluster; 0: the plan decides)
+    int fr_tile = 0;                // ids of a tile of the count / fill passes of the ranked queries over a forward track (dppr_debug_ftrack_rank; 0: the plan decides)
     int fp_chunk = 0;               // rounds of the forward push between two read-backs; 0: the plan's choice (dppr_debug_forward_push)
     dppr::FTrack ftracks[16];       // the forward tracks (DPPR_FTRACK_MAX)
     float ft_ms[4] = {-1.0f, -1.0f, -1.0f, -1.0f}; // dppr_set_profiling: device time of the last track call's load, fix-up, rounds, store (dppr_debug_ftrack_ms)

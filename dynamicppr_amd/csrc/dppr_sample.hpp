@@ -55,6 +55,61 @@ __device__ __forceinline__ void sm_level(const double *src, int src_row, double 
     }
 }
 
+// The weights of a subtile, in LDS [lane][id] (s_a), leave lane-major; the subtile's levels 1 .. 7 between the two arrays, level 8
+// into the tile's eight (s_n8). Shared by k_sm_leaves and its sibling over a forward track (dppr_ftrack_rank.hpp: k_fr_leaves).
+__device__ __forceinline__ void sm_subtile_out(double *s_a, double *s_b, double *s_n8, unsigned *s_cnt, int n, const SmTree &t, long long base, int sb,
+                                               double *__restrict__ leaves, double *__restrict__ low) {
+    constexpr int ROW_A = SM_SUB + 1, ROW_B = SM_SUB / 2;
+    for (int o = threadIdx.x; o < SM_SUB * n; o += SM_BLOCK) {
+        const int lane = o / SM_SUB, id = o % SM_SUB;
+        leaves[(size_t)lane * (size_t)t.Vt + (size_t)base + id] = s_a[lane * ROW_A + id];
+    }
+    // levels 1 .. 7 between the two arrays, level 8 into the tile's eight
+    sm_level<true>(s_a, ROW_A, s_b, ROW_B, 128, n, s_cnt, low ? low + sample_low_off(t.Vt, 1) + (base >> 1) : nullptr, t.Vt);
+    __syncthreads();
+    sm_level<false>(s_b, ROW_B, s_a, ROW_A, 64, n, s_cnt, low ? low + sample_low_off(t.Vt, 2) + (base >> 2) : nullptr, t.Vt);
+    __syncthreads();
+    sm_level<false>(s_a, ROW_A, s_b, ROW_B, 32, n, s_cnt, low ? low + sample_low_off(t.Vt, 3) + (base >> 3) : nullptr, t.Vt);
+    __syncthreads();
+    sm_level<false>(s_b, ROW_B, s_a, ROW_A, 16, n, s_cnt, low ? low + sample_low_off(t.Vt, 4) + (base >> 4) : nullptr, t.Vt);
+    __syncthreads();
+    sm_level<false>(s_a, ROW_A, s_b, ROW_B, 8, n, s_cnt, low ? low + sample_low_off(t.Vt, 5) + (base >> 5) : nullptr, t.Vt);
+    __syncthreads();
+    sm_level<false>(s_b, ROW_B, s_a, ROW_A, 4, n, s_cnt, low ? low + sample_low_off(t.Vt, 6) + (base >> 6) : nullptr, t.Vt);
+    __syncthreads();
+    sm_level<false>(s_a, ROW_A, s_b, ROW_B, 2, n, s_cnt, low ? low + sample_low_off(t.Vt, 7) + (base >> 7) : nullptr, t.Vt);
+    __syncthreads();
+    sm_level<false>(s_b, ROW_B, s_n8 + sb, 8, 1, n, s_cnt, nullptr, 0);
+}
+
+// ... after the eight subtiles of a tile: one thread per lane adds the levels 9 .. 11, the nodes of levels 8 .. 11 are stored and
+// the lane's positive leaves join its support (one integer atomic per lane and tile). The caller has synchronised.
+__device__ __forceinline__ void sm_tile_nodes(const double *s_n8, const unsigned *s_cnt, int n, const SmTree &t, int tile, double *__restrict__ nodes,
+                                              int *__restrict__ support) {
+    if (threadIdx.x < n) { // levels 8 .. 11 of this lane's tile
+        const int lane = threadIdx.x;
+        double *nd = nodes + (size_t)lane * t.node_stride;
+        double y[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            y[j] = s_n8[lane * 8 + j];
+            nd[t.off[8] + (size_t)tile * 8 + j] = y[j];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            y[j] = __dadd_rn(y[2 * j], y[2 * j + 1]);
+            nd[t.off[9] + (size_t)tile * 4 + j] = y[j];
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            y[j] = __dadd_rn(y[2 * j], y[2 * j + 1]);
+            nd[t.off[10] + (size_t)tile * 2 + j] = y[j];
+        }
+        nd[t.off[11] + (size_t)tile] = __dadd_rn(y[0], y[1]);
+        if (s_cnt[lane]) atomicAdd(&support[lane], (int)s_cnt[lane]);
+    }
+}
+
 // p: the state, rows of gw doubles. leaves [n][t.Vt], nodes [n][t.node_stride], low [n][t.Vt] or NULL.
 template <int KIND, class T>
 __global__ __launch_bounds__(SM_BLOCK) void k_sm_leaves(const double *__restrict__ p, int gw, int n, const int *__restrict__ ext2int,
@@ -97,50 +152,10 @@ __global__ __launch_bounds__(SM_BLOCK) void k_sm_leaves(const double *__restrict
             s_a[lane * ROW_A + id] = sample_weight(rk_score<KIND>(v, s_f[id], (s_x[id] >> lane) & 1u), min_score);
         }
         __syncthreads();
-        for (int o = threadIdx.x; o < SM_SUB * n; o += SM_BLOCK) {
-            const int lane = o / SM_SUB, id = o % SM_SUB;
-            leaves[(size_t)lane * (size_t)t.Vt + (size_t)base + id] = s_a[lane * ROW_A + id];
-        }
-        // levels 1 .. 7 between the two arrays, level 8 into the tile's eight
-        sm_level<true>(s_a, ROW_A, s_b, ROW_B, 128, n, s_cnt, low ? low + sample_low_off(t.Vt, 1) + (base >> 1) : nullptr, t.Vt);
-        __syncthreads();
-        sm_level<false>(s_b, ROW_B, s_a, ROW_A, 64, n, s_cnt, low ? low + sample_low_off(t.Vt, 2) + (base >> 2) : nullptr, t.Vt);
-        __syncthreads();
-        sm_level<false>(s_a, ROW_A, s_b, ROW_B, 32, n, s_cnt, low ? low + sample_low_off(t.Vt, 3) + (base >> 3) : nullptr, t.Vt);
-        __syncthreads();
-        sm_level<false>(s_b, ROW_B, s_a, ROW_A, 16, n, s_cnt, low ? low + sample_low_off(t.Vt, 4) + (base >> 4) : nullptr, t.Vt);
-        __syncthreads();
-        sm_level<false>(s_a, ROW_A, s_b, ROW_B, 8, n, s_cnt, low ? low + sample_low_off(t.Vt, 5) + (base >> 5) : nullptr, t.Vt);
-        __syncthreads();
-        sm_level<false>(s_b, ROW_B, s_a, ROW_A, 4, n, s_cnt, low ? low + sample_low_off(t.Vt, 6) + (base >> 6) : nullptr, t.Vt);
-        __syncthreads();
-        sm_level<false>(s_a, ROW_A, s_b, ROW_B, 2, n, s_cnt, low ? low + sample_low_off(t.Vt, 7) + (base >> 7) : nullptr, t.Vt);
-        __syncthreads();
-        sm_level<false>(s_b, ROW_B, s_n8 + sb, 8, 1, n, s_cnt, nullptr, 0);
+        sm_subtile_out(s_a, s_b, s_n8, s_cnt, n, t, base, sb, leaves, low);
     }
     __syncthreads();
-    if (threadIdx.x < n) { // levels 8 .. 11 of this lane's tile
-        const int lane = threadIdx.x;
-        double *nd = nodes + (size_t)lane * t.node_stride;
-        double y[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            y[j] = s_n8[lane * 8 + j];
-            nd[t.off[8] + (size_t)tile * 8 + j] = y[j];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            y[j] = __dadd_rn(y[2 * j], y[2 * j + 1]);
-            nd[t.off[9] + (size_t)tile * 4 + j] = y[j];
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            y[j] = __dadd_rn(y[2 * j], y[2 * j + 1]);
-            nd[t.off[10] + (size_t)tile * 2 + j] = y[j];
-        }
-        nd[t.off[11] + (size_t)tile] = __dadd_rn(y[0], y[1]);
-        if (s_cnt[lane]) atomicAdd(&support[lane], (int)s_cnt[lane]);
-    }
+    sm_tile_nodes(s_n8, s_cnt, n, t, tile, nodes, support);
 }
 
 // the levels above a tile, one workgroup per lane

@@ -82,6 +82,7 @@ EXPORTS = [
     "dppr_forward_push", "dppr_debug_forward_push",
     "dppr_ftrack_create", "dppr_ftrack_update", "dppr_ftrack_read", "dppr_ftrack_info", "dppr_ftrack_destroy", "dppr_debug_ftrack_ms",
     "dppr_ftrack_cluster", "dppr_debug_ftrack_cluster",
+    "dppr_ftrack_topk_ranked", "dppr_ftrack_rank_score_at", "dppr_ftrack_position_at", "dppr_ftrack_sample", "dppr_debug_ftrack_rank",
 ]
 
 DEST_HOST, DEST_DEVICE = 0, 1
@@ -353,6 +354,12 @@ def lib():
     # (the five arrays as plain addresses: host arrays or device memory, as `dest` says; each may be NULL)
     L.dppr_ftrack_cluster.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_int64, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.dppr_debug_ftrack_cluster.argtypes = [vp, C.c_int, C.c_int]
+    L.dppr_ftrack_topk_ranked.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_double, ip, dp, ip]
+    L.dppr_ftrack_rank_score_at.argtypes = [vp, C.c_int32, vp, ip, C.c_int32, dp]
+    L.dppr_ftrack_position_at.argtypes = [vp, C.c_int32, vp, C.c_double, ip, C.c_int32, ip, ip]
+    # (out_ids / out_w as plain addresses, as dppr_group_sample)
+    L.dppr_ftrack_sample.argtypes = [vp, C.c_int32, vp, C.c_double, C.c_uint64, C.c_uint64, C.c_int32, C.c_int, vp, vp, dp, ip, ip]
+    L.dppr_debug_ftrack_rank.argtypes = [vp, C.c_int]
     L.dppr_debug_forward.argtypes = [vp, C.c_int, C.c_int]
     L.dppr_assign.argtypes = [vp, ip, C.c_int32, dp, C.c_double, C.c_int, vp, vp, vp, i64p, vp, C.c_int64, i64p, vp, vp, vp]
     L.dppr_assign_at.argtypes = [vp, ip, C.c_int32, dp, C.c_double, ip, C.c_int32, ip, dp, ip, dp]
@@ -496,6 +503,53 @@ class ForwardTrack:
             if int(off[m]) != total:
                 raise DpprError("ftrack_cluster: the state changed between the size call and the fill")
         return ([b.as_dict() for b in best[:m]], off[:m + 1].copy(), *arrays)
+
+    # ---- ranked, position and sample queries over the track's p (include/dppr.h: dppr_ftrack_topk_ranked ..) ----
+    def topk_ranked(self, k, min_score=0.0, spec=None):
+        """Engine.group_topk_ranked over the track's columns: a list of (ids, scores), one per column, trimmed to the count. The score
+        is THE SCORE of topk_ranked from the track's own p (a seed without a row included), the degrees and neighbours those of the
+        track's epoch, the seeds of a column its start set. spec: Engine.rank_spec()."""
+        m, kk = max(self.m, 1), max(int(k), 1)
+        ids, sc, cnt = np.empty((m, kk), dtype=np.int32), np.empty((m, kk), dtype=np.float64), np.empty(m, dtype=np.int32)
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        self._e._ck(self._e._L.dppr_ftrack_topk_ranked(self._e._h, self.handle, C.byref(spec) if spec is not None else None, int(k), float(min_score),
+                                                       ids.ctypes.data_as(ip), sc.ctypes.data_as(dp), cnt.ctypes.data_as(ip)), "ftrack_topk_ranked")
+        return [(ids[i, :c].copy(), sc[i, :c].copy()) for i, c in enumerate(cnt[:self.m])]
+
+    def rank_score_at(self, ids, spec=None):
+        """The scores of every column at the given external ids: a [len(ids)][m] array (vertex-major, as Engine.group_rank_score_at)."""
+        a, pa = _i32(ids)
+        out = np.empty((len(a), max(self.m, 1)), dtype=np.float64)
+        self._e._ck(self._e._L.dppr_ftrack_rank_score_at(self._e._h, self.handle, C.byref(spec) if spec is not None else None, pa, len(a),
+                                                         out.ctypes.data_as(C.POINTER(C.c_double))), "ftrack_rank_score_at")
+        return out[:, :self.m]
+
+    def position_at(self, ids, spec=None, min_score=0.0):
+        """Where the given external ids stand in every column's order: (pos int32 [len(ids)][m], counts int32 [m]), as
+        Engine.group_position_at; rank_metrics takes a column of pos."""
+        a, pa = _i32(ids)
+        pos, cnt = np.empty((len(a), max(self.m, 1)), dtype=np.int32), np.empty(max(self.m, 1), dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        self._e._ck(self._e._L.dppr_ftrack_position_at(self._e._h, self.handle, C.byref(spec) if spec is not None else None, float(min_score), pa, len(a),
+                                                       pos.ctypes.data_as(ip), cnt.ctypes.data_as(ip)), "ftrack_position_at")
+        return pos[:, :self.m], cnt[:self.m]
+
+    def sample(self, S, spec=None, min_score=0.0, seed=0, first=0, with_w=True, device_ptrs=None):
+        """S external ids per column drawn with replacement in proportion to the column's score, as Engine.group_sample with the lane
+        index = the column: (ids int32 [m][S], w float64 [m][S] or None, total [m], support [m], status [m]). device_ptrs: a dict of
+        raw device addresses (ids: m * S int32; w: m * S float64, optional) that take the draws instead: (total, support, status)."""
+        m = max(self.m, 1)
+        total, support, status = np.empty(m, dtype=np.float64), np.empty(m, dtype=np.int32), np.empty(m, dtype=np.int32)
+        head = (self._e._h, self.handle, C.byref(spec) if spec is not None else None, float(min_score), int(seed), int(first), int(S))
+        tail = (total.ctypes.data_as(C.POINTER(C.c_double)), support.ctypes.data_as(C.POINTER(C.c_int32)), status.ctypes.data_as(C.POINTER(C.c_int32)))
+        fn = self._e._L.dppr_ftrack_sample
+        if device_ptrs is not None:
+            self._e._ck(fn(*head, DEST_DEVICE, device_ptrs.get("ids"), device_ptrs.get("w"), *tail), "ftrack_sample")
+            return total[:self.m], support[:self.m], status[:self.m]
+        ids = np.empty((m, max(int(S), 0)), dtype=np.int32)
+        w = np.empty((m, max(int(S), 0)), dtype=np.float64) if with_w else None
+        self._e._ck(fn(*head, DEST_HOST, ids.ctypes.data, w.ctypes.data if with_w else None, *tail), "ftrack_sample")
+        return ids[:self.m], None if w is None else w[:self.m], total[:self.m], support[:self.m], status[:self.m]
 
     def times_ms(self):
         """With Engine.set_profiling(1): device ms of the engine's last track create / update: [load, fix-up, rounds, store]."""
@@ -1216,6 +1270,11 @@ class Engine:
         """Test hook of ForwardTrack.cluster: positions per tile of the prefix sum and entries per piece of a long row (0 or a power of
         two in [64, 4096]; 0: the plan decides). Every setting gives the same bits."""
         self._ck(self._L.dppr_debug_ftrack_cluster(self._h, int(scan_tile), int(piece_edges)), "debug_ftrack_cluster")
+
+    def debug_ftrack_rank(self, tile_rows=0):
+        """Test hook of ForwardTrack.topk_ranked / position_at: external ids per tile of the count / fill passes (0 or a power of two in
+        [64, 1024]; 0: the plan decides). Every setting gives the same bits."""
+        self._ck(self._L.dppr_debug_ftrack_rank(self._h, int(tile_rows)), "debug_ftrack_rank")
 
     def debug_forward_push(self, piece_edges=0, team=0, chunk_rounds=0):
         """Test hook (dppr_debug_forward_push): piece_edges and team as debug_forward; chunk_rounds rounds are enqueued between

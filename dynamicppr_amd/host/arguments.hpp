@@ -228,6 +228,10 @@ inline void PrintUsage() {
               << "--forward-cluster deg|p: with --forward-track, after the create and after every batch sweep every set's WHOLE order -- every vertex an\n"
               << "            edge names with a score > 0, by p / (outdeg + 1) (deg) or by p -- for its prefix of lowest conductance (dppr_ftrack_cluster):\n"
               << "            fcluster <first id> size <best_size> of <count> cut <cut_out> vol <vol> phi <conductance, %.17g>\n"
+              << "--forward-rank <K>: with --forward-track, after the create and after every batch print the K best of every set by the ranked query\n"
+              << "            over the track's own p (dppr_ftrack_topk_ranked; 1 <= K <= 8192) -- by the score of --rank-factor / --rank-exclude if given (the\n"
+              << "            seeds are the set's, the degrees and neighbours those of the epoch the track stands on; no --topk needed):\n"
+              << "            franked <set index> epoch <e> count <found> <v0>:<score0, %.17g> ...\n"
               << "--sample <S> [--sample-seed <X>]: after every batch draw, per source in source order, S vertices with replacement in proportion to\n"
               << "            the source's pagerank -- to the score of --rank-factor / --rank-exclude if given (no --topk needed) -- (1 <= S <= 2^20;\n"
               << "            the draws are a function of the scores, the source's lane, X and the draw number alone): sample <source> lane <lane>\n"
@@ -310,6 +314,7 @@ inline void ArgumentsChecker() {
                                   !std::isfinite(gForwardTol) || gForwardTopK < 0 || gForwardTopK > 64))
         ok = false;
     if (!gTrackCluster.empty() && (gTrackFile.empty() || (gTrackCluster != "deg" && gTrackCluster != "p"))) ok = false;
+    if (gTrackRankGiven && (gTrackFile.empty() || gTrackRank < 1 || gTrackRank > DPPR_TOPK_MAX)) ok = false;
     if (gPushBad || gTrackBad || (gPushOptsGiven && gPushFile.empty() && gTrackFile.empty())) ok = false;
     if (!gTrackFile.empty() && (gSplitInterface || !(gPushEps > 0.0) || !std::isfinite(gPushEps) || gPushRounds < 1 || gPushRounds > DPPR_FPUSH_MAX_ROUNDS ||
                                 gForwardTopK < 0 || gForwardTopK > 64 || gTrackSets.size() > (size_t)DPPR_FTRACK_MAX * DPPR_FORWARD_MAX_M))
@@ -318,7 +323,7 @@ inline void ArgumentsChecker() {
                                gForwardTopK < 0 || gForwardTopK > 64))
         ok = false;
     if ((gSampleGiven && (gSample < 1 || gSample > DPPR_SAMPLE_MAX || gSplitInterface)) || (gSampleSeedGiven && !gSampleGiven)) ok = false;
-    if (gRankGiven && ((gTopK == 0 && gPositionsFile.empty() && !gSampleGiven) || gRankFactor < 0 || gRankExclude < 0 || gSplitInterface)) ok = false;
+    if (gRankGiven && ((gTopK == 0 && gPositionsFile.empty() && !gSampleGiven && !gTrackRankGiven) || gRankFactor < 0 || gRankExclude < 0 || gSplitInterface)) ok = false;
     if (!gTargetSetsFile.empty() && (gTargetSetsBad || gTargetSets.empty() || !gSourcesFile.empty() || gSplitInterface || gNoGroups || gTopKWeightsGiven)) ok = false;
     if ((gAssignMinGiven || !gAssignOut.empty()) && !gAssign) ok = false;
     if (gAssign && (!(gAssignMin >= 0.0) || gSplitInterface || gNoGroups)) ok = false; // (one device, groups in use: checked against the sources in main)
@@ -418,6 +423,8 @@ inline void ArgumentsParser(int argc, char **argv) {
         const char *v = find(argc, argv, "--forward-cluster");
         gTrackCluster = v && *v ? v : "?"; // (no value, or an empty one: refused with the usage)
     }
+    gTrackRankGiven = has(argc, argv, "--forward-rank");
+    gTrackRank = as_int(argc, argv, "--forward-rank", 0);
     gPushOptsGiven = has(argc, argv, "--push-eps") || has(argc, argv, "--push-rounds");
     gPushEps = as_whole_double(argc, argv, "--push-eps", 0.0);
     gPushRounds = as_int(argc, argv, "--push-rounds", 64);

@@ -96,6 +96,8 @@ inline std::string gTrackFile;        // --forward-track FILE : sets as --forwar
 inline bool gTrackBad = false;        //   FILE could not be read, holds no set or more than 256, or a token is not `id` or `id:weight`
 inline std::vector<std::vector<std::pair<int32_t, double>>> gTrackSets;
 inline std::string gTrackCluster;     // --forward-cluster deg|p : with --forward-track, the full-length conductance sweep of every set's p after the create and after every batch (dppr_ftrack_cluster)
+inline bool gTrackRankGiven = false;  // --forward-rank K : with --forward-track, the K best of every set by the ranked query over the track's p after the create and after every batch (dppr_ftrack_topk_ranked; under --rank-factor / --rank-exclude if given)
+inline int gTrackRank = 0;
 inline int gForwardTopK = 5;          // --forward-topk K (0 <= K <= 64: 0 prints no vertex)
 inline int gSample = 0;               // --sample S : after every batch print one sample line per source (S draws in proportion to its score)
 inline bool gSampleGiven = false;

@@ -1104,6 +1104,31 @@ public:
                 }
             }
         }
+        // --forward-rank: the K best of every set by the ranked query over the track's own p, on the epoch the tracks stand on now
+        // (under --rank-factor / --rank-exclude if given; no mask: the program owns no device memory)
+        if (gTrackRankGiven) {
+            const size_t RK = (size_t)gTrackRank;
+            dppr_rank_spec_t spec{};
+            spec.factor = gRankGiven ? gRankFactor : DPPR_FACTOR_NONE;
+            spec.exclude = gRankGiven ? (unsigned)gRankExclude : 0u;
+            std::vector<int32_t> rids(DPPR_FORWARD_MAX_M * RK), rcnt(DPPR_FORWARD_MAX_M);
+            std::vector<double> rscore(DPPR_FORWARD_MAX_M * RK);
+            for (size_t first = 0, t = 0; first < n_sets; first += DPPR_FORWARD_MAX_M, ++t) {
+                const size_t m = std::min<size_t>(DPPR_FORWARD_MAX_M, n_sets - first);
+                int32_t at = -1;
+                DPPR_CHECK(engine, dppr_ftrack_info(engine, ftracks[t], &at, nullptr, nullptr, nullptr, nullptr, nullptr, 0));
+                DPPR_CHECK(engine, dppr_ftrack_topk_ranked(engine, ftracks[t], &spec, gTrackRank, 0.0, rids.data(), rscore.data(), rcnt.data()));
+                for (size_t j = 0; j < m; ++j) {
+                    std::snprintf(line, sizeof(line), "franked %d epoch %d count %d", (int)(first + j), (int)at, (int)rcnt[j]);
+                    out += line;
+                    for (size_t q = 0; q < (size_t)rcnt[j]; ++q) {
+                        std::snprintf(line, sizeof(line), " %d:%.17g", (int)rids[j * RK + q], rscore[j * RK + q]);
+                        out += line;
+                    }
+                    out += "\n";
+                }
+            }
+        }
         progress++;
         static std::mutex print_mu;
         std::lock_guard<std::mutex> lk(print_mu);

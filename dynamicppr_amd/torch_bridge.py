@@ -340,6 +340,56 @@ def group_sample(engine, gid, S, min_score=0.0, seed=0, first=0, factor=None, al
     return ids, w, torch.from_numpy(total), torch.from_numpy(support), torch.from_numpy(status)
 
 
+def _open_track(track, who):
+    if not isinstance(track, _eng.ForwardTrack) or track.handle < 0:
+        raise _eng.DpprError(f"{who}: an open ForwardTrack of Engine.ftrack")
+    return track
+
+
+def ftrack_topk_ranked(engine, track, k, min_score=0.0, factor=None, allow=None, deny=None, exclude=()):
+    """dppr_ftrack_topk_ranked over torch tensors: a list of (ids, scores) numpy pairs, one per column of the forward track `track`,
+    as ForwardTrack.topk_ranked returns them. factor, allow, deny and exclude are those of group_topk_ranked, in the same form; the
+    seeds of a column are its start set, the degrees and neighbours those of the epoch the track stands on."""
+    _open_track(track, "ftrack_topk_ranked")
+    spec, keep = _rank_spec(engine, factor, allow, deny, exclude, "ftrack_topk_ranked")
+    torch.cuda.synchronize(_device(engine))   # (the tensors are torch's; nothing of torch's is in flight on them when the engine reads)
+    return track.topk_ranked(k, min_score, spec)
+
+
+def ftrack_position_at(engine, track, ids, min_score=0.0, factor=None, allow=None, deny=None, exclude=()):
+    """dppr_ftrack_position_at over torch tensors: where the external ids `ids` (a host sequence or an integer tensor, at most 4096)
+    stand in every column's order under the factor, masks and exclusions of ftrack_topk_ranked. Returns (pos, counts): int32 CPU
+    tensors [len(ids)][m] (-1: the id does not qualify in the column) and [m]."""
+    _open_track(track, "ftrack_position_at")
+    spec, keep = _rank_spec(engine, factor, allow, deny, exclude, "ftrack_position_at")
+    if isinstance(ids, torch.Tensor):
+        if ids.is_floating_point() or ids.dtype == torch.bool or ids.dim() != 1:
+            raise ValueError(f"ftrack_position_at: ids is a 1-D integer tensor or a sequence, not {ids.dtype} {tuple(ids.shape)}")
+        ids = ids.detach().cpu().numpy()
+    torch.cuda.synchronize(_device(engine))   # (the tensors are torch's; nothing of torch's is in flight on them when the engine reads)
+    pos, counts = track.position_at(ids, spec, min_score)
+    return torch.from_numpy(pos.copy()), torch.from_numpy(counts.copy())
+
+
+def ftrack_sample(engine, track, S, min_score=0.0, seed=0, first=0, factor=None, allow=None, deny=None, exclude=(), with_w=True):
+    """dppr_ftrack_sample over torch tensors: S external ids per column drawn with replacement in proportion to the column's score
+    under the factor, masks and exclusions of ftrack_topk_ranked. Returns (ids, w, total, support, status): ids int32 [m, S] and w
+    float64 [m, S] (None without with_w) on the engine's device, filled in place; total float64 [m], support int32 [m] and status
+    int32 [m] as CPU tensors. ids are -1 where a column's status is not SAMPLE_OK."""
+    _open_track(track, "ftrack_sample")
+    spec, keep = _rank_spec(engine, factor, allow, deny, exclude, "ftrack_sample")
+    S = int(S)
+    if not 0 <= S <= _eng.SAMPLE_MAX:
+        raise _eng.DpprError(f"ftrack_sample: 0 <= S <= {_eng.SAMPLE_MAX}, not {S}")
+    dev = _device(engine)
+    ids = torch.empty((track.m, S), dtype=torch.int32, device=dev)
+    w = torch.empty((track.m, S), dtype=torch.float64, device=dev) if with_w else None
+    torch.cuda.synchronize(dev)   # (the tensors are torch's; nothing of torch's is in flight on them when the engine reads or writes)
+    total, support, status = track.sample(S, spec, min_score, seed, first,
+                                          device_ptrs=dict(ids=ids.data_ptr() if S else None, w=w.data_ptr() if with_w and S else None))
+    return ids, w, torch.from_numpy(total.copy()), torch.from_numpy(support.copy()), torch.from_numpy(status.copy())
+
+
 def assign(engine, groups, scale=None, min_score=0.0, prev=None, want=("best", "margin")):
     """dppr_assign over torch tensors on the engine's device: every external id gets the smallest class of largest score =
     scale[c] * p_c above min_score, or -1; the classes are the lanes of `groups` (handles of this engine) in call order. Returns a

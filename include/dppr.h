@@ -1436,8 +1436,9 @@ int dppr_debug_forward(dppr_engine *e, int piece_edges /* 0: the plan decides */
  * dppr_debug_forward_push: a test hook. piece_edges and team as dppr_debug_forward; chunk_rounds in [0, 256]: the rounds enqueued
  * between two read-backs. 0: the plan decides. Every setting gives the same bits.
  * OUT OF SCOPE: a true scatter push (a hub that receives anything is gathered whole: the price of determinism), dense start
- * vectors, the ranked and subgraph families over p. (A forward vector kept current under the stream: dppr_ftrack_*; the
- * conductance sweep of a track's p, and a fresh track is the push bit for bit: dppr_ftrack_cluster.) */
+ * vectors, the subgraph family over p. (A forward vector kept current under the stream: dppr_ftrack_*; the
+ * conductance sweep of a track's p, and a fresh track is the push bit for bit: dppr_ftrack_cluster.) (The ranked, position and
+ * sample queries over a track's p: dppr_ftrack_topk_ranked and its siblings.) */
 #define DPPR_FPUSH_SET_MAX 4096
 #define DPPR_FPUSH_MAX_ROUNDS 256
 typedef struct {
@@ -1504,8 +1505,9 @@ int dppr_debug_forward_push(dppr_engine *e, int piece_edges, int team, int chunk
  * Input rules, rejection before any device work, the id-map lock, stream, work-space ownership and DPPR_ERR_NOMEM behave as for
  * dppr_forward_push; dppr_debug_forward_push applies to the rounds unchanged, and every setting gives the same bits. No output
  * value comes from a floating-point atomic; no output position or value depends on the order of a list.
- * OUT OF SCOPE: changing a track's sets in place, tracks that span engines, the ranked and subgraph families over a
- * track's p, any change to the reverse update path. (The conductance sweep of a track's p: dppr_ftrack_cluster.) */
+ * OUT OF SCOPE: changing a track's sets in place, tracks that span engines, the subgraph family over a track's p, any change
+ * to the reverse update path. (The conductance sweep of a track's p: dppr_ftrack_cluster.) (Ranked candidates, positions and
+ * samples over a track's p: dppr_ftrack_topk_ranked / _rank_score_at / _position_at / _sample.) */
 #define DPPR_FTRACK_MAX 16
 typedef struct {
     int32_t *rounds_used; int32_t *converged; double *rem; int64_t *pushes; int64_t *left; /* [m], HOST; each may be NULL */
@@ -1577,9 +1579,9 @@ int dppr_debug_ftrack_ms(dppr_engine *e, float *out_ms /* [4] */);
  * dppr_debug_ftrack_cluster: a test hook. scan_tile 0 or a power of two in [64, 4096]: positions of a tile of the multi-tile
  * prefix sum; piece_edges 0 or a power of two in [64, 4096]: rows longer than this are walked in pieces of this many entries.
  * 0: the plan decides. Every setting gives the same bits.
- * OUT OF SCOPE: masks, factors and exclusions over a track, the ranked and subgraph families over a track, the full-length sweep
- * for slot and group states, sweeps over dppr_forward / dppr_forward_push results that are not tracks (a fresh track is the push
- * bit for bit). */
+ * OUT OF SCOPE: masks and exclusions inside the sweep, the subgraph family over a track, the full-length sweep for slot and
+ * group states, sweeps over dppr_forward / dppr_forward_push results that are not tracks (a fresh track is the push bit for
+ * bit). (Factors, masks and exclusions over a track's p, as a ranked order: dppr_ftrack_topk_ranked and its siblings.) */
 #define DPPR_FCLUSTER_BY_P           0   /* score = p[v]                              */
 #define DPPR_FCLUSTER_BY_P_OVER_DEG  1   /* score = p[v] / (double)(outdeg(v) + 1)    */
 typedef struct { int64_t count, best_size, best_cut, best_vol; double best_phi; } dppr_fcluster_t;
@@ -1590,6 +1592,88 @@ int dppr_ftrack_cluster(dppr_engine *e, int32_t track, int32_t order, double min
                         int32_t *out_ids, double *out_score,
                         int64_t *out_cut_out, int64_t *out_cut_in, int64_t *out_vol /* [cap] each, each may be NULL */);
 int dppr_debug_ftrack_cluster(dppr_engine *e, int scan_tile, int piece_edges);
+
+/* ---- rank, locate and sample over a forward track's p (backward-compatible additions, ABI 6) ----
+ * A track is the engine's answer to "where does the walk from this user or this set go, kept current per batch": the recommender
+ * and link-prediction vector. The head of its raw order is its own start set and what that set already links to; "who to follow"
+ * is the forward vector with the seeds and their out-neighbours excluded and one vertex type allowed, and a held-out edge is
+ * evaluated by the position of its head in that order. These calls point the ranked family -- dppr_rank_spec_t, the top k, the
+ * score at given ids, the positions (MRR / Hits@K / percentile) and the samples (negatives, candidates) -- at a track, on the
+ * device, instead of a dense copy of p + dppr_read_out_graph + numpy per batch. There is no `epoch` argument: as in
+ * dppr_ftrack_cluster the graph is the epoch the track stands on. Read side only: the track and every solver state are unchanged.
+ *
+ * For column c of the track and external id v, every output is defined exactly:
+ *   P            p = p_c[v] is exactly what dppr_ftrack_read returns at v (at_p). The track's state is by external id and
+ *                complete: a seed that no stored edge names holds 0.15 * w, a parked vertex keeps its value, and after deletes p
+ *                may be negative.
+ *   OUTDEG       outdeg(v) is the stored out-degree of v on the track's epoch, with multiplicity; 0 for a vertex without a live
+ *                row (no internal id, or parked).
+ *   THE SCORE    word for word THE SCORE of dppr_topk_ranked: DPPR_FACTOR_NONE / _DEV / _DEG / _INV_DEG are one explicit rounding
+ *                each, nothing fused; an f32 g is converted to double exactly; mask_dev and factor_dev are [V] by external id; a
+ *                vertex that is masked out scores exactly +0.0.
+ *   SEEDS        the seeds of column c are the ids dppr_ftrack_info lists for it, whatever their weights.
+ *   EXCLUDED     DPPR_EXCLUDE_SEEDS excludes the seeds; DPPR_EXCLUDE_IN_NEIGHBOURS / _OUT_NEIGHBOURS exclude v with a stored edge
+ *                v -> seed / seed -> v on the track's epoch, for any seed of the column. Exclusion is per column: a vertex
+ *                excluded in column 2 may rank first in column 3. An excluded vertex scores +0.0 in that column.
+ *   NO ID        THE ONE PLACE this differs from the NO ID rule of dppr_topk_ranked: a vertex without an internal id is not
+ *                p = 0. Its score follows the formula from the track's own p_c[v] with outdeg = 0, so a rowless seed is in the
+ *                raw order exactly as it is in dppr_ftrack_read's top k, and DPPR_EXCLUDE_SEEDS takes it out although it has
+ *                no row.
+ *   QUALIFIES, ORDER, POSITION, COUNTS, DUPLICATE IDS   those of dppr_group_topk_ranked / dppr_group_position_at with "lane" read
+ *                as "column" and n as the track's m: score > min_score (min_score >= 0; a +-0, negative or NaN score never
+ *                qualifies, +inf orders first), score descending then external id ascending, entries past a count hold id -1 and
+ *                0.0, pos = -1 where the id does not qualify, every external id 0 .. V - 1 takes part.
+ *   WEIGHT, TREE, UNIFORM, DESCENT, statuses   those of dppr_group_sample with the lane index i = the column; the limits are
+ *                DPPR_SAMPLE_MAX and m * S <= DPPR_SAMPLE_MAX_TOTAL.
+ *   EPOCH        a spec that reads no degree and no neighbour never looks at the graph: it works even when the track's epoch has
+ *                left the ring. Otherwise the track's epoch must be resident, else DPPR_ERR_INVALID.
+ *   INDEPENDENCE a column's outputs are a function of its own p, its seeds, the spec and the epoch: not of m, of the other columns,
+ *                of the grid or of any debug hook.
+ * Outputs: dppr_ftrack_topk_ranked ids [m][k], scores [m][k], counts [m]; dppr_ftrack_rank_score_at [n_ids][m], vertex-major;
+ * dppr_ftrack_position_at pos [n_ids][m] and counts [m] (may be NULL); dppr_ftrack_sample as dppr_group_sample with n = m.
+ * n_ids == 0 and S == 0 behave as in the group forms.
+ * ANCHORS. (a) With spec == NULL, or the all-zero spec, the ids and scores equal the top k of dppr_ftrack_read(k, min_p =
+ * min_score) bit for bit, a column whose only seed is rowless included. (b) dppr_ftrack_rank_score_at at any id equals the score
+ * that places it in (a), bit for bit. (c) With DPPR_FACTOR_INV_DEG and nothing else, on a track with no rowless seed, the first k
+ * ids and scores equal the first k of dppr_ftrack_cluster(DPPR_FCLUSTER_BY_P_OVER_DEG, min_score, max_len = k): two independent
+ * device paths, a radix sort against a selection, agreeing to the bit. (d) The position anchors (a) - (b) of
+ * dppr_group_position_at, taken against dppr_ftrack_topk_ranked. (e) The sample anchors (a) - (d) of dppr_group_sample, taken
+ * against dppr_ftrack_rank_score_at.
+ *
+ * Rejected with DPPR_ERR_INVALID before any device work, nothing written: no such track; every spec rejection of dppr_topk_ranked
+ * (enum values, exclude bits, the device-pointer range checks); k outside [1, DPPR_TOPK_MAX]; min_score negative or NaN; NULL
+ * outputs where the group forms refuse them; n_ids < 0, an id outside [0, V), n_ids > DPPR_POSITION_MAX for positions; the sample
+ * limits and a bad device destination; the epoch rule above; a broken engine.
+ * Threading and stream as dppr_ftrack_read: the id-map lock for the whole call (safe beside dppr_slide_concurrent), the solver
+ * stream, never part of an update or of a timed region.
+ * SHAPE. The track's [V][row width] plane is read in place by external id; nothing is loaded into the forward family's planes. A
+ * spec that excludes marks one 32-bit word per external id, bit c for column c (with a neighbour flag the one read of the seeds'
+ * row lengths by the host lies between the kernels, as in dppr_topk_ranked). The top k and the positions then run over a
+ * COMPACTED scratch state that holds a row only for an external id at which at least one column has score > min_score, in
+ * ascending external id: a count per tile, a scan over the tiles, ONE read of the row count by the host (as in dppr_subgraph and
+ * dppr_ftrack_cluster) and a fill that recomputes the scores and places each row by its rank inside its tile; no position comes
+ * from an atomic. A dropped row qualifies in no column, so it is in no top k, precedes no position and joins no count: the
+ * compaction cannot change a result. Zero kept rows is a valid result: every count is 0, ids are -1, positions are -1. A sample's
+ * leaves are in external-id order already; nothing is compacted there.
+ * Work space: 4 V bytes of exclusion words and 4 bytes per seed where the spec excludes, the row lengths and pieces of
+ * dppr_topk_ranked, 12 bytes per tile, 8 m + 4 bytes per kept row of scratch state (the one of dppr_group_topk_ranked, not a second
+ * one), then what the group forms take behind it; all of it is the engine's, obtained before the first kernel that uses it, grown
+ * on demand and released with the engine: after DPPR_ERR_NOMEM the track and the engine are as before. With dppr_set_profiling
+ * on, dppr_debug_query_ms reports the call, first to last kernel.
+ * dppr_debug_ftrack_rank: a test hook. tile_rows 0 (the plan decides) or a power of two in [64, 1024]: external ids per tile of
+ * the count / fill passes. Every setting gives the same bits.
+ * OUT OF SCOPE: the subgraph, patch and changes families over a track; ranked queries over one-shot dppr_forward /
+ * dppr_forward_push results (a fresh track is the push bit for bit); weight vectors across columns. */
+int dppr_ftrack_topk_ranked(dppr_engine *e, int32_t track, const dppr_rank_spec_t *spec, int32_t k, double min_score,
+                            int32_t *out_ids /* [m][k] */, double *out_score /* [m][k] */, int32_t *out_counts /* [m] */);
+int dppr_ftrack_rank_score_at(dppr_engine *e, int32_t track, const dppr_rank_spec_t *spec, const int32_t *ids, int32_t n_ids,
+                              double *out_score /* [n_ids][m] */);
+int dppr_ftrack_position_at(dppr_engine *e, int32_t track, const dppr_rank_spec_t *spec, double min_score, const int32_t *ids,
+                            int32_t n_ids, int32_t *out_pos /* [n_ids][m] */, int32_t *out_counts /* [m], may be NULL */);
+int dppr_ftrack_sample(dppr_engine *e, int32_t track, const dppr_rank_spec_t *spec, double min_score, uint64_t seed, uint64_t first,
+                       int32_t S, int dest, int32_t *out_ids /* [m][S] */, double *out_w /* may be NULL */,
+                       double *out_total /* [m] */, int32_t *out_support /* may be NULL */, int32_t *out_status /* [m] */);
+int dppr_debug_ftrack_rank(dppr_engine *e, int tile_rows);
 
 /* Windows whose sweep groups are all resident at once run a frontier loop of a source group as
  * multi-sweep launches (grid barrier between sweeps, row tables kept in LDS; dppr_multi.hpp). on by
